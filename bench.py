@@ -3,6 +3,12 @@
 bench.py -- headline benchmark of the hot path on MI355X (contract: the task statement; numbers explained in DESIGN.md 6).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|configs1|configs2|configs3|configs4] [--mbp M]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the JSON line (the fields of the timed steps: value, ms_per_step,
+roofline, valu, step_roofline, fallbacks, ...).  --full adds the side measurements that take runs of their own: kernels and
+one_shot (second and third handle), cpu_baseline, end_to_end, and with the default workload repeat_rich and other_k.
+--dump-outputs DIR writes what the last timed step handed back (sketches + graph) as DIR/<name>.npy (dump_outputs()).
 
 One STEP = one pass of the whole hot path over one batch of synthetic input already resident in HBM (2-bit packed bases,
 produced on the device by the counter-based generator of ntjoin_amd/csrc/synth.hip): sketch every assembly (ntHash +
@@ -26,9 +32,9 @@ Beside the contract's fields the JSON line carries
   valu          the same kernel against what really bounds it, VALU issue: wave64 instructions per chunk counted by the
                 generator (csrc/hash_bs_k32.inc) x chunks per launch / 1024 SIMDs x 2 cycles at 2.4 GHz
   step_roofline the whole step's algorithmic bytes (0.25 L + 70 M) over the step time
-  kernels       per-kernel GPU time of a step, measured in a second, shorter pass with one HIP-event pair per kernel
-  cpu_baseline  the oracle's `indexlr -t nproc` + graph stage in C on the host cores, on a stated sample of the workload
-  end_to_end    FASTA files (page cache) -> .tsv + .mx.dot on disk through the CLI a ntJoin user runs (never `value`)
+  kernels       (--full) per-kernel GPU time of a step, measured in a second, shorter pass with one HIP-event pair per kernel
+  cpu_baseline  (--full) the oracle's `indexlr -t nproc` + graph stage in C on the host cores, on a stated sample of the workload
+  end_to_end    (--full) FASTA files (page cache) -> .tsv + .mx.dot on disk through the CLI a ntJoin user runs (never `value`)
 """
 import argparse
 import json
@@ -654,6 +660,63 @@ def scaling_fields(wl, W, world, value, bases_total):
             "efficiency_is": f"no committed one-GPU line of workload {wl} under profiles/: run `python bench.py --workload {wl}` on one GPU"}
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 17        # entries kept of a longer array (fewer when the arrays are many: DUMP_MAX_BYTES holds)
+
+
+def dump_outputs(eng, out_dir, seed=12345):
+    """`--dump-outputs DIR`: what the step hands its caller after the last timed step -- every assembly's sketch (mxg_get_sketch)
+    and the graph (mxg_get_graph) -- as float64 .npy files, exact: 64-bit hashes are split into 32-bit halves.  An array longer
+    than the sample size keeps the entries at fixed indices drawn by a seeded generator (written beside it as <group>_index), so
+    two builds given the same arguments write the same files when they compute the same thing; `counts` holds the full lengths."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    A = int(eng.n_assemblies)
+    sk = [eng.get_sketch(a) for a in range(A)]
+    g = eng.get_graph()
+    # columns: per assembly hash hi / lo, pos, record, forward, index, record_first + its index; vertex hash hi / lo, index, pos
+    # and record per assembly; edge u, v, support, weight, index
+    n_cols = 8 * A + 3 + 2 * A + 5
+    sample = max(1, min(DUMP_SAMPLE, (DUMP_MAX_BYTES - (1 << 20)) // (8 * n_cols)))
+    files = {}
+
+    def pick(group, n):
+        if n <= sample:
+            return None
+        rng = np.random.default_rng([seed, zlib.crc32(group.encode())])
+        idx = np.sort(rng.choice(n, size=sample, replace=False))
+        files[group + "_index"] = idx
+        return idx
+
+    def put(name, arr, idx):
+        arr = np.asarray(arr)
+        files[name] = arr[..., idx] if idx is not None else arr
+
+    for a, s in enumerate(sk):
+        idx = pick(f"sketch{a}", len(s["out_hash"]))
+        put(f"sketch{a}_hash_hi", s["out_hash"] >> np.uint64(32), idx)
+        put(f"sketch{a}_hash_lo", s["out_hash"] & np.uint64(0xFFFFFFFF), idx)
+        for f in ("pos", "record", "forward"):
+            put(f"sketch{a}_{f}", s[f], idx)
+        put(f"sketch{a}_record_first", s["record_first"], pick(f"sketch{a}_record_first", len(s["record_first"])))
+    idx = pick("graph_vertex", len(g["vertex_hash"]))
+    put("graph_vertex_hash_hi", g["vertex_hash"] >> np.uint64(32), idx)
+    put("graph_vertex_hash_lo", g["vertex_hash"] & np.uint64(0xFFFFFFFF), idx)
+    put("graph_vertex_pos", g["vertex_pos"], idx)          # (assemblies, vertices)
+    put("graph_vertex_record", g["vertex_record"], idx)
+    idx = pick("graph_edge", len(g["edge_u"]))
+    for f in ("edge_u", "edge_v", "edge_support", "edge_weight"):
+        put(f"graph_{f}", g[f], idx)
+    files["counts"] = np.array([len(s["out_hash"]) for s in sk] + [len(g["vertex_hash"]), len(g["edge_u"])])
+    total = 0
+    for name, arr in files.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float64)   # every value here is an integer below 2^53 or already a float64
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        total += arr.nbytes
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs wrote {total} bytes"
+    return sorted(files)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks here -- one process per GPU, the environment torchrun
     would give them (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT on 127.0.0.1 with a free port) -- hand rank 0's
@@ -747,7 +810,16 @@ def main():
                          "kernels, no collective) and print the per-rank kernel times, the bytes each rank would send and the step time "
                          "they predict -- a prediction to hold the first real N-GPU run against, never a measurement of it")
     ap.add_argument("--other-k", action="store_true", help="only the side measurement of the routes the headline does not take (k = 24, the min variant)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, every side measurement: the per-kernel pass and one_shot, the CPU baseline, end to end "
+                         "through the CLI, the repeat-rich and other-k side runs (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step handed back (sketches + graph) to DIR/<name>.npy (one GPU)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_end_to_end = args.no_kernels = args.no_repeats = True
+    if args.dump_outputs and (args.gpus > 1 or args.dry or args.other_k):
+        sys.exit("bench.py: --dump-outputs writes the outputs of the one-GPU step (--gpus 1, no --dry / --other-k)")
     if args.other_k:
         return other_k_run()
     if args.dry:
@@ -772,6 +844,8 @@ def main():
     torch.cuda.set_device(local_rank)
     force_dist = os.environ.get("MXG_BENCH_FORCE_DIST") == "1"  # exercise the N>1 path with one rank (testing)
     multi = world > 1 or force_dist
+    if args.dump_outputs and multi:
+        sys.exit("bench.py: --dump-outputs writes the outputs of the one-GPU step")
     if multi:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -948,6 +1022,8 @@ def main():
                      "collective_timeout_s": float(os.environ.get("MXG_BENCH_COLLECTIVE_TIMEOUT_S", "120"))}
 
     st = eng.stats()
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
     if union is not None and graph_mode == "partitioned":
         gst = dict(union.stats())
         gst.update(partitioned_totals(union))      # global vertex / edge counts (collectives: every rank calls)

@@ -91,3 +91,78 @@ def test_exchange_beside_sketches_timeline():
     import itertools
     for sk, se in itertools.product([[0.3, 0.9, 0.1], [1.0, 1.0, 1.0]], [[0.5, 0.1, 0.8], [2.0, 2.0, 2.0]]):
         assert max(sum(sk) + se[-1], sk[0] + sum(se)) - 1e-12 <= f(sk, se) <= sum(sk) + sum(se) + 1e-12
+
+
+class _FakeEngine:
+    """what dump_outputs reads of an MxEngine after a step: get_sketch per assembly, get_graph (seeded arrays of bench-like sizes)"""
+
+    def __init__(self, seed, n_mx=(300_000, 250_000), nv=200_000, ne=190_000):
+        import numpy as np
+        rng = np.random.default_rng(seed)
+        self.sk = []
+        for n in n_mx:
+            rec_first = np.concatenate([[0], np.sort(rng.integers(0, n, 999)), [n]]).astype(np.uint64)
+            self.sk.append({"out_hash": rng.integers(0, 2**64 - 1, n, dtype=np.uint64, endpoint=True),
+                            "pos": rng.integers(0, 2**28, n, dtype=np.uint32), "record": rng.integers(0, 1000, n, dtype=np.uint32),
+                            "forward": rng.integers(0, 2, n, dtype=np.uint8), "record_first": rec_first})
+        A = len(n_mx)
+        self.g = {"n_assemblies": A, "vertex_hash": rng.integers(0, 2**64 - 1, nv, dtype=np.uint64, endpoint=True),
+                  "vertex_pos": rng.integers(0, 2**28, (A, nv), dtype=np.uint32), "vertex_record": rng.integers(0, 1000, (A, nv), dtype=np.uint32),
+                  "edge_u": rng.integers(0, nv, ne, dtype=np.uint32), "edge_v": rng.integers(0, nv, ne, dtype=np.uint32),
+                  "edge_support": rng.integers(1, 4, ne, dtype=np.uint32), "edge_weight": rng.random(ne) * 3}
+
+    @property
+    def n_assemblies(self):   # (a property, as MxEngine's)
+        return len(self.sk)
+
+    def get_sketch(self, a):
+        return self.sk[a]
+
+    def get_graph(self):
+        return self.g
+
+
+def test_dump_outputs_float_files_exact_sampled_and_repeatable(tmp_path):
+    """--dump-outputs: float32/float64 .npy files only, under 64 MB together, the same files for the same outputs, sampled arrays
+    taken at the written indices, and 64-bit hashes exact through their two halves"""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    # (eight assemblies: more columns than DUMP_SAMPLE entries each fit in 64 MB, the sample shrinks)
+    for n_mx in ((300_000, 250_000), (300_000,) * 4, (120_000,) * 8):
+        eng = _FakeEngine(7, n_mx)
+        d1, d2 = tmp_path / f"a{len(n_mx)}", tmp_path / f"b{len(n_mx)}"
+        names = bench.dump_outputs(eng, str(d1))
+        assert names == bench.dump_outputs(_FakeEngine(7, n_mx), str(d2))
+        files = sorted(os.listdir(d1))
+        assert files == sorted(n + ".npy" for n in names) and "counts.npy" in files
+        total = 0
+        for f in files:
+            a, b = np.load(d1 / f), np.load(d2 / f)
+            assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+            total += os.path.getsize(d1 / f)
+        assert total <= 64 << 20
+        c = np.load(d1 / "counts.npy")
+        assert c.tolist() == list(n_mx) + [200_000, 190_000]
+        idx = np.load(d1 / "sketch0_index.npy").astype(np.int64)
+        assert 0 < len(idx) < n_mx[0] and np.all(np.diff(idx) > 0)
+        assert (len(idx) < bench.DUMP_SAMPLE) == (len(n_mx) == 8) and len(np.load(d1 / "graph_edge_index.npy")) == len(idx)
+        h = eng.sk[0]["out_hash"][idx]
+        hi, lo = np.load(d1 / "sketch0_hash_hi.npy"), np.load(d1 / "sketch0_hash_lo.npy")
+        assert np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), h)
+        assert np.array_equal(np.load(d1 / "sketch0_pos.npy"), eng.sk[0]["pos"][idx].astype(np.float64))
+        assert np.load(d1 / "graph_vertex_pos.npy").shape == (len(n_mx), len(np.load(d1 / "graph_vertex_index.npy")))
+        assert np.array_equal(np.load(d1 / "sketch0_record_first.npy"), eng.sk[0]["record_first"].astype(np.float64))   # (short: whole)
+    # other outputs, other files
+    bench.dump_outputs(_FakeEngine(8), str(tmp_path / "c"))
+    assert not np.array_equal(np.load(tmp_path / "c" / "sketch0_hash_lo.npy"), np.load(tmp_path / "a2" / "sketch0_hash_lo.npy"))
+
+
+def test_plain_and_full_options():
+    """--full and --dump-outputs are options of bench.py; --dump-outputs is refused where there is no one-GPU step to dump"""
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], cwd=REPO, env=_clean_env(),
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dump-outputs", "x"], cwd=REPO,
+                         env=_clean_env(), capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--dump-outputs" in out.stderr and not os.path.exists(os.path.join(REPO, "x"))

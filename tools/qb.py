@@ -5,7 +5,7 @@ import subprocess
 import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-end-to-end"] + sys.argv[1:],
+out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-end-to-end"] + sys.argv[1:],
                      capture_output=True, text=True)
 lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
 if not lines:

@@ -4,14 +4,14 @@
 R=${ROUND:-r06}
 r=gpurun_out/$R
 mkdir -p $r
-timeout 1200 python bench.py > $r/bench_configs2.json 2> $r/bench_configs2.err
-timeout 600 python bench.py --workload configs3 --steps 5 --warmup 2 --no-end-to-end --cpu-seconds 4 > $r/bench_configs3.json 2>/dev/null
-timeout 600 python bench.py --workload configs4 --steps 3 --warmup 1 --no-end-to-end --cpu-seconds 4 > $r/bench_configs4.json 2>/dev/null
+timeout 1200 python bench.py --full > $r/bench_configs2.json 2> $r/bench_configs2.err
+timeout 600 python bench.py --full --workload configs3 --steps 5 --warmup 2 --no-end-to-end --cpu-seconds 4 > $r/bench_configs3.json 2>/dev/null
+timeout 600 python bench.py --full --workload configs4 --steps 3 --warmup 1 --no-end-to-end --cpu-seconds 4 > $r/bench_configs4.json 2>/dev/null
 timeout 600 python bench.py --workload repeats --steps 10 --warmup 3 > $r/bench_repeats.json 2>/dev/null
 timeout 600 python bench.py --workload configs2 --mbp 1000 --steps 10 --warmup 3 --no-cpu-baseline --no-end-to-end --no-kernels > $r/bench_iid.json 2>/dev/null
 for n in 2 4 8; do timeout 900 python bench.py --gpus $n --dry --steps 3 --warmup 1 > $r/bench_dry$n.json 2>/dev/null; done
-tools/prof_bench.sh ${R}_stats_configs2 --steps 10 --warmup 3 --no-end-to-end --no-repeats > /dev/null 2>&1
-tools/prof_bench.sh ${R}_stats_configs3 --workload configs3 --steps 5 --warmup 2 --no-end-to-end > /dev/null 2>&1
+tools/prof_bench.sh ${R}_stats_configs2 --full --steps 10 --warmup 3 --no-end-to-end --no-repeats > /dev/null 2>&1
+tools/prof_bench.sh ${R}_stats_configs3 --full --workload configs3 --steps 5 --warmup 2 --no-end-to-end > /dev/null 2>&1
 tools/pmc_round.sh ${R}_pmc_configs2 > /dev/null 2>&1
 tools/pmc_round.sh ${R}_pmc_configs3 --workload configs3 > /dev/null 2>&1
 tools/pmc_calib.sh $R > $r/calib.txt 2>&1

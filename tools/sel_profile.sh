@@ -3,7 +3,7 @@
 # wrong on purpose), read from bench.py's per-kernel pass.  Run on the GPU box:  tools/sel_profile.sh > gpurun_out/sel_profile.txt
 cd "$(dirname "$0")/.."
 run() {
-  python bench.py --no-cpu-baseline --no-end-to-end --steps 10 --warmup 2 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-end-to-end --steps 10 --warmup 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d.get('kernels',{}).get('ms_per_step',{})
