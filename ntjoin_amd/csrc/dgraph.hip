@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "batch_ctrl.h"
 #include "mxg_internal.h"
 #include "scan_kernels.h"
 
@@ -626,7 +627,7 @@ __device__ __forceinline__ uint32_t slot_items(unsigned long long raw, uint32_t 
 }
 
 // mxg_sketch_dg_pack_slots: the sketch may still be in flight on the stream -- its length is read on the device and the batch's
-// control words say whether it ended the common way (the predicate of k_pack_slot_dev, sketch.hip).  mode 0: n is the host's.
+// control words say whether it ended the common way (batch_ended_well).  mode 0: n is the host's.
 struct DgDevN {
     uint32_t mode;  // 0: host count; 1: count + predicate on the device; 2: the host knows the sketch is not usable
     const uint32_t *n_ptr, *ctrl;
@@ -645,8 +646,7 @@ __global__ __launch_bounds__(256) void k_dg_pack_slots(const uint64_t *__restric
         if (ok) {
             const uint32_t *ctrl = dv.ctrl;
             n = *dv.n_ptr;
-            ok = ctrl[0] == 0 && ctrl[6] == 0 && ctrl[13] == 0 && (dv.dev_gaps ? (ctrl[11] == 0 && ctrl[1] <= dv.place4) : ctrl[1] == 0) &&
-                 (ctrl[4] | ctrl[5]) != 0 && n <= dv.out_cap;
+            ok = batch_ended_well(ctrl, dv.dev_gaps, dv.place4) && n <= dv.out_cap;
         }
         if (!ok) {  // every destination sees a count far above any capacity: all ranks repeat the step the exact way
             if (blockIdx.x == 0 && threadIdx.x < L.world)

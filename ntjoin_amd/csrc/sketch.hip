@@ -42,6 +42,7 @@
 #include <functional>
 #include <type_traits>
 
+#include "batch_ctrl.h"
 #include "mxg_internal.h"
 #include "nthash_dev.h"
 #include "scan_kernels.h"
@@ -135,8 +136,8 @@ struct SparseParams {
     uint2 *arena;         // wave w owns entries [w*wave_cap, (w+1)*wave_cap): {strip (rel.), j | seq<<10}
     uint32_t wave_cap;
     uint32_t *wave_cnt;   // [n_waves] ENTRIES each wave wrote to its slice (k_reorder reads that many)
-    uint32_t *ctrl;       // [0] max over waves of their candidate count when it exceeds wave_cap (atomicMax): the host
-                          //     then redoes the batch with that capacity
+    uint32_t *ctrl;       // CW_ARENA_NEED: max over waves of their candidate count when it exceeds wave_cap (atomicMax): the
+                          //     host then redoes the batch with that capacity
     uint32_t *strip_cnt;  // [n_strips] candidates per strip
     uint32_t *wave_tot;   // [n_waves] candidates per wave, and their super-counts (scan_kernels.h; zeroed with ctrl)
     uint32_t *wave_sup;
@@ -353,7 +354,7 @@ __global__ __launch_bounds__(256) void k_hash_sparse(const SparseParams p)
         }
     }
     if (ABL != 0) {
-        if (abl_acc == 0x12345u) p.ctrl[3] = abl_acc;  // keep the ablated work alive
+        if (abl_acc == 0x12345u) p.ctrl[CW_SELECTED + 1] = abl_acc;  // keep the ablated work alive
         return;
     }
     if (s < p.strip_hi) p.strip_cnt[srel] = seq;
@@ -363,7 +364,7 @@ __global__ __launch_bounds__(256) void k_hash_sparse(const SparseParams p)
         p.wave_cnt[wave_id] = cnt_w;
         p.wave_tot[wave_id] = tot;  // k_reorder derives every wave's first ordered slot from these and the super-counts
         wtot[wv] = tot;
-        if (tot > wave_cap) atomicMax(&p.ctrl[0], tot);  // overflow: the host redoes the batch with this capacity
+        if (tot > wave_cap) atomicMax(&p.ctrl[CW_ARENA_NEED], tot);  // overflow: the host redoes the batch with this capacity
     }
     __syncthreads();
     if (threadIdx.x == 0) {  // one add per block: its four waves share a super-count (256 waves = 64 blocks)
@@ -431,7 +432,7 @@ __global__ __launch_bounds__(256) void k_bs_count(const SparseParams p, const ui
         if (lane == 0) {
             p.wave_tot[wave_id] = tot;
             wtot[wv] = tot;
-            if (tot > p.wave_cap) atomicMax(&p.ctrl[0], tot);  // more than a queue / the ordered arrays hold: the host redoes the batch
+            if (tot > p.wave_cap) atomicMax(&p.ctrl[CW_ARENA_NEED], tot);  // more than a queue / the ordered arrays hold: the host redoes the batch
         }
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -455,7 +456,7 @@ struct ReorderParams {
     uint32_t n_strips;
     const uint32_t *wave_tot;    // [n_waves] candidates per wave + super-counts (k_hash_sparse)
     const uint32_t *wave_sup;
-    uint32_t *n_cand;            // ctrl[4..5]: total, written by the block of the last wave
+    uint32_t *n_cand;            // CW_CAND: total, written by the block of the last wave
     uint32_t queue_cap;          // candidates the LDS queue holds (= wave_cap), 0: slice too large, hash per entry
     const uint32_t *strip_meta;  // run of every strip (k_hash_sparse)
     const Run *runs;
@@ -1061,7 +1062,7 @@ constexpr uint32_t GAP_DEV_MAX = 4096;  // stretches per batch the device route 
 // stretches of i.i.d. sequence, and a first sketch -- no density is known yet -- must not run out of room and go round again
 constexpr uint32_t GAP_DEV_CAP_MAX = 65536;
 // Their minimizers wait in one pool per batch, each stretch's in a region of the size it needs (k_gap_fix reserves it with one
-// add to ctrl[14]; r_start[stretch]).  Until round 4 every stretch had a region of 64 entries: a di- or trinucleotide run longer
+// add to CW_REGION_ENTRIES; r_start[stretch]).  Until round 4 every stretch had a region of 64 entries: a di- or trinucleotide run longer
 // than w reports every second or third k-mer, and each such stretch went to the host and through the dense kernels.  A pool that
 // runs out (a batch whose stretches hold more than four million minimizers) hands the stretch to the host like any other it
 // cannot keep.
@@ -1078,10 +1079,10 @@ struct EmitParams {
     const uint32_t *ovf;   // see ResolveParams
     const uint32_t *bsum;  // dense path: exclusive offsets per 1024-tile (k_count_n + k_scan_sums); sparse path: nullptr,
     const uint32_t *cnt256, *sel_sup;  // ... offsets come from k_resolve's two-level counts
-    uint32_t *n_sel;       // sparse path: ctrl[2..3], written by the tile that holds the last candidate
+    uint32_t *n_sel;       // sparse path: CW_SELECTED, written by the tile that holds the last candidate
     uint32_t *n_out;       // sparse path, optional: a second device word that receives the total (fused sketch+graph call)
-    uint32_t *host_ctrl;   // sparse path: pinned host copy of the control block (8 words), written by that tile too:
-                           // no copy on the stream, the host reads it after the stream has drained
+    uint32_t *host_ctrl;   // sparse path: the batch's host report (batch_ctrl.h), written by that tile too: no copy on the
+                           // stream, the host reads it after the stream has drained
     const Run *runs;
     const uint32_t *ctg_run0, *ctg_rec;
     const uint4 *ctg_info; // {first run, runs, first run's pos0, record} per contig, or null (virtual contigs): ctg_run0 -> runs -> ctg_rec
@@ -1133,19 +1134,19 @@ __global__ __launch_bounds__(256) void k_emit(const EmitParams p)
     __shared__ uint32_t sh[256];
     const uint32_t RKe = p.rk;  // entries per producer block
     const uint32_t n = p.n_fixed ? p.n_fixed : min(*p.n_ptr, p.n_cap);
-    const uint32_t n_g_raw = p.ovf[1];
-    if (*p.ovf || n == 0) {  // arena overflow (the host redoes the batch) or no candidate at all: only report
-        if (p.host_ctrl && blockIdx.x == 0 && threadIdx.x < 16)
-            p.host_ctrl[threadIdx.x] = threadIdx.x == 0 ? *p.ovf : (threadIdx.x == 1 ? n_g_raw : 0u);
+    const uint32_t n_g_raw = p.ovf[CW_STRETCHES];
+    if (p.ovf[CW_ARENA_NEED] || n == 0) {  // arena overflow (the host redoes the batch) or no candidate at all: only report
+        if (p.host_ctrl && blockIdx.x == 0 && threadIdx.x < REPORT_WORDS)
+            p.host_ctrl[threadIdx.x] = threadIdx.x == RW_ARENA_NEED ? p.ovf[CW_ARENA_NEED] : (threadIdx.x == RW_STRETCHES ? n_g_raw : 0u);
         if (p.base_out && blockIdx.x == 0 && threadIdx.x == 0) *p.base_out = p.base_in ? *p.base_in : 0ull;
         return;
     }
     // stretches sketched on the device: count, their minimizers, "could not be finished here" (the host then redoes the batch)
     // (k_bs_select raises it too: slices beyond their queues / regions, more selected candidates than a slice's room)
     // (... and more stretches than this launch has blocks to place them: the grid follows what earlier sketches of the assembly met)
-    const uint32_t flag = ((p.dev_gaps || p.n_fixed) ? p.ovf[6] : 0u) | ((p.dev_gaps && n_g_raw > 4u * p.n_place && n_g_raw <= p.gcap) ? 1u : 0u);
+    const uint32_t flag = ((p.dev_gaps || p.n_fixed) ? p.ovf[CW_REDO] : 0u) | ((p.dev_gaps && n_g_raw > 4u * p.n_place && n_g_raw <= p.gcap) ? 1u : 0u);
     const uint32_t n_g = p.dev_gaps && !flag && n_g_raw <= p.gcap ? n_g_raw : 0u;
-    const uint32_t nB = n_g ? p.ovf[7] : 0u;
+    const uint32_t nB = n_g ? p.ovf[CW_STRETCH_MX] : 0u;
     const uint64_t obase = p.out_base + (p.base_in ? *p.base_in : 0ull), limit = p.out_limit;
     const uint32_t n_place = p.dev_gaps ? p.n_place : 0u;  // the grid's FIRST blocks: they start at once
     if (blockIdx.x < n_place) {  // placement of the stretches' minimizers: one wave per stretch
@@ -1223,20 +1224,21 @@ __global__ __launch_bounds__(256) void k_emit(const EmitParams p)
                 if (threadIdx.x == 0) {
                     p.n_sel[0] = all;
                     p.n_sel[1] = 0;
-                    if (p.cand_spread) {  // (ctrl[4..5]: the candidate count, where the other route's reorder kernel leaves it)
-                        p.n_sel[2] = n_report;
-                        p.n_sel[3] = 0;
+                    if (p.cand_spread) {  // (CW_CAND: the candidate count, where the other route's reorder kernel leaves it)
+                        p.n_sel[CW_CAND - CW_SELECTED] = n_report;
+                        p.n_sel[CW_CAND - CW_SELECTED + 1] = 0;
                     }
                     if (p.n_out) *p.n_out = (uint32_t)(obase + total);
                     if (p.base_out) *p.base_out = obase + total;
                 }
-                if (p.host_ctrl && threadIdx.x < 16) {  // layout: see HostCtrl
+                if (p.host_ctrl && threadIdx.x < REPORT_WORDS) {
                     const uint32_t w = threadIdx.x;
-                    p.host_ctrl[w] = w == 1 ? n_g_raw : w == 2 ? all : w == 3 ? flag : w == 4 ? n_report : w == 5 ? nB
-                                   : w == 6 ? (uint32_t)total : w == 7 ? (uint32_t)(total >> 32)
-                                   : w == 8 ? (uint32_t)obase : w == 9 ? (uint32_t)(obase >> 32)
-                                   : (w == 10 && p.dev_gaps) ? p.ovf[10] : (w == 11 && p.dev_gaps && !flag) ? p.ovf[11] : w == 12 ? p.ovf[13]
-                                   : (w == 15 && p.n_fixed) ? p.ovf[15] : 0u;  // ([15]: the stretches k_sel_stretch was asked for)
+                    p.host_ctrl[w] = w == RW_STRETCHES ? n_g_raw : w == RW_SELECTED ? all : w == RW_REDO ? flag : w == RW_CAND ? n_report
+                                   : w == RW_STRETCH_MX ? nB : w == RW_TOTAL ? (uint32_t)total : w == RW_TOTAL + 1 ? (uint32_t)(total >> 32)
+                                   : w == RW_OUT_BASE ? (uint32_t)obase : w == RW_OUT_BASE + 1 ? (uint32_t)(obase >> 32)
+                                   : (w == RW_GAP_KMERS && p.dev_gaps) ? p.ovf[CW_GAP_KMERS]
+                                   : (w == RW_DEFERRED && p.dev_gaps && !flag) ? p.ovf[CW_DEFERRED]
+                                   : w == RW_SLICE_GAVE_UP ? p.ovf[CW_SLICE_GAVE_UP] : (w == RW_SEL_REQS && p.n_fixed) ? p.ovf[CW_SEL_REQS] : 0u;
                 }
             }
         }
@@ -1402,12 +1404,12 @@ __global__ __launch_bounds__(256) void k_merge(const MergeParams p)
 //                stretch minimizers before each; a few extra blocks put the stretches' minimizers in between; reports
 // Anything this route cannot hold -- more than GAP_DEV_MAX stretches, a stretch longer than GAP_DEV_NMAX k-mers or with more
 // invalid bases inside than the block's words take, minimizers beyond the batch's pool -- is left out here: more than
-// GAP_DEV_MAX stretches raise ctrl[6] and the host redoes the batch; single stretches are handed to the host (defer_stretch).
+// GAP_DEV_MAX stretches raise CW_REDO and the host redoes the batch; single stretches are handed to the host (defer_stretch).
 constexpr uint32_t GAP_DEV_NMAX = 4096;
 
 struct GapFixParams {
     const uint4 *gaps;   // {contig, k_lo, k_hi, reporting candidate} in arrival order (k_resolve)
-    uint32_t *ctrl;      // [1] stretches, [6] "host must redo", [10] k-mers hashed here
+    uint32_t *ctrl;      // reads CW_STRETCHES, CW_ARENA_NEED; counts CW_GAP_KMERS, CW_REGION_ENTRIES, CW_DEFERRED; raises CW_REDO
     const Run *runs;
     const uint32_t *ctg_run0, *ctg_rec;
     const uint8_t *ctg_drop;
@@ -1422,7 +1424,7 @@ struct GapFixParams {
     uint32_t pool;       // entries of the pool (GAP_DEV_POOL; MXG_GAP_POOL: test knob)
     uint32_t gcap;       // stretches the per-stretch arrays hold
     uint64_t *r_key;     // [GAP_DEV_MAX] contig << 32 | k_lo
-    uint4 *defer;        // [GAP_DEFER_MAX] (pinned host memory) stretches left to the host: ctrl[11] of them
+    uint4 *defer;        // [GAP_DEFER_MAX] (pinned host memory) stretches left to the host: CW_DEFERRED of them
     HashTab tab;
 };
 
@@ -1431,9 +1433,9 @@ struct GapFixParams {
 // and merges its minimizers into the assembly's sketch (Driver::merge_deferred).  One thread of the block calls this.
 __device__ __forceinline__ void defer_stretch(const GapFixParams &p, const uint4 gp)
 {
-    const uint32_t at = atomicAdd(&p.ctrl[11], 1u);
+    const uint32_t at = atomicAdd(&p.ctrl[CW_DEFERRED], 1u);
     if (at < GAP_DEFER_MAX) p.defer[at] = gp;
-    else p.ctrl[6] = 1;
+    else p.ctrl[CW_REDO] = 1;
 }
 
 // One stretch by one block of 256 threads.  The work arrays are the caller's: LDS for the common stretches (k_gap_fix, at
@@ -1547,8 +1549,8 @@ __device__ __forceinline__ void gap_fix_one(const GapFixParams &p, const uint32_
     for (uint32_t i = i0; i < i1 && i0 < n; ++i) cnt += (selbits[i >> 5] >> (i & 31u)) & 1u;
     uint32_t o = block_exclusive_256(cnt, sh);
     const uint32_t total = sh[255];
-    if (threadIdx.x == 0) atomicAdd(&p.ctrl[10], n);
-    if (threadIdx.x == 0) sh[0] = total ? atomicAdd(&p.ctrl[14], total) : 0u;  // (sh: the scan is done with it)
+    if (threadIdx.x == 0) atomicAdd(&p.ctrl[CW_GAP_KMERS], n);
+    if (threadIdx.x == 0) sh[0] = total ? atomicAdd(&p.ctrl[CW_REGION_ENTRIES], total) : 0u;  // (sh: the scan is done with it)
     __syncthreads();
     const uint32_t region = sh[0];
     __syncthreads();
@@ -1578,8 +1580,8 @@ __global__ __launch_bounds__(256) void k_gap_fix(const GapFixParams p)
 {
     // GAP_FIX_BLOCKS blocks walk the stretches (a block of 51 KB per possible stretch -- 2048, nearly all with nothing to do -- came
     // to the CUs in three rounds: 36 us per launch beside the other stream's kernels)
-    const uint32_t n_g = p.ctrl[1];
-    if (blockIdx.x >= n_g || n_g > p.gcap || p.ctrl[0]) return;
+    const uint32_t n_g = p.ctrl[CW_STRETCHES];
+    if (blockIdx.x >= n_g || n_g > p.gcap || p.ctrl[CW_ARENA_NEED]) return;
     __shared__ uint64_t lh[GAP_DEV_NSMALL];
     __shared__ uint16_t lidx[2][GAP_DEV_NSMALL];
     __shared__ uint32_t selbits[GAP_DEV_NSMALL / 32];
@@ -1603,7 +1605,7 @@ __global__ __launch_bounds__(256) void k_gap_fix(const GapFixParams p)
 }
 
 struct GapPostParams {
-    uint32_t *ctrl;  // [1] stretches, [6] flag, [7] <- minimizers found in them
+    uint32_t *ctrl;  // reads CW_STRETCHES, CW_ARENA_NEED; raises CW_REDO; CW_STRETCH_MX <- minimizers found in them
     const uint32_t *r_cnt; const uint64_t *r_key;
     // the stretches in (contig, first k-mer) order: key, minimizers in the stretches before it ([n] = all), index of its region
     uint64_t *s_key; uint32_t *s_off, *s_src;
@@ -1624,11 +1626,11 @@ __global__ __launch_bounds__(GPB) void k_gap_post(const GapPostParams p)
     __shared__ uint64_t keys[CH];
     __shared__ uint32_t cnts[CH];
     __shared__ uint32_t part_rank[GPB], part_off[GPB];
-    const uint32_t n_g = p.ctrl[1];
-    if (n_g == 0 || n_g > p.gcap || p.ctrl[0]) {
+    const uint32_t n_g = p.ctrl[CW_STRETCHES];
+    if (n_g == 0 || n_g > p.gcap || p.ctrl[CW_ARENA_NEED]) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
-            p.ctrl[7] = 0;
-            if (n_g > p.gcap) p.ctrl[6] = 1;
+            p.ctrl[CW_STRETCH_MX] = 0;
+            if (n_g > p.gcap) p.ctrl[CW_REDO] = 1;
         }
         return;
     }
@@ -1679,7 +1681,7 @@ __global__ __launch_bounds__(GPB) void k_gap_post(const GapPostParams p)
             __syncthreads();
         }
         if (threadIdx.x == 0) {
-            p.ctrl[7] = part_rank[0];
+            p.ctrl[CW_STRETCH_MX] = part_rank[0];
             p.s_off[n_g] = part_rank[0];
         }
     }
@@ -1825,11 +1827,6 @@ __global__ __launch_bounds__(256) void k_stretch_tiles(const StretchParams p)
         }
 }
 
-// Pinned host copy of a batch's control block (16 words), written by the batch's last kernel:
-// [0] largest wave count if a wave overflowed its arena slice, [1] candidate-free stretches, [2] minimizers among the
-// candidates, [3] "the device route could not finish the stretches", [4] candidates, [5] minimizers inside stretches,
-// [6..7] minimizers of the batch, [8..9] where the batch starts in the assembly's sketch, [10] k-mers hashed by k_gap_fix,
-// [11] stretches left to the host (their {contig, first, last k-mer} in the batch's slice of pinned_defer)
 // ------------------------------------------------------------------------------------------------------
 // host driver
 // ------------------------------------------------------------------------------------------------------
@@ -1920,6 +1917,11 @@ struct OutArrays {
     uint64_t n = 0;
     uint64_t cap() const { return std::min<uint64_t>({hash->bytes / 8, pos->bytes / 4, rec->bytes / 4, fwd->bytes}); }
 };
+// minimizers an assembly's output arrays hold
+static uint64_t out_capacity(const Assembly *a)
+{
+    return std::min<uint64_t>({a->d_hash.bytes / 8, a->d_pos.bytes / 4, a->d_rec.bytes / 4, a->d_fwd.bytes});
+}
 
 static int out_reserve(mxg_handle *h, OutArrays &o, uint64_t need, hipStream_t st)
 {
@@ -1943,13 +1945,26 @@ static void build_strip_tables(const std::vector<Run> &runs, int S, std::vector<
     if (s >= (1ull << 32)) *overflow = true;
 }
 
-// pinned host copies of the batches' control blocks: 16 words each; the last slot belongs to the synchronous path
+// pinned slots for the batches' host reports (batch_ctrl.h), each with a list of the stretches its batch deferred to the host;
+// the last slot belongs to the synchronous path
 constexpr uint32_t PINNED_SLOTS = 1024;
 static int ensure_pinned_ctrl(mxg_handle *h)
 {
-    if (!h->pinned_ctrl) MXG_HIP(h, hipHostMalloc((void **)&h->pinned_ctrl, (size_t)PINNED_SLOTS * 64));
+    if (!h->pinned_ctrl) MXG_HIP(h, hipHostMalloc((void **)&h->pinned_ctrl, (size_t)PINNED_SLOTS * REPORT_BYTES));
     if (!h->pinned_defer) MXG_HIP(h, hipHostMalloc((void **)&h->pinned_defer, (size_t)PINNED_SLOTS * GAP_DEFER_MAX * 16));
     return MXG_OK;
+}
+static uint32_t *report_slot(const mxg_handle *h, size_t i) { return h->pinned_ctrl + REPORT_WORDS * i; }
+// the deferred list that goes with the report at `report`
+static uint4 *deferred_list(const mxg_handle *h, const uint32_t *report)
+{
+    return reinterpret_cast<uint4 *>(h->pinned_defer) + (size_t)((report - h->pinned_ctrl) / REPORT_WORDS) * GAP_DEFER_MAX;
+}
+// appends the stretches the batch of `report` deferred to the host
+static void take_deferred(const mxg_handle *h, const uint32_t *report, std::vector<uint4> &out)
+{
+    const uint4 *src = deferred_list(h, report);
+    out.insert(out.end(), src, src + std::min(BatchReport{report}.n_deferred(), GAP_DEFER_MAX));
 }
 
 struct Driver {
@@ -1974,9 +1989,8 @@ struct Driver {
     }
     double gap_expect = -1.0;  // stretches the plan expects of the batch for the stretch kernels (< 0: not known)
 
-    // SC_CTRL holds the control block (16 words) followed by the two super-count arrays of the batch (scan_kernels.h):
+    // SC_CTRL holds the device control block (CTRL_WORDS) followed by the two super-count arrays of the batch (scan_kernels.h):
     // per hash-kernel wave, then per k_resolve block; ctrl_bytes() of it are zeroed by the batch's one memset
-    static constexpr uint32_t CTRL_WORDS = 16;
     uint32_t n_wave_sup = 0;
     uint32_t *wave_sup() { return sc(SC_CTRL).as<uint32_t>() + CTRL_WORDS; }
     uint32_t *sel_sup(uint32_t) { return wave_sup() + n_wave_sup; }
@@ -2024,20 +2038,15 @@ struct Driver {
         return b;
     }
 
-    // sparse path: resolve + gap detection + per-256 counts (SC_CNT256 + super-counts behind the control block) in ONE
-    // launch; emit(..., true) turns them into offsets, places the minimizers and writes the total to ctrl[2..3]
-    int resolve_count(const Tables &T, uint32_t n_cap, uint32_t ctg_lo, uint32_t ctg_hi, uint64_t tau, uint32_t n_likely)
+    // k_resolve's parameters on both paths, without the fused count (SC_SEL must hold n_cap flags)
+    ResolveParams resolve_params(const Tables &T, uint32_t n_cap, uint32_t ctg_lo, uint32_t ctg_hi, uint64_t tau)
     {
-        if (!n_cap) return MXG_OK;
-        MXG_HIP(h, sc(SC_SEL).ensure(std::max<uint32_t>(n_cap, 16)));
-        const uint32_t blocks = ((grid_cand ? std::min(grid_cand, n_cap) : n_cap) + RK - 1) / RK;
-        MXG_HIP(h, sc(SC_CNT256).ensure((size_t)blocks * 4 + 64));
         uint32_t *ctrl = sc(SC_CTRL).as<uint32_t>();
         ResolveParams rp;
         rp.ch = sc(SC_CAND_H).as<uint64_t>();
         rp.ck = sc(SC_CAND_K).as<uint32_t>();
         rp.cc = sc(SC_CAND_C).as<uint32_t>();
-        rp.n_ptr = ctrl + 4;
+        rp.n_ptr = ctrl + CW_CAND;
         rp.n_cap = n_cap;
         rp.n_likely = 0;
         rp.ovf = ctrl;
@@ -2050,7 +2059,23 @@ struct Driver {
         rp.ctg_hi = ctg_hi;
         rp.gaps = sc(SC_GAPS).as<uint4>();
         rp.gap_cap = GAP_CAP;
-        rp.gap_count = ctrl + 1;
+        rp.gap_count = ctrl + CW_STRETCHES;
+        rp.cnt256 = nullptr;
+        rp.sel_sup = nullptr;
+        rp.cs_h = nullptr;
+        rp.cs_k = rp.cs_c = nullptr;
+        return rp;
+    }
+
+    // sparse path: resolve + gap detection + per-256 counts (SC_CNT256 + super-counts behind the control block) in ONE
+    // launch; emit(..., true) turns them into offsets, places the minimizers and writes the total to CW_SELECTED
+    int resolve_count(const Tables &T, uint32_t n_cap, uint32_t ctg_lo, uint32_t ctg_hi, uint64_t tau, uint32_t n_likely)
+    {
+        if (!n_cap) return MXG_OK;
+        MXG_HIP(h, sc(SC_SEL).ensure(std::max<uint32_t>(n_cap, 16)));
+        const uint32_t blocks = ((grid_cand ? std::min(grid_cand, n_cap) : n_cap) + RK - 1) / RK;
+        MXG_HIP(h, sc(SC_CNT256).ensure((size_t)blocks * 4 + 64));
+        ResolveParams rp = resolve_params(T, n_cap, ctg_lo, ctg_hi, tau);
         rp.cnt256 = sc(SC_CNT256).as<uint32_t>();
         rp.sel_sup = sel_sup(n_cap);
         MXG_HIP(h, sc(SC_CS_H).ensure((size_t)blocks * RK * 8));
@@ -2075,43 +2100,21 @@ struct Driver {
         return MXG_OK;
     }
 
-    // resolve -> count -> scan over candidates already in SC_CAND_*; n candidates read from ctrl[4] (<= n_cap)
+    // resolve -> count -> scan over candidates already in SC_CAND_*; n candidates read from CW_CAND (<= n_cap)
     template <bool GAPS>
     int resolve_and_count(const Tables &T, uint32_t n_cap, uint32_t ctg_lo, uint32_t ctg_hi, uint64_t tau)
     {
         const uint32_t n_tiles = (n_cap + TILE - 1) / TILE;
         MXG_HIP(h, sc(SC_SEL).ensure(std::max<uint32_t>(n_cap, 16)));
         MXG_HIP(h, sc(SC_BSUM).ensure((size_t)n_tiles * 4 + 16));
-        uint32_t *ctrl = sc(SC_CTRL).as<uint32_t>();
-        ResolveParams rp;
-        rp.ch = sc(SC_CAND_H).as<uint64_t>();
-        rp.ck = sc(SC_CAND_K).as<uint32_t>();
-        rp.cc = sc(SC_CAND_C).as<uint32_t>();
-        rp.n_ptr = ctrl + 4;
-        rp.n_cap = n_cap;
-        rp.n_likely = 0;
-        rp.ovf = ctrl;
-        rp.tau = tau;
-        rp.ctg_nk = T.d_ctg_nk;
-        rp.ctg_drop = T.d_ctg_drop;
-        rp.w = h->cfg.w;
-        rp.sel = sc(SC_SEL).as<uint8_t>();
-        rp.ctg_lo = ctg_lo;
-        rp.ctg_hi = ctg_hi;
-        rp.gaps = sc(SC_GAPS).as<uint4>();
-        rp.gap_cap = GAP_CAP;
-        rp.gap_count = ctrl + 1;
-        rp.cnt256 = nullptr;
-        rp.sel_sup = nullptr;
-        rp.cs_h = nullptr;
-        rp.cs_k = rp.cs_c = nullptr;
+        const ResolveParams rp = resolve_params(T, n_cap, ctg_lo, ctg_hi, tau);
         if (n_cap) {
             hipLaunchKernelGGL((k_resolve<GAPS, false>), dim3((n_cap + RK - 1) / RK), dim3(RK), 0, st, rp);
             hipLaunchKernelGGL(k_count_n, dim3(n_tiles), dim3(256), 0, st, rp.sel, rp.n_ptr, n_cap,
                                sc(SC_BSUM).as<uint32_t>());
         }
         hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, sc(SC_BSUM).as<uint32_t>(), n_tiles,
-                           reinterpret_cast<uint64_t *>(ctrl + 2));
+                           reinterpret_cast<uint64_t *>(sc(SC_CTRL).as<uint32_t>() + CW_SELECTED));
         MXG_HIP(h, hipGetLastError());
         return MXG_OK;
     }
@@ -2136,20 +2139,20 @@ struct Driver {
              uint64_t out_base, bool fused = false, uint32_t *host_ctrl = nullptr, const ChainIO *io = nullptr,
              uint32_t rk = RK, uint32_t n_fixed = 0, const uint32_t *cand_spread = nullptr)
     {
-        const uint64_t limit = std::min<uint64_t>({oh.bytes / 8, op.bytes / 4, orc.bytes / 4, of.bytes});
+        const uint64_t limit = OutArrays{&oh, &op, &orc, &of}.cap();
         if (!n_cap) return MXG_OK;
         EmitParams ep;
         ep.sel = sc(SC_SEL).as<uint8_t>();
         ep.ch = sc(SC_CAND_H).as<uint64_t>();
         ep.ck = sc(SC_CAND_K).as<uint32_t>();
         ep.cc = sc(SC_CAND_C).as<uint32_t>();
-        ep.n_ptr = sc(SC_CTRL).as<uint32_t>() + 4;
+        ep.n_ptr = sc(SC_CTRL).as<uint32_t>() + CW_CAND;
         ep.ovf = sc(SC_CTRL).as<uint32_t>();
         ep.n_cap = n_cap;
         ep.bsum = fused ? nullptr : sc(SC_BSUM).as<uint32_t>();
         ep.cnt256 = fused ? sc(SC_CNT256).as<uint32_t>() : nullptr;
         ep.sel_sup = fused ? sel_sup(n_cap) : nullptr;
-        ep.n_sel = sc(SC_CTRL).as<uint32_t>() + 2;
+        ep.n_sel = sc(SC_CTRL).as<uint32_t>() + CW_SELECTED;
         ep.host_ctrl = host_ctrl;
         ep.n_out = host_ctrl ? n_out : nullptr;
         ep.runs = T.d_runs;
@@ -2224,8 +2227,9 @@ struct Driver {
             MXG_HIP(h, sc(SC_CAND_K).ensure(nk * 4));
             MXG_HIP(h, sc(SC_CAND_C).ensure(nk * 4));
             const uint32_t n_cand = (uint32_t)nk;
-            uint32_t ctrl_init[8] = {0, 0, 0, 0, n_cand, 0, 0, 0};
-            MXG_HIP(h, hipMemcpyAsync(sc(SC_CTRL).p, ctrl_init, 32, hipMemcpyHostToDevice, st));
+            uint32_t ctrl_init[8] = {};
+            ctrl_init[CW_CAND] = n_cand;
+            MXG_HIP(h, hipMemcpyAsync(sc(SC_CTRL).p, ctrl_init, sizeof(ctrl_init), hipMemcpyHostToDevice, st));
             DenseParams hp;
             hp.packed = d_packed;
             hp.runs = T.d_runs;
@@ -2255,10 +2259,9 @@ struct Driver {
             MXG_HIP(h, hipGetLastError());
             if ((rc = resolve_and_count<false>(T, n_cand, (uint32_t)c0, (uint32_t)c1, ~0ull)) != MXG_OK) return rc;
             if (!count_as_hash && (rc = ev_end()) != MXG_OK) return rc;
-            uint32_t ctrl[4];
-            MXG_HIP(h, hipMemcpyAsync(ctrl, sc(SC_CTRL).p, 16, hipMemcpyDeviceToHost, st));
+            uint64_t total = 0;
+            MXG_HIP(h, hipMemcpyAsync(&total, sc(SC_CTRL).as<uint32_t>() + CW_SELECTED, 8, hipMemcpyDeviceToHost, st));
             MXG_HIP(h, hipStreamSynchronize(st));
-            const uint64_t total = (uint64_t)ctrl[2] | ((uint64_t)ctrl[3] << 32);
             if ((rc = out_reserve(h, out, out.n + total, st)) != MXG_OK) return rc;
             if ((rc = emit(d_packed, T, n_cand, *out.hash, *out.pos, *out.rec, *out.fwd, out.n)) != MXG_OK) return rc;
             out.n += total;
@@ -2380,11 +2383,11 @@ struct Driver {
         return wave_cap;
     }
     // Enqueue one batch completely (hash -> order -> resolve+count -> speculative emit at out.n); the last kernel writes
-    // the control block to `ctrl_host` (PINNED host memory); NO host sync.  *n_cap_out = capacity the candidate arrays were sized for.
+    // the batch's report to `ctrl_host` (a pinned slot); NO host sync.  *n_cap_out = capacity the candidate arrays were sized for.
     // grid of the hash kernel: one block per tile of 256 strips (a few persistent blocks per CU with an equal number of tiles each
     // were an experiment of round 2, measured and dropped)
     uint32_t sparse_grid(uint32_t n_tiles, uint64_t) const { return n_tiles; }
-    // stretches sketched on the device, one block each (results wait in their regions for k_gap_post): reads SC_GAPS / ctrl[1]
+    // stretches sketched on the device, one block each (results wait in their regions for k_gap_post): reads SC_GAPS / CW_STRETCHES
     int enqueue_dev_gaps(Assembly *a, const Tables &T, const uint32_t *ctrl_host)
     {
         MXG_HIP(h, sc(SC_GR_HASH).ensure((size_t)GAP_DEV_POOL * 8));
@@ -2415,8 +2418,7 @@ struct Driver {
         gp.gcap = gcap;
         gp.pool = (uint32_t)std::min<uint64_t>(env_u64(h, "MXG_GAP_POOL", GAP_DEV_POOL), GAP_DEV_POOL);
         gp.r_key = sc(SC_GR_KEY).as<uint64_t>();
-        // the batch's slice of the pinned list of deferred stretches goes with its pinned control block
-        gp.defer = reinterpret_cast<uint4 *>(h->pinned_defer) + (size_t)((ctrl_host - h->pinned_ctrl) / 16) * GAP_DEFER_MAX;
+        gp.defer = deferred_list(h, ctrl_host);
         gp.tab = h->tab;
         // (no more blocks than the launch expects stretches -- what k_emit has placing blocks for: a block of 51 KB that finds
         // nothing to do still has to be brought to a CU, 22 us for 768 of them behind k_sel_stretch, which leaves few stretches over)
@@ -2551,7 +2553,7 @@ struct Driver {
         op.n_strips = g.n_strips;
         op.wave_tot = sp.wave_tot;
         op.wave_sup = sp.wave_sup;
-        op.n_cand = sp.ctrl + 4;
+        op.n_cand = sp.ctrl + CW_CAND;
         op.strip_meta = bs_bitmap ? T.d_strip_run : sp.strip_meta;
         op.runs = sp.runs;
         op.run_strip0 = sp.run_strip0;
@@ -2676,7 +2678,7 @@ struct Driver {
         bp.ovf_e = sc(SC_CAND_K).as<uint32_t>();
         bp.ovf_cap = b.ovf_cap;
         bp.n_ovf = b.n_ovf;
-        bp.ovf_next = sc(SC_CTRL).as<uint32_t>() + 12;
+        bp.ovf_next = sc(SC_CTRL).as<uint32_t>() + CW_REGION_TICKET;
         bp.rk = b.rk;
         bp.cs = sc(SC_CS_H).as<uint4>();
         bp.cnt = sc(SC_CNT256).as<uint32_t>();
@@ -2775,15 +2777,15 @@ struct Driver {
         return f(behind);
     }
 
-    // Second half of a sparse batch, after the host has read the control block `ctrl` of a run that did not overflow:
+    // Second half of a sparse batch, after the host has read the report `r` of a run that did not overflow:
     // accept the speculative emit, or (candidate-free stretches) emit to staging, run the dense fix-up, merge.
     // The candidate arrays of that run must still be intact in this driver's scratch.
-    int complete_batch(Assembly *a, const Tables &T, const BatchGeom &g, OutArrays &out, const uint32_t *ctrl, uint32_t n_cap)
+    int complete_batch(Assembly *a, const Tables &T, const BatchGeom &g, OutArrays &out, const BatchReport r, uint32_t n_cap)
     {
         const size_t c0 = g.c0, c1 = g.c1;
-        const uint64_t n_cand = ctrl[4];  // (layout: FinParams)
-        uint32_t n_gaps = ctrl[1];
-        const uint64_t total = ctrl[2];
+        const uint64_t n_cand = r.n_cand();
+        uint32_t n_gaps = r.n_stretches();
+        const uint64_t total = r.n_selected();
         h->stat_candidates += n_cand;
         a->cand_hint = (uint32_t)std::min<uint64_t>(n_cand, 0xFFFFFFFFull);
         int rc;
@@ -2971,23 +2973,24 @@ struct Driver {
             uint64_t wave_cap = default_wave_cap(S, cand_frac);
             int rcp = ensure_pinned_ctrl(h);
             if (rcp != MXG_OK) return rcp;
-            uint32_t *const ctrl = h->pinned_ctrl + 16 * (PINNED_SLOTS - 1);  // the slot of the synchronous path
+            uint32_t *const ctrl = report_slot(h, PINNED_SLOTS - 1);  // the slot of the synchronous path
+            const BatchReport r{ctrl};
             uint64_t n_cap64 = 0;
             for (int attempt = 0;; ++attempt) {
                 uint32_t n_cap_now = 0;
-                memset(ctrl, 0xFF, 64);
+                std::fill_n(ctrl, REPORT_WORDS, REPORT_UNSET);
                 int rc = enqueue_sparse(a, T, g, wave_cap, tau_hi, out, ctrl, &n_cap_now);
                 if (rc != MXG_OK) return rc;
                 n_cap64 = n_cap_now;
                 MXG_HIP(h, stream_wait(st));
-                if (ctrl[0] == 0) break;  // no wave overflowed its slice
+                if (r.arena_need() == 0) break;  // no wave overflowed its slice
                 if (attempt >= 2) return set_err(h, MXG_EDEVICE, "internal error: candidate arena keeps overflowing");
-                wave_cap = std::min<uint64_t>((uint64_t)ctrl[0] + 64, 64ull * S);  // exact need is known: redo the batch
+                wave_cap = std::min<uint64_t>((uint64_t)r.arena_need() + 64, 64ull * S);  // exact need is known: redo the batch
                 h->arena_cap_hint = wave_cap;
             }
-            uint32_t ctrl_copy[16];
-            memcpy(ctrl_copy, ctrl, 64);
-            int rcb = complete_batch(a, T, g, out, ctrl_copy, (uint32_t)n_cap64);
+            uint32_t ctrl_copy[REPORT_WORDS];
+            std::copy_n(ctrl, REPORT_WORDS, ctrl_copy);
+            int rcb = complete_batch(a, T, g, out, BatchReport{ctrl_copy}, (uint32_t)n_cap64);
             if (rcb != MXG_OK) return rcb;
             c0 = c1;
         }
@@ -3251,8 +3254,8 @@ int sketch_assembly(mxg_handle *h, Assembly *a)
 }
 
 // xchg_pack's kernel with everything read on the device: the sketch may still be in flight on the stream.  The header
-// says -1 (the caller exchanges sizes first) unless the batch ended the common way -- no arena overflow, no
-// candidate-free stretch, at least one candidate -- and the sketch fits the slot and the output arrays.
+// says -1 (the caller exchanges sizes first) unless the batch ended the common way (batch_ended_well) and the sketch fits
+// the slot and the output arrays.
 __global__ __launch_bounds__(256) void k_pack_slot_dev(const uint64_t *__restrict__ hash, const uint32_t *__restrict__ pos,
                                                        const uint32_t *__restrict__ rec, const uint32_t *__restrict__ n_ptr,
                                                        const uint32_t *__restrict__ ctrl, uint64_t out_cap, uint64_t cap,
@@ -3265,12 +3268,7 @@ __global__ __launch_bounds__(256) void k_pack_slot_dev(const uint64_t *__restric
         return;
     }
     const uint64_t n = *n_ptr;
-    // the same predicate as sketch_finish's (batch_ended_well): no arena overflow, no flag from the stretch kernels (word 6) or from
-    // the slice kernel (word 13: a slice gave up), stretches either absent or -- on the device route -- all placed (none deferred,
-    // and no more of them than k_emit's launch had placing blocks for: k_emit then places none and tells the host through ITS
-    // word 3 only, which this kernel does not see)
-    const bool ok = ctrl[0] == 0 && ctrl[6] == 0 && ctrl[13] == 0 && (dev_gaps ? (ctrl[11] == 0 && ctrl[1] <= place4) : ctrl[1] == 0) && (ctrl[4] | ctrl[5]) != 0 &&
-                    n <= cap && n <= out_cap;
+    const bool ok = batch_ended_well(ctrl, dev_gaps, place4) && n <= cap && n <= out_cap;
     if (i == 0) *header = ok ? (long long)n : -1ll;
     if (!ok || i >= n) return;
     reinterpret_cast<uint64_t *>(region)[i] = hash[i];
@@ -3297,8 +3295,7 @@ __global__ __launch_bounds__(256) void k_pack_part_dev(const uint64_t *__restric
         return;
     }
     const uint64_t n = *n_ptr;
-    const bool ok = ctrl[0] == 0 && ctrl[6] == 0 && ctrl[13] == 0 && (dev_gaps ? (ctrl[11] == 0 && ctrl[1] <= place4) : ctrl[1] == 0) && (ctrl[4] | ctrl[5]) != 0 &&
-                    n <= cap && n <= out_cap && n_rec <= rcap;
+    const bool ok = batch_ended_well(ctrl, dev_gaps, place4) && n <= cap && n <= out_cap && n_rec <= rcap;
     if (i == 0) {
         header[0] = ok ? (long long)n : -1ll;
         header[1] = n_rec;
@@ -3373,7 +3370,7 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
         Driver::BatchGeom g;
         int slot;
         uint32_t n_cap;
-        uint32_t *hc;  // pinned control block
+        uint32_t *hc;  // the batch's report (pinned)
         bool bs;       // went through the k = 32 route (no candidate arrays to finish from)
         uint32_t place4 = 0;  // stretches the batch's k_emit launch has placing blocks for (4 * n_place)
     };
@@ -3507,8 +3504,8 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
             } else if (use_bs && drv.st != st_hash) {
                 MXG_HIP(h, hipStreamWaitEvent(drv.st, ev_hash, 0));
             }
-            it.hc = h->pinned_ctrl + 16 * items.size();
-            memset(it.hc, 0xFF, 64);
+            it.hc = report_slot(h, items.size());
+            std::fill_n(it.hc, REPORT_WORDS, REPORT_UNSET);
             Driver::ChainIO io;
             io.dev_gaps = plans[i].dev_gaps;
             {   // placing blocks for twice the stretches the plan expects of this batch (+ 256), at most for all the arrays hold; a
@@ -3564,7 +3561,7 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
     auto pack_part = [&](size_t i, hipStream_t st, Driver *drv, uint32_t place4) -> int {
         Assembly *a = list[i];
         if (xp->dg) {  // the partitioned graph stage's item slots instead of an exchange part
-            const uint64_t oc = std::min<uint64_t>({a->d_hash.bytes / 8, a->d_pos.bytes / 4, a->d_rec.bytes / 4, a->d_fwd.bytes});
+            const uint64_t oc = out_capacity(a);
             MXG_HIP(h, h->d_nmx.ensure(MXG_MAX_ASSEMBLIES * 4));
             const int rcd = dg_pack_slots_dev(h, a, (uint32_t)i, *xp->dg, st, state[i] == 1 ? 1u : (state[i] == 2 ? 0u : 2u),
                                               h->d_nmx.as<uint32_t>() + i, drv ? drv->sc(SC_CTRL).as<uint32_t>() : nullptr, oc,
@@ -3575,7 +3572,7 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
             return MXG_OK;
         }
         const uint64_t cap = xp->caps[i];
-        const uint64_t out_cap = std::min<uint64_t>({a->d_hash.bytes / 8, a->d_pos.bytes / 4, a->d_rec.bytes / 4, a->d_fwd.bytes});
+        const uint64_t out_cap = out_capacity(a);
         const long long fixed = state[i] == 1 ? -2ll : (state[i] == 2 ? 0ll : -1ll);
         const uint32_t grid = state[i] == 1 ? (uint32_t)std::max<uint64_t>((cap + 255) / 256, 1) : 1u;
         unsigned char *part = static_cast<unsigned char *>(xp->d_parts[i]);
@@ -3644,7 +3641,7 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
         for (size_t i = 0; !xp->d_parts && !xp->dg && i < n; ++i) {
             Assembly *a = list[i];
             const uint64_t cap = xp->caps[i];
-            const uint64_t out_cap = std::min<uint64_t>({a->d_hash.bytes / 8, a->d_pos.bytes / 4, a->d_rec.bytes / 4, a->d_fwd.bytes});
+            const uint64_t out_cap = out_capacity(a);
             const long long fixed = state[i] == 1 ? -2ll : (state[i] == 2 ? 0ll : -1ll);
             const uint32_t grid = state[i] == 1 ? (uint32_t)std::max<uint64_t>((cap + 255) / 256, 1) : 1u;
             hipLaunchKernelGGL(k_pack_slot_dev, dim3(grid), dim3(256), 0, h->stream, a->d_hash.as<uint64_t>(),
@@ -3673,7 +3670,7 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
             MXG_HIP(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
             for (size_t i = 0; i < n; ++i) {
                 Assembly *a = list[i];
-                const uint64_t cap = std::min<uint64_t>({a->d_hash.bytes / 8, a->d_pos.bytes / 4, a->d_rec.bytes / 4, a->d_fwd.bytes});
+                const uint64_t cap = out_capacity(a);
                 // (2 per window on i.i.d. sequence; repeat-rich sequence reaches ~3.8: what an earlier sketch of the assembly ended
                 // with, 10 % on top, so that the fused graph survives on exactly the inputs the output arrays were widened for)
                 const uint64_t iid = (uint64_t)(2.3 * (double)a->total_kmers / (double)(h->cfg.w + 1)) + 2048;
@@ -3692,44 +3689,36 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
     auto evaluate = [&](size_t i, bool final) -> int {
         Assembly *a = list[i];
         const size_t q0 = q_lo[i], q1 = q_hi[i];
-        const uint64_t cap = std::min<uint64_t>({a->d_hash.bytes / 8, a->d_pos.bytes / 4, a->d_rec.bytes / 4, a->d_fwd.bytes});
+        const uint64_t cap = out_capacity(a);
+        // (the one-call modes have already used the counts on the device: a stretch deferred to the host undoes them)
+        auto ended_well = [&](size_t q) { return BatchReport{items[q].hc}.ended_well(plans[i].dev_gaps, !chain_modes, items[q].bs); };
         bool good = true;
         uint64_t total = 0, n_cand = 0, gap_kmers = 0;
         for (size_t q = q0; q < q1; ++q) {
-            const uint32_t *c = items[q].hc;
-            const uint64_t t = (uint64_t)c[6] | ((uint64_t)c[7] << 32);
-            // (the one-call modes have already used the counts on the device: a stretch handed to the host undoes them)
-            const bool dev = plans[i].dev_gaps && !(chain_modes && c[11] != 0 && c[11] != 0xFFFFFFFFu);
-            // (not the device route: any stretch sends the batch to the general route below)
-            // (a batch without any candidate: k_bs_select reports its contigs as stretches; the other route leaves it to the host)
-            good = good && c[0] == 0 && c[3] == 0 && c[12] == 0 && (c[4] != 0 || items[q].bs) && c[4] != 0xFFFFFFFFu && (dev || c[1] == 0);
-            total += t;
-            n_cand += c[4];
-            gap_kmers += c[10] == 0xFFFFFFFFu ? 0 : c[10];
-            if (items[q].bs && c[15] != 0xFFFFFFFFu) h->stat_slice_stretches += c[15];
+            const BatchReport r{items[q].hc};
+            good = good && ended_well(q);
+            total += r.total();
+            n_cand += r.n_cand();
+            gap_kmers += r.gap_kmers();
+            if (items[q].bs) h->stat_slice_stretches += r.sel_requests();
+            // what the batches saw of candidate-free stretches sizes the next sketch's batches (sparse_plan): real genomes hold
+            // far more of them than the i.i.d. estimate (satellite arrays, low-complexity runs)
+            // (1e-12: "a sketch has reported" -- an assembly whose stretches all went through k_sel_stretch leaves none over)
+            if (r.reported() && items[q].g.nk) a->gap_rate_hint = std::max({a->gap_rate_hint, (double)r.n_stretches() / (double)items[q].g.nk, 1e-12});
         }
         if (!(good && total <= cap) && knob_set(h, "MXG_DEBUG_BATCH")) {  // (diagnostics: the reports of an assembly's batches)
             for (size_t q = q0; q < q1; ++q) {
-                const uint32_t *c = items[q].hc;
+                const BatchReport r{items[q].hc};
                 fprintf(stderr, "[mxg] asm %zu batch %zu: ovf %u gaps %u sel %u flag %u cand %u nB %u total %u obase %u gapk %u (cap %llu)\n", i,
-                        q - q0, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[8], c[10], (unsigned long long)cap);
+                        q - q0, r.arena_need(), r.n_stretches(), r.n_selected(), r.w[RW_REDO], r.n_cand(), r.w[RW_STRETCH_MX],
+                        (uint32_t)r.total(), (uint32_t)r.out_base(), r.w[RW_GAP_KMERS], (unsigned long long)cap);
             }
         }
-        // what the batches saw of candidate-free stretches sizes the next sketch's batches (sparse_plan): real genomes hold
-        // far more of them than the i.i.d. estimate (satellite arrays, low-complexity runs)
-        for (size_t q = q0; q < q1; ++q) {
-            const uint32_t *c = items[q].hc;
-            // (1e-12: "a sketch has reported" -- an assembly whose stretches all went through k_sel_stretch leaves none over)
-            if (c[1] != 0xFFFFFFFFu && items[q].g.nk) a->gap_rate_hint = std::max({a->gap_rate_hint, (double)c[1] / (double)items[q].g.nk, 1e-12});
-        }
+        const BatchReport first{items[q0].hc};
         if (good && total <= cap) {
             // stretches the device route left to the host (too long, too many minimizers, invalid bases inside)
             std::vector<uint4> deferred;
-            for (size_t q = q0; q < q1 && !chain_modes; ++q) {
-                const uint32_t nd = items[q].hc[11] == 0xFFFFFFFFu ? 0u : std::min(items[q].hc[11], GAP_DEFER_MAX);
-                const uint4 *src = reinterpret_cast<const uint4 *>(h->pinned_defer) + (size_t)((items[q].hc - h->pinned_ctrl) / 16) * GAP_DEFER_MAX;
-                deferred.insert(deferred.end(), src, src + nd);
-            }
+            for (size_t q = q0; q < q1 && !chain_modes; ++q) take_deferred(h, items[q].hc, deferred);
             uint64_t n_final = total;
             if (!deferred.empty()) {
                 if ((rc = drv0.merge_deferred(a, tabs[i], deferred, total, &n_final)) != MXG_OK) return rc;
@@ -3740,20 +3729,19 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
             a->has_sketch = true;
             h->stat_candidates += n_cand;
             h->stat_dense_kmers += gap_kmers;
-            for (size_t q = q0; q < q1; ++q) a->cand_hints[q - q0] = items[q].hc[4];
+            for (size_t q = q0; q < q1; ++q) a->cand_hints[q - q0] = BatchReport{items[q].hc}.n_cand();
             a->cand_hint = a->cand_hints[0];
             state[i] = 2;
             if (fused && total > gb.n_bound[i]) fused = false;  // a sketch outgrew the bound the graph stage was sized for
             ++n_fast;
-        } else if (q1 - q0 == 1 && !items[q0].bs && items[q0].hc[0] == 0 && items[q0].hc[4] != 0xFFFFFFFFu &&
-                   last_on_slot[items[q0].slot] == q0) {
+        } else if (q1 - q0 == 1 && !items[q0].bs && first.arena_need() == 0 && first.reported() && last_on_slot[items[q0].slot] == q0) {
             // one batch, no arena overflow, and its candidate arrays are still intact in the driver's scratch: finish from
             // there the general way (staging emit, dense fix-up of the stretches, merge) instead of redoing the batch
             Driver &drv = *drvs[items[q0].slot];
             OutArrays out{&a->d_hash, &a->d_pos, &a->d_rec, &a->d_fwd, 0};
-            uint32_t ctrl_copy[16];
-            memcpy(ctrl_copy, items[q0].hc, 64);
-            if ((rc = drv.complete_batch(a, tabs[i], items[q0].g, out, ctrl_copy, items[q0].n_cap)) != MXG_OK) return rc;
+            uint32_t ctrl_copy[REPORT_WORDS];
+            std::copy_n(first.w, REPORT_WORDS, ctrl_copy);
+            if ((rc = drv.complete_batch(a, tabs[i], items[q0].g, out, BatchReport{ctrl_copy}, items[q0].n_cap)) != MXG_OK) return rc;
             MXG_HIP(h, hipStreamSynchronize(drv.st));
             a->n_mx = out.n;
             a->has_sketch = true;
@@ -3763,14 +3751,14 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
             // ten times that), with batches sized for the stretch density just seen (gap_rate_hint, above), every grid sized by
             // the batch's own candidate count where it reported one, and slices as large as the largest wave asked for
             for (size_t q = q0; q < q1; ++q) {
-                const uint32_t *c = items[q].hc;
-                if (c[0] != 0 && c[0] != 0xFFFFFFFFu) h->arena_cap_hint = std::max<uint64_t>(h->arena_cap_hint, (uint64_t)c[0] + 64);
+                const BatchReport r{items[q].hc};
+                if (r.reported() && r.arena_need() != 0) h->arena_cap_hint = std::max<uint64_t>(h->arena_cap_hint, (uint64_t)r.arena_need() + 64);
             }
             // (k_bs_select again unless the slice kernel itself gave up somewhere -- a slice beyond its queue with no region left,
-            // more selected candidates than a slice's room: word 12 -- and not merely more stretches than a batch holds)
+            // more selected candidates than a slice's room: RW_SLICE_GAVE_UP -- and not merely more stretches than a batch holds)
             a->sel_again = true;
             for (size_t q = q0; q < q1; ++q)
-                if (items[q].bs && items[q].hc[12] != 0) a->sel_again = false;
+                if (items[q].bs && items[q].hc[RW_SLICE_GAVE_UP] != 0) a->sel_again = false;
             a->cand_hints.clear();  // (the batches will be cut differently)
             a->cand_hint = 0xFFFFFFFEu;
             a->full_grid_once = true;
@@ -3781,22 +3769,20 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
             // where its predecessors end), redo the first bad one and everything behind it batch by batch through the
             // synchronous route.  That route finishes stretches from the host, so it takes the threshold of the host route
             // (18 candidates per window: a stretch per ~10^8 k-mers instead of one per ~2 x 10^6).
-            const bool dev = plans[i].dev_gaps;
             uint64_t offset = 0, nc = 0, gk = 0;
             size_t j = q0;
             for (; j < q1; ++j) {
-                const uint32_t *c = items[j].hc;
-                const uint64_t t = (uint64_t)c[6] | ((uint64_t)c[7] << 32), ob = (uint64_t)c[8] | ((uint64_t)c[9] << 32);
-                const bool ok = c[0] == 0 && c[3] == 0 && c[12] == 0 && (c[4] != 0 || items[j].bs) && c[4] != 0xFFFFFFFFu && (dev || c[1] == 0) && ob == offset &&
-                                offset + t <= cap;
-                if (!ok) break;
-                offset += t;
-                nc += c[4];
-                gk += c[10] == 0xFFFFFFFFu ? 0 : c[10];
-                a->cand_hints[j - q0] = c[4];
+                const BatchReport r{items[j].hc};
+                if (!(ended_well(j) && r.out_base() == offset && offset + r.total() <= cap)) break;
+                offset += r.total();
+                nc += r.n_cand();
+                gk += r.gap_kmers();
+                a->cand_hints[j - q0] = r.n_cand();
             }
-            for (size_t q = j; q < q1; ++q)  // (next time: the whole grid for what did not report, the count for what did)
-                a->cand_hints[q - q0] = items[q].hc[4] != 0xFFFFFFFFu && items[q].hc[4] != 0 ? items[q].hc[4] : 0xFFFFFFFEu;
+            for (size_t q = j; q < q1; ++q) {  // (next time: the whole grid for what did not report, the count for what did)
+                const BatchReport r{items[q].hc};
+                a->cand_hints[q - q0] = r.reported() && r.n_cand() != 0 ? r.n_cand() : 0xFFFFFFFEu;
+            }
             a->cand_hint = a->cand_hints[0];
             SparsePlan rp = plans[i];
             if (!h->cfg.cand_per_window && 18.0 / (double)h->cfg.w <= 0.125) {
@@ -3810,11 +3796,7 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
             if (j == q0) ++h->stat_sync_assemblies;
             // (the batches that are kept may have left stretches to the host: their lists are read before anything reuses the slots)
             std::vector<uint4> deferred;
-            for (size_t q = q0; q < j; ++q) {
-                const uint32_t nd = items[q].hc[11] == 0xFFFFFFFFu ? 0u : std::min(items[q].hc[11], GAP_DEFER_MAX);
-                const uint4 *src = reinterpret_cast<const uint4 *>(h->pinned_defer) + (size_t)((items[q].hc - h->pinned_ctrl) / 16) * GAP_DEFER_MAX;
-                deferred.insert(deferred.end(), src, src + nd);
-            }
+            for (size_t q = q0; q < j; ++q) take_deferred(h, items[q].hc, deferred);
             if ((rc = drv0.sparse_all(a, tabs[i], out, rp.tau_hi, rp.frac, items[j].g.c0)) != MXG_OK) return rc;
             MXG_HIP(h, hipStreamSynchronize(drv0.st));
             uint64_t n_final = out.n;
@@ -3885,18 +3867,14 @@ int sketch_finish(mxg_handle *h)
     for (size_t i = 0; i < list.size(); ++i) {
         Assembly *a = list[i];
         if (state[i] == 1) {
-            const uint32_t *c = h->pinned_ctrl + 16 * q++;
-            const uint64_t total = (uint64_t)c[6] | ((uint64_t)c[7] << 32), n_cand = c[4];
-            const uint64_t cap = std::min<uint64_t>({a->d_hash.bytes / 8, a->d_pos.bytes / 4, a->d_rec.bytes / 4, a->d_fwd.bytes});
-            // evaluate()'s `good` for a one-call mode, and what k_pack_slot_dev checked on the device: word 3 = the stretch kernels'
-            // flag, word 12 = the slice kernel gave up on a slice (its output is then truncated), stretches absent or all placed on
-            // the device (word 11 = handed to the host: the counts the pack kernel used would be without them)
-            const bool dev = i < devg.size() && devg[i] && c[11] == 0;
-            if (c[0] == 0 && c[3] == 0 && c[12] == 0 && (dev || c[1] == 0) && n_cand > 0 && c[4] != 0xFFFFFFFFu && total <= cap) {
-                a->n_mx = total;
+            const BatchReport r{report_slot(h, q++)};
+            // what the pack kernel decided on the device (batch_ended_well): its counts include no deferred stretch, and it packs
+            // no batch without candidates
+            if (r.ended_well(i < devg.size() && devg[i], false, false) && r.total() <= out_capacity(a)) {
+                a->n_mx = r.total();
                 a->has_sketch = true;
-                h->stat_candidates += n_cand;
-                a->cand_hint = (uint32_t)n_cand;
+                h->stat_candidates += r.n_cand();
+                a->cand_hint = r.n_cand();
                 continue;
             }
         } else if (state[i] == 2) {
@@ -4099,7 +4077,7 @@ struct UnpackSlotParams {
     uint64_t *hash;
     uint32_t *pos, *rec;
     uint32_t *n_dev;        // device word that receives the total (GraphBounds::n_ptr)
-    uint32_t *host_total;   // pinned: total, 0xFFFFFFFF if some rank's header says "does not fit"
+    uint32_t *host_total;   // pinned: total, REPORT_UNSET if some rank's header says "does not fit"
 };
 
 __global__ __launch_bounds__(256) void k_unpack_slot(const UnpackSlotParams p)
@@ -4118,7 +4096,7 @@ __global__ __launch_bounds__(256) void k_unpack_slot(const UnpackSlotParams p)
     }
     if (r == 0 && i == 0) {
         *p.n_dev = bad ? 0u : (uint32_t)total;
-        *p.host_total = bad ? 0xFFFFFFFFu : (uint32_t)total;
+        *p.host_total = bad ? REPORT_UNSET : (uint32_t)total;
     }
     if (bad || (long long)i >= mine) return;
     const unsigned char *reg = p.all + (size_t)r * p.slot_bytes + p.region_off;
@@ -4159,7 +4137,7 @@ __global__ __launch_bounds__(256) void k_unpack_part(const UnpackPartParams p)
     }
     if (r == 0 && i == 0) {
         *p.n_dev = bad ? 0u : (uint32_t)total;
-        *p.host_total = bad ? 0xFFFFFFFFu : (uint32_t)total;
+        *p.host_total = bad ? REPORT_UNSET : (uint32_t)total;
     }
     if (bad || (long long)i >= mine) return;
     const unsigned char *reg = p.all + (size_t)r * p.part_bytes + XCHG_PART_HEAD;
@@ -4199,7 +4177,9 @@ int xchg_unpack_graph(mxg_handle *h, const void *d_all, uint32_t world, uint64_t
         MXG_HIP(h, a->d_hash.ensure(std::max<uint64_t>(bound * 8, 16)));
         MXG_HIP(h, a->d_pos.ensure(std::max<uint64_t>(bound * 4, 16)));
         MXG_HIP(h, a->d_rec.ensure(std::max<uint64_t>(bound * 4, 16)));
-        h->pinned_ctrl[16 * ai] = 0xFFFFFFFFu;
+        // (no batch is in flight: assembly ai's report slot holds its unpacked total instead, REPORT_UNSET if it did not fit)
+        uint32_t *const host_total = report_slot(h, ai);
+        *host_total = REPORT_UNSET;
         if (d_all_parts) {
             UnpackPartParams pp;
             pp.all = static_cast<const unsigned char *>(d_all_parts[ai]);
@@ -4212,7 +4192,7 @@ int xchg_unpack_graph(mxg_handle *h, const void *d_all, uint32_t world, uint64_t
             pp.pos = a->d_pos.as<uint32_t>();
             pp.rec = a->d_rec.as<uint32_t>();
             pp.n_dev = h->d_nmx.as<uint32_t>() + ai;
-            pp.host_total = h->pinned_ctrl + 16 * ai;
+            pp.host_total = host_total;
             hipLaunchKernelGGL(k_unpack_part, dim3((uint32_t)std::max<uint64_t>((caps[ai] + 255) / 256, 1), world), dim3(256), 0,
                                h->stream, pp);
         }
@@ -4228,7 +4208,7 @@ int xchg_unpack_graph(mxg_handle *h, const void *d_all, uint32_t world, uint64_t
         up.pos = a->d_pos.as<uint32_t>();
         up.rec = a->d_rec.as<uint32_t>();
         up.n_dev = h->d_nmx.as<uint32_t>() + ai;
-        up.host_total = h->pinned_ctrl + 16 * ai;
+        up.host_total = host_total;
         if (!d_all_parts)
             hipLaunchKernelGGL(k_unpack_slot, dim3((uint32_t)std::max<uint64_t>((caps[ai] + 255) / 256, 1), world), dim3(256), 0,
                                h->stream, up);
@@ -4248,9 +4228,9 @@ int xchg_unpack_graph(mxg_handle *h, const void *d_all, uint32_t world, uint64_t
     if (rc != MXG_OK) return rc;
     bool bad = false;
     for (size_t ai = 0; ai < A; ++ai) {
-        const uint32_t t = h->pinned_ctrl[16 * ai];
-        bad = bad || t == 0xFFFFFFFFu;
-        h->asms[ai]->n_mx = t == 0xFFFFFFFFu ? 0 : t;
+        const uint32_t t = *report_slot(h, ai);
+        bad = bad || t == REPORT_UNSET;
+        h->asms[ai]->n_mx = t == REPORT_UNSET ? 0 : t;
     }
     if (bad) {
         h->graph.valid = false;

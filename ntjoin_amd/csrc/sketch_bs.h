@@ -1,6 +1,7 @@
 // sketch_bs.h -- the k = 32 route of the sketch stage: bit-sliced ring filter (bs_kernels.h) + one kernel that turns its
 // candidate bitmap into selected minimizers (exact hashes, window decision, candidate-free stretches).  Launchers for sketch.hip.
 #pragma once
+#include "batch_ctrl.h"
 #include "mxg_internal.h"
 
 namespace mxg {
@@ -39,11 +40,11 @@ struct BsSelParams {
     uint64_t tau;
     uint32_t qcap;               // raw candidates a wave's LDS queue holds
     // a slice with more raw candidates than qcap works in one of n_ovf global-memory regions of ovf_cap entries (a wave's
-    // worst case: 64 S) instead; no region left: the host redoes the batch (ctrl[6])
+    // worst case: 64 S) instead; no region left: the host redoes the batch (CW_REDO)
     uint64_t *ovf_h;
     uint32_t *ovf_e;
     uint32_t ovf_cap, n_ovf;
-    uint32_t *ovf_next;          // ticket counter of the regions (zeroed with the control block)
+    uint32_t *ovf_next;          // ticket counter of the regions (CW_REGION_TICKET)
     // results: the selected candidates of slice s from entry s * rk on + two-level counts (k_emit), stretches (k_gap_fix)
     uint32_t rk;
     uint4 *cs;                   // {hash lo, hash hi, k-mer index, contig}
@@ -52,10 +53,10 @@ struct BsSelParams {
     uint32_t gap_cap;
     uint32_t gap_nmax;           // k-mers of the longest stretch reported in one piece (0: any); see sel_push_gap
     uint32_t *cand_spread;       // 64 counters, 32 words apart: the slices' own candidates (k_emit adds them up for the report)
-    uint32_t *ctrl;              // [1] stretches, [6] "the host must redo this batch"
+    uint32_t *ctrl;              // CW_STRETCHES, CW_REDO, CW_SLICE_GAVE_UP, CW_SEL_REQS (batch_ctrl.h)
     uint32_t ablate;             // (profiling builds: every slice stops after phase n; 0 = run)
     // inl_amax != 0: a slice's stretches become requests for k_sel_stretch, {contig, first, last k-mer, slice | number in the
-    // slice << 24 | stretches of the slice << 27}, the slice's requests next to one another; ctrl[15] counts them (0: every
+    // slice << 24 | stretches of the slice << 27}, the slice's requests next to one another; CW_SEL_REQS counts them (0: every
     // stretch goes straight to k_gap_fix)
     uint32_t inl_amax;
     uint4 *ireq;
@@ -74,7 +75,7 @@ struct SelStretchParams {
     uint32_t *cnt, *sup;
     const uint4 *ireq;
     uint32_t ireq_cap;
-    uint32_t *ctrl;              // [15] requests, [1] stretches (what does not fit here goes on to k_gap_fix)
+    uint32_t *ctrl;              // CW_SEL_REQS requests, CW_STRETCHES (what does not fit here goes on to k_gap_fix)
     uint32_t *tickets;           // 64 counters, 32 words apart, zero: request 64 t + c is handed out by ticket t of counter c
     uint4 *gaps;
     uint32_t gap_cap, gap_nmax;

@@ -183,7 +183,7 @@ __device__ __forceinline__ void push_gap(uint4 *gaps, uint32_t gap_cap, uint32_t
     uint32_t s = lo, flag = 0u;
     for (;;) {
         const uint32_t e = nmax && hi - s >= nmax ? s + nmax - 1u : hi;
-        const uint32_t idx = atomicAdd(&ctrl[1], 1u);
+        const uint32_t idx = atomicAdd(&ctrl[CW_STRETCHES], 1u);
         if (idx < gap_cap) gaps[idx] = make_uint4(c, s, e, hint | flag);
         if (e == hi) break;
         s = e - w + 1u;  // (the piece's last window; the next piece's own windows start one k-mer behind it)
@@ -476,7 +476,7 @@ __device__ __forceinline__ void sel_decide(const BsSelParams &p, SelCtx &c, cons
         const uint32_t n_i = min(c.misc[2], SEL_REQ);
         const bool to_kernel = pr->inl_amax != 0u;  // (else: every stretch straight to k_gap_fix)
         uint32_t base = 0xFFFFFFFFu - SEL_REQ;
-        if (to_kernel && lane == 0) base = atomicAdd(&pr->ctrl[15], n_i);
+        if (to_kernel && lane == 0) base = atomicAdd(&pr->ctrl[CW_SEL_REQS], n_i);
         base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
         uint32_t ln = lane;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(1024) void k_bs_select(const BsSelParams p)
     if (lane == 0) {
         const BsSelParams *q = sel_rare_params();
         if (own_w) atomicAdd(&q->cand_spread[((blockIdx.x * nwv + wib) & 63u) * 32u], own_w);
-        if (flag) q->ctrl[6] = q->ctrl[13] = 1;  // ([13]: it was this kernel that gave up)
+        if (flag) q->ctrl[CW_REDO] = q->ctrl[CW_SLICE_GAVE_UP] = 1;
     }
 }
 
@@ -881,7 +881,7 @@ __global__ __launch_bounds__(SST_WAVES * 64, 5) void k_sel_stretch(const SelStre
     __shared__ uint4 rtab[16];
     __shared__ uint64_t Xs[SST_WAVES][2 * 64 * SEL_INL_R];
     __shared__ uint4 tmps[SST_WAVES][SEL_INL_TMP];
-    const uint32_t n_req = min(p.ctrl[15], p.ireq_cap);
+    const uint32_t n_req = min(p.ctrl[CW_SEL_REQS], p.ireq_cap);
     if (blockIdx.x * SST_WAVES >= n_req) return;
     for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) byte_tab[i] = p.byte_tab[i];
     if (threadIdx.x < 16u) rtab[threadIdx.x] = p.tab.e[threadIdx.x];
