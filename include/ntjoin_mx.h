@@ -353,6 +353,19 @@ typedef struct mxg_segments_view {
     const uint32_t *seg_stat;        /* 5 per run: vertices, min pos, max pos, increasing pairs, decreasing pairs */
 } mxg_segments_view;
 int mxg_path_segments(mxg_handle *h, int assembly, mxg_segments_view *out);
+/* --mkt: determine_orientation (bin/ntjoin_assemble.py:30-50) decides every run that is not strictly monotone by
+   pymannkendall.original_test(positions) (:37-40), whose decision reads two exact integers of the run x_0..x_{n-1}:
+       s = sum over i < j of sign(x_j - x_i),   tie_term = sum over groups of t equal values of t(t-1)(2t+5)
+   (the test's variance is (n(n-1)(2n+5) - tie_term) / 18).  O(n log^2 n) per run, on the device.
+   mxg_path_segments_mk: s and tie_term of every run of the last mxg_path_segments, in its order, over the same positions
+                         (MXG_EINVAL if there was none since the last mxg_find_paths, or it was for another assembly); host
+                         copies owned by the handle, like mxg_segments_view.
+   mxg_mk_stats:         the same for runs the caller gives: run r = values[run_first[r] .. run_first[r+1]) (run_first has
+                         n_runs + 1 entries; runs of 0 or 1 values give 0, 0), results written to s[n_runs], tie_term[n_runs].
+   A tie term beyond 2^64 - 1 (a group of more than about 2*10^6 equal values) fails with MXG_ELIMIT. */
+int mxg_path_segments_mk(mxg_handle *h, int assembly, const int64_t **s, const uint64_t **tie_term, uint64_t *n_segments);
+int mxg_mk_stats(mxg_handle *h, const uint32_t *values, const uint64_t *run_first /* n_runs + 1 */, uint64_t n_runs,
+                 int64_t *s, uint64_t *tie_term);
 int mxg_mx_extremes(mxg_handle *h, int assembly, const uint32_t **min_pos, const uint32_t **max_pos, uint64_t *n_records);
 
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------

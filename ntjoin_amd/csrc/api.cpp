@@ -856,6 +856,32 @@ int mxg_mx_extremes(mxg_handle *h, int assembly, const uint32_t **min_pos, const
     return MXG_OK;
 }
 
+int mxg_path_segments_mk(mxg_handle *h, int assembly, const int64_t **s, const uint64_t **tie_term, uint64_t *n_segments)
+{
+    if (!h || !s || !tie_term || !n_segments || assembly < 0) return MXG_EINVAL;
+    try {
+        int rc = path_segments_mk(h, (uint32_t)assembly);
+        if (rc != MXG_OK) return rc;
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_path_segments_mk");
+    }
+    *s = h->segs.mk_s.data();
+    *tie_term = h->segs.mk_tie.data();
+    *n_segments = h->segs.mk_s.size();
+    return MXG_OK;
+}
+
+int mxg_mk_stats(mxg_handle *h, const uint32_t *values, const uint64_t *run_first, uint64_t n_runs, int64_t *s,
+                 uint64_t *tie_term)
+{
+    if (!h || !run_first || (n_runs && (!s || !tie_term || (!values && run_first[n_runs])))) return MXG_EINVAL;
+    try {
+        return mk_stats(h, values, run_first, n_runs, s, tie_term);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_mk_stats");
+    }
+}
+
 // ---- distributed graph stage (dgraph.hip; the collectives are the caller's) -----------------------------------------
 #define DG_TRY(expr)                                                                     \
     try {                                                                                \

@@ -178,9 +178,12 @@ struct Paths {  // result of mxg_find_paths (host copies)
     std::vector<uint32_t> component;  // [n_paths] component (root vertex index) of the globally filtered graph
 };
 
-struct Segments {  // results of mxg_path_segments / mxg_mx_extremes (host copies)
+struct Segments {  // results of mxg_path_segments / mxg_mx_extremes / mxg_path_segments_mk (host copies)
+    int assembly = -1;                          // the segments' assembly (-1: none since the last mxg_find_paths)
     std::vector<uint32_t> path, record, first;  // per segment
     std::vector<uint32_t> stat;                 // per segment: n, min pos, max pos, increasing pairs, decreasing pairs
+    std::vector<int64_t> mk_s;                  // per segment: Mann-Kendall S
+    std::vector<uint64_t> mk_tie;               // ... and tie term
     std::vector<uint32_t> ext_min, ext_max;     // per record of the assembly last asked for
 };
 
@@ -230,6 +233,7 @@ struct mxg_handle {
     bool dg_ghost_on = false;
     mxg::Paths paths;
     mxg::DevBuf pbuf[48];  // scratch of paths.hip
+    mxg::DevBuf mkbuf[8];  // scratch of mk.hip
     mxg::Segments segs;
     mxg::Timers tm;
     mxg::HashTab tab{};
@@ -431,6 +435,12 @@ int dg_edges_slots(mxg_handle *h, const void *d_recv, uint32_t world, uint32_t M
                    uint32_t *overflow);
 int path_segments(mxg_handle *h, uint32_t assembly);
 int mx_extremes(mxg_handle *h, uint32_t assembly);
+int path_segments_mk(mxg_handle *h, uint32_t assembly);
+// mk.hip: Mann-Kendall S and tie term of the runs [d_first[r], d_first[r + 1]) of d_x (device arrays, d_first with n_runs + 1
+// entries; d_x is sorted in place run by run), len[r] = the runs' lengths on the host
+int mk_runs(mxg_handle *h, uint32_t *d_x, const uint32_t *d_first, uint32_t n_runs, uint32_t n_total,
+            const std::vector<uint32_t> &len, int64_t *s, uint64_t *tie_term);
+int mk_stats(mxg_handle *h, const uint32_t *values, const uint64_t *run_first, uint64_t n_runs, int64_t *s, uint64_t *tie_term);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm
 int flags_to_host(mxg_handle *h, Assembly *a);
 

@@ -24,7 +24,7 @@ static constexpr uint32_t NIL = 0xFFFFFFFFu;
 // scratch buffers of this file (mxg_handle::pbuf); PV / PF / PC keep the paths on the device after find_paths
 enum { ALIVE, COMP, SUB, DEG, NONLIN, FLAG, CNTV, CNTE, CNTD1, MAXDEG, FILL, NB, NBE, KEY0, KEY1, KEY2, SUCC0, CNT0, END0,
        SUCC1, CNT1, END1, SIZE, ISSRC, FIRST, RANK, BSUM, TOTAL, PV, PF, PC, SG_FLAG, SG_EXCL, SG_FIRST, SG_REC, SG_PATH,
-       SG_STAT, XT_MIN, XT_MAX, PBUF_COUNT };
+       SG_STAT, XT_MIN, XT_MAX, SG_MKX, PBUF_COUNT };
 static_assert(PBUF_COUNT <= 48, "mxg_handle::pbuf too small");
 
 __device__ __forceinline__ uint32_t find_root(uint32_t *parent, uint32_t v)
@@ -375,6 +375,7 @@ int find_paths(mxg_handle *h, int64_t n_min)
     MXG_HIP(h, hipSetDevice(h->device));
     Paths &P = h->paths;
     P = Paths();
+    h->segs.assembly = -1;  // the segments of the paths before are gone
     const uint32_t nv = (uint32_t)g.nv, ne = (uint32_t)g.ne, A = g.n_asm;
     if (nv == 0) {
         P.first.assign(1, 0);
@@ -647,9 +648,13 @@ int path_segments(mxg_handle *h, uint32_t a)
     if (a >= g.n_asm) return set_err(h, MXG_EINVAL, "assembly index %u out of range", a);
     MXG_HIP(h, hipSetDevice(h->device));
     Segments &S = h->segs;
-    S.path.clear(); S.record.clear(); S.first.clear(); S.stat.clear();
+    S.path.clear(); S.record.clear(); S.first.clear(); S.stat.clear(); S.mk_s.clear(); S.mk_tie.clear();
+    S.assembly = -1;
     const uint32_t n = (uint32_t)P.vertex.size(), n_paths = (uint32_t)P.component.size();
-    if (n == 0) return MXG_OK;
+    if (n == 0) {
+        S.assembly = (int)a;
+        return MXG_OK;
+    }
     DevBuf *B = h->pbuf;
     const uint32_t *pv = B[PV].as<uint32_t>();
     const uint64_t *pf = B[PF].as<uint64_t>();
@@ -683,7 +688,47 @@ int path_segments(mxg_handle *h, uint32_t a)
     MXG_HIP(h, hipMemcpyAsync(S.first.data(), B[SG_FIRST].p, (size_t)n_seg * 4, hipMemcpyDeviceToHost, h->stream));
     MXG_HIP(h, hipMemcpyAsync(S.stat.data(), B[SG_STAT].p, (size_t)n_seg * 20, hipMemcpyDeviceToHost, h->stream));
     MXG_HIP(h, hipStreamSynchronize(h->stream));
+    S.assembly = (int)a;
     return MXG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// --mkt (determine_orientation, reference bin/ntjoin_assemble.py:37-40): the Mann-Kendall statistics of every segment of
+// the last path_segments, over the same positions ks_stats reads (mk.hip does the counting)
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ks_mk_values(const uint32_t *__restrict__ pv, uint32_t n, const uint32_t *__restrict__ vpos,
+                                                    uint32_t nv, uint32_t *x)
+{
+    uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t v = pv[i];
+    x[i] = v < nv ? vpos[v] : 0u;
+}
+
+int path_segments_mk(mxg_handle *h, uint32_t a)
+{
+    Graph &g = h->graph;
+    Segments &S = h->segs;
+    if (!g.valid || !h->paths.valid || S.assembly < 0)
+        return set_err(h, MXG_EINVAL, "mxg_path_segments_mk: call mxg_path_segments first");
+    if ((uint32_t)S.assembly != a)
+        return set_err(h, MXG_EINVAL, "mxg_path_segments_mk: the last mxg_path_segments was for assembly %d, not %u", S.assembly, a);
+    const uint32_t n_seg = (uint32_t)S.path.size(), n = (uint32_t)h->paths.vertex.size();
+    S.mk_s.assign(n_seg, 0);
+    S.mk_tie.assign(n_seg, 0);
+    if (n_seg == 0) return MXG_OK;
+    if (n >= 0x7FFFFFFFu) return set_err(h, MXG_ELIMIT, "mxg_path_segments_mk: %u path vertices (at most 2^31 - 2)", n);
+    MXG_HIP(h, hipSetDevice(h->device));
+    DevBuf *B = h->pbuf;
+    MXG_HIP(h, B[SG_MKX].ensure((size_t)n * 4 + 16));
+    // the runs are the segments: seg_first plus the end of the last one (SG_FIRST has room behind it)
+    MXG_HIP(h, hipMemsetD32Async((hipDeviceptr_t)(B[SG_FIRST].as<uint32_t>() + n_seg), (int)n, 1, h->stream));
+    hipLaunchKernelGGL(ks_mk_values, dim3((n + 255) / 256), dim3(256), 0, h->stream, B[PV].as<uint32_t>(), n,
+                       h->g_vpos.as<uint32_t>() + (size_t)a * g.nv_stride, (uint32_t)g.nv, B[SG_MKX].as<uint32_t>());
+    MXG_HIP(h, hipGetLastError());
+    std::vector<uint32_t> len(n_seg);
+    for (uint32_t s = 0; s < n_seg; ++s) len[s] = S.stat[(size_t)s * 5];
+    return mk_runs(h, B[SG_MKX].as<uint32_t>(), B[SG_FIRST].as<uint32_t>(), n_seg, n, len, S.mk_s.data(), S.mk_tie.data());
 }
 
 }  // namespace mxg

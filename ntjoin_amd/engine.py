@@ -355,6 +355,25 @@ class MxEngine:
                 "first": _np(v.seg_first, n, np.uint32), "n": st[:, 0], "min_pos": st[:, 1], "max_pos": st[:, 2],
                 "inc": st[:, 3], "dec": st[:, 4]}
 
+    def path_segments_mk(self, a):
+        """Mann-Kendall statistics of the runs of the last path_segments(a), aligned with them (--mkt): dict of arrays
+        s (int64: sum over i < j of sign(x_j - x_i)) and tie_term (uint64: sum over groups of t equal positions of
+        t(t-1)(2t+5))"""
+        s, t, n = C.POINTER(C.c_int64)(), C.POINTER(C.c_uint64)(), C.c_uint64()
+        self._check(self._lib.mxg_path_segments_mk(self._h, int(a), C.byref(s), C.byref(t), C.byref(n)))
+        return {"s": _np(s, n.value, np.int64), "tie_term": _np(t, n.value, np.uint64)}
+
+    def mk_stats(self, values, run_first):
+        """the same statistics of caller-given runs: run r = values[run_first[r]:run_first[r + 1]] -> (s int64, tie_term uint64)"""
+        x = np.ascontiguousarray(values, dtype=np.uint32)
+        rf = np.ascontiguousarray(run_first, dtype=np.uint64)
+        if rf.ndim != 1 or len(rf) == 0 or int(rf[-1]) > len(x):
+            raise ValueError("mk_stats: run_first needs n_runs + 1 offsets, the last one at most len(values)")
+        n_runs = len(rf) - 1
+        s, t = np.zeros(n_runs, dtype=np.int64), np.zeros(n_runs, dtype=np.uint64)
+        self._check(self._lib.mxg_mk_stats(self._h, x.ctypes.data, rf.ctypes.data, n_runs, s.ctypes.data, t.ctypes.data))
+        return s, t
+
     def mx_extremes(self, a):
         """per record of assembly a: (min, max) position over its graph vertices; None for records without one"""
         mn, mx, n = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.c_uint64()

@@ -11,6 +11,7 @@ Instead of TSVs the engine can sketch FASTA directly: pass fasta={tsv_name: fast
 WRITTEN (checkpoint files, ntJoin:202 `.SECONDARY`) rather than read.
 """
 import datetime
+import math
 import sys
 
 import numpy as np
@@ -20,6 +21,38 @@ from .engine import MxEngine
 from .ntjoin_utils import MxGraph, sketch_views
 
 COLOURS = ["red", "green", "blue", "purple", "orange", "turquoise", "pink", "yellow", "orchid", "salmon"]
+
+MK_Z975 = 1.959963984540054  # scipy.stats.norm.ppf(0.975): original_test's threshold on |z| at alpha = 0.05
+_SQRT1_2 = 0.7071067811865476
+
+
+def _norm_cdf(a):
+    "the standard normal CDF as scipy.special.ndtr (what norm.cdf evaluates) forms it, on math.erf / math.erfc"
+    x = a * _SQRT1_2
+    z = abs(x)
+    if z < _SQRT1_2:
+        return 0.5 + 0.5 * math.erf(x)
+    y = 0.5 * math.erfc(z)
+    return 1.0 - y if x > 0 else y
+
+
+def mk_orientation(n, s, tie_term):
+    """--mkt decision of determine_orientation (reference bin/ntjoin_assemble.py:37-40) for a run of n positions with
+    Mann-Kendall score s and tie term sum t(t-1)(2t+5): pymannkendall.original_test's z, p and h, then '+' / '-' when
+    h and p <= 0.05, else '?'.  (p is kept as the reference computes it: near |z| = 1.96 it can exceed 0.05 while h holds.)"""
+    n, s, tie_term = int(n), int(s), int(tie_term)
+    var = (n * (n - 1) * (2 * n + 5) - tie_term) / 18
+    if s > 0:
+        z = (s - 1) / math.sqrt(var)
+    elif s < 0:
+        z = (s + 1) / math.sqrt(var)
+    else:
+        z = 0.0
+    p = 2 * (1 - _norm_cdf(abs(z)))
+    h = abs(z) > MK_Z975
+    if h and p <= 0.05:
+        return "+" if z > 0 else "-"
+    return "?"
 
 
 class Ntjoin:
@@ -169,11 +202,24 @@ class Ntjoin:
                 return "-"
         return "?"
 
-    def format_paths(self, lengths=None, g=20, G=0, m=90):
+    @staticmethod
+    def _orientation_mkt(n, inc, dec, s, tie_term):
+        "determine_orientation with --mkt: the strictly monotone checks first, then the Mann-Kendall test (:32-40)"
+        if n > 1:
+            if dec == 0 and inc == n - 1:
+                return "+"
+            if inc == 0 and dec == n - 1:
+                return "-"
+            return mk_orientation(n, s, tie_term)
+        return "?"
+
+    def format_paths(self, lengths=None, g=20, G=0, m=90, mkt=False):
         """format_path (:175-218) for every path of the last find_paths() and the target assembly: one list per path of
         [contig, ori, start, end, contig_size, first_mx, terminal_mx, gap_size, raw_gap_size].  The per-minimizer work
         (grouping by contig, min/max, orientation tallies) is the library's (mxg_path_segments, mxg_mx_extremes); the
-        gap estimate between two oriented runs (calculate_gap_size :68-112) reads a handful of graph entries here."""
+        gap estimate between two oriented runs (calculate_gap_size :68-112) reads a handful of graph entries here.
+        mkt=True (ntJoin --mkt): a run that is not strictly monotone is decided by the Mann-Kendall test (mk_orientation on
+        the library's mxg_path_segments_mk) instead of the m percentage rule."""
         eng, k = self._engine, int(getattr(self.args, "k", 32))
         tgt = len(self._order) - 1
         ids = eng.record_ids(tgt, eng.n_records(tgt))
@@ -198,8 +244,12 @@ class Ntjoin:
         out = [[] for _ in self._found]
         kept = [[] for _ in self._found]
         cols = [seg[c].tolist() for c in ("path", "record", "first", "n", "min_pos", "max_pos", "inc", "dec")]
-        for p, rec, first, n, mn, mx, inc, dec in zip(*cols):
-            ori = self.determine_orientation(n, inc, dec, m)
+        if mkt:
+            mk = eng.path_segments_mk(tgt)
+            oris = [self._orientation_mkt(n, inc, dec, s, t) for n, inc, dec, s, t in
+                    zip(cols[3], cols[6], cols[7], mk["s"].tolist(), mk["tie_term"].tolist())]
+        for i, (p, rec, first, n, mn, mx, inc, dec) in enumerate(zip(*cols)):
+            ori = oris[i] if mkt else self.determine_orientation(n, inc, dec, m)
             if ori == "?":
                 continue
             ctg, verts, lo = ids[rec], self._found[p][1], first - offsets[p]
