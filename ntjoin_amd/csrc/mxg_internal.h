@@ -204,6 +204,15 @@ struct TimedSpan {
     int kind;  // 0 hash, 1 everything behind it (coarse timing), 2 reorder, 3 resolve, 4 emit (fine timing)
 };
 
+// what sketch_assemblies (sketch.hip) knows of an assembly's sketch while the step runs, and what mxg_sketch_pack leaves
+// for sketch_finish
+enum class AsmState : int {
+    Sync = 0,      // not (or no longer) in the streams: the synchronous path sketches it
+    Enqueued = 1,  // its batches are in the streams, their reports not read yet
+    Done = 2,      // its sketch is complete (an assembly without k-mers is, from the start)
+    Retry = 3,     // its batches did not all end the common way: enqueue it once more
+};
+
 }  // namespace mxg
 
 struct mxg_handle {
@@ -255,7 +264,7 @@ struct mxg_handle {
     // scratch reused across calls
     mxg::DevBuf scratch[4][40];  // indexed by mxg::Scratch (sketch.hip): one set per in-flight sketch driver (= stream)
     std::vector<mxg::Assembly *> pend_list;  // mxg_sketch_pack in flight: assemblies and how each was enqueued
-    std::vector<int> pend_state;
+    std::vector<mxg::AsmState> pend_state;
     std::vector<unsigned char> pend_dev;     // ... and whether its stretches went the device route (sketch_finish accepts those)
     mxg::DevBuf g_part;     // partitioned join (graph.hip): partition offsets of every bucketing block
     mxg::DevBuf g_recs1;    // two-level join: the coarse partitions' records

@@ -3235,9 +3235,52 @@ static SparsePlan sparse_plan(const mxg_handle *h, const Assembly *a)
     return sp;
 }
 
+// ---- small idioms of the host orchestration below ------------------------------------------------------------------
+static int lazy_event(mxg_handle *h, hipEvent_t &e)  // an event of the handle, created at its first use
+{
+    if (!e) MXG_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return MXG_OK;
+}
+// ... and entry i of a list of them that grows on demand
+static int lazy_event_at(mxg_handle *h, std::vector<hipEvent_t> &list, size_t i, hipEvent_t *e)
+{
+    while (list.size() <= i) {
+        hipEvent_t x = nullptr;
+        const int rc = lazy_event(h, x);
+        if (rc != MXG_OK) return rc;
+        list.push_back(x);
+    }
+    *e = list[i];
+    return MXG_OK;
+}
+static int wait_all_streams(mxg_handle *h)
+{
+    MXG_HIP(h, stream_wait(h->stream));
+    MXG_HIP(h, stream_wait(h->stream2));
+    for (hipStream_t sx : h->stream_x)
+        if (sx) MXG_HIP(h, stream_wait(sx));
+    return MXG_OK;
+}
+static int join_second_stream(mxg_handle *h)  // what follows on the handle's main stream runs behind the second stream's work too
+{
+    const int rc = lazy_event(h, h->ev_join);
+    if (rc != MXG_OK) return rc;
+    MXG_HIP(h, hipEventRecord(h->ev_join, h->stream2));
+    MXG_HIP(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    return MXG_OK;
+}
+static OutArrays out_arrays(Assembly *a, uint64_t n0 = 0) { return OutArrays{&a->d_hash, &a->d_pos, &a->d_rec, &a->d_fwd, n0}; }
+// The header word the pack kernels (k_pack_slot_dev, k_pack_part_dev) are given: -2 = the sketch is in flight, decide on the
+// device; otherwise what the host already knows: an empty assembly (0), or one that is not through the one-batch pipeline (-1:
+// the caller exchanges sizes first)
+static long long pack_header_code(AsmState s) { return s == AsmState::Enqueued ? -2ll : (s == AsmState::Done ? 0ll : -1ll); }
+// ... and the same three cases as dg_pack_slots_dev's mode (dgraph.hip): 1 = count and predicate on the device, 0 = the host's
+// count (an empty assembly), 2 = the host knows the sketch is not usable
+static uint32_t dg_pack_mode(AsmState s) { return s == AsmState::Enqueued ? 1u : (s == AsmState::Done ? 0u : 2u); }
+
 static int run_sketch_sync(mxg_handle *h, Assembly *a, const Tables &T, Driver &drv)
 {
-    OutArrays out{&a->d_hash, &a->d_pos, &a->d_rec, &a->d_fwd, 0};
+    OutArrays out = out_arrays(a);
     const SparsePlan sp = sparse_plan(h, a);
     int rc = sp.sparse ? drv.sparse_all(a, T, out, sp.tau_hi, sp.frac) : drv.dense_all(a->d_packed, T, out, true);
     if (rc != MXG_OK) return rc;
@@ -3331,6 +3374,29 @@ __global__ __launch_bounds__(1024) void k_part_starts(const long long *__restric
     }
 }
 
+// what a step (SketchStep) knows of one assembly
+struct AsmRun {
+    Tables T{};
+    SparsePlan plan{};
+    AsmState state = AsmState::Sync;
+    // Two ranges of SketchStep::items, the same until the assembly is enqueued a second time: [q_lo, q_hi) are the batches of the
+    // CURRENT attempt, whose reports evaluate() reads; [first_lo, first_hi) stay those of the FIRST attempt -- the batch the pack
+    // kernels look at (its stream slot's control words, its place4), and "was enqueued at all" for the statistics at the end of
+    // the step.  Both are empty for an assembly that never reached the streams.
+    size_t q_lo = 0, q_hi = 0, first_lo = 0, first_hi = 0;
+};
+
+// how one attempt at an assembly is cut into batches (cut_batches), and what its filter leaves for the batches behind the first
+struct AsmCut {
+    bool enqueue = false;  // false: nothing goes to the streams, the assembly stays on the synchronous path
+    bool use_bs = false;   // the k = 32 route: the bit-sliced filter runs over the whole assembly
+    bool sel_ok = false;   // ... and k_bs_select takes its batches (bgs: one geometry per batch)
+    std::vector<Driver::BatchGeom> gs;
+    std::vector<BsSelGeom> bgs;
+    hipEvent_t ev_hash = nullptr;   // enqueue_filter: "the filter has run" (several batches: those on other streams wait for it)
+    hipStream_t st_hash = nullptr;  // ... and the stream it ran on
+};
+
 // Every assembly is cut into batches of whole records (SPARSE_BATCH_KMERS) and EVERY batch of EVERY assembly is enqueued
 // completely -- hash -> order -> resolve (-> stretches on the device) -> emit -- alternating between the handle's two
 // streams with their own scratch, before the host waits once for both streams.  A batch starts in the assembly's sketch
@@ -3339,6 +3405,546 @@ __global__ __launch_bounds__(1024) void k_part_starts(const long long *__restric
 // latency-bound tail.  What did not end the common way (arena overflow, stretches the device route could not hold,
 // output beyond its estimate) is redone afterwards: from the candidate arrays when they are still intact in the
 // scratch, else through the synchronous path.
+// One SketchStep is one call of sketch_assemblies: its members are what the phases share, its methods are the phases.
+struct SketchStep {
+    struct Item {
+        size_t asm_i;
+        Driver::BatchGeom g;
+        int slot;
+        uint32_t n_cap;
+        uint32_t *hc;  // the batch's report (pinned)
+        bool bs;       // went through the k = 32 route (no candidate arrays to finish from)
+        uint32_t place4 = 0;  // stretches the batch's k_emit launch has placing blocks for (4 * n_place)
+    };
+    struct BatchSum {  // the reports of an assembly's batches, summed (good: every one of them ended the common way)
+        bool good = true;
+        uint64_t total = 0, n_cand = 0, gap_kmers = 0;
+    };
+    struct PackGeom { long long fixed; uint32_t grid; uint64_t out_cap; };  // what the two pack kernels have in common
+
+    mxg_handle *h;
+    Assembly *const *list;
+    size_t n;
+    bool fuse_graph;
+    const XchgPackReq *xp;
+    uint32_t n_str;
+    Driver drv0, drv1, drv2, drv3;
+    Driver *drvs[4] = {&drv0, &drv1, &drv2, &drv3};
+    bool one_stream, chain_modes, bs_env, bs_select, stagger, defer_emits, dbg_cold;
+    std::vector<AsmRun> runs;
+    std::vector<Item> items;
+    size_t last_on_slot[4] = {(size_t)-1, (size_t)-1, (size_t)-1, (size_t)-1};
+    size_t n_enq = 0, next_slot = 0;
+    int last_sel_slot = -1;  // the stream slot the last slice kernel of this call went to
+    bool fused = false;      // the graph stage ran behind the sketches, and nothing has invalidated it since
+    GraphBounds gb;
+    size_t n_fast = 0;  // assemblies whose every batch ended the common way
+    std::chrono::steady_clock::time_point t_cold;  // (the last cold_mark)
+
+    SketchStep(mxg_handle *h_, Assembly *const *list_, size_t n_, bool fuse_graph_, const XchgPackReq *xp_, uint32_t n_str_)
+        : h(h_), list(list_), n(n_), fuse_graph(fuse_graph_), xp(xp_), n_str(n_str_), drv0(h_, 0), drv1(h_, 1), drv2(h_, n_str_ > 2 ? 2 : 1),
+          drv3(h_, n_str_ > 3 ? 3 : 1), runs(n_)
+    {
+        // profiling (tools/pmc_r03.sh): every batch on the handle's main stream, so that no two kernels overlap.  Every batch then uses
+        // slot 0 (one scratch set, in stream order); the calls that keep one batch per assembly in flight for the stage behind them
+        // (mxg_sketch_graph, mxg_sketch_pack) need a scratch set per assembly and ignore the switch.
+        one_stream = knob_set(h, "MXG_ONE_STREAM") && !fuse_graph && !xp;
+        if (one_stream) {
+            drvs[1] = drvs[2] = drvs[3] = &drv0;
+            n_str = 1;
+        }
+        bs_env = env_u64(h, "MXG_BS", 1) != 0;
+        bs_select = env_u64(h, "MXG_BS_SELECT", 1) != 0;  // k_bs_select instead of count -> reorder -> resolve
+        const uint64_t stagger_knob = knob_u64(h, "MXG_STAGGER", 1);
+        stagger = stagger_knob != 0;
+        // (an assembly's k_emit behind the NEXT assembly's slice kernel, beside that assembly's stretch kernels: enqueued in its own
+        // place it starts when the next filter lets go of the GPU and lands on the next slice kernel, whose blocks need whole CUs --
+        // 529 us for the target's launch against 450 for the reference's under rocprofv3; MXG_DEFER_EMIT=0: in its own place)
+        defer_emits = knob_u64(h, "MXG_DEFER_EMIT", 1) != 0 && stagger_knob == 1;
+        chain_modes = fuse_graph || xp;  // (these two need one batch per assembly)
+        dbg_cold = knob_set(h, "MXG_DEBUG_COLD");  // (diagnostics: where the host's time goes before and between the enqueues)
+    }
+
+    void cold_mark(const char *what, size_t i)
+    {
+        if (!dbg_cold) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[mxg] sketch_assemblies: %s %zu: %.3f ms\n", what, i, std::chrono::duration<double, std::milli>(now - t_cold).count());
+        t_cold = now;
+    }
+
+    // the first batch of the assembly's first attempt (null: it never reached the streams)
+    const Item *first_item(size_t i) const { return runs[i].first_hi > runs[i].first_lo ? &items[runs[i].first_lo] : nullptr; }
+
+    // ---- enqueue -----------------------------------------------------------------------------------------------------
+    // the route of assembly i and its batches: host arithmetic, but for what bs_prepare uploads (c.enqueue stays false: not for the streams)
+    int cut_batches(size_t i, int attempt, AsmCut &c)
+    {
+        AsmRun &r = runs[i];
+        Assembly *a = list[i];
+        int rc;
+        r.plan = sparse_plan(h, a);
+        if (!r.plan.sparse || i >= MXG_MAX_ASSEMBLIES) return MXG_OK;
+        // the k = 32 route: the bit-sliced filter over the whole assembly, then one k_bs_select per batch (sketch_bs.hip); a second
+        // attempt (a batch did not end the common way: slices beyond their queues, stretches beyond the device route) and run
+        // tables with short runs between invalid bases take count -> reorder -> resolve behind the same bitmap
+        bool use_bs = bs_env && bs_possible(h, a);
+        bool sel_ok = use_bs && bs_select && (attempt == 0 || a->sel_again);
+        cold_mark_g(h, "(enqueue_asm begins)");
+        if (use_bs) {
+            if ((rc = bs_prepare(h, a)) != MXG_OK) return rc;
+            cold_mark_g(h, "bs_prepare");
+            use_bs = a->bs_ready;
+            if (use_bs && sel_ok && (a->sel_H_S != a->S_sparse || a->sel_H_w != h->cfg.w)) {
+                a->sel_H = bs_select_halo(a, a->S_sparse, h->cfg.w);
+                a->sel_H_S = a->S_sparse;
+                a->sel_H_w = h->cfg.w;
+            }
+            sel_ok = sel_ok && use_bs && a->sel_H != 0;
+        }
+        // k_bs_select has no candidate arrays to size: its batches are as large as the stretch budget and 32-bit k-mer counts allow
+        // (an assembly of 3 Gbp: two batches, ten launches in all, where the other route cuts seven)
+        const size_t n_ctg = r.T.ctg_rec->size();
+        for (int pass = sel_ok ? 0 : 1; pass < 2; ++pass) {
+            uint64_t budget = r.plan.batch_kmers;
+            if (pass == 0) {
+                const uint64_t big = env_u64(h, "MXG_SEL_BATCH_KMERS", 3600ull << 20);  // (k-mers of a batch are counted in 32 bits)
+                budget = std::min<uint64_t>(r.plan.gap_kmers ? r.plan.gap_kmers : big, big);
+                if (knob_set(h, "MXG_SPARSE_BATCH_KMERS")) budget = std::min<uint64_t>(budget, SPARSE_BATCH_KMERS);  // (test knob)
+            }
+            c.gs.clear();
+            c.bgs.clear();
+            for (size_t c0 = 0; c0 < n_ctg;) {
+                Driver::BatchGeom g;
+                drv0.batch_geom(r.T, c0, g, budget);
+                c.gs.push_back(g);
+                c0 = g.c1;
+            }
+            if (pass == 1) break;
+            for (size_t b = 0; sel_ok && b < c.gs.size(); ++b) {
+                c.bgs.push_back(drv0.sel_geom(a, c.gs[b], r.plan.frac));
+                sel_ok = c.bgs.back().ok;  // (strips and selected entries are counted in 32 bits: bs_select_geom checks them)
+            }
+            if (sel_ok) break;
+        }
+        cold_mark_g(h, "halo + batch geometry");
+        if (c.gs.empty() || (chain_modes && c.gs.size() > 1) || items.size() + c.gs.size() >= PINNED_SLOTS - 1) return MXG_OK;
+        c.use_bs = use_bs;
+        c.sel_ok = sel_ok && use_bs;
+        c.enqueue = true;
+        return MXG_OK;
+    }
+
+    // the k = 32 filter over assembly i, once per assembly, on the first batch's stream (drv)
+    int enqueue_filter(size_t i, AsmCut &c, Driver &drv)
+    {
+        Assembly *a = list[i];
+        int rc;
+        c.st_hash = drv.st;
+        // ... behind the slice kernel of the assembly before it when that runs on another stream: each of the two fills
+        // the register file, side by side they only take turns; the tails behind the slice kernel (stretches, emit)
+        // leave room.  Only for assemblies of 2^31 k-mers and more: there the free-running streams gain 1 % of the step
+        // (3.20 against 3.24 ms at 3 Gbp + 3 Gbp, tools/stagger_try.sh) and a filter that shares the GPU with a slice
+        // kernel takes 0.64 ms instead of 0.44 -- neither kernel's time says anything about the kernel any more; at
+        // 1 Gbp + 1 Gbp, where the tails weigh more, running free is 6 % faster and stays.  (MXG_STAGGER=0: never)
+        hipEvent_t behind = nullptr;
+        // (mxg_sketch_pack_parts: always -- the assembly before this one must END first, its part travels beside this filter)
+        if (stagger && !one_stream && last_sel_slot >= 0 && drvs[last_sel_slot] != &drv &&
+            (a->total_kmers >= (1ull << 31) || (xp && (xp->d_parts || xp->dg))))
+            behind = h->ev_sel_done[last_sel_slot];
+        if (c.sel_ok && (rc = drv.clear_sel_ctrl(c.bgs[0])) != MXG_OK) return rc;
+        if ((rc = bs_edges(h, a, drv.st)) != MXG_OK) return rc;  // (the two blocks that copy the edge chunks need not wait)
+        if (behind) MXG_HIP(h, hipStreamWaitEvent(drv.st, behind, 0));
+        if ((rc = drv.ev_begin(a->total_bases, true)) != MXG_OK) return rc;
+        if ((rc = bs_hash(h, a, runs[i].plan.tau_hi, drv.st)) != MXG_OK) return rc;
+        h->stat_bs_bases += a->total_bases;
+        if ((rc = drv.ev_end()) != MXG_OK) return rc;
+        if (c.gs.size() > 1) {
+            if ((rc = lazy_event_at(h, h->ev_bs, i, &c.ev_hash)) != MXG_OK) return rc;
+            MXG_HIP(h, hipEventRecord(c.ev_hash, drv.st));
+        }
+        return MXG_OK;
+    }
+
+    // batch b of assembly i -> a stream, behind the assembly's filter
+    int enqueue_batch(size_t i, int attempt, AsmCut &c, size_t b, OutArrays &out)
+    {
+        const SparsePlan &plan = runs[i].plan;
+        Assembly *a = list[i];
+        int rc;
+        // a single-batch assembly keeps the round-1 placement: the LAST assembly goes to driver 0 = the handle's main
+        // stream (whatever follows the sketches on that stream then waits for the other stream's chain, which has
+        // finished earlier); batches of a multi-batch assembly simply alternate
+        size_t sl;
+        if (one_stream) sl = 0;
+        else if (c.gs.size() == 1) sl = h->own_stream ? ((n - 1 - i) & 1) : (i & 1);
+        else sl = next_slot++ % n_str;
+        Driver &drv = *drvs[sl];
+        Item it;
+        it.asm_i = i;
+        it.g = c.gs[b];
+        it.slot = (int)sl;
+        it.n_cap = 0;
+        it.bs = c.sel_ok;
+        if (c.use_bs && attempt > 0) {
+            // (the bitmap of the first attempt is still there, and every stream has been waited for)
+        } else if (c.use_bs && b == 0) {
+            if ((rc = enqueue_filter(i, c, drv)) != MXG_OK) return rc;
+        } else if (c.use_bs && drv.st != c.st_hash) {
+            MXG_HIP(h, hipStreamWaitEvent(drv.st, c.ev_hash, 0));
+        }
+        it.hc = report_slot(h, items.size());
+        std::fill_n(it.hc, REPORT_WORDS, REPORT_UNSET);
+        Driver::ChainIO io;
+        io.dev_gaps = plan.dev_gaps;
+        {   // placing blocks for twice the stretches the plan expects of this batch (+ 256), at most for all the arrays hold; a
+            // batch that meets more than its launch can place reports so and is enqueued again with the density it met
+            const double expect = plan.gap_rate * (double)it.g.nk;
+            const uint32_t place4 = (uint32_t)std::min<double>((double)plan.gcap, 2.0 * expect + 256.0);
+            drv.set_gaps(plan.gcap, a->gap_rate_hint > 0 ? (place4 + 3u) / 4u : plan.gcap / 4u, a->gap_rate_hint > 0 ? expect : -1.0);
+            if (const uint64_t forced = knob_u64(h, "MXG_GAP_PLACE", 0))  // test knob: placing blocks for this many stretches
+                drv.set_gaps(plan.gcap, (uint32_t)std::min<uint64_t>((forced + 3u) / 4u, plan.gcap / 4u));
+            it.place4 = 4u * drv.n_place;
+        }
+        // tiles of 32 slices in k_emit (0.18 against 0.21 ms per step at 3 Gbp + 3 Gbp) unless stretches are so dense that
+        // most tiles of that size would hold one (the tile then searches the stretch keys per minimizer: repeat-rich
+        // sequence is 2 % slower with 32, 6 % with 64; tools/sweep_emit_ecb.sh)
+        io.ecb = plan.gap_rate * 32.0 * 64.0 * a->S_sparse < 0.5 ? 32u : 16u;
+        uint64_t *chain = h->d_chain.as<uint64_t>();
+        io.base_in = b == 0 ? nullptr : chain + (items.size() - 1);
+        io.base_out = c.gs.size() > 1 ? chain + items.size() : nullptr;
+        if (b > 0 && drvs[items.back().slot] != &drv) {  // predecessor on the other stream: wait for its count before the emit
+            if ((rc = lazy_event_at(h, h->ev_sync, items.size(), &io.wait)) != MXG_OK) return rc;
+            MXG_HIP(h, hipEventRecord(io.wait, drvs[items.back().slot]->st));
+        }
+        drv.n_out = chain_modes ? h->d_nmx.as<uint32_t>() + i : nullptr;
+        if (c.sel_ok) {
+            drv.defer_emit = defer_emits && !chain_modes && c.gs.size() == 1 && !one_stream;
+            if ((rc = drv.enqueue_sel(a, runs[i].T, it.g, c.bgs[b], plan.tau_hi, out, it.hc, &io)) != MXG_OK) return rc;
+            // the emits other drivers hold back (the assembly before this one): behind this slice kernel
+            for (Driver *od : drvs)
+                if (od != &drv && (rc = od->flush_emit(h->ev_sel_done[sl])) != MXG_OK) return rc;
+            last_sel_slot = (int)sl;
+        } else if ((rc = drv.enqueue_sparse(a, runs[i].T, it.g, drv.default_wave_cap(a->S_sparse, plan.frac), plan.tau_hi, out, it.hc,
+                                            &it.n_cap, &io, a->cand_hints[b], c.use_bs ? a->d_bs_out.as<uint32_t>() + 4 : nullptr)) != MXG_OK)
+            return rc;
+        last_on_slot[sl] = items.size();
+        items.push_back(it);
+        return MXG_OK;
+    }
+
+    // the batches of assembly i -> the streams (attempt 0; attempt 1: once more for an assembly whose batches did not all end
+    // the common way, now sized by what the first attempt saw: stretch density, candidate counts, slice capacity)
+    int enqueue_asm(size_t i, int attempt)
+    {
+        AsmRun &r = runs[i];
+        Assembly *a = list[i];
+        int rc;
+        r.q_lo = r.q_hi = items.size();
+        if (attempt == 0) r.first_lo = r.first_hi = items.size();
+        r.state = AsmState::Sync;
+        AsmCut c;
+        if ((rc = cut_batches(i, attempt, c)) != MXG_OK || !c.enqueue) return rc;
+        OutArrays out = out_arrays(a);
+        // chain words: [item] = where the NEXT batch starts
+        MXG_HIP(h, h->d_chain.ensure((size_t)PINNED_SLOTS * 8));
+        if (a->cand_hints.size() != c.gs.size()) a->cand_hints.assign(c.gs.size(), a->full_grid_once ? 0xFFFFFFFEu : 0u);
+        a->full_grid_once = false;
+        for (size_t b = 0; b < c.gs.size(); ++b)
+            if ((rc = enqueue_batch(i, attempt, c, b, out)) != MXG_OK) return rc;
+        r.state = AsmState::Enqueued;
+        r.q_hi = items.size();
+        if (attempt == 0) r.first_hi = r.q_hi;
+        return MXG_OK;
+    }
+
+    // ---- mxg_sketch_pack and its kin -----------------------------------------------------------------------------------
+    PackGeom pack_geom(size_t i, uint64_t cap) const
+    {
+        const AsmState s = runs[i].state;
+        return PackGeom{pack_header_code(s), s == AsmState::Enqueued ? (uint32_t)std::max<uint64_t>((cap + 255) / 256, 1) : 1u, out_capacity(list[i])};
+    }
+
+    // assembly i's exchange part (or, xp->dg, its item slots of the partitioned graph stage) on stream st, and the event that says so.
+    // drv: the driver that ran its one batch (null: the assembly is not in the streams, the header says so)
+    int pack_part(size_t i, hipStream_t st, Driver *drv, uint32_t place4)
+    {
+        Assembly *a = list[i];
+        const AsmState s = runs[i].state;
+        const uint32_t dev_gaps = s == AsmState::Enqueued && runs[i].plan.dev_gaps ? 1u : 0u;
+        int rc;
+        if (xp->dg) {  // the partitioned graph stage's item slots instead of an exchange part
+            rc = dg_pack_slots_dev(h, a, (uint32_t)i, *xp->dg, st, dg_pack_mode(s), h->d_nmx.as<uint32_t>() + i,
+                                   drv ? drv->sc(SC_CTRL).as<uint32_t>() : nullptr, out_capacity(a), dev_gaps, place4);
+            if (rc != MXG_OK) return rc;
+        } else {
+            const uint64_t cap = xp->caps[i];
+            const PackGeom pg = pack_geom(i, cap);
+            unsigned char *part = static_cast<unsigned char *>(xp->d_parts[i]);
+            const uint64_t rcap = xp->rcaps[i], n_rec = a->recs.size();
+            uint32_t *starts = reinterpret_cast<uint32_t *>(part + XCHG_PART_HEAD + 12 * cap);
+            const bool with_starts = s == AsmState::Enqueued && n_rec <= rcap && n_rec != 0;
+            if (with_starts) MXG_HIP(h, hipMemsetAsync(starts, 0xFF, 4 * n_rec, st));
+            hipLaunchKernelGGL(k_pack_part_dev, dim3(pg.grid), dim3(256), 0, st, a->d_hash.as<uint64_t>(), a->d_pos.as<uint32_t>(),
+                               a->d_rec.as<uint32_t>(), h->d_nmx.as<uint32_t>() + i,
+                               drv ? drv->sc(SC_CTRL).as<uint32_t>() : h->d_nmx.as<uint32_t>(), pg.out_cap, cap, pg.fixed,
+                               reinterpret_cast<long long *>(part), part + XCHG_PART_HEAD, (uint32_t)std::min<uint64_t>(n_rec, 0xFFFFFFFFu),
+                               (uint32_t)std::min<uint64_t>(rcap, 0xFFFFFFFFu), dev_gaps, place4);
+            if (with_starts)
+                hipLaunchKernelGGL(k_part_starts, dim3(1), dim3(1024), 0, st, reinterpret_cast<const long long *>(part), starts, (uint32_t)n_rec);
+            MXG_HIP(h, hipGetLastError());
+        }
+        if ((rc = lazy_event(h, h->ev_part[i])) != MXG_OK) return rc;
+        MXG_HIP(h, hipEventRecord(h->ev_part[i], st));
+        return MXG_OK;
+    }
+
+    // mxg_sketch_pack: every assembly's sketch into its region of the one exchange slot, on the handle's main stream
+    void pack_slots()
+    {
+        unsigned char *base = static_cast<unsigned char *>(xp->d_slot);
+        uint64_t off = xp->head_bytes;
+        for (size_t i = 0; i < n; ++i) {
+            Assembly *a = list[i];
+            const uint64_t cap = xp->caps[i];
+            const PackGeom pg = pack_geom(i, cap);
+            const Item *it = first_item(i);
+            hipLaunchKernelGGL(k_pack_slot_dev, dim3(pg.grid), dim3(256), 0, h->stream, a->d_hash.as<uint64_t>(), a->d_pos.as<uint32_t>(),
+                               a->d_rec.as<uint32_t>(), h->d_nmx.as<uint32_t>() + i, drvs[it ? it->slot : 0]->sc(SC_CTRL).as<uint32_t>(),
+                               pg.out_cap, cap, pg.fixed, reinterpret_cast<long long *>(base) + i, base + off,
+                               runs[i].plan.dev_gaps ? 1u : 0u, it ? it->place4 : 0u);
+            off += 16 * cap;
+        }
+    }
+
+    // the pack kernels behind the sketches, and what sketch_finish needs to complete the step
+    int pack_all()
+    {
+        int rc;
+        // the second stream joins the first; the pack kernels follow the sketches on it and read the counts there.  No
+        // host sync: mxg_sketch_finish completes the bookkeeping after the caller's next sync on this stream.
+        if ((rc = join_second_stream(h)) != MXG_OK) return rc;
+        if (xp->d_parts || xp->dg) {  // (parts: what was enqueued is packed already; the others say 0 / -1)
+            for (size_t i = 0; i < n; ++i)
+                if (runs[i].state != AsmState::Enqueued && (rc = pack_part(i, h->stream, nullptr, 0)) != MXG_OK) return rc;
+        } else {
+            pack_slots();
+        }
+        MXG_HIP(h, hipGetLastError());
+        h->pend_list.assign(list, list + n);
+        h->pend_state.resize(n);
+        h->pend_dev.assign(n, 0);
+        for (size_t i = 0; i < n; ++i) {
+            h->pend_state[i] = runs[i].state;
+            h->pend_dev[i] = runs[i].plan.dev_gaps ? 1 : 0;
+        }
+        return MXG_OK;
+    }
+
+    // ---- mxg_sketch_graph ------------------------------------------------------------------------------------------------
+    // the graph stage behind the sketches, when every assembly of the handle is in the streams with one batch
+    int enqueue_fused_graph()
+    {
+        if (!(fuse_graph && n_enq == n && n == h->asms.size() && n <= MXG_MAX_ASSEMBLIES)) return MXG_OK;
+        for (size_t i = 0; i < n; ++i)
+            if (list[i] != h->asms[i]) return MXG_OK;
+        // the second stream joins the first; the graph stage follows the sketches on it
+        int rc;
+        if ((rc = join_second_stream(h)) != MXG_OK) return rc;
+        for (size_t i = 0; i < n; ++i) {
+            Assembly *a = list[i];
+            const uint64_t cap = out_capacity(a);
+            // (2 per window on i.i.d. sequence; repeat-rich sequence reaches ~3.8: what an earlier sketch of the assembly ended
+            // with, 10 % on top, so that the fused graph survives on exactly the inputs the output arrays were widened for)
+            const uint64_t iid = (uint64_t)(2.3 * (double)a->total_kmers / (double)(h->cfg.w + 1)) + 2048;
+            gb.n_bound[i] = std::min<uint64_t>(cap, std::max<uint64_t>(iid, a->n_mx_seen + a->n_mx_seen / 10 + 2048));
+            gb.n_ptr[i] = h->d_nmx.as<uint32_t>() + i;
+        }
+        fused = build_graph(h, GRAPH_FULL, nullptr, 0, &gb) == MXG_OK;  // (its sync is this call's sync)
+        return MXG_OK;
+    }
+
+    // ---- after the wait: what became of the batches --------------------------------------------------------------------------
+    // (the one-call modes have already used the counts on the device: a stretch deferred to the host undoes them)
+    bool ended_well(size_t i, size_t q) const { return BatchReport{items[q].hc}.ended_well(runs[i].plan.dev_gaps, !chain_modes, items[q].bs); }
+
+    BatchSum summarize(size_t i)
+    {
+        Assembly *a = list[i];
+        BatchSum s;
+        for (size_t q = runs[i].q_lo; q < runs[i].q_hi; ++q) {
+            const BatchReport r{items[q].hc};
+            s.good = s.good && ended_well(i, q);
+            s.total += r.total();
+            s.n_cand += r.n_cand();
+            s.gap_kmers += r.gap_kmers();
+            if (items[q].bs) h->stat_slice_stretches += r.sel_requests();
+            // what the batches saw of candidate-free stretches sizes the next sketch's batches (sparse_plan): real genomes hold
+            // far more of them than the i.i.d. estimate (satellite arrays, low-complexity runs)
+            // (1e-12: "a sketch has reported" -- an assembly whose stretches all went through k_sel_stretch leaves none over)
+            if (r.reported() && items[q].g.nk) a->gap_rate_hint = std::max({a->gap_rate_hint, (double)r.n_stretches() / (double)items[q].g.nk, 1e-12});
+        }
+        return s;
+    }
+
+    // (diagnostics, MXG_DEBUG_BATCH: the reports of an assembly's batches)
+    void print_reports(size_t i, uint64_t cap) const
+    {
+        for (size_t q = runs[i].q_lo; q < runs[i].q_hi; ++q) {
+            const BatchReport r{items[q].hc};
+            fprintf(stderr, "[mxg] asm %zu batch %zu: ovf %u gaps %u sel %u flag %u cand %u nB %u total %u obase %u gapk %u (cap %llu)\n", i,
+                    q - runs[i].q_lo, r.arena_need(), r.n_stretches(), r.n_selected(), r.w[RW_REDO], r.n_cand(), r.w[RW_STRETCH_MX],
+                    (uint32_t)r.total(), (uint32_t)r.out_base(), r.w[RW_GAP_KMERS], (unsigned long long)cap);
+        }
+    }
+
+    // every batch ended the common way and the sketch fits its arrays: it is complete, once the stretches the device route left
+    // to the host (if any) are merged in
+    int accept(size_t i, const BatchSum &s)
+    {
+        Assembly *a = list[i];
+        const size_t q0 = runs[i].q_lo, q1 = runs[i].q_hi;
+        // stretches the device route left to the host (too long, too many minimizers, invalid bases inside)
+        std::vector<uint4> deferred;
+        for (size_t q = q0; q < q1 && !chain_modes; ++q) take_deferred(h, items[q].hc, deferred);
+        uint64_t n_final = s.total;
+        if (!deferred.empty()) {
+            int rc;
+            if ((rc = drv0.merge_deferred(a, runs[i].T, deferred, s.total, &n_final)) != MXG_OK) return rc;
+            h->stat_deferred += deferred.size();
+            fused = false;  // (the graph stage ran on a sketch without them)
+        }
+        a->n_mx = n_final;
+        a->has_sketch = true;
+        h->stat_candidates += s.n_cand;
+        h->stat_dense_kmers += s.gap_kmers;
+        for (size_t q = q0; q < q1; ++q) a->cand_hints[q - q0] = BatchReport{items[q].hc}.n_cand();
+        a->cand_hint = a->cand_hints[0];
+        runs[i].state = AsmState::Done;
+        if (fused && s.total > gb.n_bound[i]) fused = false;  // a sketch outgrew the bound the graph stage was sized for
+        ++n_fast;
+        return MXG_OK;
+    }
+
+    // the assembly's one batch from the candidate arrays in its driver's scratch, the general way (staging emit, dense fix-up of
+    // the stretches, merge)
+    int finish_from_scratch(size_t i)
+    {
+        Assembly *a = list[i];
+        const Item &it = items[runs[i].q_lo];
+        Driver &drv = *drvs[it.slot];
+        OutArrays out = out_arrays(a);
+        uint32_t ctrl_copy[REPORT_WORDS];
+        std::copy_n(it.hc, REPORT_WORDS, ctrl_copy);
+        int rc;
+        if ((rc = drv.complete_batch(a, runs[i].T, it.g, out, BatchReport{ctrl_copy}, it.n_cap)) != MXG_OK) return rc;
+        MXG_HIP(h, hipStreamSynchronize(drv.st));
+        a->n_mx = out.n;
+        a->has_sketch = true;
+        runs[i].state = AsmState::Done;
+        return MXG_OK;
+    }
+
+    // asks for the second attempt, and leaves it what the first one saw
+    void ask_retry(size_t i)
+    {
+        Assembly *a = list[i];
+        const size_t q0 = runs[i].q_lo, q1 = runs[i].q_hi;
+        for (size_t q = q0; q < q1; ++q) {
+            const BatchReport r{items[q].hc};
+            if (r.reported() && r.arena_need() != 0) h->arena_cap_hint = std::max<uint64_t>(h->arena_cap_hint, (uint64_t)r.arena_need() + 64);
+        }
+        // (k_bs_select again unless the slice kernel itself gave up somewhere -- a slice beyond its queue with no region left,
+        // more selected candidates than a slice's room: RW_SLICE_GAVE_UP -- and not merely more stretches than a batch holds)
+        a->sel_again = true;
+        for (size_t q = q0; q < q1; ++q)
+            if (items[q].bs && items[q].hc[RW_SLICE_GAVE_UP] != 0) a->sel_again = false;
+        a->cand_hints.clear();  // (the batches will be cut differently)
+        a->cand_hint = 0xFFFFFFFEu;
+        a->full_grid_once = true;
+        ++h->stat_retries;
+        runs[i].state = AsmState::Retry;
+    }
+
+    // several batches: keep the leading ones that ended the common way AND lie where they belong (a batch starts
+    // where its predecessors end), redo the first bad one and everything behind it batch by batch through the
+    // synchronous route.  That route finishes stretches from the host, so it takes the threshold of the host route
+    // (18 candidates per window: a stretch per ~10^8 k-mers instead of one per ~2 x 10^6).
+    int keep_head_redo_tail(size_t i)
+    {
+        Assembly *a = list[i];
+        const size_t q0 = runs[i].q_lo, q1 = runs[i].q_hi;
+        const uint64_t cap = out_capacity(a);
+        uint64_t offset = 0, nc = 0, gk = 0;
+        size_t j = q0;
+        for (; j < q1; ++j) {
+            const BatchReport r{items[j].hc};
+            if (!(ended_well(i, j) && r.out_base() == offset && offset + r.total() <= cap)) break;
+            offset += r.total();
+            nc += r.n_cand();
+            gk += r.gap_kmers();
+            a->cand_hints[j - q0] = r.n_cand();
+        }
+        for (size_t q = j; q < q1; ++q) {  // (next time: the whole grid for what did not report, the count for what did)
+            const BatchReport r{items[q].hc};
+            a->cand_hints[q - q0] = r.reported() && r.n_cand() != 0 ? r.n_cand() : 0xFFFFFFFEu;
+        }
+        a->cand_hint = a->cand_hints[0];
+        SparsePlan rp = runs[i].plan;
+        if (!h->cfg.cand_per_window && 18.0 / (double)h->cfg.w <= 0.125) {
+            rp.frac = 18.0 / (double)h->cfg.w;
+            rp.tau_hi = std::max(2u, (uint32_t)std::min<double>(4294967294.0, rp.frac * 4294967296.0) & ~1u);
+        }
+        OutArrays out = out_arrays(a, offset);
+        h->stat_candidates += nc;
+        h->stat_dense_kmers += gk;
+        h->stat_batches_redone += q1 - j;
+        if (j == q0) ++h->stat_sync_assemblies;
+        // (the batches that are kept may have left stretches to the host: their lists are read before anything reuses the slots)
+        std::vector<uint4> deferred;
+        for (size_t q = q0; q < j; ++q) take_deferred(h, items[q].hc, deferred);
+        int rc;
+        if ((rc = drv0.sparse_all(a, runs[i].T, out, rp.tau_hi, rp.frac, items[j].g.c0)) != MXG_OK) return rc;
+        MXG_HIP(h, hipStreamSynchronize(drv0.st));
+        uint64_t n_final = out.n;
+        if (!deferred.empty()) {
+            if ((rc = drv0.merge_deferred(a, runs[i].T, deferred, out.n, &n_final)) != MXG_OK) return rc;
+            h->stat_deferred += deferred.size();
+        }
+        a->n_mx = n_final;
+        a->has_sketch = true;
+        runs[i].state = AsmState::Done;
+        return MXG_OK;
+    }
+
+    // what became of assembly i's batches: Done = its sketch is complete, Retry = enqueue it once more, Sync = synchronous path
+    int evaluate(size_t i, bool final)
+    {
+        const size_t q0 = runs[i].q_lo, n_batches = runs[i].q_hi - runs[i].q_lo;
+        const uint64_t cap = out_capacity(list[i]);
+        const BatchSum s = summarize(i);
+        const bool fits = s.good && s.total <= cap;
+        if (!fits && knob_set(h, "MXG_DEBUG_BATCH")) print_reports(i, cap);
+        const BatchReport first{items[q0].hc};
+        if (fits) return accept(i, s);
+        // one batch, no arena overflow, and its candidate arrays are still intact in the driver's scratch: finish from
+        // there the general way (staging emit, dense fix-up of the stretches, merge) instead of redoing the batch
+        if (n_batches == 1 && !items[q0].bs && first.arena_need() == 0 && first.reported() && last_on_slot[items[q0].slot] == q0)
+            return finish_from_scratch(i);
+        // several batches, first attempt: once more through the streams (a few ms per Gbp; the synchronous route costs
+        // ten times that), with batches sized for the stretch density just seen (gap_rate_hint, above), every grid sized by
+        // the batch's own candidate count where it reported one, and slices as large as the largest wave asked for
+        if ((n_batches > 1 || (items[q0].bs && runs[i].plan.dev_gaps)) && !chain_modes && !final) {
+            ask_retry(i);
+            return MXG_OK;
+        }
+        // several batches, no further attempt: the good leading batches stay, the tail goes through the synchronous route
+        if (n_batches > 1 && !chain_modes) return keep_head_redo_tail(i);
+        runs[i].state = AsmState::Sync;  // redo synchronously
+        return MXG_OK;
+    }
+};
+
 // fuse_graph: also run the graph stage, enqueued BEHIND the sketches with upper bounds for the sizes and the counts read
 // on the device (one host sync for the whole step; needs one batch per assembly).  xp: mxg_sketch_pack.
 int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_graph, const XchgPackReq *xp)
@@ -3355,493 +3961,63 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
     // (emit, stretch fix-up) has another batch's hash kernel to run beside.  Two are enough: measured on MI355X at 3 Gbp +
     // 3 Gbp, 1072 / 1076 / 1046 Gbp/s with 2 / 3 / 4 streams -- the sum of the kernels' own times (9 ms per step under
     // rocprofv3) already overlaps into 5.6 ms of wall time
-    uint32_t n_str = (uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(2, env_u64(h, "MXG_STREAMS", 2)));
+    const uint32_t n_str = (uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(2, env_u64(h, "MXG_STREAMS", 2)));
     for (uint32_t x = 0; x + 2 < n_str; ++x)
         if (!h->stream_x[x]) MXG_HIP(h, hipStreamCreateWithFlags(&h->stream_x[x], hipStreamNonBlocking));
-    Driver drv0(h, 0), drv1(h, 1), drv2(h, n_str > 2 ? 2 : 1), drv3(h, n_str > 3 ? 3 : 1);
-    // profiling (tools/pmc_r03.sh): every batch on the handle's main stream, so that no two kernels overlap.  Every batch then uses
-    // slot 0 (one scratch set, in stream order); the calls that keep one batch per assembly in flight for the stage behind them
-    // (mxg_sketch_graph, mxg_sketch_pack) need a scratch set per assembly and ignore the switch.
-    const bool one_stream = knob_set(h, "MXG_ONE_STREAM") && !fuse_graph && !xp;
-    Driver *drvs[4] = {&drv0, one_stream ? &drv0 : &drv1, one_stream ? &drv0 : &drv2, one_stream ? &drv0 : &drv3};
-    if (one_stream) n_str = 1;
-    struct Item {
-        size_t asm_i;
-        Driver::BatchGeom g;
-        int slot;
-        uint32_t n_cap;
-        uint32_t *hc;  // the batch's report (pinned)
-        bool bs;       // went through the k = 32 route (no candidate arrays to finish from)
-        uint32_t place4 = 0;  // stretches the batch's k_emit launch has placing blocks for (4 * n_place)
-    };
-    const bool bs_env = env_u64(h, "MXG_BS", 1) != 0;
-    const bool bs_select = env_u64(h, "MXG_BS_SELECT", 1) != 0;  // k_bs_select instead of count -> reorder -> resolve
-    std::vector<Tables> tabs(n);
-    std::vector<int> state(n, 0);  // 0 = synchronous path, 1 = enqueued, 2 = done
-    std::vector<SparsePlan> plans(n);
-    std::vector<Item> items;
-    std::vector<size_t> item0(n + 1, 0);
-    size_t last_on_slot[4] = {(size_t)-1, (size_t)-1, (size_t)-1, (size_t)-1};
-    size_t n_enq = 0, next_slot = 0;
-    int last_sel_slot = -1;  // the stream slot the last slice kernel of this call went to
-    const bool stagger = knob_u64(h, "MXG_STAGGER", 1) != 0;
-    // (an assembly's k_emit behind the NEXT assembly's slice kernel, beside that assembly's stretch kernels: enqueued in its own
-    // place it starts when the next filter lets go of the GPU and lands on the next slice kernel, whose blocks need whole CUs --
-    // 529 us for the target's launch against 450 for the reference's under rocprofv3; MXG_DEFER_EMIT=0: in its own place)
-    const bool defer_emits = knob_u64(h, "MXG_DEFER_EMIT", 1) != 0 && knob_u64(h, "MXG_STAGGER", 1) == 1;
+    SketchStep s(h, list, n, fuse_graph, xp, n_str);
     for (int q = 0; q < 4; ++q)
-        if (!h->ev_sel_done[q]) MXG_HIP(h, hipEventCreateWithFlags(&h->ev_sel_done[q], hipEventDisableTiming));
-    const bool chain_modes = fuse_graph || xp;  // (these two need one batch per assembly)
-    // the batches of assembly i -> the streams (attempt 0; attempt 1: once more for an assembly whose batches did not all end
-    // the common way, now sized by what the first attempt saw: stretch density, candidate counts, slice capacity)
-    std::vector<size_t> q_lo(n, 0), q_hi(n, 0);
-    auto enqueue_asm = [&](size_t i, int attempt) -> int {
-        q_lo[i] = q_hi[i] = items.size();
-        state[i] = 0;
-        plans[i] = sparse_plan(h, list[i]);
-        if (!plans[i].sparse || i >= MXG_MAX_ASSEMBLIES) return MXG_OK;
-        // the k = 32 route: the bit-sliced filter over the whole assembly, then one k_bs_select per batch (sketch_bs.hip); a second
-        // attempt (a batch did not end the common way: slices beyond their queues, stretches beyond the device route) and run
-        // tables with short runs between invalid bases take count -> reorder -> resolve behind the same bitmap
-        bool use_bs = bs_env && bs_possible(h, list[i]);
-        bool sel_ok = use_bs && bs_select && (attempt == 0 || list[i]->sel_again);
-        cold_mark_g(h, "(enqueue_asm begins)");
-        if (use_bs) {
-            if ((rc = bs_prepare(h, list[i])) != MXG_OK) return rc;
-            cold_mark_g(h, "bs_prepare");
-            use_bs = list[i]->bs_ready;
-            Assembly *a = list[i];
-            if (use_bs && sel_ok && (a->sel_H_S != a->S_sparse || a->sel_H_w != h->cfg.w)) {
-                a->sel_H = bs_select_halo(a, a->S_sparse, h->cfg.w);
-                a->sel_H_S = a->S_sparse;
-                a->sel_H_w = h->cfg.w;
-            }
-            sel_ok = sel_ok && use_bs && a->sel_H != 0;
-        }
-        // k_bs_select has no candidate arrays to size: its batches are as large as the stretch budget and 32-bit k-mer counts allow
-        // (an assembly of 3 Gbp: two batches, ten launches in all, where the other route cuts seven)
-        std::vector<Driver::BatchGeom> gs;
-        std::vector<BsSelGeom> bgs;
-        const size_t n_ctg = tabs[i].ctg_rec->size();
-        for (int pass = sel_ok ? 0 : 1; pass < 2; ++pass) {
-            uint64_t budget = plans[i].batch_kmers;
-            if (pass == 0) {
-                const uint64_t big = env_u64(h, "MXG_SEL_BATCH_KMERS", 3600ull << 20);  // (k-mers of a batch are counted in 32 bits)
-                budget = std::min<uint64_t>(plans[i].gap_kmers ? plans[i].gap_kmers : big, big);
-                if (knob_set(h, "MXG_SPARSE_BATCH_KMERS")) budget = std::min<uint64_t>(budget, SPARSE_BATCH_KMERS);  // (test knob)
-            }
-            gs.clear();
-            bgs.clear();
-            for (size_t c0 = 0; c0 < n_ctg;) {
-                Driver::BatchGeom g;
-                drv0.batch_geom(tabs[i], c0, g, budget);
-                gs.push_back(g);
-                c0 = g.c1;
-            }
-            if (pass == 1) break;
-            for (size_t b = 0; sel_ok && b < gs.size(); ++b) {
-                bgs.push_back(drv0.sel_geom(list[i], gs[b], plans[i].frac));
-                sel_ok = bgs.back().ok;  // (strips and selected entries are counted in 32 bits: bs_select_geom checks them)
-            }
-            if (sel_ok) break;
-        }
-        cold_mark_g(h, "halo + batch geometry");
-        if (gs.empty() || (chain_modes && gs.size() > 1) || items.size() + gs.size() >= PINNED_SLOTS - 1) return MXG_OK;
-        sel_ok = sel_ok && use_bs;
-        hipEvent_t ev_hash = nullptr;
-        hipStream_t st_hash = nullptr;
-        OutArrays out{&list[i]->d_hash, &list[i]->d_pos, &list[i]->d_rec, &list[i]->d_fwd, 0};
-        // chain words: [item] = where the NEXT batch starts
-        MXG_HIP(h, h->d_chain.ensure((size_t)PINNED_SLOTS * 8));
-        if (list[i]->cand_hints.size() != gs.size()) list[i]->cand_hints.assign(gs.size(), list[i]->full_grid_once ? 0xFFFFFFFEu : 0u);
-        list[i]->full_grid_once = false;
-        for (size_t b = 0; b < gs.size(); ++b) {
-            // a single-batch assembly keeps the round-1 placement: the LAST assembly goes to driver 0 = the handle's main
-            // stream (whatever follows the sketches on that stream then waits for the other stream's chain, which has
-            // finished earlier); batches of a multi-batch assembly simply alternate
-            size_t sl;
-            if (one_stream) sl = 0;
-            else if (gs.size() == 1) sl = h->own_stream ? ((n - 1 - i) & 1) : (i & 1);
-            else sl = next_slot++ % n_str;
-            Driver &drv = *drvs[sl];
-            Item it;
-            it.asm_i = i;
-            it.g = gs[b];
-            it.slot = (int)sl;
-            it.n_cap = 0;
-            it.bs = sel_ok;
-            if (use_bs && attempt > 0) {
-                // (the bitmap of the first attempt is still there, and every stream has been waited for)
-            } else if (use_bs && b == 0) {  // the filter, once per assembly, on the first batch's stream
-                st_hash = drv.st;
-                // ... behind the slice kernel of the assembly before it when that runs on another stream: each of the two fills
-                // the register file, side by side they only take turns; the tails behind the slice kernel (stretches, emit)
-                // leave room.  Only for assemblies of 2^31 k-mers and more: there the free-running streams gain 1 % of the step
-                // (3.20 against 3.24 ms at 3 Gbp + 3 Gbp, tools/stagger_try.sh) and a filter that shares the GPU with a slice
-                // kernel takes 0.64 ms instead of 0.44 -- neither kernel's time says anything about the kernel any more; at
-                // 1 Gbp + 1 Gbp, where the tails weigh more, running free is 6 % faster and stays.  (MXG_STAGGER=0: never)
-                hipEvent_t behind = nullptr;
-                // (mxg_sketch_pack_parts: always -- the assembly before this one must END first, its part travels beside this filter)
-                if (stagger && !one_stream && last_sel_slot >= 0 && drvs[last_sel_slot] != &drv &&
-                    (list[i]->total_kmers >= (1ull << 31) || (xp && (xp->d_parts || xp->dg))))
-                    behind = h->ev_sel_done[last_sel_slot];
-                if (sel_ok && (rc = drv.clear_sel_ctrl(bgs[b])) != MXG_OK) return rc;
-                if ((rc = bs_edges(h, list[i], drv.st)) != MXG_OK) return rc;  // (the two blocks that copy the edge chunks need not wait)
-                if (behind) MXG_HIP(h, hipStreamWaitEvent(drv.st, behind, 0));
-                if ((rc = drv.ev_begin(list[i]->total_bases, true)) != MXG_OK) return rc;
-                if ((rc = bs_hash(h, list[i], plans[i].tau_hi, drv.st)) != MXG_OK) return rc;
-                h->stat_bs_bases += list[i]->total_bases;
-                if ((rc = drv.ev_end()) != MXG_OK) return rc;
-                if (gs.size() > 1) {
-                    while (h->ev_bs.size() <= i) {
-                        hipEvent_t e;
-                        MXG_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                        h->ev_bs.push_back(e);
-                    }
-                    ev_hash = h->ev_bs[i];
-                    MXG_HIP(h, hipEventRecord(ev_hash, drv.st));
-                }
-            } else if (use_bs && drv.st != st_hash) {
-                MXG_HIP(h, hipStreamWaitEvent(drv.st, ev_hash, 0));
-            }
-            it.hc = report_slot(h, items.size());
-            std::fill_n(it.hc, REPORT_WORDS, REPORT_UNSET);
-            Driver::ChainIO io;
-            io.dev_gaps = plans[i].dev_gaps;
-            {   // placing blocks for twice the stretches the plan expects of this batch (+ 256), at most for all the arrays hold; a
-                // batch that meets more than its launch can place reports so and is enqueued again with the density it met
-                const double expect = plans[i].gap_rate * (double)it.g.nk;
-                const uint32_t place4 = (uint32_t)std::min<double>((double)plans[i].gcap, 2.0 * expect + 256.0);
-                drv.set_gaps(plans[i].gcap, list[i]->gap_rate_hint > 0 ? (place4 + 3u) / 4u : plans[i].gcap / 4u,
-                             list[i]->gap_rate_hint > 0 ? expect : -1.0);
-                if (const uint64_t forced = knob_u64(h, "MXG_GAP_PLACE", 0))  // test knob: placing blocks for this many stretches
-                    drv.set_gaps(plans[i].gcap, (uint32_t)std::min<uint64_t>((forced + 3u) / 4u, plans[i].gcap / 4u));
-                it.place4 = 4u * drv.n_place;
-            }
-            // tiles of 32 slices in k_emit (0.18 against 0.21 ms per step at 3 Gbp + 3 Gbp) unless stretches are so dense that
-            // most tiles of that size would hold one (the tile then searches the stretch keys per minimizer: repeat-rich
-            // sequence is 2 % slower with 32, 6 % with 64; tools/sweep_emit_ecb.sh)
-            io.ecb = plans[i].gap_rate * 32.0 * 64.0 * list[i]->S_sparse < 0.5 ? 32u : 16u;
-            uint64_t *chain = h->d_chain.as<uint64_t>();
-            io.base_in = b == 0 ? nullptr : chain + (items.size() - 1);
-            io.base_out = gs.size() > 1 ? chain + items.size() : nullptr;
-            if (b > 0 && drvs[items.back().slot] != &drv) {  // predecessor on the other stream: wait for its count before the emit
-                while (h->ev_sync.size() <= items.size()) {
-                    hipEvent_t e;
-                    MXG_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                    h->ev_sync.push_back(e);
-                }
-                hipEvent_t e = h->ev_sync[items.size()];
-                MXG_HIP(h, hipEventRecord(e, drvs[items.back().slot]->st));
-                io.wait = e;
-            }
-            drv.n_out = nullptr;
-            if (fuse_graph || xp) {
-                MXG_HIP(h, h->d_nmx.ensure(MXG_MAX_ASSEMBLIES * 4));
-                drv.n_out = h->d_nmx.as<uint32_t>() + i;
-            }
-            if (sel_ok) {
-                drv.defer_emit = defer_emits && !chain_modes && gs.size() == 1 && !one_stream;
-                if ((rc = drv.enqueue_sel(list[i], tabs[i], it.g, bgs[b], plans[i].tau_hi, out, it.hc, &io)) != MXG_OK) return rc;
-                // the emits other drivers hold back (the assembly before this one): behind this slice kernel
-                for (Driver *od : drvs)
-                    if (od != &drv && (rc = od->flush_emit(h->ev_sel_done[sl])) != MXG_OK) return rc;
-                last_sel_slot = (int)sl;
-            } else if ((rc = drv.enqueue_sparse(list[i], tabs[i], it.g, drv.default_wave_cap(list[i]->S_sparse, plans[i].frac),
-                                                plans[i].tau_hi, out, it.hc, &it.n_cap, &io, list[i]->cand_hints[b],
-                                                use_bs ? list[i]->d_bs_out.as<uint32_t>() + 4 : nullptr)) != MXG_OK)
-                return rc;
-            last_on_slot[sl] = items.size();
-            items.push_back(it);
-        }
-        state[i] = 1;
-        q_hi[i] = items.size();
-        return MXG_OK;
-    };
-    auto pack_part = [&](size_t i, hipStream_t st, Driver *drv, uint32_t place4) -> int {
-        Assembly *a = list[i];
-        if (xp->dg) {  // the partitioned graph stage's item slots instead of an exchange part
-            const uint64_t oc = out_capacity(a);
-            MXG_HIP(h, h->d_nmx.ensure(MXG_MAX_ASSEMBLIES * 4));
-            const int rcd = dg_pack_slots_dev(h, a, (uint32_t)i, *xp->dg, st, state[i] == 1 ? 1u : (state[i] == 2 ? 0u : 2u),
-                                              h->d_nmx.as<uint32_t>() + i, drv ? drv->sc(SC_CTRL).as<uint32_t>() : nullptr, oc,
-                                              state[i] == 1 && plans[i].dev_gaps ? 1u : 0u, place4);
-            if (rcd != MXG_OK) return rcd;
-            if (!h->ev_part[i]) MXG_HIP(h, hipEventCreateWithFlags(&h->ev_part[i], hipEventDisableTiming));
-            MXG_HIP(h, hipEventRecord(h->ev_part[i], st));
-            return MXG_OK;
-        }
-        const uint64_t cap = xp->caps[i];
-        const uint64_t out_cap = out_capacity(a);
-        const long long fixed = state[i] == 1 ? -2ll : (state[i] == 2 ? 0ll : -1ll);
-        const uint32_t grid = state[i] == 1 ? (uint32_t)std::max<uint64_t>((cap + 255) / 256, 1) : 1u;
-        unsigned char *part = static_cast<unsigned char *>(xp->d_parts[i]);
-        const uint64_t rcap = xp->rcaps[i], n_rec = a->recs.size();
-        uint32_t *starts = reinterpret_cast<uint32_t *>(part + XCHG_PART_HEAD + 12 * cap);
-        MXG_HIP(h, h->d_nmx.ensure(MXG_MAX_ASSEMBLIES * 4));
-        if (state[i] == 1 && n_rec <= rcap && n_rec) MXG_HIP(h, hipMemsetAsync(starts, 0xFF, 4 * n_rec, st));
-        hipLaunchKernelGGL(k_pack_part_dev, dim3(grid), dim3(256), 0, st, a->d_hash.as<uint64_t>(), a->d_pos.as<uint32_t>(),
-                           a->d_rec.as<uint32_t>(), h->d_nmx.as<uint32_t>() + i,
-                           drv ? drv->sc(SC_CTRL).as<uint32_t>() : h->d_nmx.as<uint32_t>(), out_cap, cap, fixed,
-                           reinterpret_cast<long long *>(part), part + XCHG_PART_HEAD, (uint32_t)std::min<uint64_t>(n_rec, 0xFFFFFFFFu),
-                           (uint32_t)std::min<uint64_t>(rcap, 0xFFFFFFFFu), state[i] == 1 && plans[i].dev_gaps ? 1u : 0u, place4);
-        if (state[i] == 1 && n_rec <= rcap && n_rec)
-            hipLaunchKernelGGL(k_part_starts, dim3(1), dim3(1024), 0, st, reinterpret_cast<const long long *>(part), starts, (uint32_t)n_rec);
-        MXG_HIP(h, hipGetLastError());
-        if (!h->ev_part[i]) MXG_HIP(h, hipEventCreateWithFlags(&h->ev_part[i], hipEventDisableTiming));
-        MXG_HIP(h, hipEventRecord(h->ev_part[i], st));
-        return MXG_OK;
-    };
-    const bool dbg_cold = knob_set(h, "MXG_DEBUG_COLD");  // (diagnostics: where the host's time goes before and between the enqueues)
-    auto t_cold = std::chrono::steady_clock::now();
-    auto cold_mark = [&](const char *what, size_t i) {
-        if (!dbg_cold) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[mxg] sketch_assemblies: %s %zu: %.3f ms\n", what, i, std::chrono::duration<double, std::milli>(now - t_cold).count());
-        t_cold = now;
-    };
+        if ((rc = lazy_event(h, h->ev_sel_done[q])) != MXG_OK) return rc;
+    if (s.chain_modes) MXG_HIP(h, h->d_nmx.ensure(MXG_MAX_ASSEMBLIES * 4));  // (the sketches' sizes on the device, for the stage behind them)
+    s.t_cold = std::chrono::steady_clock::now();
     for (size_t i = 0; i < n; ++i) {
-        item0[i] = items.size();
         bool empty = false;
-        if ((rc = prepare_sketch(h, list[i], tabs[i], &empty)) != MXG_OK) return rc;
-        cold_mark("prepare_sketch", i);
+        if ((rc = prepare_sketch(h, list[i], s.runs[i].T, &empty)) != MXG_OK) return rc;
+        s.cold_mark("prepare_sketch", i);
         if (empty) {
-            state[i] = 2;
+            s.runs[i].state = AsmState::Done;
             continue;
         }
-        if ((rc = enqueue_asm(i, 0)) != MXG_OK) return rc;
-        cold_mark("enqueue_asm", i);
-        if (state[i] == 1) ++n_enq;
-        if (xp && (xp->d_parts || xp->dg) && state[i] == 1) {
+        if ((rc = s.enqueue_asm(i, 0)) != MXG_OK) return rc;
+        s.cold_mark("enqueue_asm", i);
+        if (s.runs[i].state != AsmState::Enqueued) continue;
+        ++s.n_enq;
+        if (xp && (xp->d_parts || xp->dg)) {
             // mxg_sketch_pack_parts: this assembly's part right behind its k_emit, on the stream that ran it -- the caller's
             // all-gather of the part travels while the next assembly is sketched
-            const Item &it = items[q_lo[i]];
-            if ((rc = pack_part(i, drvs[it.slot]->st, drvs[it.slot], it.place4)) != MXG_OK) return rc;
+            const SketchStep::Item &it = s.items[s.runs[i].q_lo];
+            if ((rc = s.pack_part(i, s.drvs[it.slot]->st, s.drvs[it.slot], it.place4)) != MXG_OK) return rc;
         }
     }
-    for (Driver *od : drvs)  // (the last assembly's emit, held back for an assembly that did not come)
+    for (Driver *od : s.drvs)  // (the last assembly's emit, held back for an assembly that did not come)
         if ((rc = od->flush_emit(nullptr)) != MXG_OK) return rc;
-    item0[n] = items.size();
-    for (size_t i = n; i-- > 0;)
-        if (state[i] != 1) item0[i] = item0[i + 1];  // (assemblies without items: empty range)
-    std::vector<int> slot_of(n, 0);
+    if (xp) return s.pack_all();
+    if ((rc = s.enqueue_fused_graph()) != MXG_OK) return rc;
+    if ((rc = wait_all_streams(h)) != MXG_OK) return rc;
     for (size_t i = 0; i < n; ++i)
-        if (state[i] == 1) slot_of[i] = items[item0[i]].slot;
-    if (xp) {
-        // the second stream joins the first; the pack kernels follow the sketches on it and read the counts there.  No
-        // host sync: mxg_sketch_finish completes the bookkeeping after the caller's next sync on this stream.
-        if (!h->ev_join) MXG_HIP(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-        MXG_HIP(h, hipEventRecord(h->ev_join, h->stream2));
-        MXG_HIP(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
-        MXG_HIP(h, h->d_nmx.ensure(MXG_MAX_ASSEMBLIES * 4));
-        unsigned char *base = static_cast<unsigned char *>(xp->d_slot);
-        uint64_t off = xp->head_bytes;
-        for (size_t i = 0; (xp->d_parts || xp->dg) && i < n; ++i)  // (parts: what was enqueued is packed already; the others say 0 / -1)
-            if (state[i] != 1 && (rc = pack_part(i, h->stream, nullptr, 0)) != MXG_OK) return rc;
-        for (size_t i = 0; !xp->d_parts && !xp->dg && i < n; ++i) {
-            Assembly *a = list[i];
-            const uint64_t cap = xp->caps[i];
-            const uint64_t out_cap = out_capacity(a);
-            const long long fixed = state[i] == 1 ? -2ll : (state[i] == 2 ? 0ll : -1ll);
-            const uint32_t grid = state[i] == 1 ? (uint32_t)std::max<uint64_t>((cap + 255) / 256, 1) : 1u;
-            hipLaunchKernelGGL(k_pack_slot_dev, dim3(grid), dim3(256), 0, h->stream, a->d_hash.as<uint64_t>(),
-                               a->d_pos.as<uint32_t>(), a->d_rec.as<uint32_t>(), h->d_nmx.as<uint32_t>() + i,
-                               drvs[slot_of[i]]->sc(SC_CTRL).as<uint32_t>(), out_cap, cap, fixed,
-                               reinterpret_cast<long long *>(base) + i, base + off, plans[i].dev_gaps ? 1u : 0u,
-                               state[i] == 1 ? items[item0[i]].place4 : 0u);
-            off += 16 * cap;
-        }
-        MXG_HIP(h, hipGetLastError());
-        h->pend_list.assign(list, list + n);
-        h->pend_state = state;
-        h->pend_dev.assign(n, 0);
-        for (size_t i = 0; i < n; ++i) h->pend_dev[i] = plans[i].dev_gaps ? 1 : 0;
-        return MXG_OK;
-    }
-    bool fused = false;
-    GraphBounds gb;
-    if (fuse_graph && n_enq == n && n == h->asms.size() && n <= MXG_MAX_ASSEMBLIES) {
-        bool same = true;
-        for (size_t i = 0; i < n; ++i) same = same && list[i] == h->asms[i];
-        if (same) {
-            // the second stream joins the first; the graph stage follows the sketches on it
-            if (!h->ev_join) MXG_HIP(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-            MXG_HIP(h, hipEventRecord(h->ev_join, h->stream2));
-            MXG_HIP(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
-            for (size_t i = 0; i < n; ++i) {
-                Assembly *a = list[i];
-                const uint64_t cap = out_capacity(a);
-                // (2 per window on i.i.d. sequence; repeat-rich sequence reaches ~3.8: what an earlier sketch of the assembly ended
-                // with, 10 % on top, so that the fused graph survives on exactly the inputs the output arrays were widened for)
-                const uint64_t iid = (uint64_t)(2.3 * (double)a->total_kmers / (double)(h->cfg.w + 1)) + 2048;
-                gb.n_bound[i] = std::min<uint64_t>(cap, std::max<uint64_t>(iid, a->n_mx_seen + a->n_mx_seen / 10 + 2048));
-                gb.n_ptr[i] = h->d_nmx.as<uint32_t>() + i;
-            }
-            fused = build_graph(h, GRAPH_FULL, nullptr, 0, &gb) == MXG_OK;  // (its sync is this call's sync)
-        }
-    }
-    MXG_HIP(h, stream_wait(h->stream));
-    MXG_HIP(h, stream_wait(h->stream2));
-    for (hipStream_t sx : h->stream_x)
-        if (sx) MXG_HIP(h, stream_wait(sx));
-    size_t n_fast = 0;  // assemblies whose every batch ended the common way
-    // what became of assembly i's batches: state 2 = its sketch is complete, 3 = enqueue it once more, 0 = synchronous path
-    auto evaluate = [&](size_t i, bool final) -> int {
-        Assembly *a = list[i];
-        const size_t q0 = q_lo[i], q1 = q_hi[i];
-        const uint64_t cap = out_capacity(a);
-        // (the one-call modes have already used the counts on the device: a stretch deferred to the host undoes them)
-        auto ended_well = [&](size_t q) { return BatchReport{items[q].hc}.ended_well(plans[i].dev_gaps, !chain_modes, items[q].bs); };
-        bool good = true;
-        uint64_t total = 0, n_cand = 0, gap_kmers = 0;
-        for (size_t q = q0; q < q1; ++q) {
-            const BatchReport r{items[q].hc};
-            good = good && ended_well(q);
-            total += r.total();
-            n_cand += r.n_cand();
-            gap_kmers += r.gap_kmers();
-            if (items[q].bs) h->stat_slice_stretches += r.sel_requests();
-            // what the batches saw of candidate-free stretches sizes the next sketch's batches (sparse_plan): real genomes hold
-            // far more of them than the i.i.d. estimate (satellite arrays, low-complexity runs)
-            // (1e-12: "a sketch has reported" -- an assembly whose stretches all went through k_sel_stretch leaves none over)
-            if (r.reported() && items[q].g.nk) a->gap_rate_hint = std::max({a->gap_rate_hint, (double)r.n_stretches() / (double)items[q].g.nk, 1e-12});
-        }
-        if (!(good && total <= cap) && knob_set(h, "MXG_DEBUG_BATCH")) {  // (diagnostics: the reports of an assembly's batches)
-            for (size_t q = q0; q < q1; ++q) {
-                const BatchReport r{items[q].hc};
-                fprintf(stderr, "[mxg] asm %zu batch %zu: ovf %u gaps %u sel %u flag %u cand %u nB %u total %u obase %u gapk %u (cap %llu)\n", i,
-                        q - q0, r.arena_need(), r.n_stretches(), r.n_selected(), r.w[RW_REDO], r.n_cand(), r.w[RW_STRETCH_MX],
-                        (uint32_t)r.total(), (uint32_t)r.out_base(), r.w[RW_GAP_KMERS], (unsigned long long)cap);
-            }
-        }
-        const BatchReport first{items[q0].hc};
-        if (good && total <= cap) {
-            // stretches the device route left to the host (too long, too many minimizers, invalid bases inside)
-            std::vector<uint4> deferred;
-            for (size_t q = q0; q < q1 && !chain_modes; ++q) take_deferred(h, items[q].hc, deferred);
-            uint64_t n_final = total;
-            if (!deferred.empty()) {
-                if ((rc = drv0.merge_deferred(a, tabs[i], deferred, total, &n_final)) != MXG_OK) return rc;
-                h->stat_deferred += deferred.size();
-                fused = false;  // (the graph stage ran on a sketch without them)
-            }
-            a->n_mx = n_final;
-            a->has_sketch = true;
-            h->stat_candidates += n_cand;
-            h->stat_dense_kmers += gap_kmers;
-            for (size_t q = q0; q < q1; ++q) a->cand_hints[q - q0] = BatchReport{items[q].hc}.n_cand();
-            a->cand_hint = a->cand_hints[0];
-            state[i] = 2;
-            if (fused && total > gb.n_bound[i]) fused = false;  // a sketch outgrew the bound the graph stage was sized for
-            ++n_fast;
-        } else if (q1 - q0 == 1 && !items[q0].bs && first.arena_need() == 0 && first.reported() && last_on_slot[items[q0].slot] == q0) {
-            // one batch, no arena overflow, and its candidate arrays are still intact in the driver's scratch: finish from
-            // there the general way (staging emit, dense fix-up of the stretches, merge) instead of redoing the batch
-            Driver &drv = *drvs[items[q0].slot];
-            OutArrays out{&a->d_hash, &a->d_pos, &a->d_rec, &a->d_fwd, 0};
-            uint32_t ctrl_copy[REPORT_WORDS];
-            std::copy_n(first.w, REPORT_WORDS, ctrl_copy);
-            if ((rc = drv.complete_batch(a, tabs[i], items[q0].g, out, BatchReport{ctrl_copy}, items[q0].n_cap)) != MXG_OK) return rc;
-            MXG_HIP(h, hipStreamSynchronize(drv.st));
-            a->n_mx = out.n;
-            a->has_sketch = true;
-            state[i] = 2;
-        } else if ((q1 - q0 > 1 || (items[q0].bs && plans[i].dev_gaps)) && !chain_modes && !final) {
-            // several batches, first attempt: once more through the streams (a few ms per Gbp; the synchronous route costs
-            // ten times that), with batches sized for the stretch density just seen (gap_rate_hint, above), every grid sized by
-            // the batch's own candidate count where it reported one, and slices as large as the largest wave asked for
-            for (size_t q = q0; q < q1; ++q) {
-                const BatchReport r{items[q].hc};
-                if (r.reported() && r.arena_need() != 0) h->arena_cap_hint = std::max<uint64_t>(h->arena_cap_hint, (uint64_t)r.arena_need() + 64);
-            }
-            // (k_bs_select again unless the slice kernel itself gave up somewhere -- a slice beyond its queue with no region left,
-            // more selected candidates than a slice's room: RW_SLICE_GAVE_UP -- and not merely more stretches than a batch holds)
-            a->sel_again = true;
-            for (size_t q = q0; q < q1; ++q)
-                if (items[q].bs && items[q].hc[RW_SLICE_GAVE_UP] != 0) a->sel_again = false;
-            a->cand_hints.clear();  // (the batches will be cut differently)
-            a->cand_hint = 0xFFFFFFFEu;
-            a->full_grid_once = true;
-            ++h->stat_retries;
-            state[i] = 3;
-        } else if (q1 - q0 > 1 && !chain_modes) {
-            // several batches: keep the leading ones that ended the common way AND lie where they belong (a batch starts
-            // where its predecessors end), redo the first bad one and everything behind it batch by batch through the
-            // synchronous route.  That route finishes stretches from the host, so it takes the threshold of the host route
-            // (18 candidates per window: a stretch per ~10^8 k-mers instead of one per ~2 x 10^6).
-            uint64_t offset = 0, nc = 0, gk = 0;
-            size_t j = q0;
-            for (; j < q1; ++j) {
-                const BatchReport r{items[j].hc};
-                if (!(ended_well(j) && r.out_base() == offset && offset + r.total() <= cap)) break;
-                offset += r.total();
-                nc += r.n_cand();
-                gk += r.gap_kmers();
-                a->cand_hints[j - q0] = r.n_cand();
-            }
-            for (size_t q = j; q < q1; ++q) {  // (next time: the whole grid for what did not report, the count for what did)
-                const BatchReport r{items[q].hc};
-                a->cand_hints[q - q0] = r.reported() && r.n_cand() != 0 ? r.n_cand() : 0xFFFFFFFEu;
-            }
-            a->cand_hint = a->cand_hints[0];
-            SparsePlan rp = plans[i];
-            if (!h->cfg.cand_per_window && 18.0 / (double)h->cfg.w <= 0.125) {
-                rp.frac = 18.0 / (double)h->cfg.w;
-                rp.tau_hi = std::max(2u, (uint32_t)std::min<double>(4294967294.0, rp.frac * 4294967296.0) & ~1u);
-            }
-            OutArrays out{&a->d_hash, &a->d_pos, &a->d_rec, &a->d_fwd, offset};
-            h->stat_candidates += nc;
-            h->stat_dense_kmers += gk;
-            h->stat_batches_redone += q1 - j;
-            if (j == q0) ++h->stat_sync_assemblies;
-            // (the batches that are kept may have left stretches to the host: their lists are read before anything reuses the slots)
-            std::vector<uint4> deferred;
-            for (size_t q = q0; q < j; ++q) take_deferred(h, items[q].hc, deferred);
-            if ((rc = drv0.sparse_all(a, tabs[i], out, rp.tau_hi, rp.frac, items[j].g.c0)) != MXG_OK) return rc;
-            MXG_HIP(h, hipStreamSynchronize(drv0.st));
-            uint64_t n_final = out.n;
-            if (!deferred.empty()) {
-                if ((rc = drv0.merge_deferred(a, tabs[i], deferred, out.n, &n_final)) != MXG_OK) return rc;
-                h->stat_deferred += deferred.size();
-            }
-            a->n_mx = n_final;
-            a->has_sketch = true;
-            state[i] = 2;
-        } else {
-            state[i] = 0;  // redo synchronously
-        }
-        return MXG_OK;
-    };
-    for (size_t i = 0; i < n; ++i)
-        if (state[i] == 1 && (rc = evaluate(i, chain_modes)) != MXG_OK) return rc;
-    {
+        if (s.runs[i].state == AsmState::Enqueued && (rc = s.evaluate(i, s.chain_modes)) != MXG_OK) return rc;
+    {   // the assemblies that asked for it, once more through the streams
         std::vector<size_t> again;
         for (size_t i = 0; i < n; ++i)
-            if (state[i] == 3) again.push_back(i);
+            if (s.runs[i].state == AsmState::Retry) again.push_back(i);
         for (size_t i : again)
-            if ((rc = enqueue_asm(i, 1)) != MXG_OK) return rc;
-        for (Driver *od : drvs)
+            if ((rc = s.enqueue_asm(i, 1)) != MXG_OK) return rc;
+        for (Driver *od : s.drvs)
             if ((rc = od->flush_emit(nullptr)) != MXG_OK) return rc;
-        if (!again.empty()) {
-            MXG_HIP(h, stream_wait(h->stream));
-            MXG_HIP(h, stream_wait(h->stream2));
-            for (hipStream_t sx : h->stream_x)
-                if (sx) MXG_HIP(h, stream_wait(sx));
-        }
+        if (!again.empty() && (rc = wait_all_streams(h)) != MXG_OK) return rc;
         for (size_t i : again)
-            if (state[i] == 1 && (rc = evaluate(i, true)) != MXG_OK) return rc;
+            if (s.runs[i].state == AsmState::Enqueued && (rc = s.evaluate(i, true)) != MXG_OK) return rc;
     }
-    if (n_fast != n) fused = false;  // not the common case everywhere: the graph stage ran on incomplete input
-    for (size_t i = 0; i < n; ++i) {
-        if (state[i] != 0) continue;
-        if (item0[i + 1] > item0[i]) {  // (was enqueued: the common route did not finish it)
+    if (s.n_fast != n) s.fused = false;  // not the common case everywhere: the graph stage ran on incomplete input
+    for (size_t i = 0; i < n; ++i) {  // what the streams did not finish: the synchronous path
+        if (s.runs[i].state != AsmState::Sync) continue;
+        if (s.first_item(i)) {  // (was enqueued: the common route did not finish it)
             ++h->stat_sync_assemblies;
-            h->stat_batches_redone += item0[i + 1] - item0[i];
+            h->stat_batches_redone += s.runs[i].first_hi - s.runs[i].first_lo;
         }
-        if ((rc = run_sketch_sync(h, list[i], tabs[i], drv0)) != MXG_OK) return rc;
+        if ((rc = run_sketch_sync(h, list[i], s.runs[i].T, s.drv0)) != MXG_OK) return rc;
     }
-    if ((rc = drv0.collect()) != MXG_OK) return rc;
-    if (fuse_graph && !fused) {
+    if ((rc = s.drv0.collect()) != MXG_OK) return rc;
+    if (fuse_graph && !s.fused) {
         h->graph.valid = false;
         return build_graph(h);
     }
@@ -3857,7 +4033,7 @@ int sketch_finish(mxg_handle *h)
     MXG_HIP(h, stream_wait(h->stream));
     MXG_HIP(h, stream_wait(h->stream2));
     std::vector<Assembly *> list;
-    std::vector<int> state;
+    std::vector<AsmState> state;
     std::vector<unsigned char> devg;
     list.swap(h->pend_list);
     state.swap(h->pend_state);
@@ -3866,7 +4042,7 @@ int sketch_finish(mxg_handle *h)
     size_t q = 0;  // (one item per enqueued assembly, in order)
     for (size_t i = 0; i < list.size(); ++i) {
         Assembly *a = list[i];
-        if (state[i] == 1) {
+        if (state[i] == AsmState::Enqueued) {
             const BatchReport r{report_slot(h, q++)};
             // what the pack kernel decided on the device (batch_ended_well): its counts include no deferred stretch, and it packs
             // no batch without candidates
@@ -3877,7 +4053,7 @@ int sketch_finish(mxg_handle *h)
                 a->cand_hint = r.n_cand();
                 continue;
             }
-        } else if (state[i] == 2) {
+        } else if (state[i] == AsmState::Done) {
             continue;  // (empty: prepare_sketch left it complete)
         }
         Tables T;
