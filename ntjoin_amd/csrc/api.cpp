@@ -103,6 +103,8 @@ void mxg_destroy(mxg_handle *h)
     h->asms.clear();
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+    if (h->ev_plan) (void)hipEventDestroy(h->ev_plan);
+    graph_drop_plan(h);
     for (hipEvent_t e : h->ev_part)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev_sync) (void)hipEventDestroy(e);

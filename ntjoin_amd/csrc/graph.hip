@@ -273,11 +273,23 @@ __device__ __forceinline__ uint32_t pj_slot(unsigned long long *keys, uint64_t k
 // every 4096-record region of a coarse partition into P sub-partitions (rows of M: rows2 per coarse partition); block
 // blockIdx.x = c * P + b joins sub-partition b of coarse partition c.
 constexpr uint32_t PJ1_CS = 32;  // words between the coarse partitions' cursors (own 128-byte lines: same-line atomics serialise)
+// A coarse partition's cap1 records are ONE run that all assemblies fill through one cursor (n_sub = 1), or -- the fused call that
+// partitions every assembly behind its own k_emit, while the others are still being sketched -- one 4096-aligned sub-range per
+// assembly, [off, off + cap) of the partition, with a cursor per (coarse partition, assembly): level 2 of an assembly then sorts
+// that assembly's rows only, and needs nothing of the others.  The rows of a partition stay its 4096-record pieces in order,
+// whosever they are: the join walks them as before.  Cursor of (partition c, sub-range s): word (c * n_sub + s) * PJ1_CS.
+struct PjSub {
+    uint32_t n_sub, s, off, cap;
+};
+struct PjSubCaps {  // what the join asks the cursors: did a sub-range outgrow its capacity
+    uint32_t n_sub;
+    uint32_t cap[MXG_MAX_ASSEMBLIES];
+};
 // NARROW (at most 16 assemblies): the seen and dup masks share one word per slot (32 KB of LDS per block instead of 44)
 template <bool NARROW>
 __global__ __launch_bounds__(256) void k_pj_join(uint4 *recs, const uint32_t *__restrict__ M, uint32_t P, uint32_t n_rows,
                                                  uint64_t *host_fail, uint32_t force_fail, const uint32_t *__restrict__ cursor,
-                                                 uint32_t cap1, uint32_t rows2, const AsmSet p)
+                                                 uint32_t cap1, uint32_t rows2, const AsmSet p, const PjSubCaps caps)
 {
     const uint32_t full = p.full;
     __shared__ unsigned long long keys[PJ_T + 1];
@@ -289,11 +301,13 @@ __global__ __launch_bounds__(256) void k_pj_join(uint4 *recs, const uint32_t *__
     if (cursor) {
         const uint32_t c = blockIdx.x / P;
         b = blockIdx.x % P;
-        const uint32_t n_c = min(cursor[c * PJ1_CS], cap1);
-        n_rows = (n_c + PJ_IPB - 1) / PJ_IPB;
+        // (sub-ranges: every row of the partition -- k_pj2_bucket leaves an empty row where a sub-range has no records)
+        n_rows = caps.n_sub > 1 ? rows2 : (min(cursor[c * PJ1_CS], cap1) + PJ_IPB - 1) / PJ_IPB;
         M += (size_t)c * rows2 * (P + 1);
         rec_off = c * cap1;
-        if (cursor[c * PJ1_CS] > cap1 && threadIdx.x == 0) *host_fail = 1;  // the coarse partition overflowed: global table
+        if (threadIdx.x == 0)
+            for (uint32_t s = 0; s < caps.n_sub; ++s)
+                if (cursor[(c * caps.n_sub + s) * PJ1_CS] > caps.cap[s]) *host_fail = 1;  // the coarse partition overflowed: global table
     }
     for (uint32_t s = threadIdx.x; s <= PJ_T; s += 256) {
         keys[s] = HT_EMPTY;
@@ -424,7 +438,7 @@ __global__ __launch_bounds__(256) void k_pj_join(uint4 *recs, const uint32_t *__
 template <bool NARROW>
 __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_t *__restrict__ M, uint32_t P, uint32_t n_parts,
                                                       uint64_t *host_fail, uint32_t force_fail, const uint32_t *__restrict__ cursor,
-                                                      uint32_t cap1, uint32_t rows2, const AsmSet p)
+                                                      uint32_t cap1, uint32_t rows2, const AsmSet p, const PjSubCaps caps)
 {
     const uint32_t full = p.full;
     __shared__ unsigned long long keys[PJ_T + 1];
@@ -495,7 +509,9 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
         if (threadIdx.x == 0) {
             failed = force_fail;
             const uint32_t c = part / P;
-            if (part % P == 0 && cursor[c * PJ1_CS] > cap1) *host_fail = 1;  // the coarse partition overflowed: global table
+            if (part % P == 0)
+                for (uint32_t s = 0; s < caps.n_sub; ++s)
+                    if (cursor[(c * caps.n_sub + s) * PJ1_CS] > caps.cap[s]) *host_fail = 1;  // the coarse partition overflowed: global table
         }
         __syncthreads();
         auto locate = [&](uint32_t q) {
@@ -580,10 +596,12 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
 // level 1 of the two-level join: 4096 minimizers per block (the same item order as k_pj_bucket), LDS histogram over P1
 // coarse partitions (hash bits 52..63), ONE device-scope add per non-empty (block, partition) bin reserves the bin's place
 // in the partition (4096 / P1 records per add; the cursors sit on their own lines), then the records are dealt out.
+// The launch covers 256-blocks [blk_lo, blk_hi) of the concatenated assemblies: all of them, or (sub.n_sub > 1) those of assembly
+// sub.s, whose records go to its own sub-range of every coarse partition.
 __device__ __forceinline__ uint32_t pj1_part(uint64_t key, uint32_t p1mask) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 52) & p1mask; }
 
-__global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t nb, uint32_t p1mask, uint32_t cap1, uint32_t *cursor,
-                                                     uint4 *recs1, uint32_t *sup, uint32_t n_sup)
+__global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t blk_lo, uint32_t blk_hi, uint32_t p1mask, uint32_t cap1,
+                                                     uint32_t *cursor, uint4 *recs1, uint32_t *sup, uint32_t n_sup, const PjSub subr)
 {
     extern __shared__ uint32_t pj_lds[];
     uint32_t *hist = pj_lds, *start = pj_lds + p1mask + 1;
@@ -591,7 +609,7 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
         for (uint32_t i = threadIdx.x; i < n_sup; i += PJ_BT) sup[i] = 0;
     constexpr uint32_t U = PJ_IPB / PJ_BT, BPU = PJ_BT / 256;
     const uint32_t j = blockIdx.x, sub = threadIdx.x >> 8, t256 = threadIdx.x & 255u;
-    const uint32_t blk0 = j * (PJ_IPB / 256);
+    const uint32_t blk0 = blk_lo + j * (PJ_IPB / 256);
     uint64_t key[U];
     uint32_t ia[U], ii[U], live = 0;
 #pragma unroll
@@ -599,8 +617,8 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
         const uint32_t blk = blk0 + u * BPU + sub;
         key[u] = 0;
         ia[u] = ii[u] = 0;
-        if (blk >= nb) continue;
-        const uint32_t a = asm_of_block(p, blk);
+        if (blk >= blk_hi) continue;
+        const uint32_t a = subr.n_sub > 1 ? subr.s : asm_of_block(p, blk);
         const uint32_t i = (blk - p.bstart[a]) * 256u + t256, n = asm_n(p, a);
         const bool lv = i < n;
         if (lv) key[u] = p.hash[a][i];
@@ -621,7 +639,7 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
     __syncthreads();
     for (uint32_t b = threadIdx.x; b <= p1mask; b += PJ_BT) {
         const uint32_t c = hist[b];
-        start[b] = c ? atomicAdd(&cursor[b * PJ1_CS], c) : 0u;
+        start[b] = c ? atomicAdd(&cursor[(b * subr.n_sub + subr.s) * PJ1_CS], c) : 0u;
         hist[b] = 0;  // from here on: records of this bin already placed
     }
     __syncthreads();
@@ -630,7 +648,7 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
         if (!((live >> u) & 1u)) continue;
         const uint32_t b = pj1_part(key[u], p1mask);
         const uint32_t pos = start[b] + atomicAdd(&hist[b], 1u);
-        if (pos < cap1) recs1[(size_t)b * cap1 + pos] = make_uint4((uint32_t)key[u], (uint32_t)(key[u] >> 32), ii[u], ia[u]);
+        if (pos < subr.cap) recs1[(size_t)b * cap1 + subr.off + pos] = make_uint4((uint32_t)key[u], (uint32_t)(key[u] >> 32), ii[u], ia[u]);
         else p.slot[ia[u] & ~PJ_REC_DUP][ii[u]] = 0;  // beyond the capacity: no verdict will come (the cursor says so, k_pj_join reports it and
                                         // the host redoes the stage with the global table); leave a harmless one behind
     }
@@ -649,20 +667,22 @@ constexpr uint32_t PJ_VERDICT_REF = 2u;  // low bits of a verdict word that is n
                                          // the upper bits name a minimizer of the same assembly whose verdict holds for this one
 __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint4 *__restrict__ recs1, const uint32_t *__restrict__ cursor,
                                                     uint32_t cap1, uint32_t rows2, uint32_t pmask, uint32_t *M, uint4 *recs2,
-                                                    uint32_t skew_lim)
+                                                    uint32_t skew_lim, const PjSub subr)
 {
     extern __shared__ uint32_t pj_lds[];
     uint32_t *hist = pj_lds, *start = pj_lds + pmask + 1;
     __shared__ uint32_t sh[256];
     const uint32_t j = blockIdx.x, c = blockIdx.y;
-    const uint32_t n_all = cursor[c * PJ1_CS], n_c = min(n_all, cap1);
+    // (the launch sorts the rows of ONE sub-range of every coarse partition: j counts from the sub-range's first row)
+    const uint32_t n_all = cursor[(c * subr.n_sub + subr.s) * PJ1_CS], n_c = min(n_all, subr.cap);
+    const uint32_t row_j = subr.off / PJ_IPB + j;
     if (j * PJ_IPB >= n_c) {  // (block-uniform) nothing of this coarse partition in this region: an empty row (k_pj_join_pipe
-        uint32_t *row = M + ((size_t)c * rows2 + j) * (pmask + 2);  // reads every row of the partition without asking the cursor)
+        uint32_t *row = M + ((size_t)c * rows2 + row_j) * (pmask + 2);  // reads every row of the partition without asking the cursor)
         for (uint32_t b = threadIdx.x; b <= pmask + 1; b += PJ_BT) row[b] = 0;
         return;
     }
     constexpr uint32_t U = PJ_IPB / PJ_BT;
-    const size_t base = (size_t)c * cap1 + (size_t)j * PJ_IPB;
+    const size_t base = (size_t)c * cap1 + subr.off + (size_t)j * PJ_IPB;
     uint4 rec[U];
     uint32_t live = 0;
 #pragma unroll
@@ -736,7 +756,7 @@ __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint
     if (b0 < P)
         for (uint32_t u = 0; u < per; ++u) cn += hist[b0 + u];
     uint32_t run = block_exclusive<PJ_BT / 64>(cn, sh);
-    uint32_t *row = M + ((size_t)c * rows2 + j) * (P + 1);
+    uint32_t *row = M + ((size_t)c * rows2 + row_j) * (P + 1);
     if (b0 < P)
         for (uint32_t u = 0; u < per; ++u) {
             const uint32_t cb = hist[b0 + u];
@@ -1112,6 +1132,7 @@ int build_graph(mxg_handle *h, int mode, const void *d_msgs, uint64_t n_msgs, co
         h->pj_overflowed = false;
         h->pj_cap1_P1 = 0;
         h->pj_cap1_need = 0;
+        h->pj_sub_P1 = 0;
     }
     if (!gb) h->pj_learnt_sig = sig;
     int rc = build_graph_impl(h, mode, d_msgs, n_msgs, gb, h->pj_overflowed);
@@ -1131,39 +1152,59 @@ int build_graph(mxg_handle *h, int mode, const void *d_msgs, uint64_t n_msgs, co
     return rc;
 }
 
-static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_t n_msgs, const GraphBounds *gb, bool global_table)
+// The join's layout: everything build_graph_impl derives from the assemblies' sizes (the sketches' own, or the bounds gb of the
+// fused call) before it launches anything -- which join, how many partitions of what capacity, where every array lies -- and the
+// allocations that go with it.  The fused call plans before its first filter is launched (graph_plan_early) and hands the plan on.
+struct JoinPlan {
+    uint32_t A = 0;
+    uint64_t N = 0, nvs = 0;
+    uint64_t n_of[MXG_MAX_ASSEMBLIES] = {};
+    uint32_t cap = 0, mask = 0, full = 0;
+    uint32_t P = 0, P1 = 0, cap1 = 0, rows2 = 0;
+    bool two_level = false, pj = false, dg_pj = false;
+    uint32_t pj_force_fail = 0;
+    size_t nb0 = 0;
+    uint64_t *pj_mask0 = nullptr;
+    uint32_t *pj_bpref0 = nullptr;
+    AsmSet as_all;
+    uint32_t nb = 0;
+    uint32_t n_items = 0, e_blocks = 0;
+    uint32_t n_fsup = 0, n_esup = 0;
+    uint32_t *fsup = nullptr, *esup = nullptr, *cnt = nullptr;
+    // two-level join
+    uint32_t *M = nullptr, *cursor = nullptr;
+    uint4 *recs1 = nullptr, *recs2 = nullptr;
+    bool split = false;  // a sub-range of every coarse partition per assembly (PjSub)
+    PjSubCaps sc;
+    uint32_t sub_off[MXG_MAX_ASSEMBLIES] = {}, skew_lim[MXG_MAX_ASSEMBLIES] = {};
+    size_t clear_words = 0;  // split: super-counts and cursors are one run of g_cnt, cleared by one fill
+};
+
+static int plan_join(mxg_handle *h, int mode, const GraphBounds *gb, bool global_table, bool split, JoinPlan &pl)
 {
-    MXG_HIP(h, hipSetDevice(h->device));
     const uint32_t A = (uint32_t)h->asms.size();
     if (A == 0) return set_err(h, MXG_EINVAL, "mxg_build_graph: no assemblies");
     if (A > MXG_MAX_ASSEMBLIES) return set_err(h, MXG_ELIMIT, "at most %d assemblies", MXG_MAX_ASSEMBLIES);
+    pl = JoinPlan();
+    pl.A = A;
     uint64_t N = 0, nmin = ~0ull;
-    std::vector<uint64_t> n_of(A);
+    uint64_t *const n_of = pl.n_of;
     for (uint32_t ai = 0; ai < A; ++ai) {
         Assembly *a = h->asms[ai];
         if (!gb && !a->has_sketch) return set_err(h, MXG_EINVAL, "assembly '%s' has no sketch (call mxg_sketch)", a->name.c_str());
         n_of[ai] = gb ? gb->n_bound[ai] : a->n_mx;
         N += n_of[ai];
         nmin = std::min(nmin, n_of[ai]);
-        if (mode != GRAPH_DG_EDGES && mode != GRAPH_DG_EDGES_APPLIED) a->flags_valid = a->flags_on_host = false;
     }
     if (N >= (1ull << 30)) return set_err(h, MXG_ELIMIT, "too many minimizers for one table (%llu)", (unsigned long long)N);
-    Graph &g = h->graph;
+    pl.N = N;
     const bool resume = mode == GRAPH_DG_EDGES || mode == GRAPH_DG_EDGES_APPLIED;  // second half on the owner's handle
-    if (!resume) g = Graph();
-    g.n_asm = A;
-    const bool fine = (h->cfg.flags & MXG_FLAG_TIMING_FINE) != 0 && mode == GRAPH_FULL;
-    const bool timing = (h->cfg.flags & MXG_FLAG_TIMING) != 0 || fine;
-    if (fine && !h->ev_g[0]) {
-        MXG_HIP(h, hipEventCreate(&h->ev_g[0]));
-        MXG_HIP(h, hipEventCreate(&h->ev_g[1]));
-    }
-    if (timing) MXG_HIP(h, hipEventRecord(h->ev0, h->stream));
 
     uint32_t cap = 1024;
     while (cap < 2 * N) cap <<= 1;
-    const uint32_t mask = cap - 1;
-    const uint32_t full = (A == 32) ? 0xFFFFFFFFu : ((1u << A) - 1u);
+    pl.cap = cap;
+    pl.mask = cap - 1;
+    pl.full = (A == 32) ? 0xFFFFFFFFu : ((1u << A) - 1u);
     // the join: LDS tables per hash partition (the whole-stage call, up to PJ_MAX_P partitions of <= 1280 records), else
     // the global table.  MXG_GRAPH_JOIN=global|lds and MXG_PJ_FORCE_FAIL=1 are test knobs (knob_*: as the handle first saw them).
     uint32_t P = 256;
@@ -1172,16 +1213,38 @@ static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_
     // beyond PJ_MAX_P partitions of <= 1280 records: two levels -- P1 coarse partitions, each sorted into 256 sub-partitions
     // (MXG_PJ_TWO_LEVEL=1 forces them on small inputs: test knob)
     uint32_t P1 = 0, cap1 = 0, rows2 = 0;
+    bool fits32 = true;
+    pl.sc.n_sub = 1;
+    for (uint32_t a = 0; a < MXG_MAX_ASSEMBLIES; ++a) pl.sc.cap[a] = 0;
     if (P > PJ_MAX_P || knob_u64(h, "MXG_PJ_TWO_LEVEL", 0)) {
         P = 256;
         P1 = 2;
         while ((uint64_t)P1 * P * 1000 < N) P1 <<= 1;
-        uint64_t c1 = (N / P1) + (N / P1) / 4 + 4096;  // 25 % above the mean (hash skew: keys of large multiplicity)
-        if (h->pj_cap1_P1 == P1) c1 = std::max<uint64_t>(c1, h->pj_cap1_need);  // (what an earlier call's cursors asked for)
-        cap1 = (uint32_t)((c1 + PJ_IPB - 1) / PJ_IPB * PJ_IPB);
+        if (split) {  // a sub-range per assembly, each with the slack of the whole: 25 % above ITS mean
+            uint64_t c_all = 0;
+            for (uint32_t a = 0; a < A; ++a) {
+                const uint64_t mean = n_of[a] / P1;
+                uint64_t c1 = mean + mean / 4 + 4096;
+                if (h->pj_sub_P1 == P1) c1 = std::max<uint64_t>(c1, h->pj_sub_need[a]);  // (what an earlier call's cursors asked for)
+                c1 = (c1 + PJ_IPB - 1) / PJ_IPB * PJ_IPB;
+                pl.sub_off[a] = (uint32_t)std::min<uint64_t>(c_all, 0xFFFFF000u);
+                pl.sc.cap[a] = (uint32_t)std::min<uint64_t>(c1, 0xFFFFF000u);
+                pl.skew_lim[a] = (uint32_t)std::min<uint64_t>(mean + mean / 32 + 2048, 0xFFFFFFFFull);  // 3 % above the mean
+                c_all += c1;
+            }
+            pl.sc.n_sub = A;
+            pl.split = true;
+            cap1 = (uint32_t)std::min<uint64_t>(c_all, 0xFFFFF000u);
+            fits32 = c_all <= 0xFFFFF000u;  // (a coarse partition's records are counted in 32 bits)
+        } else {
+            uint64_t c1 = (N / P1) + (N / P1) / 4 + 4096;  // 25 % above the mean (hash skew: keys of large multiplicity)
+            if (h->pj_cap1_P1 == P1) c1 = std::max<uint64_t>(c1, h->pj_cap1_need);  // (what an earlier call's cursors asked for)
+            cap1 = (uint32_t)((c1 + PJ_IPB - 1) / PJ_IPB * PJ_IPB);
+            pl.sc.cap[0] = cap1;
+        }
         rows2 = cap1 / PJ_IPB;
     }
-    const bool two_level = P1 != 0 && P1 <= 4096 && (uint64_t)P1 * cap1 < (1ull << 32) && (uint64_t)P1 * P * (PJ_T + 1) < (1ull << 29);
+    const bool two_level = P1 != 0 && P1 <= 4096 && fits32 && (uint64_t)P1 * cap1 < (1ull << 32) && (uint64_t)P1 * P * (PJ_T + 1) < (1ull << 29);
     // (k_pj_join's verdict word carries the index of the key's minimizer in assembly 0 above three flag bits, k_pj2_bucket's
     // reference that of a minimizer of the same assembly: < 2^29)
     uint64_t n_max = 0;
@@ -1191,9 +1254,15 @@ static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_
     const bool dg_pj = mode == GRAPH_DG_VERTICES && gb != nullptr && !h->dg_pj_off;
     const bool pj = (mode == GRAPH_FULL || dg_pj) && !global_table && (P1 == 0 || two_level) && P <= PJ_MAX_P &&
                     n_max < (1ull << 29) && !(join_env && !strcmp(join_env, "global"));
-    const uint32_t pj_force_fail = knob_u64(h, "MXG_PJ_FORCE_FAIL", 0) ? 1u : 0u;
+    pl.P = P;
+    pl.P1 = P1;
+    pl.cap1 = cap1;
+    pl.rows2 = rows2;
+    pl.two_level = two_level;
+    pl.dg_pj = dg_pj;
+    pl.pj = pj;
+    pl.pj_force_fail = knob_u64(h, "MXG_PJ_FORCE_FAIL", 0) ? 1u : 0u;
 
-    if (!resume) h->stat_graph_join = pj ? (two_level ? 2 : 1) : 3;
     if (!pj) MXG_HIP(h, h->g_keys.ensure(((size_t)cap + 1) * sizeof(Slot)));  // (the partitioned join keeps its N records here)
     // global table: slot -> vertex id; partitioned join: assembly 0's shared mask (8 B per 64 minimizers) + block prefix
     // (+ partitioned join: one "follower" bit per minimizer of every assembly, pj_run_role)
@@ -1201,20 +1270,15 @@ static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_
     size_t nb_all = 0;
     for (uint32_t a = 0; a < A; ++a) nb_all += (size_t)((n_of[a] + 255) / 256);
     MXG_HIP(h, h->g_vid.ensure(pj ? (nb0 + nb_all) * 4 * 8 + nb0 * 4 + 64 : ((size_t)cap + 1) * 4));
-    uint64_t *const pj_mask0 = h->g_vid.as<uint64_t>();
-    uint64_t *const pj_fol = pj_mask0 + nb0 * 4;
-    uint32_t *const pj_bpref0 = reinterpret_cast<uint32_t *>(pj_fol + nb_all * 4);
+    pl.nb0 = nb0;
+    pl.pj_mask0 = h->g_vid.as<uint64_t>();
+    uint64_t *const pj_fol = pl.pj_mask0 + nb0 * 4;
+    pl.pj_bpref0 = reinterpret_cast<uint32_t *>(pj_fol + nb_all * 4);
     MXG_HIP(h, h->g_ctl.ensure(CTL_WORDS * 8));
-    if (pj) {
-        // (nothing to clear: every word of M and of the record regions that is read is written by this call)
-    } else if (!resume) {
-        MXG_HIP(h, hipMemsetAsync(h->g_keys.p, 0xFF, ((size_t)cap + 1) * sizeof(Slot), h->stream));  // one fill: see Slot
-    }
-    uint64_t *ctl = h->g_ctl.as<uint64_t>();  // every word the host reads below is written by a kernel of this call
 
-    AsmSet as_all;
+    AsmSet &as_all = pl.as_all;
     as_all.n_asm = A;
-    as_all.full = full;
+    as_all.full = pl.full;
     as_all.fol = pj ? pj_fol : nullptr;
     uint32_t nb = 0;
     for (uint32_t a = 0; a < A; ++a) {
@@ -1230,7 +1294,6 @@ static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_
         as_all.slot[a] = as->d_slot.as<uint32_t>();
         as_all.flags[a] = as->d_flags.as<uint8_t>();
         as_all.shared[a] = as->d_shared.as<uint8_t>();
-        as->flags_valid = true;
     }
     as_all.bstart[A] = nb;
     for (uint32_t a = A; a < MXG_MAX_ASSEMBLIES; ++a) {
@@ -1241,52 +1304,215 @@ static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_
         as_all.slot[a] = nullptr;
         as_all.flags[a] = as_all.shared[a] = nullptr;
     }
+    pl.nb = nb;
     // vertex arrays are strided by an upper bound of the vertex count (every vertex occurs once in every assembly), so
     // this stage needs no host sync before its kernels: they read the counts from the control block in HBM
     const uint64_t nvs = nmin;  // stride
-    if (!h->pinned_gctl) MXG_HIP(h, hipHostMalloc((void **)&h->pinned_gctl, CTL_WORDS * 8));
-    uint64_t *const hctl = h->pinned_gctl;
-    memset(hctl, 0, CTL_WORDS * 8);
-    uint64_t *const pj_fail = dg_pj ? dg_pj_fail_word(h) : hctl + CTL_PJ_FAIL;  // (the device word: cleared by dg_owner_slots)
+    pl.nvs = nvs;
     if (nvs > 0 && (uint64_t)A * nvs >= (1ull << 32)) return set_err(h, MXG_ELIMIT, "graph too large for 32-bit item indices");
-    const size_t anv = (size_t)A * nvs;
-    const uint32_t n_items = (uint32_t)anv;
-    const uint32_t e_blocks = (n_items + 255) / 256;
+    pl.n_items = (uint32_t)((size_t)A * nvs);
+    pl.e_blocks = (pl.n_items + 255) / 256;
     // per-256 counts of the two counting kernels and their super-counts (scan_kernels.h): [sup of k_flags, one run
     // per assembly | sup of k_edge_flags | cnt of k_flags]; k_insert zeroes the super-counts
-    const uint32_t n_fsup = ((nb >> SUP_SHIFT) + A + 1) * SUP_STRIDE, n_esup = sup_words(e_blocks);
-    MXG_HIP(h, h->g_cnt.ensure(((size_t)n_fsup + n_esup + nb) * 4 + 64));
-    uint32_t *fsup = h->g_cnt.as<uint32_t>(), *esup = fsup + n_fsup, *cnt = esup + n_esup;
+    // (split: the cursors of the sub-ranges lie between the super-counts and the counts, so that one fill clears both)
+    pl.n_fsup = ((nb >> SUP_SHIFT) + A + 1) * SUP_STRIDE;
+    pl.n_esup = sup_words(pl.e_blocks);
+    const bool cursors_here = pl.split && pj && two_level;
+    const size_t n_cur = cursors_here ? (size_t)P1 * A * PJ1_CS : 0;
+    MXG_HIP(h, h->g_cnt.ensure(((size_t)pl.n_fsup + pl.n_esup + n_cur + nb) * 4 + 64));
+    pl.fsup = h->g_cnt.as<uint32_t>();
+    pl.esup = pl.fsup + pl.n_fsup;
+    pl.cnt = pl.esup + pl.n_esup + n_cur;
+    pl.clear_words = (size_t)pl.n_fsup + pl.n_esup + n_cur;
     if (nb && !resume && pj && two_level) {
-        const uint32_t n_rows1 = (nb + PJ_IPB / 256 - 1) / (PJ_IPB / 256);
         const size_t n_recs = (size_t)P1 * cap1;
         MXG_HIP(h, h->g_part.ensure((size_t)P1 * rows2 * (P + 1) * 4 + (size_t)P1 * PJ1_CS * 4));
         MXG_HIP(h, h->g_keys.ensure(n_recs * sizeof(uint4)));   // level-2 records (what k_flags_pj reads)
         MXG_HIP(h, h->g_recs1.ensure(n_recs * sizeof(uint4)));  // level-1 records
-        uint32_t *M = h->g_part.as<uint32_t>();
-        uint32_t *cursor = M + (size_t)P1 * rows2 * (P + 1);
-        MXG_HIP(h, hipMemsetAsync(cursor, 0, (size_t)P1 * PJ1_CS * 4, h->stream));
-        uint4 *recs1 = h->g_recs1.as<uint4>(), *recs2 = h->g_keys.as<uint4>();
-        hipLaunchKernelGGL(k_pj1_scatter, dim3(n_rows1), dim3(PJ_BT), (size_t)P1 * 8, h->stream, as_all, nb, P1 - 1, cap1, cursor, recs1,
-                           fsup, n_fsup + n_esup);
-        const uint32_t skew_lim = (uint32_t)std::min<uint64_t>(N / P1 + N / P1 / 32 + 2048, 0xFFFFFFFFull);  // 3 % above the mean
-        hipLaunchKernelGGL(k_pj2_bucket, dim3(rows2, P1), dim3(PJ_BT), (size_t)P * 8, h->stream, as_all, recs1, cursor, cap1, rows2, P - 1, M,
-                           recs2, knob_u64(h, "MXG_PJ_SKEW", 0) ? 0u : skew_lim);
+        pl.M = h->g_part.as<uint32_t>();
+        pl.cursor = cursors_here ? pl.esup + pl.n_esup : pl.M + (size_t)P1 * rows2 * (P + 1);
+        pl.recs1 = h->g_recs1.as<uint4>();
+        pl.recs2 = h->g_keys.as<uint4>();
+    }
+    return MXG_OK;
+}
+
+// levels 1 and 2 of the two-level join for the 256-blocks of assemblies [a_lo, a_hi) on stream st
+static void launch_partition(mxg_handle *h, const JoinPlan &pl, uint32_t a_lo, uint32_t a_hi, hipStream_t st, uint32_t n_sup_clear)
+{
+    const uint32_t blk_lo = pl.as_all.bstart[a_lo], blk_hi = pl.as_all.bstart[a_hi];
+    const uint32_t n_rows1 = (blk_hi - blk_lo + PJ_IPB / 256 - 1) / (PJ_IPB / 256);
+    PjSub sub{1u, 0u, 0u, pl.cap1};
+    uint32_t skew_lim = (uint32_t)std::min<uint64_t>(pl.N / pl.P1 + pl.N / pl.P1 / 32 + 2048, 0xFFFFFFFFull);  // 3 % above the mean
+    if (pl.split) {
+        sub = PjSub{pl.A, a_lo, pl.sub_off[a_lo], pl.sc.cap[a_lo]};
+        skew_lim = pl.skew_lim[a_lo];
+    }
+    if (n_rows1)
+        hipLaunchKernelGGL(k_pj1_scatter, dim3(n_rows1), dim3(PJ_BT), (size_t)pl.P1 * 8, st, pl.as_all, blk_lo, blk_hi, pl.P1 - 1, pl.cap1,
+                           pl.cursor, pl.recs1, pl.fsup, n_sup_clear, sub);
+    hipLaunchKernelGGL(k_pj2_bucket, dim3(sub.cap / PJ_IPB, pl.P1), dim3(PJ_BT), (size_t)pl.P * 8, st, pl.as_all, pl.recs1, pl.cursor, pl.cap1,
+                       pl.rows2, pl.P - 1, pl.M, pl.recs2, knob_u64(h, "MXG_PJ_SKEW", 0) ? 0u : skew_lim, sub);
+}
+
+// A timed span of kind 5 (flush_timers adds it to ms_join and ms_graph).  What ms_join means on the early path, in one place:
+// MXG_FLAG_TIMING_FINE puts one such span around each assembly's two partition kernels on that assembly's stream.  A span runs
+// from the moment the stream reaches the kernels to their end, so for an assembly whose kernels wait for room beside another
+// assembly's filter or slice kernel it holds that wait too (the reference's: ~530 us for ~100 us of work at 3 Gbp + 3 Gbp) and
+// ms_join is then an upper bound of the join's work, not its share of the step.  Plain MXG_FLAG_TIMING records nothing here:
+// ms_graph is the span of build_graph_impl on the main stream, i.e. the stage from the join kernel on; the last assembly's level
+// 1 + 2, which do lie on the critical path behind its k_emit, are in neither ms_hash nor ms_graph (profiles/r07).
+// The span is appended to h->ev_spans, where Driver::ev_end() closes ev_spans.back(): callers must have no driver span open
+// (graph_partition_early runs behind enqueue_asm, which has closed its spans; k_emit is never held back in the one-call modes).
+static int ev_pair(mxg_handle *h, hipEvent_t *a, hipEvent_t *b)
+{
+    while (h->ev_pool.size() < h->ev_used + 2) {
+        hipEvent_t e;
+        MXG_HIP(h, hipEventCreate(&e));
+        h->ev_pool.push_back(e);
+    }
+    *a = h->ev_pool[h->ev_used];
+    *b = h->ev_pool[h->ev_used + 1];
+    h->ev_used += 2;
+    h->ev_spans.push_back(TimedSpan{*a, *b, 0, false, 5});
+    return MXG_OK;
+}
+
+int graph_plan_early(mxg_handle *h, const GraphBounds &gb, bool *early)
+{
+    *early = false;
+    h->pj_early_done = 0;
+    if (knob_u64(h, "MXG_PJ_EARLY", 1) == 0) return MXG_OK;
+    MXG_HIP(h, hipSetDevice(h->device));
+    if (!h->pj_plan) h->pj_plan = new JoinPlan;
+    JoinPlan &pl = *h->pj_plan;
+    // (a set of sizes the graph stage refuses: build_graph says so behind the sketches, as it always has)
+    const std::string err_before = h->err;
+    if (plan_join(h, GRAPH_FULL, &gb, h->pj_overflowed, true, pl) != MXG_OK || !(pl.pj && pl.two_level && pl.split && pl.nb)) {
+        pl = JoinPlan();
+        h->err = err_before;  // (not this call's error: the stage itself reports it if it still holds then)
+        return MXG_OK;
+    }
+    // the cursors of the sub-ranges and the super-counts of the counting kernels, in front of everything: both streams' partition
+    // kernels wait for this fill (ev_plan)
+    MXG_HIP(h, hipMemsetAsync(pl.fsup, 0, pl.clear_words * 4, h->stream));
+    if (!h->ev_plan) MXG_HIP(h, hipEventCreateWithFlags(&h->ev_plan, hipEventDisableTiming));
+    MXG_HIP(h, hipEventRecord(h->ev_plan, h->stream));
+    *early = true;
+    return MXG_OK;
+}
+
+int graph_partition_early(mxg_handle *h, uint32_t a, hipStream_t st)
+{
+    const JoinPlan *pl = h->pj_plan;
+    if (!pl || !pl->split || a != h->pj_early_done || a >= pl->A) return MXG_OK;  // (out of turn: the stage will partition by itself)
+    if (h->asms[a]->d_hash.as<uint64_t>() != pl->as_all.hash[a] || h->asms[a]->d_slot.as<uint32_t>() != pl->as_all.slot[a]) return MXG_OK;  // (arrays moved since)
+    if (st != h->stream) MXG_HIP(h, hipStreamWaitEvent(st, h->ev_plan, 0));
+    const bool fine = (h->cfg.flags & MXG_FLAG_TIMING_FINE) != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (fine) {
+        const int rc = ev_pair(h, &e0, &e1);
+        if (rc != MXG_OK) return rc;
+        MXG_HIP(h, hipEventRecord(e0, st));
+    }
+    launch_partition(h, *pl, a, a + 1, st, 0u);
+    MXG_HIP(h, hipGetLastError());
+    if (fine) MXG_HIP(h, hipEventRecord(e1, st));
+    ++h->pj_early_done;
+    return MXG_OK;
+}
+
+void graph_drop_plan(mxg_handle *h)
+{
+    delete h->pj_plan;
+    h->pj_plan = nullptr;
+}
+
+static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_t n_msgs, const GraphBounds *gb, bool global_table)
+{
+    MXG_HIP(h, hipSetDevice(h->device));
+    // the plan of the fused call, if this is the stage it was made for and every assembly has been partitioned under the sketches;
+    // whatever comes after (a second attempt, a later call) plans and partitions for itself
+    bool early = h->pj_plan && h->pj_plan->split && h->pj_early_done != 0 && h->pj_early_done == h->pj_plan->A && gb && mode == GRAPH_FULL &&
+                 !global_table && h->pj_plan->A == h->asms.size();
+    for (uint32_t a = 0; early && a < h->pj_plan->A; ++a) early = gb->n_bound[a] == h->pj_plan->n_of[a] && gb->n_ptr[a] == h->pj_plan->as_all.n_ptr[a];
+    h->pj_early_done = 0;
+    JoinPlan own;
+    if (!early) {
+        const int rc = plan_join(h, mode, gb, global_table, false, own);
+        if (rc != MXG_OK) {
+            if (mode != GRAPH_DG_EDGES && mode != GRAPH_DG_EDGES_APPLIED)
+                for (Assembly *a : h->asms) a->flags_valid = a->flags_on_host = false;
+            return rc;
+        }
+    }
+    const JoinPlan &pl = early ? *h->pj_plan : own;
+    const uint32_t A = pl.A;
+    const uint64_t *const n_of = pl.n_of;
+    const bool resume = mode == GRAPH_DG_EDGES || mode == GRAPH_DG_EDGES_APPLIED;  // second half on the owner's handle
+    for (uint32_t ai = 0; ai < A; ++ai) {
+        Assembly *a = h->asms[ai];
+        if (!resume) a->flags_on_host = false;
+        a->flags_valid = true;
+    }
+    Graph &g = h->graph;
+    if (!resume) g = Graph();
+    g.n_asm = A;
+    const bool fine = (h->cfg.flags & MXG_FLAG_TIMING_FINE) != 0 && mode == GRAPH_FULL;
+    const bool timing = (h->cfg.flags & MXG_FLAG_TIMING) != 0 || fine;
+    if (fine && !h->ev_g[0]) {
+        MXG_HIP(h, hipEventCreate(&h->ev_g[0]));
+        MXG_HIP(h, hipEventCreate(&h->ev_g[1]));
+    }
+    if (timing) MXG_HIP(h, hipEventRecord(h->ev0, h->stream));
+
+    const uint32_t cap = pl.cap, mask = pl.mask;
+    const uint32_t P = pl.P, P1 = pl.P1, cap1 = pl.cap1, rows2 = pl.rows2;
+    const bool two_level = pl.two_level, dg_pj = pl.dg_pj, pj = pl.pj;
+    const uint32_t pj_force_fail = pl.pj_force_fail;
+    if (!resume) h->stat_graph_join = (pj ? (two_level ? 2 : 1) : 3) | (early ? 0x400 : 0);
+    const size_t nb0 = pl.nb0;
+    uint64_t *const pj_mask0 = pl.pj_mask0;
+    uint32_t *const pj_bpref0 = pl.pj_bpref0;
+    if (pj) {
+        // (nothing to clear: every word of M and of the record regions that is read is written by this call)
+    } else if (!resume) {
+        MXG_HIP(h, hipMemsetAsync(h->g_keys.p, 0xFF, ((size_t)cap + 1) * sizeof(Slot), h->stream));  // one fill: see Slot
+    }
+    uint64_t *ctl = h->g_ctl.as<uint64_t>();  // every word the host reads below is written by a kernel of this call
+    const AsmSet &as_all = pl.as_all;
+    const uint32_t nb = pl.nb;
+    const uint64_t nvs = pl.nvs;
+    if (!h->pinned_gctl) MXG_HIP(h, hipHostMalloc((void **)&h->pinned_gctl, CTL_WORDS * 8));
+    uint64_t *const hctl = h->pinned_gctl;
+    memset(hctl, 0, CTL_WORDS * 8);
+    uint64_t *const pj_fail = dg_pj ? dg_pj_fail_word(h) : hctl + CTL_PJ_FAIL;  // (the device word: cleared by dg_owner_slots)
+    const size_t anv = (size_t)A * nvs;
+    const uint32_t n_items = pl.n_items, e_blocks = pl.e_blocks;
+    const uint32_t n_fsup = pl.n_fsup, n_esup = pl.n_esup;
+    uint32_t *fsup = pl.fsup, *esup = pl.esup, *cnt = pl.cnt;
+    if (nb && !resume && pj && two_level) {
+        uint32_t *M = pl.M, *cursor = pl.cursor;
+        uint4 *recs2 = pl.recs2;
+        if (!early) {  // (else: both levels ran behind every assembly's own k_emit, the cursors were cleared in front of the step)
+            MXG_HIP(h, hipMemsetAsync(cursor, 0, (size_t)P1 * PJ1_CS * 4, h->stream));
+            launch_partition(h, pl, 0, A, h->stream, n_fsup + n_esup);
+        }
         const uint64_t pipe_blocks = knob_u64(h, "MXG_PJ_PIPE", 1024);  // (0: one block per partition, k_pj_join)
         if (pipe_blocks && rows2 <= 256) {
             const uint32_t nblk = (uint32_t)std::min<uint64_t>(pipe_blocks, (uint64_t)P1 * P);
             if (A <= 16)
                 hipLaunchKernelGGL(k_pj_join_pipe<true>, dim3(nblk), dim3(256), 0, h->stream, recs2, M, P, P1 * P, pj_fail,
-                                   pj_force_fail, cursor, cap1, rows2, as_all);
+                                   pj_force_fail, cursor, cap1, rows2, as_all, pl.sc);
             else
                 hipLaunchKernelGGL(k_pj_join_pipe<false>, dim3(nblk), dim3(256), 0, h->stream, recs2, M, P, P1 * P, pj_fail,
-                                   pj_force_fail, cursor, cap1, rows2, as_all);
+                                   pj_force_fail, cursor, cap1, rows2, as_all, pl.sc);
         } else if (A <= 16)
             hipLaunchKernelGGL(k_pj_join<true>, dim3(P1 * P), dim3(256), 0, h->stream, recs2, M, P, 0u, pj_fail, pj_force_fail,
-                               cursor, cap1, rows2, as_all);
+                               cursor, cap1, rows2, as_all, pl.sc);
         else
             hipLaunchKernelGGL(k_pj_join<false>, dim3(P1 * P), dim3(256), 0, h->stream, recs2, M, P, 0u, pj_fail, pj_force_fail,
-                               cursor, cap1, rows2, as_all);
+                               cursor, cap1, rows2, as_all, pl.sc);
         hipLaunchKernelGGL(k_flags_pj, dim3(nb), dim3(256), 0, h->stream, as_all, cnt, fsup, pj_mask0);
     } else if (nb && !resume && pj) {
         const uint32_t n_rows = (nb + PJ_IPB / 256 - 1) / (PJ_IPB / 256);  // bucketing blocks = record regions = rows of M
@@ -1298,10 +1524,10 @@ static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_
                            n_fsup + n_esup);
         if (A <= 16)
             hipLaunchKernelGGL(k_pj_join<true>, dim3(P), dim3(256), 0, h->stream, recs, M, P, n_rows, pj_fail, pj_force_fail, nullptr,
-                               0u, 0u, as_all);
+                               0u, 0u, as_all, pl.sc);
         else
             hipLaunchKernelGGL(k_pj_join<false>, dim3(P), dim3(256), 0, h->stream, recs, M, P, n_rows, pj_fail, pj_force_fail, nullptr,
-                               0u, 0u, as_all);
+                               0u, 0u, as_all, pl.sc);
         hipLaunchKernelGGL(k_flags_pj, dim3(nb), dim3(256), 0, h->stream, as_all, cnt, fsup, pj_mask0);
     } else if (nb && !resume) {
         hipLaunchKernelGGL(k_insert, dim3(nb), dim3(256), 0, h->stream, as_all, h->g_keys.as<Slot>(), mask, cap, fsup,
@@ -1429,12 +1655,36 @@ static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_
     MXG_HIP(h, stream_wait(h->stream));  // the stage's only sync; results stay in HBM
     if (pj && hctl[CTL_PJ_FAIL]) {  // a partition outgrew its LDS table: redo with the global table
         if (two_level && !pj_force_fail) {  // ... unless it was a coarse partition's capacity, and only that
-            std::vector<uint32_t> cur((size_t)P1 * PJ1_CS);
-            const uint32_t *d_cur = h->g_part.as<uint32_t>() + (size_t)P1 * rows2 * (P + 1);
-            MXG_HIP(h, hipMemcpy(cur.data(), d_cur, cur.size() * 4, hipMemcpyDeviceToHost));
-            uint32_t mx = 0;
-            for (uint32_t c = 0; c < P1; ++c) mx = std::max(mx, cur[(size_t)c * PJ1_CS]);
-            if (mx > cap1 && (h->pj_cap1_P1 != P1 || h->pj_cap1_need < mx)) {
+            const uint32_t n_sub = pl.sc.n_sub;
+            std::vector<uint32_t> cur((size_t)P1 * n_sub * PJ1_CS);
+            MXG_HIP(h, hipMemcpy(cur.data(), pl.cursor, cur.size() * 4, hipMemcpyDeviceToHost));
+            uint64_t mx = 0;  // the fullest coarse partition, all assemblies together: what the one-cursor layout must hold
+            for (uint32_t c = 0; c < P1; ++c) {
+                uint64_t all = 0;
+                for (uint32_t s = 0; s < n_sub; ++s) all += cur[((size_t)c * n_sub + s) * PJ1_CS];
+                mx = std::max(mx, all);
+            }
+            if (pl.split) {
+                // a sub-range outgrew its capacity: the next fused call sizes that assembly's sub-ranges by what the cursors counted,
+                // and the attempt that follows this one (one cursor per coarse partition) by the partitions' totals
+                bool learnt = false;
+                if (h->pj_sub_P1 != P1) std::fill_n(h->pj_sub_need, MXG_MAX_ASSEMBLIES, 0ull);
+                h->pj_sub_P1 = P1;
+                for (uint32_t s = 0; s < n_sub; ++s) {
+                    uint64_t ms = 0;
+                    for (uint32_t c = 0; c < P1; ++c) ms = std::max<uint64_t>(ms, cur[((size_t)c * n_sub + s) * PJ1_CS]);
+                    if (ms > pl.sc.cap[s] && h->pj_sub_need[s] < ms) {
+                        h->pj_sub_need[s] = ms + ms / 8 + 4096;
+                        learnt = true;
+                    }
+                }
+                if (learnt) {
+                    if (h->pj_cap1_P1 != P1) h->pj_cap1_need = 0;
+                    h->pj_cap1_P1 = P1;
+                    h->pj_cap1_need = std::max<uint64_t>(h->pj_cap1_need, mx + mx / 8 + 4096);
+                    return RC_RETRY_PJ;
+                }
+            } else if (mx > cap1 && (h->pj_cap1_P1 != P1 || h->pj_cap1_need < mx)) {
                 h->pj_cap1_P1 = P1;
                 h->pj_cap1_need = (uint64_t)mx + mx / 8 + 4096;
                 return RC_RETRY_PJ;

@@ -213,6 +213,8 @@ enum class AsmState : int {
     Retry = 3,     // its batches did not all end the common way: enqueue it once more
 };
 
+struct JoinPlan;  // graph.hip: the layout of the graph stage's join (plan_join)
+
 }  // namespace mxg
 
 struct mxg_handle {
@@ -256,6 +258,14 @@ struct mxg_handle {
     uint32_t pj_cap1_P1 = 0;     // two-level join: coarse partitions and the records one of them must hold, as an earlier call's
     uint64_t pj_cap1_need = 0;   // cursors reported them (a key of large multiplicity skews the partitions)
     uint64_t pj_learnt_sig = 0;  // the sketches (count and sizes) the three fields around this one were learnt on
+    // fused call: the join as it was planned before the sketches (graph_plan_early), how many assemblies have been partitioned behind
+    // their own k_emit since (graph_partition_early), the event behind the plan's clears, and what the sub-ranges of a coarse partition
+    // must hold per assembly, as an earlier call's cursors reported it (pj_cap1_need's counterpart)
+    mxg::JoinPlan *pj_plan = nullptr;
+    uint32_t pj_early_done = 0;
+    hipEvent_t ev_plan = nullptr;
+    uint32_t pj_sub_P1 = 0;
+    uint64_t pj_sub_need[MXG_MAX_ASSEMBLIES] = {};
     bool pj_overflowed = false;  // graph stage: the partitioned join overflowed once (build_graph then starts with the global table)
     bool dg_pj_off = false;      // owner of a partitioned graph stage: the LDS join failed once over the slots (global table from then on)
     uint64_t stat_retries = 0;   // assemblies enqueued a second time (their batches did not all end the common way)
@@ -412,6 +422,14 @@ struct GraphBounds {  // fused sketch+graph call: per assembly an upper bound of
 };
 int build_graph(mxg_handle *h, int mode = GRAPH_FULL, const void *d_msgs = nullptr, uint64_t n_msgs = 0,
                 const GraphBounds *gb = nullptr);
+// The fused call's two-level join, partitioned under the sketches (MXG_PJ_EARLY=0: never).  graph_plan_early lays the join out from
+// the bounds before the first filter is launched (allocations; cursors and super-counts cleared on the main stream) and says
+// whether the join is one to partition early; graph_partition_early puts levels 1 and 2 of assembly a on stream st, behind that
+// assembly's k_emit.  The next build_graph uses the partitions if every assembly has been through it, and partitions from
+// scratch otherwise; either way it leaves nothing of the plan in force.
+int graph_plan_early(mxg_handle *h, const GraphBounds &gb, bool *early);
+int graph_partition_early(mxg_handle *h, uint32_t a, hipStream_t st);
+void graph_drop_plan(mxg_handle *h);  // (mxg_destroy)
 int xchg_pack(mxg_handle *h, void *d_slot, uint64_t head_bytes, const uint64_t *caps);
 int xchg_unpack_graph(mxg_handle *h, const void *d_all, uint32_t world, uint64_t slot_bytes, uint64_t head_bytes,
                       const uint64_t *caps, const uint64_t *rec_offsets, const void *const *d_all_parts = nullptr,

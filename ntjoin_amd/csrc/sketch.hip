@@ -3437,6 +3437,7 @@ struct SketchStep {
     size_t n_enq = 0, next_slot = 0;
     int last_sel_slot = -1;  // the stream slot the last slice kernel of this call went to
     bool fused = false;      // the graph stage ran behind the sketches, and nothing has invalidated it since
+    bool early = false;      // the join is planned (plan_early_join) and every assembly enqueued so far has been partitioned behind its k_emit
     GraphBounds gb;
     size_t n_fast = 0;  // assemblies whose every batch ended the common way
     std::chrono::steady_clock::time_point t_cold;  // (the last cold_mark)
@@ -3742,15 +3743,19 @@ struct SketchStep {
     }
 
     // ---- mxg_sketch_graph ------------------------------------------------------------------------------------------------
-    // the graph stage behind the sketches, when every assembly of the handle is in the streams with one batch
-    int enqueue_fused_graph()
+    // what enqueue_fused_graph asks of the call, as far as it is known before anything is enqueued: the assemblies are the handle's,
+    // in the handle's order (whether each gets into the streams with one batch shows when it is enqueued)
+    bool fused_graph_possible() const
     {
-        if (!(fuse_graph && n_enq == n && n == h->asms.size() && n <= MXG_MAX_ASSEMBLIES)) return MXG_OK;
+        if (!(fuse_graph && n == h->asms.size() && n <= MXG_MAX_ASSEMBLIES)) return false;
         for (size_t i = 0; i < n; ++i)
-            if (list[i] != h->asms[i]) return MXG_OK;
-        // the second stream joins the first; the graph stage follows the sketches on it
-        int rc;
-        if ((rc = join_second_stream(h)) != MXG_OK) return rc;
+            if (list[i] != h->asms[i]) return false;
+        return true;
+    }
+
+    // the sizes the graph stage is laid out for while the sketches are in flight (after prepare_sketch: the output arrays exist)
+    void fused_bounds()
+    {
         for (size_t i = 0; i < n; ++i) {
             Assembly *a = list[i];
             const uint64_t cap = out_capacity(a);
@@ -3760,6 +3765,36 @@ struct SketchStep {
             gb.n_bound[i] = std::min<uint64_t>(cap, std::max<uint64_t>(iid, a->n_mx_seen + a->n_mx_seen / 10 + 2048));
             gb.n_ptr[i] = h->d_nmx.as<uint32_t>() + i;
         }
+    }
+
+    // The join laid out, its arrays allocated and its cursors cleared before the first filter is launched, so that every assembly can
+    // be partitioned behind its own k_emit (partition_early) instead of behind the last assembly's.
+    int plan_early_join()
+    {
+        fused_bounds();
+        return graph_plan_early(h, gb, &early);
+    }
+
+    // assembly i is in the streams: levels 1 and 2 of the join on its stream, behind its k_emit.  An assembly that did not get
+    // there ends it for the step: the graph stage will not follow the sketches either.
+    int partition_early(size_t i)
+    {
+        if (!early) return MXG_OK;
+        if (runs[i].state != AsmState::Enqueued || runs[i].q_hi != runs[i].q_lo + 1) {
+            early = false;
+            return MXG_OK;
+        }
+        return graph_partition_early(h, (uint32_t)i, drvs[items[runs[i].q_lo].slot]->st);
+    }
+
+    // the graph stage behind the sketches, when every assembly of the handle is in the streams with one batch
+    int enqueue_fused_graph()
+    {
+        if (!(fused_graph_possible() && n_enq == n)) return MXG_OK;
+        // the second stream joins the first; the graph stage follows the sketches on it
+        int rc;
+        if ((rc = join_second_stream(h)) != MXG_OK) return rc;
+        fused_bounds();
         fused = build_graph(h, GRAPH_FULL, nullptr, 0, &gb) == MXG_OK;  // (its sync is this call's sync)
         return MXG_OK;
     }
@@ -3969,16 +4004,35 @@ int sketch_assemblies(mxg_handle *h, Assembly *const *list, size_t n, bool fuse_
         if ((rc = lazy_event(h, h->ev_sel_done[q])) != MXG_OK) return rc;
     if (s.chain_modes) MXG_HIP(h, h->d_nmx.ensure(MXG_MAX_ASSEMBLIES * 4));  // (the sketches' sizes on the device, for the stage behind them)
     s.t_cold = std::chrono::steady_clock::now();
+    // mxg_sketch_graph: the join is planned before the first assembly is enqueued, which takes every assembly's tables and output
+    // arrays first (MXG_PJ_EARLY=0: planned behind the sketches, partitioned behind the last of them)
+    const bool plan_first = s.fused_graph_possible() && knob_u64(h, "MXG_PJ_EARLY", 1) != 0;
+    std::vector<char> is_empty(n, 0);
+    if (plan_first) {
+        bool any_empty = false;
+        for (size_t i = 0; i < n; ++i) {
+            bool empty = false;
+            if ((rc = prepare_sketch(h, list[i], s.runs[i].T, &empty)) != MXG_OK) return rc;
+            s.cold_mark("prepare_sketch", i);
+            is_empty[i] = empty;
+            any_empty = any_empty || empty;
+        }
+        if (!any_empty && (rc = s.plan_early_join()) != MXG_OK) return rc;
+        s.cold_mark("plan_early_join", 0);
+    }
     for (size_t i = 0; i < n; ++i) {
-        bool empty = false;
-        if ((rc = prepare_sketch(h, list[i], s.runs[i].T, &empty)) != MXG_OK) return rc;
-        s.cold_mark("prepare_sketch", i);
+        bool empty = is_empty[i] != 0;
+        if (!plan_first) {
+            if ((rc = prepare_sketch(h, list[i], s.runs[i].T, &empty)) != MXG_OK) return rc;
+            s.cold_mark("prepare_sketch", i);
+        }
         if (empty) {
             s.runs[i].state = AsmState::Done;
             continue;
         }
         if ((rc = s.enqueue_asm(i, 0)) != MXG_OK) return rc;
         s.cold_mark("enqueue_asm", i);
+        if ((rc = s.partition_early(i)) != MXG_OK) return rc;
         if (s.runs[i].state != AsmState::Enqueued) continue;
         ++s.n_enq;
         if (xp && (xp->d_parts || xp->dg)) {
@@ -4082,6 +4136,9 @@ int flush_timers(mxg_handle *h)
             h->tm.ms_hash += ms;
             h->tm.launches_hash += 1;
             h->tm.hash_bases += e.bases;
+        } else if (e.kind == 5) {  // the join's partition kernels behind an assembly's k_emit (graph_partition_early)
+            h->tm.ms_join += ms;
+            h->tm.ms_graph += ms;
         } else {
             h->tm.ms_resolve += ms;
             if (e.kind == 2) h->tm.ms_reorder += ms;
