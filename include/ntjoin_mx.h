@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MXG_ABI_VERSION 2
+#define MXG_ABI_VERSION 3
 
 /* error codes */
 #define MXG_OK 0
@@ -368,6 +368,33 @@ int mxg_path_segments_mk(mxg_handle *h, int assembly, const int64_t **s, const u
 int mxg_mk_stats(mxg_handle *h, const uint32_t *values, const uint64_t *run_first /* n_runs + 1 */, uint64_t n_runs,
                  int64_t *s, uint64_t *tie_term);
 int mxg_mx_extremes(mxg_handle *h, int assembly, const uint32_t **min_pos, const uint32_t **max_pos, uint64_t *n_records);
+
+/* ---- next row (f5): the overlap stage's cut points -------------------------------------------------------------------
+   What the reference's default run (overlap=True, ntJoin:39) computes between the paths and the scaffold sequence: the
+   joined segments are written to <prefix>.segments.fa with their middles hard-masked (print_scaffolds,
+   bin/ntjoin_assemble.py:556-578; get_valid_regions, bin/ntjoin_overlap.py:98-114), that file is sketched with
+   btllib.Indexlr at (overlap_k, overlap_w) (adjust_for_trimming :468-499), every node keeps the minimizers of its
+   overlapping ends that occur once (tally_minimizers_overlap :501-516), and for every junction with a negative raw gap
+   merge_overlapping (bin/ntjoin_overlap.py:20-88) builds an igraph graph of the two filtered lists and picks the cut.
+   Here: no file, no graph; the segments' ends are sketched from the assembly's packed bases.
+   Node i of path p is nodes[path_first[p] + i]: the bases [start, end) of `record`, reverse-complemented when `reverse`;
+   raw_gap is the raw gap size to the NEXT node of the path (read for every node, the last one included, as the reference's
+   position filter reads it).  Paths hold the nodes with an orientation only and have at least two of them (:562-568).
+   Results per node: start_adjust / end_adjust as PathNode holds them (0 = none, bin/path_node.py:41-45), and
+   cut_found[node] = 1 when the junction between the node and the next one got a cut (end_adjust of the node and
+   start_adjust of the next; either may be 0 and still be a cut).  k and w are the call's own (ntJoin: --overlap_k 15
+   --overlap_w 10), the hash variant is the handle's.  The assembly must hold bases; sketches, graph and paths of the
+   handle are left as they are.  MXG_EINVAL: an assembly without bases, start >= end, end beyond the record, a path of
+   fewer than two nodes, a segment whose first or last base is invalid (the reference asserts there).  MXG_ELIMIT: k > 256
+   or w > 4096. */
+typedef struct mxg_overlap_node {
+    uint32_t record, start, end;
+    int32_t raw_gap;
+    uint8_t reverse, pad[3];
+} mxg_overlap_node;
+int mxg_overlap_cuts(mxg_handle *h, int assembly, uint32_t k, uint32_t w, const mxg_overlap_node *nodes,
+                     const uint64_t *path_first /* n_paths + 1 */, uint64_t n_paths, uint32_t *start_adjust,
+                     uint32_t *end_adjust, uint8_t *cut_found /* per node: junction to the next */);
 
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------
    No counterpart in the reference (it is one process).  Uniqueness and intersection need every occurrence of a hash in

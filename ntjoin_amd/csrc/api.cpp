@@ -322,6 +322,7 @@ int mxg_add_assembly_packed_device_pieces(mxg_handle *h, const char *name, doubl
     if (!d_packed || !rec_start || !rec_len || !piece_lo || !piece_hi || !piece_drop)
         return commit(h, a, set_err(h, MXG_EINVAL, "null argument"));
     const uint32_t k = h->cfg.k, w = h->cfg.w;
+    a->holds_pieces = true;
     uint64_t end = 0, lo_rec = n_records, hi_rec = 0;
     for (uint64_t r = 0; r < n_records && rc == MXG_OK; ++r) {
         Record rec;
@@ -881,6 +882,20 @@ int mxg_mk_stats(mxg_handle *h, const uint32_t *values, const uint64_t *run_firs
         return mk_stats(h, values, run_first, n_runs, s, tie_term);
     } catch (const std::bad_alloc &) {
         return set_err(h, MXG_ENOMEM, "out of host memory in mxg_mk_stats");
+    }
+}
+
+int mxg_overlap_cuts(mxg_handle *h, int assembly, uint32_t k, uint32_t w, const mxg_overlap_node *nodes, const uint64_t *path_first,
+                     uint64_t n_paths, uint32_t *start_adjust, uint32_t *end_adjust, uint8_t *cut_found)
+{
+    if (!h) return MXG_EINVAL;
+    if (assembly < 0 || (size_t)assembly >= h->asms.size()) return set_err(h, MXG_EINVAL, "mxg_overlap_cuts: no assembly %d", assembly);
+    if (!path_first || (n_paths && path_first[n_paths] && (!nodes || !start_adjust || !end_adjust || !cut_found)))
+        return set_err(h, MXG_EINVAL, "mxg_overlap_cuts: null argument");
+    try {
+        return overlap_cuts(h, h->asms[assembly], assembly, k, w, nodes, path_first, n_paths, start_adjust, end_adjust, cut_found);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_overlap_cuts");
     }
 }
 

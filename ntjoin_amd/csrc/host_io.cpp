@@ -346,6 +346,9 @@ struct Ingest {
                 ++run_len;
             } else {
                 close_run();  // fpos = position of the invalid base = one past the run's last base
+                const uint64_t g = a->recs.back().base_off + fpos;
+                if (!a->inv.empty() && a->inv.back().second == g) ++a->inv.back().second;
+                else a->inv.emplace_back(g, g + 1);
             }
             ++fpos;
             if (slot == 15) {
@@ -615,6 +618,7 @@ int load_fasta(mxg_handle *h, Assembly *a, const char *path, uint32_t shard, uin
             a->split_first_cont = hi > lo && in.pieces[lo].cont;
             in.lengths_only = in.collect_runs = false;
             in.split = true;
+            a->holds_pieces = true;
             in.all_runs.clear();
             f.rewind();
         }

@@ -427,9 +427,11 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
         const Record &rec = a->recs[r];
         std::vector<std::pair<uint32_t, uint32_t>> rec_runs;  // (pos0, n_kmers)
         uint32_t state = 0;
-        uint64_t run_start = 0;
+        uint64_t run_start = 0, inv_start = 0;
         auto flip = [&](uint64_t at_rel, uint32_t to) {
             if (to == state) return;
+            if (to && at_rel > inv_start) a->inv.emplace_back(rec.base_off + inv_start, rec.base_off + at_rel);
+            if (!to) inv_start = at_rel;
             if (to) run_start = at_rel;
             else if (at_rel - run_start >= k) rec_runs.emplace_back((uint32_t)run_start, (uint32_t)(at_rel - run_start - k + 1));
             state = to;
@@ -446,6 +448,7 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
             if (state != lv[q]) return set_err(h, MXG_EDEVICE, "internal error: validity tracking out of step in '%s'", path);
         }
         flip(rec.len, 0);
+        if (rec.len > inv_start) a->inv.emplace_back(rec.base_off + inv_start, rec.base_off + rec.len);
         uint64_t nk = 0;
         for (auto &rr : rec_runs) nk += rr.second;
         if (nk >= w && nk > 0) {

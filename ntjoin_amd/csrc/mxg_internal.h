@@ -103,6 +103,13 @@ struct Assembly {
     std::string text;                // concatenated record text as read (kept unless MXG_FLAG_DROP_SEQ)
     bool has_text = false;
     std::vector<uint32_t> h_packed;  // host 2-bit packing (dropped after upload)
+    // the invalid (non-ACGTU) bases as maximal intervals [first, second) of global base indices, in base order.  Unlike the run
+    // table below (runs of >= k bases of eligible records, for the handle's k and w) this holds for any k and w: what
+    // mxg_overlap_cuts (overlap.hip) decides validity by.  Empty for packed-device input (no invalid bases by contract).
+    std::vector<std::pair<uint64_t, uint64_t>> inv;
+    DevBuf d_inv;              // ... uploaded by the first mxg_overlap_cuts
+    bool inv_on_device = false;
+    bool holds_pieces = false;  // split load: the handle holds pieces of records, not whole records
     // device ingest (ingest.hip): the raw FASTA text in HBM + the tile index that maps a base to its byte
     bool text_on_device = false;
     uint64_t text_bytes = 0;
@@ -245,6 +252,7 @@ struct mxg_handle {
     mxg::Paths paths;
     mxg::DevBuf pbuf[48];  // scratch of paths.hip
     mxg::DevBuf mkbuf[8];  // scratch of mk.hip
+    mxg::DevBuf ovbuf[16];  // scratch of overlap.hip
     mxg::Segments segs;
     mxg::Timers tm;
     mxg::HashTab tab{};
@@ -468,6 +476,9 @@ int path_segments_mk(mxg_handle *h, uint32_t assembly);
 int mk_runs(mxg_handle *h, uint32_t *d_x, const uint32_t *d_first, uint32_t n_runs, uint32_t n_total,
             const std::vector<uint32_t> &len, int64_t *s, uint64_t *tie_term);
 int mk_stats(mxg_handle *h, const uint32_t *values, const uint64_t *run_first, uint64_t n_runs, int64_t *s, uint64_t *tie_term);
+// overlap.hip: the cut points of every overlapping junction of the given paths (mxg_overlap_cuts)
+int overlap_cuts(mxg_handle *h, Assembly *a, int assembly, uint32_t k, uint32_t w, const mxg_overlap_node *nodes,
+                 const uint64_t *path_first, uint64_t n_paths, uint32_t *start_adjust, uint32_t *end_adjust, uint8_t *cut_found);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm
 int flags_to_host(mxg_handle *h, Assembly *a);
 

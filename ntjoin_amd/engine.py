@@ -374,6 +374,27 @@ class MxEngine:
         self._check(self._lib.mxg_mk_stats(self._h, x.ctypes.data, rf.ctypes.data, n_runs, s.ctypes.data, t.ctypes.data))
         return s, t
 
+    OVERLAP_NODE = np.dtype([("record", "<u4"), ("start", "<u4"), ("end", "<u4"), ("raw_gap", "<i4"), ("reverse", "u1"),
+                             ("pad", "u1", (3,))])
+
+    def overlap_cuts(self, assembly, nodes, path_first, k=15, w=10):
+        """mxg_overlap_cuts: nodes = array of OVERLAP_NODE (or rows (record, start, end, raw_gap, reverse)), path_first = n_paths + 1
+        offsets -> dict(start_adjust u32[n], end_adjust u32[n], cut_found bool[n]: the junction behind node i got a cut)"""
+        if not (isinstance(nodes, np.ndarray) and nodes.dtype == self.OVERLAP_NODE):
+            rows = np.asarray(nodes, dtype=np.int64).reshape(-1, 5)
+            nodes = np.zeros(len(rows), dtype=self.OVERLAP_NODE)
+            for j, name in enumerate(("record", "start", "end", "raw_gap", "reverse")):
+                nodes[name] = rows[:, j]
+        nodes = np.ascontiguousarray(nodes)
+        pf = np.ascontiguousarray(path_first, dtype=np.uint64)
+        if len(pf) < 1 or int(pf[-1]) != len(nodes):
+            raise ValueError("overlap_cuts: path_first needs n_paths + 1 offsets, the last one len(nodes)")
+        n = len(nodes)
+        sa, ea, cf = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.mxg_overlap_cuts(self._h, int(assembly), int(k), int(w), nodes.ctypes.data, pf.ctypes.data, len(pf) - 1,
+                                               sa.ctypes.data, ea.ctypes.data, cf.ctypes.data))
+        return {"start_adjust": sa, "end_adjust": ea, "cut_found": cf.astype(bool)}
+
     def mx_extremes(self, a):
         """per record of assembly a: (min, max) position over its graph vertices; None for records without one"""
         mn, mx, n = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.c_uint64()

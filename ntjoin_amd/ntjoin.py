@@ -283,6 +283,43 @@ class Ntjoin:
                 u[7], u[8] = gap, mean_dist - a_over - b_over
         return out
 
+    def trim_overlaps(self, paths, overlap_k=None, overlap_w=None):
+        """The cut points of the reference's overlap stage (adjust_for_trimming, bin/ntjoin_assemble.py:468-516, and
+        merge_overlapping, bin/ntjoin_overlap.py:20-88) for paths as format_paths() returns them.  Nodes of orientation '?'
+        and paths left with fewer than two nodes are dropped, as print_scaffolds does (:558-575); per input path the list of
+        (start_adjust, end_adjust) of its kept nodes comes back ([] for a dropped path; 0 = no adjustment).  k and w
+        default to args.overlap_k / args.overlap_w, then 15 / 10 (ntJoin:39)."""
+        k = int(overlap_k if overlap_k is not None else getattr(self.args, "overlap_k", None) or 15)
+        w = int(overlap_w if overlap_w is not None else getattr(self.args, "overlap_w", None) or 10)
+        eng, tgt = self._engine, len(self._order) - 1
+        if tgt < 0:
+            raise ValueError("trim_overlaps: no target assembly has been loaded")
+        if self._order[tgt] not in self._fasta:
+            raise ValueError("trim_overlaps: the target was loaded from a minimizer TSV, which holds no bases; the overlap stage "
+                             "sketches the segments' ends, so the target must come from FASTA (Ntjoin(fasta={target: path}))")
+        index = {rid: r for r, rid in enumerate(eng.record_ids(tgt, eng.n_records(tgt)))}
+        rows, first, kept = [], [0], []
+        for path in paths:
+            nodes = [nd for nd in path if nd[1] != "?"]
+            if len(nodes) < 2:
+                kept.append(0)
+                continue
+            for i, nd in enumerate(nodes):
+                if nd[0] not in index:
+                    raise ValueError(f"trim_overlaps: path {len(kept)} node {i}: the target holds no contig {nd[0]!r}")
+                rows.append((index[nd[0]], nd[2], nd[3], nd[8], nd[1] == "-"))
+            first.append(len(rows))
+            kept.append(len(nodes))
+        if not rows:
+            return [[] for _ in paths]
+        res = eng.overlap_cuts(tgt, rows, first, k=k, w=w)
+        sa, ea = res["start_adjust"].tolist(), res["end_adjust"].tolist()
+        out, at = [], 0
+        for n in kept:
+            out.append(list(zip(sa[at:at + n], ea[at:at + n])))
+            at += n
+        return out
+
     def print_graph(self, graph, out_prefix=None):
         "Prints the minimizer graph in dot format"
         out_graph = (self.args.p + ".mx.dot") if out_prefix is None else (out_prefix + "mx.dot")
