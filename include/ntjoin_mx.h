@@ -112,6 +112,16 @@ typedef struct mxg_graph_view {
     const double *edge_weight;    /* sum of weights over support, in assembly order (ntjoin_utils.py:54-56) */
 } mxg_graph_view;
 
+/* mxg_stats::graph_join: which join the last mxg_build_graph ended with (low byte), and what happened on the way (bits)  */
+enum mxg_graph_join {
+    MXG_JOIN_LDS = 1,           /* LDS tables per hash partition                                                            */
+    MXG_JOIN_LDS_TWO_LEVEL = 2, /* the same behind coarse partitions (two levels)                                           */
+    MXG_JOIN_GLOBAL = 3,        /* one global table                                                                         */
+    MXG_JOIN_RESIZED = 0x100,   /* coarse partitions re-sized and the join redone                                           */
+    MXG_JOIN_GAVE_UP = 0x200,   /* the LDS join gave up and the global table ran (a slot that was reserved)                 */
+    MXG_JOIN_EARLY = 0x400      /* mxg_sketch_graph partitioned every assembly behind its own sketch (MXG_PJ_EARLY)         */
+};
+
 typedef struct mxg_stats {
     uint32_t struct_size;
     uint32_t n_assemblies;
@@ -136,10 +146,7 @@ typedef struct mxg_stats {
     double ms_vertices;        /* vertex ids + adjacency arrays                                  */
     double ms_edges;           /* edge flags + edge compaction                                   */
     uint64_t bs_filter_bases;  /* bases covered by the bit-sliced filter (k = 32 route; 0: the rolling-hash kernel ran) */
-    uint64_t graph_join;       /* the last mxg_build_graph's join: 1 = LDS tables per hash partition, 2 = the same behind coarse
-                                  partitions (two levels), 3 = one global table; | 0x100: coarse partitions re-sized and the join
-                                  redone, | 0x200: the LDS join gave up and the global table ran (a slot that was reserved),
-                                  | 0x400: mxg_sketch_graph partitioned every assembly behind its own sketch (MXG_PJ_EARLY)     */
+    uint64_t graph_join;       /* the last mxg_build_graph's join: one of the three joins | what happened on the way (mxg_graph_join) */
     /* what the common route (every batch enqueued once, one host sync) could not finish: candidate floods beyond the estimate,
        stretches the device route cannot hold, output beyond its bound.  Such batches are redone one by one behind the good ones */
     uint64_t batches_redone;   /* batches redone through the synchronous route                               */

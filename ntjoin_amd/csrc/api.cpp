@@ -152,9 +152,7 @@ static int commit(mxg_handle *h, Assembly *a, int rc)
     h->asms.push_back(a);
     if (prewarm_assembly(h, a) != MXG_OK) h->err.clear();  // (what cannot be prepared now is reported by the sketch that needs it)
     h->graph.valid = false;
-    h->pj_overflowed = false;
-    h->pj_cap1_P1 = 0;
-    h->pj_cap1_need = 0;
+    h->pj_learnt.assembly_added();
     return (int)h->asms.size() - 1;
 }
 
@@ -932,7 +930,7 @@ int mxg_dg_vertices(mxg_handle *h, void *d_n_vertices)
 {
     if (!h || !d_n_vertices) return MXG_EINVAL;
     try {
-        int rc = build_graph(h, GRAPH_DG_VERTICES, d_n_vertices, 0);
+        int rc = build_graph(h, GraphCall::dg_vertices(d_n_vertices));
         if (rc == MXG_OK && h->own_stream && hipStreamSynchronize(h->stream) != hipSuccess) rc = MXG_EDEVICE;
         return rc;  // (own stream: the word feeds a collective on another stream)
     } catch (const std::bad_alloc &) {
@@ -977,7 +975,7 @@ int mxg_dg_edges(mxg_handle *h, const void *d_msgs, uint64_t n_msgs, uint64_t *n
 {
     if (!h || (n_msgs && !d_msgs)) return MXG_EINVAL;
     try {
-        int rc = build_graph(h, GRAPH_DG_EDGES, d_msgs, n_msgs);
+        int rc = build_graph(h, GraphCall::dg_edges(d_msgs, n_msgs));
         if (rc != MXG_OK) return rc;
     } catch (const std::bad_alloc &) {
         return set_err(h, MXG_ENOMEM, "out of host memory in mxg_dg_edges");

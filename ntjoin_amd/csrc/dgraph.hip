@@ -868,7 +868,7 @@ int dg_owner_slots(mxg_handle *h, uint32_t world, uint32_t n_asm, const uint32_t
         gb.n_ptr[ai] = h->d_nmx.as<uint32_t>() + ai;
     }
     MXG_HIP(h, hipGetLastError());
-    rc = build_graph(h, GRAPH_DG_VERTICES, d_nv, 0, &gb);
+    rc = build_graph(h, GraphCall::dg_vertices(d_nv, &gb));
     if (rc == MXG_OK && h->own_stream) MXG_HIP(h, hipStreamSynchronize(h->stream));  // d_nv feeds a collective elsewhere
     return rc;
 }
@@ -962,12 +962,12 @@ int dg_edges_slots(mxg_handle *h, const void *d_recv, uint32_t world, uint32_t M
                                ovf);
         MXG_HIP(h, hipGetLastError());
     }
-    int rc = build_graph(h, GRAPH_DG_EDGES_APPLIED);
+    int rc = build_graph(h, GraphCall::dg_edges_applied());
     if (rc != MXG_OK) return rc;
     uint32_t back[MXG_MAX_ASSEMBLIES + 4];
     MXG_HIP(h, hipMemcpy(back, h->d_nmx.p, sizeof back, hipMemcpyDeviceToHost));
     for (uint32_t ai = 0; ai < A; ++ai) h->asms[ai]->n_mx = back[ai];  // the real item counts
-    if (back[MXG_MAX_ASSEMBLIES + 2] | back[MXG_MAX_ASSEMBLIES + 3]) h->dg_pj_off = true;  // (the LDS join failed: reported as overflow above)
+    if (back[MXG_MAX_ASSEMBLIES + 2] | back[MXG_MAX_ASSEMBLIES + 3]) h->pj_learnt.dg_off = true;  // (the LDS join failed: reported as overflow above)
     if (n_vertices) *n_vertices = g.nv;
     if (n_edges) *n_edges = g.ne;
     if (overflow) *overflow = back[MXG_MAX_ASSEMBLIES];

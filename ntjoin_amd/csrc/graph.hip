@@ -142,9 +142,7 @@ __global__ __launch_bounds__(256) void k_flags(const AsmSet p, const Slot *__res
 // through the record position k_pj_bucket stored in slot[a][i].  Slot numbers are partition * (PJ_T + 1) + local slot.
 // A partition with more distinct keys than its table holds reports failure through pinned host memory and build_graph
 // redoes the stage with the global table.
-constexpr uint32_t PJ_IPB = 4096;  // items per bucketing block = 16 blocks of 256
-constexpr uint32_t PJ_T = 2048;    // slots of a partition's table (+1: the slot of the key that equals the empty mark)
-constexpr uint32_t PJ_MAX_P = 4096;
+// (PJ_IPB items per bucketing block, PJ_T slots per table, at most PJ_MAX_P partitions: join_plan.h)
 
 __device__ __forceinline__ uint32_t pj_part(uint64_t key, uint32_t pmask)
 {
@@ -272,7 +270,7 @@ __device__ __forceinline__ uint32_t pj_slot(unsigned long long *keys, uint64_t k
 // partitions of capacity cap1 (coarse partition c holds cursor[c * PJ1_CS] records from c * cap1 on), k_pj2_bucket has sorted
 // every 4096-record region of a coarse partition into P sub-partitions (rows of M: rows2 per coarse partition); block
 // blockIdx.x = c * P + b joins sub-partition b of coarse partition c.
-constexpr uint32_t PJ1_CS = 32;  // words between the coarse partitions' cursors (own 128-byte lines: same-line atomics serialise)
+// (PJ1_CS words between the coarse partitions' cursors: join_plan.h)
 // A coarse partition's cap1 records are ONE run that all assemblies fill through one cursor (n_sub = 1), or -- the fused call that
 // partitions every assembly behind its own k_emit, while the others are still being sketched -- one 4096-aligned sub-range per
 // assembly, [off, off + cap) of the partition, with a cursor per (coarse partition, assembly): level 2 of an assembly then sorts
@@ -1097,9 +1095,6 @@ static int d2h(mxg_handle *h, std::vector<T> &dst, const void *src, size_t n)
     return MXG_OK;
 }
 
-// control block g_ctl (u64 words): [0..A) shared count per assembly, [32] edge count, [33] unique count
-static constexpr int CTL_EDGES = 32, CTL_WORDS = 40;
-
 __global__ __launch_bounds__(256) void k_count_unique(const uint8_t *__restrict__ flags, uint32_t n, unsigned long long *counter)
 {
     uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -1108,75 +1103,65 @@ __global__ __launch_bounds__(256) void k_count_unique(const uint8_t *__restrict_
     if ((threadIdx.x & 63u) == 0 && m) atomicAdd(counter, (unsigned long long)__popcll(m));
 }
 
-// mode GRAPH_FULL: the whole stage.  The distributed graph (dgraph.hip) runs it in two halves on the OWNER's handle:
-// GRAPH_DG_VERTICES stops after the vertices (and records the vertex id of every item), GRAPH_DG_EDGES resumes with the
-// adjacency taken from messages instead of from the handle's own record order.
-// gb (fused sketch+graph call, GRAPH_FULL only): the sketches are still being computed on the stream; sizes are the
-// bounds gb->n_bound[a], the kernels read the counts from gb->n_ptr[a] on the device.
-static constexpr int CTL_PJ_FAIL = 34;  // pinned control block: a partition's table overflowed (k_pj_join)
-static constexpr int RC_RETRY_GLOBAL = 1, RC_RETRY_PJ = 2;
+// The stage's control block (u64 words): g_ctl in HBM, which the kernels count in, and its pinned host copy (pinned_gctl), which
+// k_edges and the join kernels write for the host to read behind the stage's one sync.
+enum CtlWord : uint32_t {
+    CTL_SHARED = 0,    // [0..MXG_MAX_ASSEMBLIES) shared minimizers per assembly (equal by construction): the vertex count
+    CTL_EDGES = 32,    // edge count
+    CTL_UNIQUE = 33,   // unique count (reserved: mxg_get_stats counts lazily from the flags)
+    CTL_PJ_FAIL = 34,  // host copy only: a partition's table or a coarse partition's capacity overflowed (k_pj_join)
+    CTL_WORDS = 40,
+};
+static_assert(CTL_SHARED + MXG_MAX_ASSEMBLIES <= CTL_EDGES, "the per-assembly counts end before the other words");
 
-static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_t n_msgs, const GraphBounds *gb, bool global_table);
+static int build_graph_impl(mxg_handle *h, const GraphCall &c, bool global_table);
 
-int build_graph(mxg_handle *h, int mode, const void *d_msgs, uint64_t n_msgs, const GraphBounds *gb)
+int build_graph(mxg_handle *h, const GraphCall &c)
 {
-    // (a handle whose minimizers once overflowed a partition -- a key of huge multiplicity: satellite arrays -- goes straight to
-    // the global table afterwards: the same assemblies would overflow again)
     h->stat_graph_join = 0;
     uint64_t how = 0;
-    // what the handle learnt from an overflow (start with the global table; a coarse partition's capacity) holds for the sketches it
-    // was learnt on: other sketches -- new assemblies, a borrowed buffer refilled and sketched again -- start with the defaults
-    uint64_t sig = 0x9E3779B97F4A7C15ull * (h->asms.size() + 1);
-    for (const Assembly *a : h->asms) sig = (sig ^ a->n_mx) * 0x100000001B3ull;
-    if (!gb && (h->pj_overflowed || h->pj_cap1_P1) && h->pj_learnt_sig != sig) {
-        h->pj_overflowed = false;
-        h->pj_cap1_P1 = 0;
-        h->pj_cap1_need = 0;
-        h->pj_sub_P1 = 0;
+    JoinLearnt &learnt = h->pj_learnt;
+    // what the handle learnt from an overflow holds for the sketches it was learnt on.  (The fused call and the owner's slots, c.gb:
+    // the sizes are bounds, the sketches' own are not known yet -- the signature is neither compared nor taken.)
+    if (!c.gb) {
+        uint64_t n_mx[MXG_MAX_ASSEMBLIES];
+        const uint32_t n = (uint32_t)std::min<size_t>(h->asms.size(), MXG_MAX_ASSEMBLIES);
+        for (uint32_t a = 0; a < n; ++a) n_mx[a] = h->asms[a]->n_mx;
+        learnt.sketches_are(JoinLearnt::signature(n, n_mx));
     }
-    if (!gb) h->pj_learnt_sig = sig;
-    int rc = build_graph_impl(h, mode, d_msgs, n_msgs, gb, h->pj_overflowed);
+    // (a handle whose minimizers once overflowed a partition -- a key of huge multiplicity: satellite arrays -- goes straight to
+    // the global table afterwards: the same assemblies would overflow again)
+    int rc = build_graph_impl(h, c, learnt.overflowed);
     // (a coarse partition outgrew its capacity -- hash skew: a key of large multiplicity -- while the tables held: once more with
     // the capacity the cursors ask for, which the handle keeps)
     if (rc == RC_RETRY_PJ) {
-        how |= 0x100;
-        rc = build_graph_impl(h, mode, d_msgs, n_msgs, gb, false);
+        how |= MXG_JOIN_RESIZED;
+        rc = build_graph_impl(h, c, false);
     }
     if (rc == RC_RETRY_PJ) rc = RC_RETRY_GLOBAL;
     if (rc == RC_RETRY_GLOBAL) {
-        how |= 0x200;
-        h->pj_overflowed = true;
-        rc = build_graph_impl(h, mode, d_msgs, n_msgs, gb, true);
+        how |= MXG_JOIN_GAVE_UP;
+        learnt.gave_up();
+        rc = build_graph_impl(h, c, true);
     }
     h->stat_graph_join |= how;
     return rc;
 }
 
-// The join's layout: everything build_graph_impl derives from the assemblies' sizes (the sketches' own, or the bounds gb of the
-// fused call) before it launches anything -- which join, how many partitions of what capacity, where every array lies -- and the
-// allocations that go with it.  The fused call plans before its first filter is launched (graph_plan_early) and hands the plan on.
-struct JoinPlan {
-    uint32_t A = 0;
-    uint64_t N = 0, nvs = 0;
-    uint64_t n_of[MXG_MAX_ASSEMBLIES] = {};
-    uint32_t cap = 0, mask = 0, full = 0;
-    uint32_t P = 0, P1 = 0, cap1 = 0, rows2 = 0;
-    bool two_level = false, pj = false, dg_pj = false;
+// The join's layout: the shape join_shape derives from the assemblies' sizes (the sketches' own, or the bounds gb of the fused
+// call) before anything is launched, where every array lies, and the allocations that go with it.  The fused call plans before
+// its first filter is launched (graph_plan_early) and hands the plan on.
+struct JoinPlan : JoinShape {
     uint32_t pj_force_fail = 0;
-    size_t nb0 = 0;
     uint64_t *pj_mask0 = nullptr;
     uint32_t *pj_bpref0 = nullptr;
     AsmSet as_all;
-    uint32_t nb = 0;
-    uint32_t n_items = 0, e_blocks = 0;
     uint32_t n_fsup = 0, n_esup = 0;
     uint32_t *fsup = nullptr, *esup = nullptr, *cnt = nullptr;
     // two-level join
     uint32_t *M = nullptr, *cursor = nullptr;
     uint4 *recs1 = nullptr, *recs2 = nullptr;
-    bool split = false;  // a sub-range of every coarse partition per assembly (PjSub)
     PjSubCaps sc;
-    uint32_t sub_off[MXG_MAX_ASSEMBLIES] = {}, skew_lim[MXG_MAX_ASSEMBLIES] = {};
     size_t clear_words = 0;  // split: super-counts and cursors are one run of g_cnt, cleared by one fill
 };
 
@@ -1186,91 +1171,38 @@ static int plan_join(mxg_handle *h, int mode, const GraphBounds *gb, bool global
     if (A == 0) return set_err(h, MXG_EINVAL, "mxg_build_graph: no assemblies");
     if (A > MXG_MAX_ASSEMBLIES) return set_err(h, MXG_ELIMIT, "at most %d assemblies", MXG_MAX_ASSEMBLIES);
     pl = JoinPlan();
-    pl.A = A;
-    uint64_t N = 0, nmin = ~0ull;
-    uint64_t *const n_of = pl.n_of;
+    JoinRequest rq;
+    rq.A = A;
     for (uint32_t ai = 0; ai < A; ++ai) {
         Assembly *a = h->asms[ai];
         if (!gb && !a->has_sketch) return set_err(h, MXG_EINVAL, "assembly '%s' has no sketch (call mxg_sketch)", a->name.c_str());
-        n_of[ai] = gb ? gb->n_bound[ai] : a->n_mx;
-        N += n_of[ai];
-        nmin = std::min(nmin, n_of[ai]);
+        rq.n_of[ai] = gb ? gb->n_bound[ai] : a->n_mx;
     }
-    if (N >= (1ull << 30)) return set_err(h, MXG_ELIMIT, "too many minimizers for one table (%llu)", (unsigned long long)N);
-    pl.N = N;
-    const bool resume = mode == GRAPH_DG_EDGES || mode == GRAPH_DG_EDGES_APPLIED;  // second half on the owner's handle
-
-    uint32_t cap = 1024;
-    while (cap < 2 * N) cap <<= 1;
-    pl.cap = cap;
-    pl.mask = cap - 1;
-    pl.full = (A == 32) ? 0xFFFFFFFFu : ((1u << A) - 1u);
-    // the join: LDS tables per hash partition (the whole-stage call, up to PJ_MAX_P partitions of <= 1280 records), else
-    // the global table.  MXG_GRAPH_JOIN=global|lds and MXG_PJ_FORCE_FAIL=1 are test knobs (knob_*: as the handle first saw them).
-    uint32_t P = 256;
-    while ((uint64_t)P * 1280 < N) P <<= 1;
+    rq.mode = mode;
+    rq.bounds = gb != nullptr;
+    rq.global_table = global_table;
+    rq.split = split;
+    // MXG_GRAPH_JOIN=global|lds, MXG_PJ_TWO_LEVEL=1 (two levels on small inputs) and MXG_PJ_FORCE_FAIL=1 are test knobs (knob_*:
+    // as the handle first saw them)
     const char *join_env = knob_raw(h, "MXG_GRAPH_JOIN");
-    // beyond PJ_MAX_P partitions of <= 1280 records: two levels -- P1 coarse partitions, each sorted into 256 sub-partitions
-    // (MXG_PJ_TWO_LEVEL=1 forces them on small inputs: test knob)
-    uint32_t P1 = 0, cap1 = 0, rows2 = 0;
-    bool fits32 = true;
-    pl.sc.n_sub = 1;
-    for (uint32_t a = 0; a < MXG_MAX_ASSEMBLIES; ++a) pl.sc.cap[a] = 0;
-    if (P > PJ_MAX_P || knob_u64(h, "MXG_PJ_TWO_LEVEL", 0)) {
-        P = 256;
-        P1 = 2;
-        while ((uint64_t)P1 * P * 1000 < N) P1 <<= 1;
-        if (split) {  // a sub-range per assembly, each with the slack of the whole: 25 % above ITS mean
-            uint64_t c_all = 0;
-            for (uint32_t a = 0; a < A; ++a) {
-                const uint64_t mean = n_of[a] / P1;
-                uint64_t c1 = mean + mean / 4 + 4096;
-                if (h->pj_sub_P1 == P1) c1 = std::max<uint64_t>(c1, h->pj_sub_need[a]);  // (what an earlier call's cursors asked for)
-                c1 = (c1 + PJ_IPB - 1) / PJ_IPB * PJ_IPB;
-                pl.sub_off[a] = (uint32_t)std::min<uint64_t>(c_all, 0xFFFFF000u);
-                pl.sc.cap[a] = (uint32_t)std::min<uint64_t>(c1, 0xFFFFF000u);
-                pl.skew_lim[a] = (uint32_t)std::min<uint64_t>(mean + mean / 32 + 2048, 0xFFFFFFFFull);  // 3 % above the mean
-                c_all += c1;
-            }
-            pl.sc.n_sub = A;
-            pl.split = true;
-            cap1 = (uint32_t)std::min<uint64_t>(c_all, 0xFFFFF000u);
-            fits32 = c_all <= 0xFFFFF000u;  // (a coarse partition's records are counted in 32 bits)
-        } else {
-            uint64_t c1 = (N / P1) + (N / P1) / 4 + 4096;  // 25 % above the mean (hash skew: keys of large multiplicity)
-            if (h->pj_cap1_P1 == P1) c1 = std::max<uint64_t>(c1, h->pj_cap1_need);  // (what an earlier call's cursors asked for)
-            cap1 = (uint32_t)((c1 + PJ_IPB - 1) / PJ_IPB * PJ_IPB);
-            pl.sc.cap[0] = cap1;
-        }
-        rows2 = cap1 / PJ_IPB;
+    rq.join_global = join_env && !strcmp(join_env, "global");
+    rq.force_two_level = knob_u64(h, "MXG_PJ_TWO_LEVEL", 0) != 0;
+    switch (join_shape(rq, h->pj_learnt, pl)) {
+    case JS_TOO_MANY_MINIMIZERS: return set_err(h, MXG_ELIMIT, "too many minimizers for one table (%llu)", (unsigned long long)pl.N);
+    case JS_TOO_MANY_ITEMS: return set_err(h, MXG_ELIMIT, "graph too large for 32-bit item indices");
+    case JS_OK: break;
     }
-    const bool two_level = P1 != 0 && P1 <= 4096 && fits32 && (uint64_t)P1 * cap1 < (1ull << 32) && (uint64_t)P1 * P * (PJ_T + 1) < (1ull << 29);
-    // (k_pj_join's verdict word carries the index of the key's minimizer in assembly 0 above three flag bits, k_pj2_bucket's
-    // reference that of a minimizer of the same assembly: < 2^29)
-    uint64_t n_max = 0;
-    for (uint32_t a = 0; a < A; ++a) n_max = std::max(n_max, n_of[a]);
-    // (the owner's half of the partitioned graph stage takes the LDS join too when it runs over fixed slots -- gb: the counts on the
-    // device, nobody waits for the host before the verdicts leave -- and says "failed" through a DEVICE word: dg_pj_fail_word)
-    const bool dg_pj = mode == GRAPH_DG_VERTICES && gb != nullptr && !h->dg_pj_off;
-    const bool pj = (mode == GRAPH_FULL || dg_pj) && !global_table && (P1 == 0 || two_level) && P <= PJ_MAX_P &&
-                    n_max < (1ull << 29) && !(join_env && !strcmp(join_env, "global"));
-    pl.P = P;
-    pl.P1 = P1;
-    pl.cap1 = cap1;
-    pl.rows2 = rows2;
-    pl.two_level = two_level;
-    pl.dg_pj = dg_pj;
-    pl.pj = pj;
     pl.pj_force_fail = knob_u64(h, "MXG_PJ_FORCE_FAIL", 0) ? 1u : 0u;
+    pl.sc.n_sub = pl.n_sub;
+    for (uint32_t a = 0; a < MXG_MAX_ASSEMBLIES; ++a) pl.sc.cap[a] = pl.sub_cap[a];
+    const uint64_t *const n_of = pl.n_of;
+    const uint32_t nb = pl.nb, P = pl.P, P1 = pl.P1;
 
-    if (!pj) MXG_HIP(h, h->g_keys.ensure(((size_t)cap + 1) * sizeof(Slot)));  // (the partitioned join keeps its N records here)
+    if (!pl.pj) MXG_HIP(h, h->g_keys.ensure(((size_t)pl.cap + 1) * sizeof(Slot)));  // (the partitioned join keeps its N records here)
     // global table: slot -> vertex id; partitioned join: assembly 0's shared mask (8 B per 64 minimizers) + block prefix
     // (+ partitioned join: one "follower" bit per minimizer of every assembly, pj_run_role)
-    const size_t nb0 = (size_t)((n_of[0] + 255) / 256);
-    size_t nb_all = 0;
-    for (uint32_t a = 0; a < A; ++a) nb_all += (size_t)((n_of[a] + 255) / 256);
-    MXG_HIP(h, h->g_vid.ensure(pj ? (nb0 + nb_all) * 4 * 8 + nb0 * 4 + 64 : ((size_t)cap + 1) * 4));
-    pl.nb0 = nb0;
+    const size_t nb0 = pl.nb0, nb_all = nb;
+    MXG_HIP(h, h->g_vid.ensure(pl.pj ? (nb0 + nb_all) * 4 * 8 + nb0 * 4 + 64 : ((size_t)pl.cap + 1) * 4));
     pl.pj_mask0 = h->g_vid.as<uint64_t>();
     uint64_t *const pj_fol = pl.pj_mask0 + nb0 * 4;
     pl.pj_bpref0 = reinterpret_cast<uint32_t *>(pj_fol + nb_all * 4);
@@ -1279,8 +1211,7 @@ static int plan_join(mxg_handle *h, int mode, const GraphBounds *gb, bool global
     AsmSet &as_all = pl.as_all;
     as_all.n_asm = A;
     as_all.full = pl.full;
-    as_all.fol = pj ? pj_fol : nullptr;
-    uint32_t nb = 0;
+    as_all.fol = pl.pj ? pj_fol : nullptr;
     for (uint32_t a = 0; a < A; ++a) {
         Assembly *as = h->asms[a];
         MXG_HIP(h, as->d_slot.ensure(std::max<uint64_t>(n_of[a] * 4, 16)));
@@ -1288,49 +1219,37 @@ static int plan_join(mxg_handle *h, int mode, const GraphBounds *gb, bool global
         MXG_HIP(h, as->d_shared.ensure(std::max<uint64_t>(n_of[a], 16)));
         as_all.n[a] = (uint32_t)n_of[a];
         as_all.n_ptr[a] = gb ? gb->n_ptr[a] : nullptr;
-        as_all.bstart[a] = nb;
-        nb += (uint32_t)((n_of[a] + 255) / 256);
         as_all.hash[a] = as->d_hash.as<uint64_t>();
         as_all.slot[a] = as->d_slot.as<uint32_t>();
         as_all.flags[a] = as->d_flags.as<uint8_t>();
         as_all.shared[a] = as->d_shared.as<uint8_t>();
     }
-    as_all.bstart[A] = nb;
     for (uint32_t a = A; a < MXG_MAX_ASSEMBLIES; ++a) {
         as_all.n[a] = 0;
         as_all.n_ptr[a] = nullptr;
-        as_all.bstart[a + 1] = nb;
         as_all.hash[a] = nullptr;
         as_all.slot[a] = nullptr;
         as_all.flags[a] = as_all.shared[a] = nullptr;
     }
-    pl.nb = nb;
-    // vertex arrays are strided by an upper bound of the vertex count (every vertex occurs once in every assembly), so
-    // this stage needs no host sync before its kernels: they read the counts from the control block in HBM
-    const uint64_t nvs = nmin;  // stride
-    pl.nvs = nvs;
-    if (nvs > 0 && (uint64_t)A * nvs >= (1ull << 32)) return set_err(h, MXG_ELIMIT, "graph too large for 32-bit item indices");
-    pl.n_items = (uint32_t)((size_t)A * nvs);
-    pl.e_blocks = (pl.n_items + 255) / 256;
+    std::copy(pl.bstart, pl.bstart + MXG_MAX_ASSEMBLIES + 1, as_all.bstart);
     // per-256 counts of the two counting kernels and their super-counts (scan_kernels.h): [sup of k_flags, one run
     // per assembly | sup of k_edge_flags | cnt of k_flags]; k_insert zeroes the super-counts
     // (split: the cursors of the sub-ranges lie between the super-counts and the counts, so that one fill clears both)
     pl.n_fsup = ((nb >> SUP_SHIFT) + A + 1) * SUP_STRIDE;
     pl.n_esup = sup_words(pl.e_blocks);
-    const bool cursors_here = pl.split && pj && two_level;
-    const size_t n_cur = cursors_here ? (size_t)P1 * A * PJ1_CS : 0;
-    MXG_HIP(h, h->g_cnt.ensure(((size_t)pl.n_fsup + pl.n_esup + n_cur + nb) * 4 + 64));
+    MXG_HIP(h, h->g_cnt.ensure(((size_t)pl.n_fsup + pl.n_esup + pl.n_cur + nb) * 4 + 64));
     pl.fsup = h->g_cnt.as<uint32_t>();
     pl.esup = pl.fsup + pl.n_fsup;
-    pl.cnt = pl.esup + pl.n_esup + n_cur;
-    pl.clear_words = (size_t)pl.n_fsup + pl.n_esup + n_cur;
-    if (nb && !resume && pj && two_level) {
-        const size_t n_recs = (size_t)P1 * cap1;
-        MXG_HIP(h, h->g_part.ensure((size_t)P1 * rows2 * (P + 1) * 4 + (size_t)P1 * PJ1_CS * 4));
+    pl.cnt = pl.esup + pl.n_esup + pl.n_cur;
+    pl.clear_words = (size_t)pl.n_fsup + pl.n_esup + pl.n_cur;
+    const bool resume = mode == GRAPH_DG_EDGES || mode == GRAPH_DG_EDGES_APPLIED;  // second half on the owner's handle
+    if (nb && !resume && pl.pj && pl.two_level) {
+        const size_t n_recs = (size_t)P1 * pl.cap1;
+        MXG_HIP(h, h->g_part.ensure((size_t)P1 * pl.rows2 * (P + 1) * 4 + (size_t)P1 * PJ1_CS * 4));
         MXG_HIP(h, h->g_keys.ensure(n_recs * sizeof(uint4)));   // level-2 records (what k_flags_pj reads)
         MXG_HIP(h, h->g_recs1.ensure(n_recs * sizeof(uint4)));  // level-1 records
         pl.M = h->g_part.as<uint32_t>();
-        pl.cursor = cursors_here ? pl.esup + pl.n_esup : pl.M + (size_t)P1 * rows2 * (P + 1);
+        pl.cursor = pl.n_cur ? pl.esup + pl.n_esup : pl.M + (size_t)P1 * pl.rows2 * (P + 1);
         pl.recs1 = h->g_recs1.as<uint4>();
         pl.recs2 = h->g_keys.as<uint4>();
     }
@@ -1345,7 +1264,7 @@ static void launch_partition(mxg_handle *h, const JoinPlan &pl, uint32_t a_lo, u
     PjSub sub{1u, 0u, 0u, pl.cap1};
     uint32_t skew_lim = (uint32_t)std::min<uint64_t>(pl.N / pl.P1 + pl.N / pl.P1 / 32 + 2048, 0xFFFFFFFFull);  // 3 % above the mean
     if (pl.split) {
-        sub = PjSub{pl.A, a_lo, pl.sub_off[a_lo], pl.sc.cap[a_lo]};
+        sub = PjSub{pl.A, a_lo, pl.sub_off[a_lo], pl.sub_cap[a_lo]};
         skew_lim = pl.skew_lim[a_lo];
     }
     if (n_rows1)
@@ -1388,7 +1307,7 @@ int graph_plan_early(mxg_handle *h, const GraphBounds &gb, bool *early)
     JoinPlan &pl = *h->pj_plan;
     // (a set of sizes the graph stage refuses: build_graph says so behind the sketches, as it always has)
     const std::string err_before = h->err;
-    if (plan_join(h, GRAPH_FULL, &gb, h->pj_overflowed, true, pl) != MXG_OK || !(pl.pj && pl.two_level && pl.split && pl.nb)) {
+    if (plan_join(h, GRAPH_FULL, &gb, h->pj_learnt.overflowed, true, pl) != MXG_OK || !(pl.pj && pl.two_level && pl.split && pl.nb)) {
         pl = JoinPlan();
         h->err = err_before;  // (not this call's error: the stage itself reports it if it still holds then)
         return MXG_OK;
@@ -1428,296 +1347,343 @@ void graph_drop_plan(mxg_handle *h)
     h->pj_plan = nullptr;
 }
 
-static int build_graph_impl(mxg_handle *h, int mode, const void *d_msgs, uint64_t n_msgs, const GraphBounds *gb, bool global_table)
+// The fused call's plan, if this is the stage it was made for and every assembly has been partitioned under the sketches; whatever
+// comes after (a second attempt, a later call) plans and partitions for itself, into `own`.  Either way nothing of the early
+// plan stays in force.
+static int take_or_make_plan(mxg_handle *h, const GraphCall &c, bool global_table, JoinPlan &own, const JoinPlan **plan)
 {
-    MXG_HIP(h, hipSetDevice(h->device));
-    // the plan of the fused call, if this is the stage it was made for and every assembly has been partitioned under the sketches;
-    // whatever comes after (a second attempt, a later call) plans and partitions for itself
-    bool early = h->pj_plan && h->pj_plan->split && h->pj_early_done != 0 && h->pj_early_done == h->pj_plan->A && gb && mode == GRAPH_FULL &&
-                 !global_table && h->pj_plan->A == h->asms.size();
-    for (uint32_t a = 0; early && a < h->pj_plan->A; ++a) early = gb->n_bound[a] == h->pj_plan->n_of[a] && gb->n_ptr[a] == h->pj_plan->as_all.n_ptr[a];
+    const JoinPlan *ep = h->pj_plan;
+    bool early = ep && ep->split && h->pj_early_done != 0 && h->pj_early_done == ep->A && c.gb && c.mode == GRAPH_FULL && !global_table &&
+                 ep->A == h->asms.size();
+    for (uint32_t a = 0; early && a < ep->A; ++a) early = c.gb->n_bound[a] == ep->n_of[a] && c.gb->n_ptr[a] == ep->as_all.n_ptr[a];
     h->pj_early_done = 0;
-    JoinPlan own;
-    if (!early) {
-        const int rc = plan_join(h, mode, gb, global_table, false, own);
-        if (rc != MXG_OK) {
-            if (mode != GRAPH_DG_EDGES && mode != GRAPH_DG_EDGES_APPLIED)
-                for (Assembly *a : h->asms) a->flags_valid = a->flags_on_host = false;
-            return rc;
-        }
-    }
-    const JoinPlan &pl = early ? *h->pj_plan : own;
-    const uint32_t A = pl.A;
-    const uint64_t *const n_of = pl.n_of;
-    const bool resume = mode == GRAPH_DG_EDGES || mode == GRAPH_DG_EDGES_APPLIED;  // second half on the owner's handle
-    for (uint32_t ai = 0; ai < A; ++ai) {
-        Assembly *a = h->asms[ai];
-        if (!resume) a->flags_on_host = false;
-        a->flags_valid = true;
-    }
-    Graph &g = h->graph;
-    if (!resume) g = Graph();
-    g.n_asm = A;
-    const bool fine = (h->cfg.flags & MXG_FLAG_TIMING_FINE) != 0 && mode == GRAPH_FULL;
-    const bool timing = (h->cfg.flags & MXG_FLAG_TIMING) != 0 || fine;
-    if (fine && !h->ev_g[0]) {
-        MXG_HIP(h, hipEventCreate(&h->ev_g[0]));
-        MXG_HIP(h, hipEventCreate(&h->ev_g[1]));
-    }
-    if (timing) MXG_HIP(h, hipEventRecord(h->ev0, h->stream));
+    *plan = early ? ep : &own;
+    if (early) return MXG_OK;
+    const int rc = plan_join(h, c.mode, c.gb, global_table, false, own);
+    if (rc != MXG_OK && c.mode != GRAPH_DG_EDGES && c.mode != GRAPH_DG_EDGES_APPLIED)
+        for (Assembly *a : h->asms) a->flags_valid = a->flags_on_host = false;
+    return rc;
+}
 
-    const uint32_t cap = pl.cap, mask = pl.mask;
-    const uint32_t P = pl.P, P1 = pl.P1, cap1 = pl.cap1, rows2 = pl.rows2;
-    const bool two_level = pl.two_level, dg_pj = pl.dg_pj, pj = pl.pj;
-    const uint32_t pj_force_fail = pl.pj_force_fail;
-    if (!resume) h->stat_graph_join = (pj ? (two_level ? 2 : 1) : 3) | (early ? 0x400 : 0);
-    const size_t nb0 = pl.nb0;
-    uint64_t *const pj_mask0 = pl.pj_mask0;
-    uint32_t *const pj_bpref0 = pl.pj_bpref0;
-    if (pj) {
-        // (nothing to clear: every word of M and of the record regions that is read is written by this call)
-    } else if (!resume) {
-        MXG_HIP(h, hipMemsetAsync(h->g_keys.p, 0xFF, ((size_t)cap + 1) * sizeof(Slot), h->stream));  // one fill: see Slot
+// One attempt at the stage: the phases of build_graph_impl, in the order it enqueues them.
+struct GraphStage {
+    mxg_handle *const h;
+    const GraphCall &c;
+    const JoinPlan &pl;
+    const bool early;   // the plan is the fused call's: levels 1 and 2 have run behind every assembly's own k_emit
+    const bool resume;  // second half on the owner's handle: flags and vertices are there
+    const bool fine, timing;
+    Graph &g;
+    uint64_t *ctl = nullptr, *hctl = nullptr;  // the control block in HBM and its pinned host copy
+    uint64_t *pj_fail = nullptr;               // where the LDS join reports failure
+
+    GraphStage(mxg_handle *h_, const GraphCall &c_, const JoinPlan &pl_, bool early_)
+        : h(h_), c(c_), pl(pl_), early(early_), resume(c_.mode == GRAPH_DG_EDGES || c_.mode == GRAPH_DG_EDGES_APPLIED),
+          fine((h_->cfg.flags & MXG_FLAG_TIMING_FINE) != 0 && c_.mode == GRAPH_FULL), timing((h_->cfg.flags & MXG_FLAG_TIMING) != 0 || fine),
+          g(h_->graph)
+    {
     }
-    uint64_t *ctl = h->g_ctl.as<uint64_t>();  // every word the host reads below is written by a kernel of this call
-    const AsmSet &as_all = pl.as_all;
-    const uint32_t nb = pl.nb;
-    const uint64_t nvs = pl.nvs;
-    if (!h->pinned_gctl) MXG_HIP(h, hipHostMalloc((void **)&h->pinned_gctl, CTL_WORDS * 8));
-    uint64_t *const hctl = h->pinned_gctl;
-    memset(hctl, 0, CTL_WORDS * 8);
-    uint64_t *const pj_fail = dg_pj ? dg_pj_fail_word(h) : hctl + CTL_PJ_FAIL;  // (the device word: cleared by dg_owner_slots)
-    const size_t anv = (size_t)A * nvs;
-    const uint32_t n_items = pl.n_items, e_blocks = pl.e_blocks;
-    const uint32_t n_fsup = pl.n_fsup, n_esup = pl.n_esup;
-    uint32_t *fsup = pl.fsup, *esup = pl.esup, *cnt = pl.cnt;
-    if (nb && !resume && pj && two_level) {
-        uint32_t *M = pl.M, *cursor = pl.cursor;
-        uint4 *recs2 = pl.recs2;
-        if (!early) {  // (else: both levels ran behind every assembly's own k_emit, the cursors were cleared in front of the step)
-            MXG_HIP(h, hipMemsetAsync(cursor, 0, (size_t)P1 * PJ1_CS * 4, h->stream));
-            launch_partition(h, pl, 0, A, h->stream, n_fsup + n_esup);
+    bool joins() const { return pl.nb && !resume; }
+    size_t anv() const { return (size_t)pl.A * pl.nvs; }
+
+    // host state, the first timer, the table's fill, the control blocks
+    int begin()
+    {
+        for (uint32_t ai = 0; ai < pl.A; ++ai) {
+            Assembly *a = h->asms[ai];
+            if (!resume) a->flags_on_host = false;
+            a->flags_valid = true;
         }
-        const uint64_t pipe_blocks = knob_u64(h, "MXG_PJ_PIPE", 1024);  // (0: one block per partition, k_pj_join)
-        if (pipe_blocks && rows2 <= 256) {
-            const uint32_t nblk = (uint32_t)std::min<uint64_t>(pipe_blocks, (uint64_t)P1 * P);
-            if (A <= 16)
-                hipLaunchKernelGGL(k_pj_join_pipe<true>, dim3(nblk), dim3(256), 0, h->stream, recs2, M, P, P1 * P, pj_fail,
-                                   pj_force_fail, cursor, cap1, rows2, as_all, pl.sc);
-            else
-                hipLaunchKernelGGL(k_pj_join_pipe<false>, dim3(nblk), dim3(256), 0, h->stream, recs2, M, P, P1 * P, pj_fail,
-                                   pj_force_fail, cursor, cap1, rows2, as_all, pl.sc);
-        } else if (A <= 16)
-            hipLaunchKernelGGL(k_pj_join<true>, dim3(P1 * P), dim3(256), 0, h->stream, recs2, M, P, 0u, pj_fail, pj_force_fail,
-                               cursor, cap1, rows2, as_all, pl.sc);
+        if (!resume) g = Graph();
+        g.n_asm = pl.A;
+        if (fine && !h->ev_g[0]) {
+            MXG_HIP(h, hipEventCreate(&h->ev_g[0]));
+            MXG_HIP(h, hipEventCreate(&h->ev_g[1]));
+        }
+        if (timing) MXG_HIP(h, hipEventRecord(h->ev0, h->stream));
+        if (!resume)
+            h->stat_graph_join = (pl.pj ? (pl.two_level ? MXG_JOIN_LDS_TWO_LEVEL : MXG_JOIN_LDS) : MXG_JOIN_GLOBAL) | (early ? MXG_JOIN_EARLY : 0);
+        // (the LDS joins clear nothing: every word of M and of the record regions that is read is written by this call)
+        if (!pl.pj && !resume) MXG_HIP(h, hipMemsetAsync(h->g_keys.p, 0xFF, ((size_t)pl.cap + 1) * sizeof(Slot), h->stream));  // one fill: see Slot
+        ctl = h->g_ctl.as<uint64_t>();  // every word the host reads of it is written by a kernel of this call
+        if (!h->pinned_gctl) MXG_HIP(h, hipHostMalloc((void **)&h->pinned_gctl, CTL_WORDS * 8));
+        hctl = h->pinned_gctl;
+        memset(hctl, 0, CTL_WORDS * 8);
+        pj_fail = pl.dg_pj ? dg_pj_fail_word(h) : hctl + CTL_PJ_FAIL;  // (the device word: cleared by dg_owner_slots)
+        return MXG_OK;
+    }
+
+    // k_pj_join over the n_parts partitions of `recs`, one block each -- or, behind two levels (cursor: the coarse partitions'),
+    // k_pj_join_pipe with MXG_PJ_PIPE blocks that take partitions in turn (0: never) while a partition's rows fit its pipeline
+    void launch_join(uint4 *recs, uint32_t *M, uint32_t n_parts, uint32_t n_rows, const uint32_t *cursor)
+    {
+        const bool narrow = pl.A <= 16;  // the seen and dup masks share one word per slot
+        const uint32_t cap1 = cursor ? pl.cap1 : 0u, rows2 = cursor ? pl.rows2 : 0u;
+        const uint64_t pipe_blocks = cursor ? knob_u64(h, "MXG_PJ_PIPE", 1024) : 0;
+        if (pipe_blocks && rows2 <= 256)
+            hipLaunchKernelGGL(narrow ? k_pj_join_pipe<true> : k_pj_join_pipe<false>, dim3((uint32_t)std::min<uint64_t>(pipe_blocks, n_parts)),
+                               dim3(256), 0, h->stream, recs, M, pl.P, n_parts, pj_fail, pl.pj_force_fail, cursor, cap1, rows2, pl.as_all, pl.sc);
         else
-            hipLaunchKernelGGL(k_pj_join<false>, dim3(P1 * P), dim3(256), 0, h->stream, recs2, M, P, 0u, pj_fail, pj_force_fail,
-                               cursor, cap1, rows2, as_all, pl.sc);
-        hipLaunchKernelGGL(k_flags_pj, dim3(nb), dim3(256), 0, h->stream, as_all, cnt, fsup, pj_mask0);
-    } else if (nb && !resume && pj) {
-        const uint32_t n_rows = (nb + PJ_IPB / 256 - 1) / (PJ_IPB / 256);  // bucketing blocks = record regions = rows of M
-        MXG_HIP(h, h->g_part.ensure((size_t)n_rows * (P + 1) * 4));
+            hipLaunchKernelGGL(narrow ? k_pj_join<true> : k_pj_join<false>, dim3(n_parts), dim3(256), 0, h->stream, recs, M, pl.P, n_rows,
+                               pj_fail, pl.pj_force_fail, cursor, cap1, rows2, pl.as_all, pl.sc);
+    }
+    int join_two_level()
+    {
+        if (!early) {  // (else: both levels ran behind every assembly's own k_emit, the cursors were cleared in front of the step)
+            MXG_HIP(h, hipMemsetAsync(pl.cursor, 0, (size_t)pl.P1 * PJ1_CS * 4, h->stream));
+            launch_partition(h, pl, 0, pl.A, h->stream, pl.n_fsup + pl.n_esup);
+        }
+        launch_join(pl.recs2, pl.M, pl.P1 * pl.P, 0u, pl.cursor);
+        hipLaunchKernelGGL(k_flags_pj, dim3(pl.nb), dim3(256), 0, h->stream, pl.as_all, pl.cnt, pl.fsup, pl.pj_mask0);
+        return MXG_OK;
+    }
+    int join_one_level()
+    {
+        const uint32_t n_rows = (pl.nb + PJ_IPB / 256 - 1) / (PJ_IPB / 256);  // bucketing blocks = record regions = rows of M
+        MXG_HIP(h, h->g_part.ensure((size_t)n_rows * (pl.P + 1) * 4));
         MXG_HIP(h, h->g_keys.ensure((size_t)n_rows * PJ_IPB * sizeof(uint4)));
         uint32_t *M = h->g_part.as<uint32_t>();
         uint4 *recs = h->g_keys.as<uint4>();
-        hipLaunchKernelGGL(k_pj_bucket, dim3(n_rows), dim3(PJ_BT), (size_t)P * 8, h->stream, as_all, nb, P - 1, M, recs, fsup,
-                           n_fsup + n_esup);
-        if (A <= 16)
-            hipLaunchKernelGGL(k_pj_join<true>, dim3(P), dim3(256), 0, h->stream, recs, M, P, n_rows, pj_fail, pj_force_fail, nullptr,
-                               0u, 0u, as_all, pl.sc);
-        else
-            hipLaunchKernelGGL(k_pj_join<false>, dim3(P), dim3(256), 0, h->stream, recs, M, P, n_rows, pj_fail, pj_force_fail, nullptr,
-                               0u, 0u, as_all, pl.sc);
-        hipLaunchKernelGGL(k_flags_pj, dim3(nb), dim3(256), 0, h->stream, as_all, cnt, fsup, pj_mask0);
-    } else if (nb && !resume) {
-        hipLaunchKernelGGL(k_insert, dim3(nb), dim3(256), 0, h->stream, as_all, h->g_keys.as<Slot>(), mask, cap, fsup,
-                           n_fsup + n_esup);
-        // flags + shared minimizers per 256 of every assembly (their totals, equal by construction, land in ctl[a])
-        hipLaunchKernelGGL(k_flags, dim3(nb), dim3(256), 0, h->stream, as_all, h->g_keys.as<Slot>(), cnt, fsup);
+        hipLaunchKernelGGL(k_pj_bucket, dim3(n_rows), dim3(PJ_BT), (size_t)pl.P * 8, h->stream, pl.as_all, pl.nb, pl.P - 1, M, recs, pl.fsup,
+                           pl.n_fsup + pl.n_esup);
+        launch_join(recs, M, pl.P, n_rows, nullptr);
+        hipLaunchKernelGGL(k_flags_pj, dim3(pl.nb), dim3(256), 0, h->stream, pl.as_all, pl.cnt, pl.fsup, pl.pj_mask0);
+        return MXG_OK;
     }
-    MXG_HIP(h, hipGetLastError());
-    if (fine) MXG_HIP(h, hipEventRecord(h->ev_g[0], h->stream));
-    if (nvs > 0) {
-        MXG_HIP(h, h->g_vhash.ensure(nvs * 8));
-        MXG_HIP(h, h->g_vpos.ensure(anv * 4));
-        MXG_HIP(h, h->g_vrec.ensure(anv * 4));
-        MXG_HIP(h, h->g_fv.ensure(anv * 4));
-        MXG_HIP(h, h->g_frec.ensure(anv * 4));
-        MXG_HIP(h, h->g_nxt.ensure(2 * anv * 4));  // adj[A][nvs] = {successor, predecessor}: k_adjacency writes every entry that is read;
-        if (mode == GRAPH_DG_EDGES) MXG_HIP(h, hipMemsetAsync(h->g_nxt.p, 0xFF, 2 * anv * 4, h->stream));  // messages set single words
-        if (pj && nb && !resume) {
-            VertexPjParams vp;
-            vp.as = as_all;
-            for (uint32_t a = 0; a < MXG_MAX_ASSEMBLIES; ++a) {
-                vp.pos[a] = a < A ? h->asms[a]->d_pos.as<uint32_t>() : nullptr;
-                vp.rec[a] = a < A ? h->asms[a]->d_rec.as<uint32_t>() : nullptr;
-                vp.ivid[a] = nullptr;
-                if (a < A && mode == GRAPH_DG_VERTICES) {
-                    MXG_HIP(h, h->asms[a]->d_ivid.ensure((size_t)n_of[a] * 4 + 16));
-                    vp.ivid[a] = h->asms[a]->d_ivid.as<uint32_t>();
-                }
-            }
-            vp.cnt = cnt;
-            vp.sup = fsup;
-            vp.n_shared = ctl;
-            vp.mask0 = pj_mask0;
-            vp.bpref0 = pj_bpref0;
-            vp.vhash = h->g_vhash.as<uint64_t>();
-            vp.vpos = h->g_vpos.as<uint32_t>();
-            vp.vrec = h->g_vrec.as<uint32_t>();
-            vp.fv = h->g_fv.as<uint32_t>();
-            vp.frec = h->g_frec.as<uint32_t>();
-            vp.nvs = (uint32_t)nvs;
-            hipLaunchKernelGGL(k_block_prefix, dim3((uint32_t)((nb0 + 255) / 256)), dim3(256), 0, h->stream, cnt + as_all.bstart[0],
-                               fsup + sup_start(as_all, 0), (uint32_t)nb0, pj_bpref0);
-            hipLaunchKernelGGL(k_vertices_pj, dim3(nb), dim3(256), 0, h->stream, vp);
-        }
-        for (uint32_t a = 0; a < A && !resume && !pj; ++a) {  // assembly 0 assigns the vertex ids the others look up
-            Assembly *as = h->asms[a];
-            const uint32_t n = (uint32_t)n_of[a];
-            VertexParams vp;
-            vp.shared = as->d_shared.as<uint8_t>();
-            vp.cnt = cnt + as_all.bstart[a];
-            vp.sup = fsup + ((as_all.bstart[a] >> SUP_SHIFT) + a) * SUP_STRIDE;
-            vp.n_shared = ctl + a;
-            vp.slot = as->d_slot.as<uint32_t>();
-            vp.hash = as->d_hash.as<uint64_t>();
-            vp.pos = as->d_pos.as<uint32_t>();
-            vp.rec = as->d_rec.as<uint32_t>();
-            vp.n = n;
-            vp.n_ptr = gb ? gb->n_ptr[a] : nullptr;
-            vp.first = a == 0;
-            vp.vid = h->g_vid.as<uint32_t>();
-            vp.vhash = h->g_vhash.as<uint64_t>();
-            vp.vpos = h->g_vpos.as<uint32_t>() + (size_t)a * nvs;
-            vp.vrec = h->g_vrec.as<uint32_t>() + (size_t)a * nvs;
-            vp.fv = h->g_fv.as<uint32_t>() + (size_t)a * nvs;
-            vp.frec = h->g_frec.as<uint32_t>() + (size_t)a * nvs;
-            vp.ivid = nullptr;
-            if (mode == GRAPH_DG_VERTICES) {
-                MXG_HIP(h, as->d_ivid.ensure((size_t)n * 4 + 16));
-                MXG_HIP(h, hipMemsetAsync(as->d_ivid.p, 0xFF, (size_t)n * 4, h->stream));
-                vp.ivid = as->d_ivid.as<uint32_t>();
-            }
-            hipLaunchKernelGGL(k_vertices, dim3((n + 255) / 256), dim3(256), 0, h->stream, vp);
-        }
-        if (mode == GRAPH_DG_VERTICES) {  // the caller exchanges vertex ids and adjacency, then calls GRAPH_DG_EDGES;
-            g.nv_stride = nvs;            // no host sync: the vertex count stays on the device (ctl[0]) until then
-            if (d_msgs) MXG_HIP(h, hipMemcpyAsync(const_cast<void *>(d_msgs), ctl, 8, hipMemcpyDeviceToDevice, h->stream));
-            return MXG_OK;
-        }
-        if (mode == GRAPH_FULL) {
-            hipLaunchKernelGGL(k_adjacency, dim3((uint32_t)((nvs + 255) / 256), A), dim3(256), 0, h->stream,
-                               h->g_fv.as<uint32_t>(), h->g_frec.as<uint32_t>(), ctl, h->g_nxt.as<uint2>(), (uint32_t)nvs);
-        } else {  // second half on the owner: every local vertex is an item (fv = identity), adjacency from messages
-            if (n_msgs && mode == GRAPH_DG_EDGES)
-                hipLaunchKernelGGL(k_apply_msgs, dim3((uint32_t)((n_msgs + 255) / 256)), dim3(256), 0, h->stream,
-                                   static_cast<const uint4 *>(d_msgs), n_msgs, (uint32_t)nvs, h->g_nxt.as<uint32_t>());
-            hipLaunchKernelGGL(k_iota_rows, dim3((uint32_t)((nvs + 255) / 256), A), dim3(256), 0, h->stream,
-                               h->g_fv.as<uint32_t>(), (uint32_t)nvs);
-        }
+    int join_global()
+    {
+        hipLaunchKernelGGL(k_insert, dim3(pl.nb), dim3(256), 0, h->stream, pl.as_all, h->g_keys.as<Slot>(), pl.mask, pl.cap, pl.fsup,
+                           pl.n_fsup + pl.n_esup);
+        // flags + shared minimizers per 256 of every assembly (their totals, equal by construction, land in ctl[a])
+        hipLaunchKernelGGL(k_flags, dim3(pl.nb), dim3(256), 0, h->stream, pl.as_all, h->g_keys.as<Slot>(), pl.cnt, pl.fsup);
+        return MXG_OK;
+    }
+    // the launches since the last mark went in; fine timing: the span up to here ends at `ev`
+    int mark(hipEvent_t ev)
+    {
         MXG_HIP(h, hipGetLastError());
-        if (fine) MXG_HIP(h, hipEventRecord(h->ev_g[1], h->stream));
+        if (fine) MXG_HIP(h, hipEventRecord(ev, h->stream));
+        return MXG_OK;
+    }
+
+    int vertex_arrays()
+    {
+        MXG_HIP(h, h->g_vhash.ensure(pl.nvs * 8));
+        MXG_HIP(h, h->g_vpos.ensure(anv() * 4));
+        MXG_HIP(h, h->g_vrec.ensure(anv() * 4));
+        MXG_HIP(h, h->g_fv.ensure(anv() * 4));
+        MXG_HIP(h, h->g_frec.ensure(anv() * 4));
+        MXG_HIP(h, h->g_nxt.ensure(2 * anv() * 4));  // adj[A][nvs] = {successor, predecessor}: k_adjacency writes every entry that is read;
+        if (c.mode == GRAPH_DG_EDGES) MXG_HIP(h, hipMemsetAsync(h->g_nxt.p, 0xFF, 2 * anv() * 4, h->stream));  // messages set single words
+        return MXG_OK;
+    }
+    // GRAPH_DG_VERTICES: where the vertex id of every item of assembly a goes
+    int item_vids(uint32_t a, uint32_t **ivid)
+    {
+        *ivid = nullptr;
+        if (c.mode != GRAPH_DG_VERTICES) return MXG_OK;
+        MXG_HIP(h, h->asms[a]->d_ivid.ensure((size_t)pl.n_of[a] * 4 + 16));
+        *ivid = h->asms[a]->d_ivid.as<uint32_t>();
+        return MXG_OK;
+    }
+    int fill(VertexPjParams &vp)
+    {
+        vp.as = pl.as_all;
+        for (uint32_t a = 0; a < MXG_MAX_ASSEMBLIES; ++a) {
+            vp.pos[a] = a < pl.A ? h->asms[a]->d_pos.as<uint32_t>() : nullptr;
+            vp.rec[a] = a < pl.A ? h->asms[a]->d_rec.as<uint32_t>() : nullptr;
+            vp.ivid[a] = nullptr;
+            int rc;
+            if (a < pl.A && (rc = item_vids(a, &vp.ivid[a])) != MXG_OK) return rc;
+        }
+        vp.cnt = pl.cnt;
+        vp.sup = pl.fsup;
+        vp.n_shared = ctl + CTL_SHARED;
+        vp.mask0 = pl.pj_mask0;
+        vp.bpref0 = pl.pj_bpref0;
+        vp.vhash = h->g_vhash.as<uint64_t>();
+        vp.vpos = h->g_vpos.as<uint32_t>();
+        vp.vrec = h->g_vrec.as<uint32_t>();
+        vp.fv = h->g_fv.as<uint32_t>();
+        vp.frec = h->g_frec.as<uint32_t>();
+        vp.nvs = (uint32_t)pl.nvs;
+        return MXG_OK;
+    }
+    int vertices_pj()  // behind an LDS join
+    {
+        VertexPjParams vp;
+        const int rc = fill(vp);
+        if (rc != MXG_OK) return rc;
+        hipLaunchKernelGGL(k_block_prefix, dim3((uint32_t)((pl.nb0 + 255) / 256)), dim3(256), 0, h->stream, pl.cnt + pl.as_all.bstart[0],
+                           pl.fsup + sup_start(pl.as_all, 0), (uint32_t)pl.nb0, pl.pj_bpref0);
+        hipLaunchKernelGGL(k_vertices_pj, dim3(pl.nb), dim3(256), 0, h->stream, vp);
+        return MXG_OK;
+    }
+    int fill(VertexParams &vp, uint32_t a)
+    {
+        Assembly *as = h->asms[a];
+        const size_t row = (size_t)a * pl.nvs;
+        vp.shared = as->d_shared.as<uint8_t>();
+        vp.cnt = pl.cnt + pl.as_all.bstart[a];
+        vp.sup = pl.fsup + sup_start(pl.as_all, a);
+        vp.n_shared = ctl + CTL_SHARED + a;
+        vp.slot = as->d_slot.as<uint32_t>();
+        vp.hash = as->d_hash.as<uint64_t>();
+        vp.pos = as->d_pos.as<uint32_t>();
+        vp.rec = as->d_rec.as<uint32_t>();
+        vp.n = (uint32_t)pl.n_of[a];
+        vp.n_ptr = c.gb ? c.gb->n_ptr[a] : nullptr;
+        vp.first = a == 0;
+        vp.vid = h->g_vid.as<uint32_t>();
+        vp.vhash = h->g_vhash.as<uint64_t>();
+        vp.vpos = h->g_vpos.as<uint32_t>() + row;
+        vp.vrec = h->g_vrec.as<uint32_t>() + row;
+        vp.fv = h->g_fv.as<uint32_t>() + row;
+        vp.frec = h->g_frec.as<uint32_t>() + row;
+        return item_vids(a, &vp.ivid);
+    }
+    int vertices_global()  // behind the global table: assembly 0 assigns the vertex ids the others look up
+    {
+        for (uint32_t a = 0; a < pl.A; ++a) {
+            VertexParams vp;
+            const int rc = fill(vp, a);
+            if (rc != MXG_OK) return rc;
+            if (vp.ivid) MXG_HIP(h, hipMemsetAsync(vp.ivid, 0xFF, (size_t)vp.n * 4, h->stream));
+            hipLaunchKernelGGL(k_vertices, dim3((vp.n + 255) / 256), dim3(256), 0, h->stream, vp);
+        }
+        return MXG_OK;
+    }
+    // GRAPH_DG_VERTICES ends here: the caller exchanges vertex ids and adjacency, then calls GRAPH_DG_EDGES.  No host sync: the
+    // vertex count stays on the device (ctl[CTL_SHARED]) until then.  (nvs == 0, an assembly without items: no vertex)
+    int hand_back_vertices()
+    {
+        g.nv_stride = pl.nvs;
+        if (!c.d_n_vertices) return MXG_OK;
+        if (pl.nvs > 0) MXG_HIP(h, hipMemcpyAsync(c.d_n_vertices, ctl + CTL_SHARED, 8, hipMemcpyDeviceToDevice, h->stream));
+        else MXG_HIP(h, hipMemsetAsync(c.d_n_vertices, 0, 8, h->stream));
+        return MXG_OK;
+    }
+
+    void adjacency_own()  // GRAPH_FULL: from the handle's own record order
+    {
+        hipLaunchKernelGGL(k_adjacency, dim3((uint32_t)((pl.nvs + 255) / 256), pl.A), dim3(256), 0, h->stream, h->g_fv.as<uint32_t>(),
+                           h->g_frec.as<uint32_t>(), ctl + CTL_SHARED, h->g_nxt.as<uint2>(), (uint32_t)pl.nvs);
+    }
+    // second half on the owner: every local vertex is an item (fv = identity), adjacency from messages (GRAPH_DG_EDGES) or in place
+    void adjacency_of_owner()
+    {
+        if (c.n_msgs && c.mode == GRAPH_DG_EDGES)
+            hipLaunchKernelGGL(k_apply_msgs, dim3((uint32_t)((c.n_msgs + 255) / 256)), dim3(256), 0, h->stream,
+                               static_cast<const uint4 *>(c.d_msgs), c.n_msgs, (uint32_t)pl.nvs, h->g_nxt.as<uint32_t>());
+        hipLaunchKernelGGL(k_iota_rows, dim3((uint32_t)((pl.nvs + 255) / 256), pl.A), dim3(256), 0, h->stream, h->g_fv.as<uint32_t>(),
+                           (uint32_t)pl.nvs);
+    }
+
+    void fill(EdgeParams &ep)
+    {
+        ep.fv = h->g_fv.as<uint32_t>();
+        ep.adj = h->g_nxt.as<uint2>();
+        ep.nv_ptr = ctl + CTL_SHARED;
+        ep.nv = (uint32_t)pl.nvs;
+        ep.n_asm = pl.A;
+        ep.eflag = h->g_eflag.as<uint8_t>();
+        ep.bsum = h->g_ebs.as<uint32_t>();
+        ep.bsuper = pl.esup;
+        ep.n_edges = ctl + CTL_EDGES;
+        ep.host_ctl = hctl;
+        ep.eu = h->g_eu.as<uint32_t>();
+        ep.ev = h->g_ev.as<uint32_t>();
+        ep.esup = h->g_esup.as<uint32_t>();
+        ep.ew = h->g_ew.as<double>();
+        for (uint32_t a = 0; a < MXG_MAX_ASSEMBLIES; ++a) ep.weights[a] = a < pl.A ? h->asms[a]->weight : 0.0;
+    }
+    int edges()
+    {
+        const uint32_t n_items = pl.n_items;
         MXG_HIP(h, h->g_eflag.ensure(n_items));
-        MXG_HIP(h, h->g_ebs.ensure((size_t)e_blocks * 4 + 64));
+        MXG_HIP(h, h->g_ebs.ensure((size_t)pl.e_blocks * 4 + 64));
         // every item yields at most one edge: size the edge arrays by that bound
         MXG_HIP(h, h->g_eu.ensure((size_t)n_items * 4));
         MXG_HIP(h, h->g_ev.ensure((size_t)n_items * 4));
         MXG_HIP(h, h->g_esup.ensure((size_t)n_items * 4));
         MXG_HIP(h, h->g_ew.ensure((size_t)n_items * 8));
         EdgeParams ep;
-        ep.fv = h->g_fv.as<uint32_t>();
-        ep.adj = h->g_nxt.as<uint2>();
-        ep.nv_ptr = ctl;
-        ep.nv = (uint32_t)nvs;
-        ep.n_asm = A;
-        ep.eflag = h->g_eflag.as<uint8_t>();
-        ep.bsum = h->g_ebs.as<uint32_t>();
-        ep.bsuper = esup;
-        ep.n_edges = ctl + CTL_EDGES;
-        ep.host_ctl = h->pinned_gctl;
-        ep.eu = h->g_eu.as<uint32_t>();
-        ep.ev = h->g_ev.as<uint32_t>();
-        ep.esup = h->g_esup.as<uint32_t>();
-        ep.ew = h->g_ew.as<double>();
-        for (uint32_t a = 0; a < MXG_MAX_ASSEMBLIES; ++a) ep.weights[a] = a < A ? h->asms[a]->weight : 0.0;
-        hipLaunchKernelGGL(k_edge_flags, dim3(e_blocks), dim3(256), 0, h->stream, ep);  // + per-256 counts
-        hipLaunchKernelGGL(k_edges, dim3(e_blocks), dim3(256), 0, h->stream, ep, n_items);
+        fill(ep);
+        hipLaunchKernelGGL(k_edge_flags, dim3(pl.e_blocks), dim3(256), 0, h->stream, ep);  // + per-256 counts
+        hipLaunchKernelGGL(k_edges, dim3(pl.e_blocks), dim3(256), 0, h->stream, ep, n_items);
         MXG_HIP(h, hipGetLastError());
-    }
-    if (mode == GRAPH_DG_VERTICES) {  // (an assembly without items: no vertex)
-        g.nv = 0;
-        g.nv_stride = 0;
-        if (d_msgs) MXG_HIP(h, hipMemsetAsync(const_cast<void *>(d_msgs), 0, 8, h->stream));
         return MXG_OK;
     }
-    if (timing) MXG_HIP(h, hipEventRecord(h->ev1, h->stream));
-    MXG_HIP(h, stream_wait(h->stream));  // the stage's only sync; results stay in HBM
-    if (pj && hctl[CTL_PJ_FAIL]) {  // a partition outgrew its LDS table: redo with the global table
-        if (two_level && !pj_force_fail) {  // ... unless it was a coarse partition's capacity, and only that
-            const uint32_t n_sub = pl.sc.n_sub;
-            std::vector<uint32_t> cur((size_t)P1 * n_sub * PJ1_CS);
-            MXG_HIP(h, hipMemcpy(cur.data(), pl.cursor, cur.size() * 4, hipMemcpyDeviceToHost));
-            uint64_t mx = 0;  // the fullest coarse partition, all assemblies together: what the one-cursor layout must hold
-            for (uint32_t c = 0; c < P1; ++c) {
-                uint64_t all = 0;
-                for (uint32_t s = 0; s < n_sub; ++s) all += cur[((size_t)c * n_sub + s) * PJ1_CS];
-                mx = std::max(mx, all);
-            }
-            if (pl.split) {
-                // a sub-range outgrew its capacity: the next fused call sizes that assembly's sub-ranges by what the cursors counted,
-                // and the attempt that follows this one (one cursor per coarse partition) by the partitions' totals
-                bool learnt = false;
-                if (h->pj_sub_P1 != P1) std::fill_n(h->pj_sub_need, MXG_MAX_ASSEMBLIES, 0ull);
-                h->pj_sub_P1 = P1;
-                for (uint32_t s = 0; s < n_sub; ++s) {
-                    uint64_t ms = 0;
-                    for (uint32_t c = 0; c < P1; ++c) ms = std::max<uint64_t>(ms, cur[((size_t)c * n_sub + s) * PJ1_CS]);
-                    if (ms > pl.sc.cap[s] && h->pj_sub_need[s] < ms) {
-                        h->pj_sub_need[s] = ms + ms / 8 + 4096;
-                        learnt = true;
-                    }
-                }
-                if (learnt) {
-                    if (h->pj_cap1_P1 != P1) h->pj_cap1_need = 0;
-                    h->pj_cap1_P1 = P1;
-                    h->pj_cap1_need = std::max<uint64_t>(h->pj_cap1_need, mx + mx / 8 + 4096);
-                    return RC_RETRY_PJ;
-                }
-            } else if (mx > cap1 && (h->pj_cap1_P1 != P1 || h->pj_cap1_need < mx)) {
-                h->pj_cap1_P1 = P1;
-                h->pj_cap1_need = (uint64_t)mx + mx / 8 + 4096;
-                return RC_RETRY_PJ;
+
+    // the stage's only sync (results stay in HBM), then: did an LDS join report failure, and what is to be done about it
+    int sync_and_verdict()
+    {
+        if (timing) MXG_HIP(h, hipEventRecord(h->ev1, h->stream));
+        MXG_HIP(h, stream_wait(h->stream));
+        if (!pl.pj || !hctl[CTL_PJ_FAIL]) return MXG_OK;
+        // a partition outgrew its LDS table: redo with the global table ... unless it was a coarse partition's capacity, and only that
+        if (!pl.two_level || pl.pj_force_fail) return RC_RETRY_GLOBAL;
+        std::vector<uint32_t> cur((size_t)pl.P1 * pl.n_sub * PJ1_CS);
+        MXG_HIP(h, hipMemcpy(cur.data(), pl.cursor, cur.size() * 4, hipMemcpyDeviceToHost));
+        return join_overflow_verdict(pl, cur.data(), h->pj_learnt);
+    }
+    int results()
+    {
+        const uint64_t nv = hctl[CTL_SHARED];
+        for (uint32_t a = 1; a < pl.A; ++a)
+            if (hctl[CTL_SHARED + a] != nv)
+                return set_err(h, MXG_EDEVICE, "internal error: shared-minimizer counts differ between assemblies (%llu vs %llu)",
+                               (unsigned long long)hctl[CTL_SHARED + a], (unsigned long long)nv);
+        g.nv = nv;
+        g.nv_stride = pl.nvs;
+        g.ne = pl.nvs > 0 ? hctl[CTL_EDGES] : 0;
+        h->stat_unique = ~0ull;  // counted lazily from the flags (mxg_get_stats)
+        if (timing) {
+            float ms = 0;
+            MXG_HIP(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            h->tm.ms_graph += ms;
+            if (fine && pl.nvs > 0) {
+                float a = 0, b = 0, c3 = 0;
+                MXG_HIP(h, hipEventElapsedTime(&a, h->ev0, h->ev_g[0]));
+                MXG_HIP(h, hipEventElapsedTime(&b, h->ev_g[0], h->ev_g[1]));
+                MXG_HIP(h, hipEventElapsedTime(&c3, h->ev_g[1], h->ev1));
+                h->tm.ms_join += a;
+                h->tm.ms_vertices += b;
+                h->tm.ms_edges += c3;
             }
         }
-        return RC_RETRY_GLOBAL;
+        g.valid = true;
+        g.host_valid = false;
+        return MXG_OK;
     }
-    const uint64_t nv = hctl[0];
-    for (uint32_t a = 1; a < A; ++a)
-        if (hctl[a] != nv)
-            return set_err(h, MXG_EDEVICE, "internal error: shared-minimizer counts differ between assemblies (%llu vs %llu)",
-                           (unsigned long long)hctl[a], (unsigned long long)nv);
-    g.nv = nv;
-    g.nv_stride = nvs;
-    g.ne = nvs > 0 ? hctl[CTL_EDGES] : 0;
-    h->stat_unique = ~0ull;  // counted lazily from the flags (mxg_get_stats)
-    if (timing) {
-        float ms = 0;
-        MXG_HIP(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        h->tm.ms_graph += ms;
-        if (fine && nvs > 0) {
-            float a = 0, b = 0, c = 0;
-            MXG_HIP(h, hipEventElapsedTime(&a, h->ev0, h->ev_g[0]));
-            MXG_HIP(h, hipEventElapsedTime(&b, h->ev_g[0], h->ev_g[1]));
-            MXG_HIP(h, hipEventElapsedTime(&c, h->ev_g[1], h->ev1));
-            h->tm.ms_join += a;
-            h->tm.ms_vertices += b;
-            h->tm.ms_edges += c;
-        }
+};
+
+// One attempt.  MXG_OK, an error, or what build_graph is to do about an LDS join that failed (JoinRetry).
+static int build_graph_impl(mxg_handle *h, const GraphCall &c, bool global_table)
+{
+    MXG_HIP(h, hipSetDevice(h->device));
+    JoinPlan own;
+    const JoinPlan *plan = nullptr;
+    int rc = take_or_make_plan(h, c, global_table, own, &plan);
+    if (rc != MXG_OK) return rc;
+    const JoinPlan &pl = *plan;
+    GraphStage s(h, c, pl, plan != &own);
+    if ((rc = s.begin()) != MXG_OK) return rc;
+    if (s.joins() && (rc = pl.pj ? (pl.two_level ? s.join_two_level() : s.join_one_level()) : s.join_global()) != MXG_OK) return rc;
+    if ((rc = s.mark(h->ev_g[0])) != MXG_OK) return rc;
+    if (pl.nvs > 0) {
+        if ((rc = s.vertex_arrays()) != MXG_OK) return rc;
+        if (!s.resume && (rc = pl.pj ? s.vertices_pj() : s.vertices_global()) != MXG_OK) return rc;
     }
-    g.valid = true;
-    g.host_valid = false;
-    return MXG_OK;
+    if (c.mode == GRAPH_DG_VERTICES) return s.hand_back_vertices();
+    if (pl.nvs > 0) {
+        if (c.mode == GRAPH_FULL) s.adjacency_own();
+        else s.adjacency_of_owner();
+        if ((rc = s.mark(h->ev_g[1])) != MXG_OK) return rc;
+        if ((rc = s.edges()) != MXG_OK) return rc;
+    }
+    if ((rc = s.sync_and_verdict()) != MXG_OK) return rc;
+    return s.results();
 }
 
 // host mirrors are filled on demand (mxg_get_graph, mxg_write_dot, mxg_get_mx_flags)

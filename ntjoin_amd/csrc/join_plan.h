@@ -1,0 +1,215 @@
+// The arithmetic of the graph stage's join, the one place that knows it: from the assemblies' sizes to which join runs and how its
+// partitions are sized (join_shape), what a handle has learnt from overflows (JoinLearnt), and what the cursors of an overflowed
+// two-level join ask for (join_overflow_verdict).  No device, no handle: graph.hip's plan_join reads the knobs, calls join_shape
+// and lays the arrays out; tests/test_join_plan_cpu.py compiles this header on its own.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+#include "ntjoin_mx.h"
+
+namespace mxg {
+
+enum { GRAPH_FULL = 0, GRAPH_DG_VERTICES = 1, GRAPH_DG_EDGES = 2, GRAPH_DG_EDGES_APPLIED = 3 /* nxt/prv already filled */ };
+
+constexpr uint32_t PJ_IPB = 4096;  // items per bucketing block = 16 blocks of 256
+constexpr uint32_t PJ_T = 2048;    // slots of a partition's table (+1: the slot of the key that equals the empty mark)
+constexpr uint32_t PJ_MAX_P = 4096;
+constexpr uint32_t PJ1_CS = 32;  // words between the coarse partitions' cursors (own 128-byte lines: same-line atomics serialise)
+constexpr uint32_t PJ_CAP_LIMIT = 0xFFFFF000u;  // a coarse partition's records are counted in 32 bits, in whole bucketing blocks
+
+// What a handle has learnt from the overflows of its LDS joins.  It holds for the sketches it was learnt on (`sig`).
+struct JoinLearnt {
+    bool overflowed = false;  // the partitioned join overflowed once (build_graph then starts with the global table)
+    uint32_t cap1_P1 = 0;     // two-level join: coarse partitions and the records one of them must hold, as an earlier call's
+    uint64_t cap1_need = 0;   // cursors reported them (a key of large multiplicity skews the partitions)
+    uint64_t sig = 0;         // the sketches (count and sizes) the fields above were learnt on
+    uint32_t sub_P1 = 0;      // fused call: what the sub-ranges of a coarse partition must hold per assembly (cap1_need's counterpart)
+    uint64_t sub_need[MXG_MAX_ASSEMBLIES] = {};
+    bool dg_off = false;      // owner of a partitioned graph stage: the LDS join failed once over the slots (global table from then on)
+
+    static uint64_t signature(uint32_t n_asm, const uint64_t *n_mx)
+    {
+        uint64_t s = 0x9E3779B97F4A7C15ull * ((uint64_t)n_asm + 1);
+        for (uint32_t a = 0; a < n_asm; ++a) s = (s ^ n_mx[a]) * 0x100000001B3ull;
+        return s;
+    }
+    // build_graph over finished sketches (not the fused call, whose sizes are still bounds): other sketches -- new assemblies, a
+    // borrowed buffer refilled and sketched again -- start with the defaults.  sub_need[] stays as it is (nothing reads it while
+    // sub_P1 is 0, and the verdict clears it when it sets sub_P1 anew); so does dg_off.
+    void sketches_are(uint64_t s)
+    {
+        if ((overflowed || cap1_P1) && sig != s) {
+            overflowed = false;
+            cap1_P1 = 0;
+            cap1_need = 0;
+            sub_P1 = 0;
+        }
+        sig = s;
+    }
+    // an assembly was added to the handle.  Leaves sub_P1 / sub_need[], sig and dg_off alone.
+    void assembly_added()
+    {
+        overflowed = false;
+        cap1_P1 = 0;
+        cap1_need = 0;
+    }
+    void gave_up() { overflowed = true; }  // the LDS join fell to the global table
+};
+
+struct JoinRequest {
+    uint32_t A = 0;                          // assemblies, 1..MXG_MAX_ASSEMBLIES
+    uint64_t n_of[MXG_MAX_ASSEMBLIES] = {};  // minimizers per assembly (the sketches' own sizes, or the bounds of the fused call)
+    int mode = GRAPH_FULL;
+    bool bounds = false;           // the sizes are bounds, the counts are still on the device
+    bool global_table = false;     // the caller asks for the global table (an earlier attempt overflowed)
+    bool split = false;            // a sub-range of every coarse partition per assembly (the fused call's early partition)
+    bool force_two_level = false;  // MXG_PJ_TWO_LEVEL
+    bool join_global = false;      // MXG_GRAPH_JOIN=global
+};
+
+enum JoinShapeError { JS_OK = 0, JS_TOO_MANY_MINIMIZERS, JS_TOO_MANY_ITEMS };
+
+// Everything the stage derives from the sizes before it launches anything: which join, how many partitions of what capacity.
+struct JoinShape {
+    uint32_t A = 0;
+    uint64_t N = 0, nvs = 0;  // minimizers of all assemblies; stride of the vertex arrays (the smallest assembly)
+    uint64_t n_of[MXG_MAX_ASSEMBLIES] = {};
+    uint32_t cap = 0, mask = 0, full = 0;  // global table: slots, slots - 1; one bit per assembly
+    uint32_t P = 0, P1 = 0, cap1 = 0, rows2 = 0;
+    bool two_level = false, pj = false, dg_pj = false;
+    bool split = false;  // a sub-range of every coarse partition per assembly (PjSub)
+    uint32_t n_sub = 1;  // sub-ranges (cursors) per coarse partition, and what each holds
+    uint32_t sub_cap[MXG_MAX_ASSEMBLIES] = {}, sub_off[MXG_MAX_ASSEMBLIES] = {}, skew_lim[MXG_MAX_ASSEMBLIES] = {};
+    uint32_t bstart[MXG_MAX_ASSEMBLIES + 1] = {};  // exclusive prefix of the assemblies' 256-element blocks
+    uint32_t nb = 0;                               // ... and their number
+    size_t nb0 = 0;                                // assembly 0's
+    uint32_t n_items = 0, e_blocks = 0;            // A * nvs items of the edge kernels, in blocks of 256
+    size_t n_cur = 0;  // split: words of the sub-ranges' cursors that lie between the super-counts and the counts
+};
+
+inline JoinShapeError join_shape(const JoinRequest &rq, const JoinLearnt &learnt, JoinShape &pl)
+{
+    pl = JoinShape();
+    const uint32_t A = pl.A = rq.A;
+    uint64_t N = 0, nmin = ~0ull, n_max = 0;
+    for (uint32_t a = 0; a < A; ++a) {
+        pl.n_of[a] = rq.n_of[a];
+        N += rq.n_of[a];
+        nmin = std::min(nmin, rq.n_of[a]);
+        n_max = std::max(n_max, rq.n_of[a]);
+    }
+    pl.N = N;
+    if (N >= (1ull << 30)) return JS_TOO_MANY_MINIMIZERS;
+    pl.cap = 1024;
+    while (pl.cap < 2 * N) pl.cap <<= 1;
+    pl.mask = pl.cap - 1;
+    pl.full = (A == 32) ? 0xFFFFFFFFu : ((1u << A) - 1u);
+    // the join: LDS tables per hash partition (the whole-stage call, up to PJ_MAX_P partitions of <= 1280 records), else
+    // the global table
+    uint32_t P = 256;
+    while ((uint64_t)P * 1280 < N) P <<= 1;
+    // beyond PJ_MAX_P partitions of <= 1280 records: two levels -- P1 coarse partitions, each sorted into 256 sub-partitions
+    uint32_t P1 = 0, cap1 = 0;
+    bool fits32 = true;
+    if (P > PJ_MAX_P || rq.force_two_level) {
+        P = 256;
+        P1 = 2;
+        while ((uint64_t)P1 * P * 1000 < N) P1 <<= 1;
+        if (rq.split) {  // a sub-range per assembly, each with the slack of the whole: 25 % above ITS mean
+            uint64_t c_all = 0;
+            for (uint32_t a = 0; a < A; ++a) {
+                const uint64_t mean = rq.n_of[a] / P1;
+                uint64_t c1 = mean + mean / 4 + 4096;
+                if (learnt.sub_P1 == P1) c1 = std::max<uint64_t>(c1, learnt.sub_need[a]);  // (what an earlier call's cursors asked for)
+                c1 = (c1 + PJ_IPB - 1) / PJ_IPB * PJ_IPB;
+                pl.sub_off[a] = (uint32_t)std::min<uint64_t>(c_all, PJ_CAP_LIMIT);
+                pl.sub_cap[a] = (uint32_t)std::min<uint64_t>(c1, PJ_CAP_LIMIT);
+                pl.skew_lim[a] = (uint32_t)std::min<uint64_t>(mean + mean / 32 + 2048, 0xFFFFFFFFull);  // 3 % above the mean
+                c_all += c1;
+            }
+            pl.n_sub = A;
+            pl.split = true;
+            cap1 = (uint32_t)std::min<uint64_t>(c_all, PJ_CAP_LIMIT);
+            fits32 = c_all <= PJ_CAP_LIMIT;
+        } else {
+            uint64_t c1 = (N / P1) + (N / P1) / 4 + 4096;  // 25 % above the mean (hash skew: keys of large multiplicity)
+            if (learnt.cap1_P1 == P1) c1 = std::max<uint64_t>(c1, learnt.cap1_need);  // (what an earlier call's cursors asked for)
+            cap1 = (uint32_t)((c1 + PJ_IPB - 1) / PJ_IPB * PJ_IPB);
+            pl.sub_cap[0] = cap1;
+        }
+        pl.rows2 = cap1 / PJ_IPB;
+    }
+    pl.P = P;
+    pl.P1 = P1;
+    pl.cap1 = cap1;
+    pl.two_level = P1 != 0 && P1 <= 4096 && fits32 && (uint64_t)P1 * cap1 < (1ull << 32) && (uint64_t)P1 * P * (PJ_T + 1) < (1ull << 29);
+    // (the owner's half of the partitioned graph stage takes the LDS join too when it runs over fixed slots -- bounds: the counts on
+    // the device, nobody waits for the host before the verdicts leave -- and says "failed" through a DEVICE word)
+    pl.dg_pj = rq.mode == GRAPH_DG_VERTICES && rq.bounds && !learnt.dg_off;
+    // (k_pj_join's verdict word carries the index of the key's minimizer in assembly 0 above three flag bits, k_pj2_bucket's
+    // reference that of a minimizer of the same assembly: n_max < 2^29)
+    pl.pj = (rq.mode == GRAPH_FULL || pl.dg_pj) && !rq.global_table && (P1 == 0 || pl.two_level) && P <= PJ_MAX_P && n_max < (1ull << 29) &&
+            !rq.join_global;
+    for (uint32_t a = 0; a < A; ++a) {
+        pl.bstart[a] = pl.nb;
+        pl.nb += (uint32_t)((rq.n_of[a] + 255) / 256);
+    }
+    for (uint32_t a = A; a <= MXG_MAX_ASSEMBLIES; ++a) pl.bstart[a] = pl.nb;
+    pl.nb0 = (size_t)((rq.n_of[0] + 255) / 256);
+    // vertex arrays are strided by an upper bound of the vertex count (every vertex occurs once in every assembly), so
+    // the stage needs no host sync before its kernels: they read the counts from the control block in HBM
+    pl.nvs = nmin;
+    if (pl.nvs > 0 && (uint64_t)A * pl.nvs >= (1ull << 32)) return JS_TOO_MANY_ITEMS;  // (cannot happen below 2^30 minimizers)
+    pl.n_items = (uint32_t)((size_t)A * pl.nvs);
+    pl.e_blocks = (pl.n_items + 255) / 256;
+    if (pl.split && pl.pj && pl.two_level) pl.n_cur = (size_t)P1 * A * PJ1_CS;
+    return JS_OK;
+}
+
+// build_graph_impl's answer to an LDS join that reported failure
+enum JoinRetry { RC_RETRY_GLOBAL = 1, RC_RETRY_PJ = 2 };
+
+// A two-level join failed and no table was forced to: was it a coarse partition's (sub-range's) capacity, and only that?  `cur`
+// is the cursor table as the device left it (P1 * n_sub cursors, PJ1_CS words apart).  RC_RETRY_PJ: `learnt` now holds what the
+// cursors ask for, and a plan made with it has room.  RC_RETRY_GLOBAL: a partition's LDS table overflowed, or the capacities
+// were learnt from these very counts already.
+inline JoinRetry join_overflow_verdict(const JoinShape &pl, const uint32_t *cur, JoinLearnt &learnt)
+{
+    const uint32_t P1 = pl.P1, n_sub = pl.n_sub;
+    uint64_t mx = 0;  // the fullest coarse partition, all assemblies together: what the one-cursor layout must hold
+    for (uint32_t c = 0; c < P1; ++c) {
+        uint64_t all = 0;
+        for (uint32_t s = 0; s < n_sub; ++s) all += cur[((size_t)c * n_sub + s) * PJ1_CS];
+        mx = std::max(mx, all);
+    }
+    if (pl.split) {
+        // a sub-range outgrew its capacity: the next fused call sizes that assembly's sub-ranges by what the cursors counted,
+        // and the attempt that follows this one (one cursor per coarse partition) by the partitions' totals
+        bool grew = false;
+        if (learnt.sub_P1 != P1) std::fill_n(learnt.sub_need, MXG_MAX_ASSEMBLIES, 0ull);
+        learnt.sub_P1 = P1;
+        for (uint32_t s = 0; s < n_sub; ++s) {
+            uint64_t ms = 0;
+            for (uint32_t c = 0; c < P1; ++c) ms = std::max<uint64_t>(ms, cur[((size_t)c * n_sub + s) * PJ1_CS]);
+            if (ms > pl.sub_cap[s] && learnt.sub_need[s] < ms) {
+                learnt.sub_need[s] = ms + ms / 8 + 4096;
+                grew = true;
+            }
+        }
+        if (grew) {
+            if (learnt.cap1_P1 != P1) learnt.cap1_need = 0;
+            learnt.cap1_P1 = P1;
+            learnt.cap1_need = std::max<uint64_t>(learnt.cap1_need, mx + mx / 8 + 4096);
+            return RC_RETRY_PJ;
+        }
+    } else if (mx > pl.cap1 && (learnt.cap1_P1 != P1 || learnt.cap1_need < mx)) {
+        learnt.cap1_P1 = P1;
+        learnt.cap1_need = mx + mx / 8 + 4096;
+        return RC_RETRY_PJ;
+    }
+    return RC_RETRY_GLOBAL;
+}
+
+}  // namespace mxg

@@ -16,6 +16,7 @@
 #include <utility>
 #include <vector>
 
+#include "join_plan.h"
 #include "ntjoin_mx.h"
 
 namespace mxg {
@@ -263,19 +264,12 @@ struct mxg_handle {
     uint64_t stat_slice_stretches = 0;  // candidate-free stretches handed to k_sel_stretch
     hipEvent_t ev_sel_done[4] = {nullptr, nullptr, nullptr, nullptr};  // recorded behind every slice kernel, per stream slot
     uint64_t stat_graph_join = 0; // mxg_stats::graph_join
-    uint32_t pj_cap1_P1 = 0;     // two-level join: coarse partitions and the records one of them must hold, as an earlier call's
-    uint64_t pj_cap1_need = 0;   // cursors reported them (a key of large multiplicity skews the partitions)
-    uint64_t pj_learnt_sig = 0;  // the sketches (count and sizes) the three fields around this one were learnt on
+    mxg::JoinLearnt pj_learnt;   // graph stage: what the LDS joins' overflows have taught this handle (join_plan.h)
     // fused call: the join as it was planned before the sketches (graph_plan_early), how many assemblies have been partitioned behind
-    // their own k_emit since (graph_partition_early), the event behind the plan's clears, and what the sub-ranges of a coarse partition
-    // must hold per assembly, as an earlier call's cursors reported it (pj_cap1_need's counterpart)
+    // their own k_emit since (graph_partition_early), the event behind the plan's clears
     mxg::JoinPlan *pj_plan = nullptr;
     uint32_t pj_early_done = 0;
     hipEvent_t ev_plan = nullptr;
-    uint32_t pj_sub_P1 = 0;
-    uint64_t pj_sub_need[MXG_MAX_ASSEMBLIES] = {};
-    bool pj_overflowed = false;  // graph stage: the partitioned join overflowed once (build_graph then starts with the global table)
-    bool dg_pj_off = false;      // owner of a partitioned graph stage: the LDS join failed once over the slots (global table from then on)
     uint64_t stat_retries = 0;   // assemblies enqueued a second time (their batches did not all end the common way)
     uint64_t stat_deferred = 0;  // candidate-free stretches the device route handed to the host
     uint64_t stat_batches_redone = 0, stat_sync_assemblies = 0;  // batches that did not end the common way / assemblies redone whole
@@ -423,13 +417,27 @@ int pack_sketch(mxg_handle *h, Assembly *a, void *d_buf, uint64_t nmax);
 int unpack_gathered(mxg_handle *h, Assembly *a, const void *d_allbuf, uint32_t world, uint64_t nmax,
                     const uint64_t *counts, const uint64_t *rec_offsets, uint64_t stride_bytes = 0);
 // graph.hip
-enum { GRAPH_FULL = 0, GRAPH_DG_VERTICES = 1, GRAPH_DG_EDGES = 2, GRAPH_DG_EDGES_APPLIED = 3 /* nxt/prv already filled */ };
 struct GraphBounds {  // fused sketch+graph call: per assembly an upper bound of its sketch and where the count will be
     uint64_t n_bound[MXG_MAX_ASSEMBLIES];
     const uint32_t *n_ptr[MXG_MAX_ASSEMBLIES];
 };
-int build_graph(mxg_handle *h, int mode = GRAPH_FULL, const void *d_msgs = nullptr, uint64_t n_msgs = 0,
-                const GraphBounds *gb = nullptr);
+// One call of the graph stage (modes: join_plan.h).  GRAPH_FULL is the whole stage.  The distributed graph (dgraph.hip) runs it in
+// two halves on the OWNER's handle: GRAPH_DG_VERTICES stops after the vertices (and records the vertex id of every item),
+// GRAPH_DG_EDGES resumes with the adjacency taken from messages, GRAPH_DG_EDGES_APPLIED with the adjacency already in place.
+struct GraphCall {
+    int mode = GRAPH_FULL;
+    // the sketches are still being computed on the stream: sizes are the bounds gb->n_bound[a], the kernels read the counts from
+    // gb->n_ptr[a] on the device (GRAPH_FULL: the fused sketch+graph call; GRAPH_DG_VERTICES: items in fixed slots)
+    const GraphBounds *gb = nullptr;
+    const void *d_msgs = nullptr;  // GRAPH_DG_EDGES: the adjacency messages (uint4 each) ...
+    uint64_t n_msgs = 0;           // ... and their number
+    void *d_n_vertices = nullptr;  // GRAPH_DG_VERTICES: where the vertex count goes (8 bytes on the device), if anywhere
+    static GraphCall full(const GraphBounds *gb = nullptr) { return GraphCall{GRAPH_FULL, gb}; }
+    static GraphCall dg_vertices(void *d_n_vertices, const GraphBounds *gb = nullptr) { return GraphCall{GRAPH_DG_VERTICES, gb, nullptr, 0, d_n_vertices}; }
+    static GraphCall dg_edges(const void *d_msgs, uint64_t n_msgs) { return GraphCall{GRAPH_DG_EDGES, nullptr, d_msgs, n_msgs}; }
+    static GraphCall dg_edges_applied() { return GraphCall{GRAPH_DG_EDGES_APPLIED}; }
+};
+int build_graph(mxg_handle *h, const GraphCall &call = GraphCall());
 // The fused call's two-level join, partitioned under the sketches (MXG_PJ_EARLY=0: never).  graph_plan_early lays the join out from
 // the bounds before the first filter is launched (allocations; cursors and super-counts cleared on the main stream) and says
 // whether the join is one to partition early; graph_partition_early puts levels 1 and 2 of assembly a on stream st, behind that

@@ -3795,7 +3795,7 @@ struct SketchStep {
         int rc;
         if ((rc = join_second_stream(h)) != MXG_OK) return rc;
         fused_bounds();
-        fused = build_graph(h, GRAPH_FULL, nullptr, 0, &gb) == MXG_OK;  // (its sync is this call's sync)
+        fused = build_graph(h, GraphCall::full(&gb)) == MXG_OK;  // (its sync is this call's sync)
         return MXG_OK;
     }
 
@@ -4457,7 +4457,7 @@ int xchg_unpack_graph(mxg_handle *h, const void *d_all, uint32_t world, uint64_t
     }
     MXG_HIP(h, hipGetLastError());
     h->graph.valid = false;
-    const int rc = build_graph(h, GRAPH_FULL, nullptr, 0, &gb);  // its sync is the exchange's sync
+    const int rc = build_graph(h, GraphCall::full(&gb));  // its sync is the exchange's sync
     if (rc != MXG_OK) return rc;
     bool bad = false;
     for (size_t ai = 0; ai < A; ++ai) {
