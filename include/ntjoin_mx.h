@@ -156,7 +156,9 @@ typedef struct mxg_stats {
     uint64_t select_slices;    /* slices of 64 strips that went through k_bs_select (k = 32 route: bitmap -> selected minimizers
                                   in one kernel; 0: count -> reorder -> resolve ran)                                           */
     uint64_t slice_stretches;  /* candidate-free stretches (>= w k-mers without a candidate) that k_sel_stretch was handed: sketched
-                                  one wave per slice right behind k_bs_select, their minimizers put into the slice's row            */
+                                  one wave per slice right behind k_bs_select, their minimizers put into the slice's row.  Counted
+                                  as entries of the batches' request arrays: a batch that fills its array (262 136 requests) counts
+                                  the array's capacity, of which up to 7 entries are tombstones of a slice that did not fit       */
 } mxg_stats;
 
 /* ---- lifecycle ------------------------------------------------------------------------------- */

@@ -2687,7 +2687,7 @@ struct Driver {
         // (the upper part of the stretch array holds the requests for k_sel_stretch, two entries each)
         bp.gap_cap = GAP_CAP - SEL_IREQ_CAP;
         bp.ireq = sc(SC_GAPS).as<uint4>() + bp.gap_cap;
-        bp.ireq_cap = SEL_IREQ_CAP - 8u;  // (k_sel_stretch reads eight entries from any request on)
+        bp.ireq_cap = sel_ireq_cap(h);  // (k_sel_stretch reads SEL_IREQ_SPARE entries from any request on: the array's layout does not move)
         // (pieces only where the host's route for what k_gap_fix hands over knows them: the tile kernel)
         bp.gap_nmax = (io && io->dev_gaps && h->cfg.w <= ST_WMAX && !knob_set(h, "MXG_STRETCH_DENSE") && !knob_set(h, "MXG_GAP_WHOLE")) ? GAP_DEV_NMAX : 0u;
         bp.ctrl = sc(SC_CTRL).as<uint32_t>();
@@ -2722,6 +2722,7 @@ struct Driver {
             sp.sup = bp.sup;
             sp.ireq = bp.ireq;
             sp.ireq_cap = bp.ireq_cap;
+            sp.n_slices = bp.n_slices;
             sp.ctrl = bp.ctrl;
             sp.tickets = bp.cand_spread + 64 * 32;
             sp.ablate = (uint32_t)env_u64(h, "MXG_SST_ABLATE", 0);
@@ -3813,7 +3814,8 @@ struct SketchStep {
             s.total += r.total();
             s.n_cand += r.n_cand();
             s.gap_kmers += r.gap_kmers();
-            if (items[q].bs) h->stat_slice_stretches += r.sel_requests();
+            // (the counter goes on counting where the array is full: what k_sel_stretch was handed ends at the capacity)
+            if (items[q].bs) h->stat_slice_stretches += sel_req_walk(r.sel_requests(), sel_ireq_cap(h));
             // what the batches saw of candidate-free stretches sizes the next sketch's batches (sparse_plan): real genomes hold
             // far more of them than the i.i.d. estimate (satellite arrays, low-complexity runs)
             // (1e-12: "a sketch has reported" -- an assembly whose stretches all went through k_sel_stretch leaves none over)

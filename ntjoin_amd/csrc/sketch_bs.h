@@ -3,6 +3,7 @@
 #pragma once
 #include "batch_ctrl.h"
 #include "mxg_internal.h"
+#include "sel_requests.h"
 
 namespace mxg {
 
@@ -15,7 +16,7 @@ constexpr uint32_t BS_CHUNK = 65536;      // base positions per chunk of the bit
 // strips, H halo strips (T + 2 H = 64).  The slice's candidates never leave the wave's LDS: bits -> queue -> exact hashes ->
 // window decision -> the selected ones, laid out per slice for k_emit (the layout k_resolve writes per block of 256 candidates).
 constexpr uint32_t SEL_PAD = 8;          // sentinel entries on either side of a wave's candidate list (the scans look at eight at a time)
-constexpr uint32_t SEL_REQ = 8;          // stretches per slice whose end lies behind the slice's strips (found by walking on)
+// (SEL_REQ, sel_requests.h: also the stretches per slice whose end lies behind the slice's strips, found by walking on)
 constexpr uint32_t SEL_GAP_DROP = 0x80000000u;  // in a reported stretch's fourth word (the reporting slice's first entry): "leave the first window's arg-min out"
 constexpr uint32_t SEL_MAX_H = 12;       // largest halo (strips) the route takes: 40 own strips per slice
 // k_sel_stretch (round 6): the candidate-free stretches that lie between two candidates of one slice are sketched by a kernel of
@@ -23,7 +24,7 @@ constexpr uint32_t SEL_MAX_H = 12;       // largest halo (strips) the route take
 constexpr uint32_t SEL_INL_R = 4;        // windows per lane in one piece of a stretch: a piece has at most 64 R windows
 constexpr uint32_t SEL_INL_PIECES = 6;   // pieces per stretch; longer stretches go to k_gap_fix
 constexpr uint32_t SEL_INL_TMP = 128;    // minimizers of one stretch (more: k_gap_fix)
-constexpr uint32_t SEL_IREQ_CAP = 1u << 18;  // requests per batch (the upper part of the stretch array)
+// (SEL_IREQ_CAP, sel_requests.h: requests per batch, the upper part of the stretch array)
 
 struct BsSelParams {
     const uint32_t *bm;          // the filter's bitmap: bit p = base position p of the packed array (bs_kernels.h)
@@ -57,10 +58,10 @@ struct BsSelParams {
     uint32_t ablate;             // (profiling builds: every slice stops after phase n; 0 = run)
     // inl_amax != 0: a slice's stretches become requests for k_sel_stretch, {contig, first, last k-mer, slice | number in the
     // slice << 24 | stretches of the slice << 27}, the slice's requests next to one another; CW_SEL_REQS counts them (0: every
-    // stretch goes straight to k_gap_fix)
+    // stretch goes straight to k_gap_fix).  At the array's capacity: sel_requests.h
     uint32_t inl_amax;
     uint4 *ireq;
-    uint32_t ireq_cap;
+    uint32_t ireq_cap;           // usable entries (SEL_IREQ_USABLE, or fewer: MXG_SEL_IREQ_CAP); SEL_IREQ_SPARE more lie behind them
 };
 
 struct SelStretchParams {
@@ -75,12 +76,20 @@ struct SelStretchParams {
     uint32_t *cnt, *sup;
     const uint4 *ireq;
     uint32_t ireq_cap;
+    uint32_t n_slices;           // slices of the batch: an entry that names another one is stepped over (sel_req_is_first)
     uint32_t *ctrl;              // CW_SEL_REQS requests, CW_STRETCHES (what does not fit here goes on to k_gap_fix)
     uint32_t *tickets;           // 64 counters, 32 words apart, zero: request 64 t + c is handed out by ticket t of counter c
     uint4 *gaps;
     uint32_t gap_cap, gap_nmax;
     uint32_t ablate;             // (profiling only, MXG_SST_ABLATE: 1 no rolls, 2 no first hash, 4 no window scans, 8 nothing per request, 32 no row update)
 };
+// requests a batch's array takes before slices fall back to k_gap_fix: SEL_IREQ_USABLE; MXG_SEL_IREQ_CAP=n (test knob): n, within
+// [1, SEL_IREQ_USABLE].  The array itself, and with it the layout of the stretch array, stays as it is.
+inline uint32_t sel_ireq_cap(const mxg_handle *h)
+{
+    const uint64_t n = knob_u64(h, "MXG_SEL_IREQ_CAP", SEL_IREQ_USABLE);
+    return (uint32_t)(n < 1 ? 1 : n > SEL_IREQ_USABLE ? SEL_IREQ_USABLE : n);
+}
 // the longest piece the window w allows (sketch_bs.hip: stretch_sketch); 0: no stretch is taken this way
 uint32_t bs_select_inline_amax(uint32_t w);
 int launch_sel_stretch(mxg_handle *h, const SelStretchParams &p, hipStream_t st);

@@ -475,7 +475,7 @@ __device__ __forceinline__ void sel_decide(const BsSelParams &p, SelCtx &c, cons
         const BsSelParams *pr = sel_rare_params();
         const uint32_t n_i = min(c.misc[2], SEL_REQ);
         const bool to_kernel = pr->inl_amax != 0u;  // (else: every stretch straight to k_gap_fix)
-        uint32_t base = 0xFFFFFFFFu - SEL_REQ;
+        uint32_t base = SEL_REQ_NO_KERNEL;
         if (to_kernel && lane == 0) base = atomicAdd(&pr->ctrl[CW_SEL_REQS], n_i);
         base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
         uint32_t ln = lane;
@@ -484,8 +484,13 @@ __device__ __forceinline__ void sel_decide(const BsSelParams &p, SelCtx &c, cons
 #endif
         if (ln < n_i) {
             const uint32_t *g = c.misc + 4u + 4u * ln;
-            if (base + n_i <= pr->ireq_cap) pr->ireq[base + ln] = make_uint4(g[0], g[1], g[2], sl | (ln << 24) | (n_i << 27));
-            else sel_push_gap(p, g[0], g[1], g[2], sl * pr->rk);  // (no room: the stretch kernels take them)
+            // (sel_requests.h.  No room for all of the slice's requests: the stretch kernels take them; the entries of the
+            // reservation in front of the capacity are walked by k_sel_stretch all the same and get a tombstone, not what an
+            // earlier batch left there)
+            const SelReqSlot slot = sel_req_slot(base, n_i, ln, pr->ireq_cap);
+            const uint32_t word = sel_req_word(sl, ln, n_i);
+            if (slot != SEL_SLOT_NONE) pr->ireq[base + ln] = make_uint4(g[0], g[1], g[2], slot == SEL_SLOT_WRITE ? word : sel_req_tombstone(word));
+            if (slot != SEL_SLOT_WRITE) sel_push_gap(p, g[0], g[1], g[2], sl * pr->rk);
         }
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) c.misc[2] = 0;
@@ -881,7 +886,7 @@ __global__ __launch_bounds__(SST_WAVES * 64, 5) void k_sel_stretch(const SelStre
     __shared__ uint4 rtab[16];
     __shared__ uint64_t Xs[SST_WAVES][2 * 64 * SEL_INL_R];
     __shared__ uint4 tmps[SST_WAVES][SEL_INL_TMP];
-    const uint32_t n_req = min(p.ctrl[CW_SEL_REQS], p.ireq_cap);
+    const uint32_t n_req = sel_req_walk(p.ctrl[CW_SEL_REQS], p.ireq_cap);
     if (blockIdx.x * SST_WAVES >= n_req) return;
     for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) byte_tab[i] = p.byte_tab[i];
     if (threadIdx.x < 16u) rtab[threadIdx.x] = p.tab.e[threadIdx.x];
@@ -900,11 +905,15 @@ __global__ __launch_bounds__(SST_WAVES * 64, 5) void k_sel_stretch(const SelStre
         if (lane == 0) r = atomicAdd(ticket, 1u);
         r = (uint32_t)__builtin_amdgcn_readfirstlane((int)r) * 64u + ((blockIdx.x * SST_WAVES + wv) & 63u);
         if (r >= n_req) break;
-        const uint4 mine = p.ireq[r + (lane & 7u)];  // (the array has eight entries to spare)
+        // (the array has SEL_IREQ_SPARE entries to spare behind ireq_cap, so every lane's read lies inside it.  Every entry in
+        // front of n_req was written by this batch -- a request or a tombstone -- and a first request at r has r + n_i <= ireq_cap
+        // (sel_requests.h): lanes q < n_i read this batch's requests; what the other lanes read, entries of other slices or,
+        // behind ireq_cap, whatever the array held, is never used: `has` below)
+        const uint4 mine = p.ireq[r + (lane & (SEL_REQ - 1u))];
         const uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mine.w);
-        if ((w0 >> 24) & 7u) continue;  // (not the slice's first request)
+        if (!sel_req_is_first(w0, p.n_slices)) continue;  // (not the slice's first request, a tombstone, or no slice of this batch)
         if (p.ablate & 8u) continue;
-        const uint32_t n_i = min(w0 >> 27, SEL_REQ), sl = w0 & 0xFFFFFFu;
+        const uint32_t n_i = sel_req_count(w0), sl = sel_req_slice(w0);
         const bool has = lane < n_i;
         const uint64_t my_key = has ? (((uint64_t)mine.x << 32) | mine.y) + 1ull : 0ull;  // (+ 1: 0 = taken / no request)
         uint4 *row = p.cs + (size_t)sl * p.rk;

@@ -6,7 +6,10 @@
     kernels count -> reorder -> resolve (MXG_BS_SELECT=0), the rolling-hash kernel (MXG_BS=0) -- against the CPU oracle on the
     same records, bit for bit, with the statistics saying which route ran;
   * slices that outgrow their LDS queue (MXG_SEL_QCAP) work in global memory, and a batch without a region left is redone;
-  * inputs the filter does not take (k != 32, the min(fwd, rev) variant) still go the old way.
+  * inputs the filter does not take (k != 32, the min(fwd, rev) variant) still go the old way;
+  * the request array of k_sel_stretch at its capacity (MXG_SEL_IREQ_CAP; csrc/sel_requests.h): every capacity from one request to
+    one more than a small input makes, batches that walk what earlier batches and other assemblies left in the array, realistic
+    records at a handful of capacities, the fused call -- no stale request is taken, no minimizer comes out twice.
 """
 import os
 import random
@@ -19,7 +22,8 @@ from tests.test_gpu_scale_paths import _check, _records
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ROUTE_KNOBS = ("MXG_GAP_POOL", "MXG_BS", "MXG_BS_SELECT", "MXG_SEL_QCAP", "MXG_SEL_RK", "MXG_GAP_WHOLE", "MXG_GAP_DEV_CAP", "MXG_SPARSE_BATCH_KMERS", "MXG_WAVE_CAP", "MXG_SPARSE_S", "MXG_DEV_GAPS", "MXG_SEL_INLINE")
+ROUTE_KNOBS = ("MXG_GAP_POOL", "MXG_BS", "MXG_BS_SELECT", "MXG_SEL_QCAP", "MXG_SEL_RK", "MXG_GAP_WHOLE", "MXG_GAP_DEV_CAP", "MXG_SPARSE_BATCH_KMERS", "MXG_WAVE_CAP", "MXG_SPARSE_S", "MXG_DEV_GAPS", "MXG_SEL_INLINE",
+               "MXG_SEL_IREQ_CAP")
 
 
 @pytest.fixture
@@ -304,3 +308,227 @@ def test_knobs_are_read_once_per_handle_and_reported(oracle, env):
         eng.add_records("x", 1.0, recs)
         eng.sketch()
         assert eng.stats()["select_slices"] > 0 and "MXG_BS_SELECT=1" in eng.knobs()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the request array of k_sel_stretch at its capacity (MXG_SEL_IREQ_CAP = usable requests per batch; csrc/sel_requests.h)
+# ---------------------------------------------------------------------------------------------------------------
+IREQ_KNOB = "MXG_SEL_IREQ_CAP"
+IREQ_USABLE = (1 << 18) - 8
+
+
+def _expected(oracle, recs, k, w):
+    """the oracle's sketch of every record, computed once per input: [(hash, position, strand)] per record"""
+    return [[(h, p, f) for h, p, f, _ in oracle.sketch(seq, k, w, _oracle.V2_SUM)] for _, seq in recs]
+
+
+def _assert_sketch(sk, want, ctx):
+    """hash, position, strand and record borders, bit for bit; and, named on its own: no minimizer twice (what a stale request for
+    k_sel_stretch does -- a stretch sketched into a row a second time -- in a batch that still ends well)"""
+    first = sk["record_first"].tolist()
+    borders = [0]
+    for exp in want:
+        borders.append(borders[-1] + len(exp))
+    for r, exp in enumerate(want):
+        lo, hi = int(first[r]), int(first[r + 1])
+        pos = sk["pos"][lo:hi].tolist()
+        assert len(set(pos)) == len(pos), ("a minimizer is duplicated", ctx, r)
+        got = list(zip(sk["out_hash"][lo:hi].tolist(), pos, sk["forward"][lo:hi].tolist()))
+        assert got == exp, (ctx, r)
+    assert first == borders and len(sk["out_hash"]) == borders[-1], ctx
+
+
+def _sketch_at_cap(env, recs, w, c, cap, want, ctx=None, calls=1):
+    """one handle, `calls` sketches of recs with the request array's capacity forced to cap (None: as shipped) -> stats"""
+    from ntjoin_amd.engine import MxEngine
+    if cap is None:
+        env.pop(IREQ_KNOB, None)
+    else:
+        env[IREQ_KNOB] = str(cap)
+    with MxEngine(k=32, w=w, cand_per_window=c) as eng:
+        eng.add_records("x", 1.0, recs)
+        for call in range(calls):
+            eng.sketch(-2)
+            _assert_sketch(eng.get_sketch(0), want, (ctx, w, c, cap, call))
+        st = eng.stats()
+        if cap is not None:
+            assert f"{IREQ_KNOB}={cap}" in eng.knobs().split(), "the handle did not read the knob"
+    return st
+
+
+def _once(st):
+    """every batch was enqueued and summed up once: the statistics are then sums over the batches as they ran"""
+    return st["batches_redone"] == 0 and st["retried_assemblies"] == 0 and st["sync_assemblies"] == 0
+
+
+def _iid(seed, n):
+    rng = random.Random(seed)
+    return "".join(rng.choice("ACGT") for _ in range(n))
+
+
+@pytest.mark.parametrize("dev_gaps", ["0", "1"])
+def test_request_capacity_every_cap_of_a_small_input(oracle, env, dev_gaps):
+    """one i.i.d. record of 200 kbp at (w = 64, c = 2), strips of 320: every slice holds far more than SEL_REQ = 8 stretches between
+    two of its candidates, so nearly every slice reserves eight requests: R = slice_stretches > L = select_slices without the
+    knob, and some slice holds at least two requests.  Reservations are contiguous, so among the capacities 1 .. R + 1 some fall
+    strictly inside a reservation of several requests, whatever order the adds landed in: the cut reservation (tombstones in front
+    of the capacity, all of the slice's stretches to k_gap_fix) is exercised for certain, as are the exact fit and the capacities
+    one entry either side of it.  The counter goes on counting at the capacity; the statistic is what the array took.
+    Measured on an MI355X: R = 87, L = 11 (ten slices with eight requests, one with seven), with and without MXG_DEV_GAPS; with
+    MXG_DEV_GAPS=1 every batch is enqueued once and the statistic is exact at all 88 capacities."""
+    recs = [("iid", _iid(4242, 200_000))]
+    env["MXG_SPARSE_S"] = "320"
+    env["MXG_DEV_GAPS"] = dev_gaps
+    want = _expected(oracle, recs, 32, 64)
+    st0 = _sketch_at_cap(env, recs, 64, 2, None, want)
+    R, L = st0["slice_stretches"], st0["select_slices"]
+    print(f"request capacity sweep (dev_gaps={dev_gaps}): R = {R} requests, L = {L} slices")
+    assert R > L > 0, (R, L)
+    assert R <= 600, R               # (a sweep of a few hundred handles; a larger R wants a shorter record)
+    exact = 0
+    for cap in range(1, R + 2):
+        st = _sketch_at_cap(env, recs, 64, 2, cap, want)
+        assert 0 < st["slice_stretches"] and st["select_slices"] >= L, cap
+        if _once(st0) and _once(st):   # (one record is one batch: its array took min(R, cap) entries)
+            assert st["slice_stretches"] == min(R, cap) and st["select_slices"] == L, (cap, st["slice_stretches"])
+            exact += 1
+    print(f"request capacity sweep (dev_gaps={dev_gaps}): {exact} of {R + 1} capacities with every batch enqueued once")
+
+
+def _several_records(seed, lengths):
+    rng = random.Random(seed)
+    return [(f"r{i}", "".join(rng.choice("ACGT") for _ in range(n))) for i, n in enumerate(lengths)]
+
+
+def test_request_capacity_stale_requests_of_earlier_batches(oracle, env):
+    """the array is never cleared: what a batch leaves in it -- requests in front of the capacity, untouched entries behind a cut
+    reservation until this was fixed -- is there when the next batch of the handle walks its min(counter, capacity) entries.
+    Batches are whole records: with a budget of 50 000 k-mers each of the six records of 40 to 90 kbp is a batch of its own (no
+    two fit one budget; more slices than the unforced run makes says that the budget took).  Two sketches per handle, capacities
+    3, 11 and half of what an average batch asks for; then a handle that sketches assembly A, and then A and another assembly B
+    of other record lengths, whose batches walk what A's left."""
+    from ntjoin_amd.engine import MxEngine
+    env["MXG_SPARSE_S"] = "320"
+    env["MXG_DEV_GAPS"] = "1"
+    w, c, budget = 64, 2, 50_000
+    recs_a = _several_records(91, [90_000, 40_000, 75_000, 55_000, 60_000, 41_000])
+    recs_b = _several_records(92, [30_000, 120_000, 47_000, 83_000, 52_000])
+    want_a, want_b = _expected(oracle, recs_a, 32, w), _expected(oracle, recs_b, 32, w)
+    one = _sketch_at_cap(env, recs_a, w, c, None, want_a, "one batch")
+    env["MXG_SPARSE_BATCH_KMERS"] = str(budget)
+    st = _sketch_at_cap(env, recs_a, w, c, None, want_a, "batches")
+    assert st["select_slices"] > one["select_slices"], "one batch: MXG_SPARSE_BATCH_KMERS did not take"
+    assert all(len(x) + len(y) - 62 > budget for (_, x), (_, y) in zip(recs_a, recs_a[1:]))
+    n_batches = len(recs_a)
+    multi = st["slice_stretches"]
+    R = multi // n_batches
+    print(f"stale requests: {st['slice_stretches']} requests in {n_batches} batches, {st['select_slices']} slices ({one['select_slices']} in one batch)")
+    assert n_batches >= 4 and R // 2 > 11
+    for cap in (3, 11, R // 2):
+        st = _sketch_at_cap(env, recs_a, w, c, cap, want_a, "two sketches of a handle", calls=2)
+        assert 0 < st["slice_stretches"] <= 2 * multi, cap   # (two sketches of the handle, every batch's count bounded by the capacity)
+        env[IREQ_KNOB] = str(cap)
+        with MxEngine(k=32, w=w, cand_per_window=c) as eng:
+            eng.add_records("a", 1.0, recs_a)
+            eng.sketch(-2)
+            _assert_sketch(eng.get_sketch(0), want_a, ("A alone", cap))
+            eng.add_records("b", 1.0, recs_b)
+            eng.sketch(-2)
+            _assert_sketch(eng.get_sketch(0), want_a, ("A beside B", cap))
+            _assert_sketch(eng.get_sketch(1), want_b, ("B behind A", cap))
+
+
+def _stretch_records():
+    """the records of test_stretches_are_sketched_behind_the_slice_kernel and of test_select_stretch_ends_behind_the_slice"""
+    rng = random.Random(77)
+    rnd = lambda n: "".join(rng.choice("ACGT") for _ in range(n))
+    plain = [("a", rnd(700000)), ("b", rnd(1500)), ("c", rnd(1031)), ("d", rnd(300000)), ("n_inside", rnd(40000) + "N" + rnd(50000) + "NNNN" + rnd(800)),
+             ("e", rnd(2200)), ("f", rnd(450000))]
+    rng = random.Random(5)
+    unit = rnd(171)
+    long_ = [("sat", rnd(30000) + unit * 400 + rnd(30000)), ("polyA", rnd(5000) + "A" * 90000 + rnd(2000)),
+             ("unit7", ("ACGGTCA" * 20000)[:100000]), ("plain", rnd(200000)), ("polyT_end", rnd(3000) + "T" * 50000)]
+    return {"between_candidates": plain, "behind_the_slice": long_}
+
+
+@pytest.mark.parametrize("which", ["between_candidates", "behind_the_slice"])
+@pytest.mark.parametrize("w,c", [(1000, 4), (300, 3), (2500, 3), (64, 2)])
+def test_request_capacity_realistic_shapes(oracle, env, which, w, c):
+    """stretches between two candidates of a slice, at a contig's start and end, across N, taken in pieces (w = 2500), and stretches
+    that end far behind the slice: capacities 1, 8, 9 (one request, one full reservation, one more), half of what the input
+    asks for, one less than that, exactly that (the last reservation fits exactly: nothing falls back)"""
+    recs = _stretch_records()[which]
+    env["MXG_SPARSE_S"] = "320"
+    env["MXG_DEV_GAPS"] = "1"
+    want = _expected(oracle, recs, 32, w)
+    st0 = _sketch_at_cap(env, recs, w, c, None, want, which)
+    R = st0["slice_stretches"]
+    print(f"realistic shapes {which} w={w} c={c}: R = {R} requests, {st0['select_slices']} slices")
+    assert R > 5 and st0["select_slices"] > 0, R
+    for cap in sorted({1, 8, 9, max(1, R // 2), R - 1, R}):
+        st = _sketch_at_cap(env, recs, w, c, cap, want, which)
+        # (the records may make several batches, each with an array of its own: every batch's count is bounded by the capacity)
+        assert 0 < st["slice_stretches"] and (st["slice_stretches"] <= R or not (_once(st0) and _once(st))), (cap, st["slice_stretches"])
+    if _once(st0) and _once(st):     # (capacity R binds in no batch: as without the knob)
+        for key in ("slice_stretches", "deferred_stretches", "dense_kmers"):
+            assert st[key] == st0[key], key
+
+
+def test_request_capacity_fused_call(oracle, env, tmp_path):
+    """mxg_sketch_graph at a capacity of nine requests (every batch cuts a reservation) against mxg_sketch + mxg_build_graph of the
+    same two assemblies at the same capacity, and against both without the knob: sketches, minimizer flags, canonical .mx.dot"""
+    import numpy as np
+    from ntjoin_amd.engine import MxEngine
+    from oracle import graph_oracle
+    env["MXG_SPARSE_S"] = "320"
+    env["MXG_DEV_GAPS"] = "1"
+    w, c = 300, 3
+    ref = _stretch_records()["between_candidates"]
+    comp = str.maketrans("ACGT", "TGCA")
+    tgt = [(f"t{i}", s[::-1].translate(comp) if i % 2 else s) for i, (_, s) in enumerate(ref) if "N" not in s][::-1]
+    want = [_expected(oracle, recs, 32, w) for recs in (ref, tgt)]
+    res = {}
+    for cap in (None, 9):
+        for fused in (False, True):
+            if cap is None:
+                env.pop(IREQ_KNOB, None)
+            else:
+                env[IREQ_KNOB] = str(cap)
+            with MxEngine(k=32, w=w, cand_per_window=c) as eng:
+                eng.add_records("ref.fa.k32.w300.tsv", 2.0, ref)
+                eng.add_records("tgt.fa.k32.w300.tsv", 1.0, tgt)
+                if fused:
+                    eng.sketch_graph()
+                else:
+                    eng.sketch(-2)
+                    eng.build_graph()
+                for a in range(2):
+                    _assert_sketch(eng.get_sketch(a), want[a], ("fused" if fused else "two calls", cap, a))
+                dot = str(tmp_path / f"{cap}_{fused}.mx.dot")
+                eng.write_dot(dot)
+                with open(dot, encoding="utf-8") as fh:
+                    res[cap, fused] = (graph_oracle.canonical_dot_from_text(fh.read()), [eng.get_mx_flags(a).copy() for a in range(2)],
+                                       eng.stats())
+    base = res[None, False]
+    assert base[2]["slice_stretches"] > 100    # (hundreds of requests: a capacity of nine binds in every batch)
+    for key, (dot, flags, st) in res.items():
+        assert dot == base[0], key
+        assert all(np.array_equal(x, y) for x, y in zip(flags, base[1])), key
+        if _once(st) and _once(base[2]):   # (nine requests per batch's array, however many batches)
+            assert st["slice_stretches"] == base[2]["slice_stretches"] if key[0] is None else 0 < st["slice_stretches"] < base[2]["slice_stretches"], key
+
+
+def test_request_capacity_that_does_not_bind(oracle, env):
+    """a capacity of what the input asks for, of more, of more than the array has (clamped to its 262 136 usable entries):
+    statistics and sketch are those of a run without the knob"""
+    recs = [("iid", _iid(4243, 150_000)), ("short", _iid(4244, 1200))]
+    env["MXG_SPARSE_S"] = "320"
+    env["MXG_DEV_GAPS"] = "1"
+    want = _expected(oracle, recs, 32, 64)
+    st0 = _sketch_at_cap(env, recs, 64, 2, None, want)
+    R = st0["slice_stretches"]
+    assert R > 8
+    for cap in (R, R + 1, 4 * R, IREQ_USABLE, 10 ** 9):
+        st = _sketch_at_cap(env, recs, 64, 2, cap, want)
+        for key in ("slice_stretches", "select_slices", "candidates", "dense_kmers", "deferred_stretches", "batches_redone", "minimizers"):
+            assert st[key] == st0[key], (cap, key)

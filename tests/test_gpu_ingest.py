@@ -2,7 +2,14 @@
 formatted ON THE DEVICE, against (a) the CPU oracle's own FASTA -> TSV driver (byte-identical files) and (b) the host parser /
 host writer of the library (MXG_HOST_INGEST=1 / MXG_HOST_TSV=1).  Shapes that stress the text handling: CRLF line ends
 (also across the 4 MiB read buffer of the host parser and across the device's 4096-byte tiles), lower case, N-runs,
-IUPAC codes, ragged line lengths, no final newline, '>' inside header lines, empty records, thousands of tiny records."""
+IUPAC codes, ragged line lengths, no final newline, '>' inside header lines, empty records, thousands of tiny records.
+The device parser's buffer of validity events at and beyond its capacity (MXG_INGEST_EV_CAP): files with a known number of changes
+on both sides of the limit, a record with an invalid base every 50 to 200 bases, and the invalid-base intervals the overlap stage
+reads behind the device parser, the host parser and the overflow's way to the host parser.
+
+Which parser ran: neither mxg_stats nor mxg_knobs says so (knobs() lists MXG_INGEST_EV_CAP once the device parser has come as far
+as its events, whether it then kept the file or handed it over).  The witness used here is the line "[mxg] load_fasta_device ..."
+that MXG_DEBUG_IO=1 prints to stderr when, and only when, the device parser finished the file."""
 import os
 import random
 import subprocess
@@ -47,6 +54,16 @@ def _messy_records(seed):
             ("startsN", "NNNN" + _seq(rng, 12_000) + "NN")]
     recs += [(f"frag{i}", _seq(rng, rng.randint(20, 2500))) for i in range(300)]
     recs.append(("last", _seq(rng, 70_000)))
+    # an invalid base (N or an IUPAC letter, either case) every 50 to 200 bases over 300 kbp: about 2400 of them, twice as many
+    # changes between valid and invalid inside the device parser's tiles (a generator of its own: the records above stay as they were)
+    rng2 = random.Random(seed + 1000)
+    s, p = list(_seq(rng2, 300_000)), 0
+    while True:
+        p += rng2.randint(50, 200)
+        if p >= len(s):
+            break
+        s[p] = rng2.choice("NnRYKMSWBDHVrykm")
+    recs.append(("scattered", "".join(s)))
     return recs
 
 
@@ -209,3 +226,134 @@ def test_fuzz_fasta_text_three_ways(tmp_path):
             out = str(tmp_path / f"{tag}{t}.tsv")
             _tsv_by_engine(fa, k, w, out, **env)
             assert open(out, "rb").read() == open(want, "rb").read(), (t, tag, k, w, width, repr(eol), len(recs))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the device parser's validity events at their capacity (MXG_INGEST_EV_CAP)
+# ---------------------------------------------------------------------------------------------------------------
+DEVICE_LINE = "[mxg] load_fasta_device"
+
+
+@pytest.fixture
+def ingest_env():
+    names = ("MXG_INGEST_EV_CAP", "MXG_HOST_INGEST", "MXG_HOST_TSV", "MXG_DEBUG_IO")
+    saved = {k: os.environ.get(k) for k in names}
+    for k in names:
+        os.environ.pop(k, None)
+    os.environ["MXG_DEBUG_IO"] = "1"
+    yield os.environ
+    for k, v in saved.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
+
+
+def _set(env, name, value):
+    if value is None:
+        env.pop(name, None)
+    else:
+        env[name] = str(value)
+
+
+# one record inside one 4096-byte tile of the file (header at offset 0, under 4000 bytes in all): every change between valid and
+# invalid bases behind the record's first base is one event of that tile
+KNOWN_EVENTS = {
+    2: lambda a, b, c: a + "N" + b + c,                       # ACGT... N ACGT...
+    3: lambda a, b, c: a + "NNN" + b + c + "RY",              # ... and an invalid end
+    4: lambda a, b, c: a + "n" + b + "K" * 40 + c,            # two islands
+}
+
+
+@pytest.mark.parametrize("changes", sorted(KNOWN_EVENTS))
+@pytest.mark.parametrize("k,w", [(15, 10), (32, 50)])
+def test_event_buffer_on_both_sides_of_its_capacity(tmp_path, ingest_env, capfd, changes, k, w):
+    """capacities 1 .. 5 on files with two, three and four changes: the device parser keeps the file iff its events fit
+    (n_ev <= capacity), else the host parser takes it; the TSV is the oracle's, byte for byte, either way"""
+    orc = _oracle.load()
+    rng = random.Random(changes)
+    seq = KNOWN_EVENTS[changes](_seq(rng, 1200), _seq(rng, 900), _seq(rng, 1100))
+    fa = str(tmp_path / "one_tile.fa")
+    _write_fasta(fa, [("r", seq)], width=70)
+    assert os.path.getsize(fa) < 4000
+    want = str(tmp_path / "want.tsv")
+    orc.fasta_to_tsv(fa, want, k, w)
+    assert os.path.getsize(want) > 1000
+    for cap in (1, 2, 3, 4, 5):
+        ingest_env["MXG_INGEST_EV_CAP"] = str(cap)
+        capfd.readouterr()
+        out = str(tmp_path / f"cap{cap}.tsv")
+        with MxEngine(k=k, w=w, threads=3) as eng:
+            eng.add_fasta("x", 1.0, fa)
+            err = capfd.readouterr().err
+            assert f"MXG_INGEST_EV_CAP={cap}" in eng.knobs().split()   # (the device parser came as far as its events)
+            eng.sketch()
+            eng.write_tsv(0, out, with_pos=True, with_strand=False, with_seq=True)
+        assert (DEVICE_LINE in err) == (changes <= cap), (changes, cap, err)
+        assert open(out, "rb").read() == open(want, "rb").read(), (changes, cap)
+
+
+@pytest.mark.parametrize("eol", ["\n", "\r\n"])
+@pytest.mark.parametrize("k,w", [(32, 100), (15, 10)])
+def test_scattered_invalid_bases_overflow_the_event_buffer(tmp_path, ingest_env, capfd, eol, k, w):
+    """thousands of events (the `scattered` record of _messy_records) against a buffer of 1, of 64 and the default: through
+    add_fasta, add_fasta_split (three parts whose concatenation is the whole) and the indexlr CLI; LF and CRLF"""
+    orc = _oracle.load()
+    fa = str(tmp_path / "messy.fa")
+    _write_fasta(fa, _messy_records(21), width=70, eol=eol)
+    want = str(tmp_path / "oracle.tsv")
+    orc.fasta_to_tsv(fa, want, k, w)
+    want_bytes = open(want, "rb").read()
+    exe = os.path.join(BIN_DIR, "indexlr")
+    for cap in (1, 64, None):
+        _set(ingest_env, "MXG_INGEST_EV_CAP", cap)
+        capfd.readouterr()
+        out = str(tmp_path / f"cap{cap}.tsv")
+        with MxEngine(k=k, w=w, threads=3) as eng:
+            eng.add_fasta("x", 1.0, fa)
+            err = capfd.readouterr().err
+            eng.sketch()
+            eng.write_tsv(0, out, with_pos=True, with_strand=False, with_seq=True)
+            whole = {key: v.copy() for key, v in eng.get_sketch(0).items() if key in ("out_hash", "pos", "record")}
+        assert (DEVICE_LINE in err) == (cap is None), (cap, err)
+        assert open(out, "rb").read() == want_bytes, cap
+        parts = []
+        for s in range(3):
+            with MxEngine(k=k, w=w) as eng:
+                eng.add_fasta_split("x", 1.0, fa, s, 3)
+                eng.sketch()
+                parts.append({key: v.copy() for key, v in eng.get_sketch(0).items() if key in ("out_hash", "pos", "record")})
+        for key in ("out_hash", "pos", "record"):
+            assert np.array_equal(np.concatenate([p[key] for p in parts]), whole[key]), (cap, key)
+        r = subprocess.run([exe, "--seq", "--long", "--pos", f"-k{k}", f"-w{w}", "-t3", fa], capture_output=True, check=True)
+        assert r.stdout == want_bytes, cap
+        assert (DEVICE_LINE in r.stderr.decode()) == (cap is None), cap
+
+
+def test_invalid_base_intervals_agree_on_every_ingest_route(tmp_path, ingest_env, capfd):
+    """mxg_overlap_cuts reads the invalid-base intervals every text ingest route fills: paths whose junctions overlap, N islands near
+    the overlapping ends among them (tests/_overlap_cases.py), behind the device parser, behind the host parser (MXG_HOST_INGEST=1)
+    and behind the device parser's overflow (one event of room): the same cut points, those of tests/_overlap_restatement.py"""
+    from tests._overlap_cases import fasta_text, make_synth
+    from tests.test_gpu_overlap import check_against_restatement
+    records, paths = make_synth(seed=20261017, n_paths=60)
+    n_islands = sum(1 for _, s in records for i, ch in enumerate(s) if ch == "N" and i and s[i - 1] != "N")
+    assert n_islands >= 8, n_islands
+    fa = str(tmp_path / "paths.fa")
+    with open(fa, "w", encoding="ascii") as fh:
+        fh.write(fasta_text(records))
+    results = []
+    for tag, knobs, device in (("device", {}, True), ("host", {"MXG_HOST_INGEST": "1"}, False), ("overflow", {"MXG_INGEST_EV_CAP": "1"}, False)):
+        for name in ("MXG_HOST_INGEST", "MXG_INGEST_EV_CAP"):
+            _set(ingest_env, name, knobs.get(name))
+        capfd.readouterr()
+        with MxEngine(k=32, w=100) as eng:   # (the handle's k and w are not the call's)
+            a = eng.add_fasta("t", 1.0, fa)
+            err = capfd.readouterr().err
+            assert (DEVICE_LINE in err) == device, (tag, err)
+            got = check_against_restatement(eng, a, records, paths, 15, 10)
+            results.append({key: v.copy() for key, v in got.items()})
+    assert results[0]["cut_found"].sum() > 20
+    for res in results[1:]:
+        for key in ("start_adjust", "end_adjust", "cut_found"):
+            assert np.array_equal(res[key], results[0][key]), key
