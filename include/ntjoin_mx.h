@@ -405,6 +405,49 @@ int mxg_overlap_cuts(mxg_handle *h, int assembly, uint32_t k, uint32_t w, const 
                      const uint64_t *path_first /* n_paths + 1 */, uint64_t n_paths, uint32_t *start_adjust,
                      uint32_t *end_adjust, uint8_t *cut_found /* per node: junction to the next */);
 
+/* ---- next row (f6): the scaffold FASTA of all paths, and what no path took ------------------------------------------------
+   What the reference's print_scaffolds loop (bin/ntjoin_assemble.py:580-613; get_fasta_segment :327-332, get_adjusted_sequence
+   :519-527, join_sequences :407-439) and print_unassigned (:628-658: bedtools complement + bedtools getfasta) produce by reading
+   the target FASTA a second time and slicing Python strings.  Here: from the text the handle already holds, on the device.
+   Node i of path p is nodes[path_first[p] + i], as print_scaffolds holds it at :580 (orientation '+' / '-' only, the last node's
+   gap already zeroed by the caller as check_terminal_node_gap_zero does).  With T = the record's bases [start, end)
+   (reversed and mapped through the table of bin/ntjoin_utils.py:145-150 when `reverse`: ACGTUNMRWSYKVHDB -> TGCAANKYWSRMBDHV,
+   the same in lower case, any other byte unchanged), L = end - start and g = gap_size, the node's piece is
+     overlap_gap < 0 (overlap stage off):  T + "N" * g
+     overlap_gap >= 0:  T[start_adjust : e] with e = end_adjust ? end_adjust : L (empty when start_adjust >= e), followed,
+                        if g > 0, by "N" * g when e == L and by "N" * overlap_gap otherwise.
+   The scaffold of path p is the concatenation of its pieces with N/n stripped from the left of the first piece and from the
+   right of the last one; the two counts come back in lead_strip[p] / tail_strip[p] (the reference moves the .path coordinates
+   by them).  assigned_fa gets ">ntJoin<p>\n<sequence>\n" per path, paths numbered in input order (:600-603).
+   Unassigned: per record, in record order, the complement of the union of the nodes' [start, end) (unadjusted, unstripped: the
+   Bed entries of :589) within [0, record length), zero-length intervals left out; unassigned_bed gets "id\tstart\tend\n" per
+   interval, unassigned_fa ">id:start-end\n<text>\n" with N/n stripped from both ends of the text (the header keeps the
+   interval's coordinates; an interval left empty is dropped from the FASTA, not from the BED); *n_unassigned = records written
+   to unassigned_fa.  Either file name may be NULL, as may lead_strip, tail_strip and n_unassigned.
+   Bytes are the record's own spelling with line ends removed; MXG_SCAF_FOLD_CASE folds a-z to A-Z in assigned_fa only.
+   MXG_EINVAL (nothing is written): an assembly whose text the handle does not hold (TSV / side-car / minimizer / packed-device
+   input, a shard or pieces of a file, text dropped by MXG_FLAG_DROP_SEQ or released by a one-shot handle), start >= end, end
+   beyond the record, a path of fewer than two nodes, end_adjust > L, a first or last piece whose text part is empty or N/n
+   throughout (the reference asserts there).  MXG_ELIMIT: 2^31 nodes or more.  Sketches, graph and paths are left as they are. */
+#define MXG_SCAF_FOLD_CASE 0x1u
+typedef struct mxg_scaffold_node {
+    uint32_t record, start, end;       /* [start, end) of the record */
+    uint32_t gap_size;                 /* Ns behind the node (PathNode.gap_size) */
+    uint32_t start_adjust, end_adjust; /* as mxg_overlap_cuts returns them; 0 = none */
+    uint8_t  reverse, pad[3];
+} mxg_scaffold_node;
+int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *nodes,
+                        const uint64_t *path_first /* n_paths + 1 */, uint64_t n_paths,
+                        int32_t overlap_gap /* < 0: overlap stage off */, uint32_t flags, const char *assigned_fa,
+                        const char *unassigned_fa /* may be NULL */, const char *unassigned_bed /* may be NULL */,
+                        uint32_t *lead_strip, uint32_t *tail_strip /* [n_paths] */, uint64_t *n_unassigned);
+/* The N/n stripped from the left and the right of every unassigned interval by the last successful mxg_write_scaffolds of the
+   handle that computed the unassigned side (any of unassigned_fa, unassigned_bed, n_unassigned given), one entry per line of the
+   BED, in its order; an interval that is N throughout has lead = its length and tail = 0.  What write_agp_unassigned
+   (bin/ntjoin_assemble.py:379-404) recomputes from the text of every record (len_diff_start, len_diff_end).  The arrays are the
+   handle's and hold until its next mxg_write_scaffolds. */
+int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals);
+
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------
    No counterpart in the reference (it is one process).  Uniqueness and intersection need every occurrence of a hash in
    one place: every minimizer travels to the rank that owns its hash, the owner runs the ordinary graph kernels on what it

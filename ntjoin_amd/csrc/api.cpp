@@ -897,6 +897,32 @@ int mxg_overlap_cuts(mxg_handle *h, int assembly, uint32_t k, uint32_t w, const 
     }
 }
 
+int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
+                        int32_t overlap_gap, uint32_t flags, const char *assigned_fa, const char *unassigned_fa, const char *unassigned_bed,
+                        uint32_t *lead_strip, uint32_t *tail_strip, uint64_t *n_unassigned)
+{
+    if (!h) return MXG_EINVAL;
+    if (assembly < 0 || (size_t)assembly >= h->asms.size()) return set_err(h, MXG_EINVAL, "mxg_write_scaffolds: no assembly %d", assembly);
+    if (!path_first || !assigned_fa || (n_paths && path_first[n_paths] && !nodes))
+        return set_err(h, MXG_EINVAL, "mxg_write_scaffolds: null argument");
+    try {
+        return write_scaffolds(h, h->asms[assembly], assembly, nodes, path_first, n_paths, overlap_gap, flags, assigned_fa, unassigned_fa,
+                               unassigned_bed, lead_strip, tail_strip, n_unassigned);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_write_scaffolds");
+    }
+}
+
+int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals)
+{
+    if (!h) return MXG_EINVAL;
+    if (!lead_strip || !tail_strip || !n_intervals) return set_err(h, MXG_EINVAL, "mxg_scaffold_strips: null argument");
+    *lead_strip = h->scaf_lead.data();
+    *tail_strip = h->scaf_tail.data();
+    *n_intervals = h->scaf_lead.size();
+    return MXG_OK;
+}
+
 // ---- distributed graph stage (dgraph.hip; the collectives are the caller's) -----------------------------------------
 #define DG_TRY(expr)                                                                     \
     try {                                                                                \
@@ -1097,6 +1123,7 @@ int mxg_write_outputs(mxg_handle *h, const char *dot_path, const char *const *ts
                 a->d_packed = nullptr;
                 a->has_bases = false;
                 a->text_on_device = false;
+                a->flat_text_on_device = false;
             }
             for (auto &set : h->scratch)
                 for (auto &b : set) b.release();

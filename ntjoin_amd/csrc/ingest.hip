@@ -27,30 +27,15 @@
 
 #include "mxg_internal.h"
 #include "scan_kernels.h"
+#include "text_index.h"
 
 namespace mxg {
-
-constexpr uint32_t ING_TILE = 4096;  // text bytes per work item: one aligned tile of the file, cut at record borders
 
 uint32_t host_threads(const mxg_handle *h)
 {
     uint32_t t = h->cfg.host_threads;
     if (!t) t = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
     return std::min(t, 256u);
-}
-
-struct IngItem {
-    uint64_t lo;   // first text byte
-    uint32_t len;  // bytes (all inside one tile)
-    uint32_t rec;  // record
-};
-
-// byte class: 0..3 = A C G T(U) (either case), 4 = any other base character (invalid), 5 = line break (not a base)
-__device__ __forceinline__ uint32_t byte_class(uint32_t b)
-{
-    if (b == '\n' || b == '\r') return 5u;
-    const uint32_t u = b & 0xDFu;  // upper case
-    return u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : (u == 'T' || u == 'U') ? 3u : 4u;
 }
 
 // thread t of an item's block owns text bytes [tile + 16 t, tile + 16 t + 16): -> base codes (2 bits each, in order),
@@ -607,34 +592,10 @@ __device__ __forceinline__ uint64_t put_dec(const TsvParams &p, uint64_t at, uin
     return at + d;
 }
 
-// text offset of base `pos` of record r: the tile by binary search over the tiles' first base indices, the 256-byte
-// sub-tile by its 16 counts, then a scan over at most 256 bytes
-__device__ __forceinline__ uint64_t text_of_base(const TsvParams &p, uint32_t r, uint32_t pos)
+// the tile index as text_of_base (text_index.h) reads it
+__device__ __forceinline__ TextIndex tsv_text_index(const TsvParams &p)
 {
-    const uint64_t want = p.rec_base[r] + pos;
-    uint64_t lo = p.rec_item0[r], hi = p.rec_item0[r + 1];
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (p.item_pbase[mid] <= want) lo = mid; else hi = mid;
-    }
-    const IngItem it = p.items[lo];
-    uint32_t local = (uint32_t)(want - p.item_pbase[lo]);
-    const uint64_t tile = it.lo & ~(uint64_t)(ING_TILE - 1);
-    uint32_t s = 0;
-    for (; s < 15; ++s) {
-        const uint32_t c = p.item_sub[lo * 16u + s];
-        if (local < c) break;
-        local -= c;
-    }
-    uint64_t a = tile + 256u * s;
-    if (a < it.lo) a = it.lo;
-    for (;; ++a) {  // (the base is there: the counts say so)
-        const uint32_t c = byte_class(p.text[a]);
-        if (c != 5u) {
-            if (local == 0) return a;
-            --local;
-        }
-    }
+    return TextIndex{p.text, p.items, p.item_pbase, p.item_sub, p.rec_item0, p.rec_base};
 }
 
 __global__ __launch_bounds__(256) void k_tsv_entries(const TsvParams p)
@@ -658,7 +619,7 @@ __global__ __launch_bounds__(256) void k_tsv_entries(const TsvParams p)
     if (p.with_seq) {
         put_win(p, at++, ':');
         if (p.text) {
-            uint64_t a = text_of_base(p, r, p.pos[i]);
+            uint64_t a = text_of_base(tsv_text_index(p), r, p.pos[i]);
             for (uint32_t u = 0; u < p.k; ++a) {
                 const unsigned char b = p.text[a];
                 if (b == '\n' || b == '\r') continue;

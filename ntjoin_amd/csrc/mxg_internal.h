@@ -114,6 +114,7 @@ struct Assembly {
     // device ingest (ingest.hip): the raw FASTA text in HBM + the tile index that maps a base to its byte
     bool text_on_device = false;
     uint64_t text_bytes = 0;
+    bool flat_text_on_device = false;  // host ingest: Assembly::text copied to d_text by the first mxg_write_scaffolds (no line ends, no index)
     DevBuf d_text, d_ing_items, d_ing_cnt, d_ing_sub, d_ing_pbase, d_ing_item0;
     std::vector<uint64_t> ing_item0;  // [n_records + 1] first tile of every record
     DevBuf d_packed_own;
@@ -254,6 +255,8 @@ struct mxg_handle {
     mxg::DevBuf pbuf[48];  // scratch of paths.hip
     mxg::DevBuf mkbuf[8];  // scratch of mk.hip
     mxg::DevBuf ovbuf[16];  // scratch of overlap.hip
+    mxg::DevBuf scbuf[8];   // scratch of scaffold.hip
+    std::vector<uint32_t> scaf_lead, scaf_tail;  // N/n stripped from either end of every unassigned interval by the last mxg_write_scaffolds
     mxg::Segments segs;
     mxg::Timers tm;
     mxg::HashTab tab{};
@@ -487,6 +490,10 @@ int mk_stats(mxg_handle *h, const uint32_t *values, const uint64_t *run_first, u
 // overlap.hip: the cut points of every overlapping junction of the given paths (mxg_overlap_cuts)
 int overlap_cuts(mxg_handle *h, Assembly *a, int assembly, uint32_t k, uint32_t w, const mxg_overlap_node *nodes,
                  const uint64_t *path_first, uint64_t n_paths, uint32_t *start_adjust, uint32_t *end_adjust, uint8_t *cut_found);
+// scaffold.hip: the scaffold FASTA of the given paths and the unassigned rest (mxg_write_scaffolds)
+int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
+                    int32_t overlap_gap, uint32_t flags, const char *assigned_fa, const char *unassigned_fa, const char *unassigned_bed,
+                    uint32_t *lead_strip, uint32_t *tail_strip, uint64_t *n_unassigned);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm
 int flags_to_host(mxg_handle *h, Assembly *a);
 

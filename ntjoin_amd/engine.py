@@ -12,6 +12,7 @@ Order of use mirrors the reference pipeline:
 All arrays returned are numpy COPIES (the library owns its buffers), hence picklable.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -32,7 +33,7 @@ def _np(ptr, n, dtype):
 
 class MxEngine:
     def __init__(self, k=32, w=1000, variant="v2", device=-1, stream=None, dense_only=False, drop_seq=False,
-                 timing=False, cand_per_window=0, timing_fine=False, threads=0):
+                 timing=False, cand_per_window=0, timing_fine=False, threads=0, one_shot=False):
         self._lib = capi.load()
         self._h = C.c_void_p()
         cfg = capi.Config()
@@ -41,7 +42,8 @@ class MxEngine:
         cfg.variant = capi.VARIANT_V1_MIN if str(variant).lower() in ("v1", "min", "1") else capi.VARIANT_V2_SUM
         cfg.device = int(device)
         cfg.flags = ((capi.FLAG_DENSE_ONLY if dense_only else 0) | (capi.FLAG_DROP_SEQ if drop_seq else 0) |
-                     (capi.FLAG_TIMING if timing else 0) | (capi.FLAG_TIMING_FINE if timing_fine else 0))
+                     (capi.FLAG_TIMING if timing else 0) | (capi.FLAG_TIMING_FINE if timing_fine else 0) |
+                     (capi.FLAG_ONE_SHOT if one_shot else 0))
         cfg.stream = C.c_void_p(stream) if stream else None
         cfg.cand_per_window = int(cand_per_window)
         cfg.host_threads = int(threads)
@@ -394,6 +396,48 @@ class MxEngine:
         self._check(self._lib.mxg_overlap_cuts(self._h, int(assembly), int(k), int(w), nodes.ctypes.data, pf.ctypes.data, len(pf) - 1,
                                                sa.ctypes.data, ea.ctypes.data, cf.ctypes.data))
         return {"start_adjust": sa, "end_adjust": ea, "cut_found": cf.astype(bool)}
+
+    SCAFFOLD_NODE = np.dtype([("record", "<u4"), ("start", "<u4"), ("end", "<u4"), ("gap_size", "<u4"), ("start_adjust", "<u4"),
+                              ("end_adjust", "<u4"), ("reverse", "u1"), ("pad", "u1", (3,))])
+
+    def write_scaffolds(self, assembly, rows, path_first, overlap_gap=None, fold_case=False, assigned=None, unassigned=None, bed=None):
+        """mxg_write_scaffolds: rows = array of SCAFFOLD_NODE (or rows (record, start, end, gap_size, start_adjust, end_adjust,
+        reverse)), path_first = n_paths + 1 offsets; overlap_gap=None: the overlap stage is off (the adjustments are not read).
+        Writes the scaffold FASTA `assigned` and, when named, the unassigned FASTA and BED -> dict(lead_strip u32[n_paths],
+        tail_strip u32[n_paths]: N/n stripped from the scaffolds' ends, n_unassigned: records in the unassigned FASTA)"""
+        if assigned is None:
+            raise ValueError("write_scaffolds: assigned= names the scaffold FASTA to write")
+        nodes = rows
+        if not (isinstance(nodes, np.ndarray) and nodes.dtype == self.SCAFFOLD_NODE):
+            arr = np.asarray(rows, dtype=np.int64).reshape(-1, 7)
+            nodes = np.zeros(len(arr), dtype=self.SCAFFOLD_NODE)
+            for j, name in enumerate(("record", "start", "end", "gap_size", "start_adjust", "end_adjust", "reverse")):
+                nodes[name] = arr[:, j]
+        nodes = np.ascontiguousarray(nodes)
+        pf = np.ascontiguousarray(path_first, dtype=np.uint64)
+        if len(pf) < 1 or int(pf[0]) != 0 or int(pf[-1]) != len(nodes):
+            raise ValueError("write_scaffolds: path_first needs n_paths + 1 offsets, the first one 0 and the last one len(nodes)")
+        n_paths = len(pf) - 1
+        lead, tail = np.zeros(n_paths, dtype=np.uint32), np.zeros(n_paths, dtype=np.uint32)
+        n_un = C.c_uint64(0)
+        enc = lambda p: None if p is None else os.fsencode(str(p))  # noqa: E731
+        self._check(self._lib.mxg_write_scaffolds(self._h, int(assembly), nodes.ctypes.data, pf.ctypes.data, n_paths,
+                                                  -1 if overlap_gap is None else int(overlap_gap),
+                                                  capi.SCAF_FOLD_CASE if fold_case else 0, enc(assigned), enc(unassigned), enc(bed),
+                                                  lead.ctypes.data, tail.ctypes.data, C.byref(n_un)))
+        return {"lead_strip": lead, "tail_strip": tail, "n_unassigned": int(n_un.value)}
+
+    def scaffold_strips(self):
+        """mxg_scaffold_strips: (lead u32[n], tail u32[n]) = N/n stripped from either end of every unassigned interval (the BED's
+        lines, in order) by the last write_scaffolds"""
+        lead, tail, n = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.c_uint64()
+        self._check(self._lib.mxg_scaffold_strips(self._h, C.byref(lead), C.byref(tail), C.byref(n)))
+        return _np(lead, n.value, np.uint32), _np(tail, n.value, np.uint32)
+
+    def write_outputs(self, dot_path, tsv_paths, with_pos=True, with_strand=False, with_seq=True):
+        """mxg_write_outputs: the .mx.dot and the TSVs of the assemblies (None: none for that assembly) in one call"""
+        arr = (C.c_char_p * max(len(tsv_paths), 1))(*[None if p is None else os.fsencode(str(p)) for p in tsv_paths])
+        self._check(self._lib.mxg_write_outputs(self._h, os.fsencode(str(dot_path)), arr, int(with_pos), int(with_strand), int(with_seq)))
 
     def mx_extremes(self, a):
         """per record of assembly a: (min, max) position over its graph vertices; None for records without one"""

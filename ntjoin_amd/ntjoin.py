@@ -12,6 +12,7 @@ WRITTEN (checkpoint files, ntJoin:202 `.SECONDARY`) rather than read.
 """
 import datetime
 import math
+import re
 import sys
 
 import numpy as np
@@ -319,6 +320,121 @@ class Ntjoin:
             out.append(list(zip(sa[at:at + n], ea[at:at + n])))
             at += n
         return out
+
+    @staticmethod
+    def _path_coords(ori, start, end, start_adjust, end_adjust):
+        "get_adjusted_start / get_adjusted_end of the reference's PathNode (bin/path_node.py:41-61)"
+        length = end - start
+        end_adj = length if end_adjust == 0 else end_adjust
+        if ori == "+":
+            return start + start_adjust, end - (length - end_adj)
+        return start + (length - end_adj), end - start_adjust
+
+    @staticmethod
+    def _write_agp(fh, scaffold_id, path_str):
+        "write_agp (:346-376): one W line per contig component and one N line per gap of the path string"
+        at, part = 1, 1
+        for comp in path_str.split():
+            ctg = re.search(r"(\S+)([\+\-])\:(\d+)-(\d+)", comp)
+            gap = re.search(r"(\d+)N", comp)
+            if ctg:
+                c_start, c_end = int(ctg.group(3)) + 1, int(ctg.group(4))
+                n = c_end - c_start + 1
+                cols = (scaffold_id, at, at + n - 1, part, "W", ctg.group(1), c_start, c_end, ctg.group(2))
+            elif gap:
+                n = int(gap.group(1))
+                cols = (scaffold_id, at, at + n - 1, part, "N", n, "scaffold", "yes", "align_genus")
+            else:
+                raise ValueError("Path string is not formatted correctly: " + path_str)
+            fh.write("\t".join(str(c) for c in cols) + "\n")
+            at += n
+            part += 1
+
+    def _write_agp_unassigned(self, agp_fh, bed):
+        """write_agp_unassigned (:379-404) for every unassigned interval that is not N throughout (= every record of the unassigned
+        FASTA): `id:start-end  1  len  1  W  id  start  end  +`, the coordinates moved by the N/n stripped from either end.  The
+        intervals are the BED's lines; the strip counts are the library's, kept from the call that wrote the files."""
+        leads, tails = (x.tolist() for x in self._engine.scaffold_strips())
+        with open(bed, encoding="utf-8") as fh:
+            for line, lead, tail in zip(fh, leads, tails):
+                ctg, lo, hi = line.rstrip("\n").split("\t")
+                n = int(hi) - int(lo) - lead - tail
+                if n <= 0:
+                    continue
+                start = int(lo) + 1 + lead
+                agp_fh.write("\t".join(str(c) for c in (f"{ctg}:{lo}-{hi}", 1, n, 1, "W", ctg, start, start + n - 1, "+")) + "\n")
+
+    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20):
+        """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
+        trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
+        than two nodes are dropped (:585-594), the last kept node's gap is zeroed (check_terminal_node_gap_zero :441-448), and the
+        library cuts the sequences from the text it holds (mxg_write_scaffolds): the target FASTA is not read again and no
+        bedtools runs.  Written: <fasta>.k<k>.w<w>.n<n>.assigned.scaffolds.fa, ...unassigned.scaffolds.fa,
+        <p>.<target tsv>.unassigned.bed, <p>.path and, with agp=True, <p>.agp.  Returns the file names by kind."""
+        eng, tgt = self._engine, len(self._order) - 1
+        if tgt < 0:
+            raise ValueError("print_scaffolds: no target assembly has been loaded")
+        target = self._order[tgt]
+        if target not in self._fasta:
+            raise ValueError("print_scaffolds: the target was loaded from a minimizer TSV, which holds no sequence; the scaffolds are "
+                             "cut from the FASTA's text, so the target must come from FASTA (Ntjoin(fasta={target: path}))")
+        match = re.search(r"^(\S+)(.k\d+.w\d+)\.tsv", target)
+        if not match:
+            raise ValueError(f"print_scaffolds: the target {target!r} is not named <fasta>.k<k>.w<w>.tsv")
+        assembly_fa, params = match.group(1), match.group(2)
+        if adjust is not None and len(adjust) != len(paths):
+            raise ValueError("print_scaffolds: adjust needs one list per path, as trim_overlaps(paths) returns")
+        index = {rid: r for r, rid in enumerate(eng.record_ids(tgt, eng.n_records(tgt)))}
+        rows, first, kept = [], [0], []
+        for p, path in enumerate(paths):
+            nodes = [list(nd) for nd in path if nd[1] != "?"]
+            if len(nodes) < 2:
+                continue
+            cuts = list(adjust[p]) if adjust is not None else [(0, 0)] * len(nodes)
+            if len(cuts) != len(nodes):
+                raise ValueError(f"print_scaffolds: path {p}: {len(cuts)} adjustments for {len(nodes)} oriented nodes")
+            nodes[-1][7] = 0
+            for i, (nd, (sa, ea)) in enumerate(zip(nodes, cuts)):
+                if nd[0] not in index:
+                    raise ValueError(f"print_scaffolds: path {p} node {i}: the target holds no contig {nd[0]!r}")
+                rows.append((index[nd[0]], nd[2], nd[3], nd[7], sa, ea, nd[1] == "-"))
+            first.append(len(rows))
+            kept.append((nodes, cuts))
+        prefix = assembly_fa + params + ".n" + str(n)
+        files = {"assigned": prefix + ".assigned.scaffolds.fa", "unassigned": prefix + ".unassigned.scaffolds.fa",
+                 "bed": self.args.p + "." + target + ".unassigned.bed", "path": self.args.p + ".path"}
+        print(datetime.datetime.today(), ": Printing output scaffolds", file=sys.stdout)
+        res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
+                                  assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"])
+        agp_fh = None
+        if agp:
+            files["agp"] = self.args.p + ".agp"
+            agp_fh = open(files["agp"], "w", encoding="utf-8")  # pylint: disable=consider-using-with
+        try:
+            with open(files["path"], "w", encoding="utf-8") as fh:
+                fh.write(assembly_fa + "\n")
+                for ct, ((nodes, cuts), lead, tail) in enumerate(zip(kept, res["lead_strip"].tolist(), res["tail_strip"].tolist())):
+                    coords = [[nd[1], nd[2], nd[3]] for nd in nodes]
+                    for c, strip, left in ((coords[0], lead, True), (coords[-1], tail, False)):  # join_sequences :413-436
+                        if strip:
+                            if (c[0] == "+") == left:
+                                c[1] += strip
+                            else:
+                                c[2] -= strip
+                    parts = []
+                    for nd, (ori, start, end), (sa, ea) in zip(nodes, coords, cuts):
+                        a_start, a_end = self._path_coords(ori, start, end, sa, ea)
+                        parts.append(f"{nd[0]}{ori}:{a_start}-{a_end} {nd[7]}N")
+                    path_str = re.sub(r"\s+\d+N$", "", " ".join(parts))
+                    fh.write(f"ntJoin{ct}\t{path_str}\n")
+                    if agp_fh:
+                        self._write_agp(agp_fh, f"ntJoin{ct}", path_str)
+            if agp_fh:
+                self._write_agp_unassigned(agp_fh, files["bed"])
+        finally:
+            if agp_fh:
+                agp_fh.close()
+        return files
 
     def print_graph(self, graph, out_prefix=None):
         "Prints the minimizer graph in dot format"
