@@ -378,6 +378,59 @@ int mxg_mk_stats(mxg_handle *h, const uint32_t *values, const uint64_t *run_firs
                  int64_t *s, uint64_t *tie_term);
 int mxg_mx_extremes(mxg_handle *h, int assembly, const uint32_t **min_pos, const uint32_t **max_pos, uint64_t *n_records);
 
+/* ---- the path stage in one call: nodes, orientations and gap sizes of all paths -------------------------------------
+   What format_path (bin/ntjoin_assemble.py:175-218) builds per path with determine_orientation (:30-50), calc_start_coord /
+   calc_end_coord (:52-65) and calculate_gap_size (:67-113), for every path of the last mxg_find_paths, in its order, from
+   what the graph and path stages left on the device.  The runs are those of mxg_path_segments (whose host copies, and those
+   of mxg_mx_extremes, this call refreshes for `assembly` as well); a run of one vertex has no orientation; longer runs are
+   '+' / '-' when strictly increasing / decreasing, otherwise by the m rule in fp64 as the reference forms it
+   (inc / double(n - 1) * 100 >= m: '+', else 100 - that >= m: '-') or, with mkt, by the Mann-Kendall decision below on the
+   statistics of mxg_path_segments_mk (decided on the host with libm, one byte per run goes back to the device).
+   Nodes are the runs with an orientation, in path order:
+       start = min pos == the record's smallest vertex position ? 0 : min pos
+       end   = max pos == the record's largest vertex position ? record length : max pos + k        (k: the handle's)
+   Gap between node i and node i + 1 of one path, u = last vertex of node i's run, v = first vertex of node i + 1's run (the
+   runs without orientation between them make the stretch u..v longer than one edge): common = AND of the support masks of
+   the path's edges from u to v; common == 0: gap = raw = g; otherwise
+       mean = (sum over the assemblies of common of |pos_b[v] - pos_b[u]|) / count - k         (integer division)
+       a = node i '+' ? end_i - pos[u] - k : pos[u] - start_i,   b = node i+1 '+' ? pos[v] - start_i+1 : end_i+1 - pos[v] - k
+       raw = mean - a - b,   gap = max(raw, g), then min(gap, G) when G > 0.
+   record_length[r] replaces the lengths the handle holds (NULL: the handle's own).  The arrays of the view are host copies
+   owned by the handle, valid until the next call of this function or mxg_destroy.
+   MXG_EINVAL: no graph or no paths, assembly out of range, struct_size too small, record_length == NULL for an assembly
+   that holds no lengths (TSV, side-car or minimizer input), or some a < 0 or b < 0 (the reference's "Gap distance estimation
+   less than 0": lengths shorter than the minimizers imply).  In that last case the kernels have finished: the message names
+   the first such path and node as "path <p> node <i>", the view is filled (gap_size = raw_gap_size = 0 at every such
+   junction) and the handle stays usable.  No other error writes to the view: a caller that zeroes it first tells the two apart by
+   node_first != NULL.
+   mxg_mk_orientation: '+', '-' or '?' for a run of n values with Mann-Kendall score s and the given tie term:
+   pymannkendall.original_test's z and p as determine_orientation reads them (:37-40), evaluated on the host. */
+typedef struct mxg_format_params {
+    uint32_t struct_size;
+    int64_t  g;        /* minimum gap size (ntJoin -g) */
+    int64_t  G;        /* maximum gap size, 0 = none (-G) */
+    double   m;        /* percentage rule (-m) */
+    uint32_t mkt;      /* != 0: --mkt */
+} mxg_format_params;
+
+typedef struct mxg_path_nodes_view {
+    uint64_t n_paths, n_nodes;
+    const uint64_t *node_first;      /* [n_paths + 1]; a path whose runs are all '?' has an empty range */
+    const uint32_t *record, *start, *end, *contig_size;
+    const uint8_t  *reverse;         /* 0 = '+', 1 = '-' */
+    const uint32_t *first_vertex, *terminal_vertex;  /* vertex indices: first_mx / terminal_mx */
+    const int64_t  *gap_size, *raw_gap_size;         /* to the NEXT node; 0, 0 on a path's last node */
+    const uint32_t *segment;         /* index of the run in mxg_segments_view order */
+} mxg_path_nodes_view;
+
+int mxg_format_paths(mxg_handle *h, int assembly, const mxg_format_params *p,
+                     const uint32_t *record_length /* NULL: the handle's own */, mxg_path_nodes_view *out);
+char mxg_mk_orientation(uint64_t n, int64_t s, uint64_t tie_term);   /* '+', '-' or '?' */
+/* The minimizer hashes of n graph vertices (mxg_graph_view.vertex_hash[vertices[i]] -> out[i]): what names first_mx / terminal_mx
+   of the nodes above (the reference's vertex names, bin/ntjoin_assemble.py:205-206), gathered on the device, so that the graph's
+   host mirror (mxg_get_graph: every array of the graph) is not made for them.  MXG_EINVAL: no graph, a vertex out of range. */
+int mxg_vertex_hashes(mxg_handle *h, const uint32_t *vertices, uint64_t n, uint64_t *out);
+
 /* ---- next row (f5): the overlap stage's cut points -------------------------------------------------------------------
    What the reference's default run (overlap=True, ntJoin:39) computes between the paths and the scaffold sequence: the
    joined segments are written to <prefix>.segments.fa with their middles hard-masked (print_scaffolds,

@@ -21,7 +21,7 @@ SYMBOLS = [
     "mxg_record_id", "mxg_record_length", "mxg_num_records", "mxg_assembly_weight",
     "mxg_sketch", "mxg_sketch_graph", "mxg_get_sketch", "mxg_get_sketch_device", "mxg_compute_strands", "mxg_set_sketch_device",
     "mxg_pack_sketch_device", "mxg_set_sketch_gathered", "mxg_set_sketch_gathered_strided", "mxg_write_tsv",
-    "mxg_build_graph", "mxg_get_mx_flags", "mxg_get_graph", "mxg_find_paths", "mxg_path_segments", "mxg_path_segments_mk", "mxg_mk_stats", "mxg_overlap_cuts", "mxg_write_scaffolds", "mxg_scaffold_strips", "mxg_mx_extremes", "mxg_dg_owner_counts", "mxg_dg_pack_items", "mxg_dg_set_items", "mxg_dg_vertices", "mxg_dg_item_results", "mxg_dg_msg_counts", "mxg_dg_pack_msgs", "mxg_dg_edges", "mxg_dg_pack_slots", "mxg_dg_owner_slots", "mxg_dg_slot_results", "mxg_dg_pack_msg_slots", "mxg_dg_edges_slots", "mxg_write_dot", "mxg_write_outputs", "mxg_dot_part_format", "mxg_dot_part_write",
+    "mxg_build_graph", "mxg_get_mx_flags", "mxg_get_graph", "mxg_find_paths", "mxg_path_segments", "mxg_path_segments_mk", "mxg_mk_stats", "mxg_format_paths", "mxg_mk_orientation", "mxg_vertex_hashes", "mxg_overlap_cuts", "mxg_write_scaffolds", "mxg_scaffold_strips", "mxg_mx_extremes", "mxg_dg_owner_counts", "mxg_dg_pack_items", "mxg_dg_set_items", "mxg_dg_vertices", "mxg_dg_item_results", "mxg_dg_msg_counts", "mxg_dg_pack_msgs", "mxg_dg_edges", "mxg_dg_pack_slots", "mxg_dg_owner_slots", "mxg_dg_slot_results", "mxg_dg_pack_msg_slots", "mxg_dg_edges_slots", "mxg_write_dot", "mxg_write_outputs", "mxg_dot_part_format", "mxg_dot_part_write",
     "mxg_py_repr_double", "mxg_py_repr_str", "mxg_get_stats", "mxg_reset_timers", "mxg_knobs",
     "mxg_synth_fill_packed_device", "mxg_synth_fill_packed_host", "mxg_synth_write_fasta",
     "mxg_plan_split", "mxg_add_assembly_packed_device_pieces", "mxg_dg_last_shared", "mxg_dg_set_ghosts",
@@ -61,6 +61,18 @@ class PathsView(C.Structure):
 class SegmentsView(C.Structure):
     _fields_ = [("n_segments", C.c_uint64), ("seg_path", C.POINTER(C.c_uint32)), ("seg_record", C.POINTER(C.c_uint32)),
                 ("seg_first", C.POINTER(C.c_uint32)), ("seg_stat", C.POINTER(C.c_uint32))]
+
+
+class FormatParams(C.Structure):  # mxg_format_params: 40 bytes (api.cpp asserts the same)
+    _fields_ = [("struct_size", C.c_uint32), ("g", C.c_int64), ("G", C.c_int64), ("m", C.c_double), ("mkt", C.c_uint32)]
+
+
+class PathNodesView(C.Structure):  # mxg_path_nodes_view: 104 bytes (api.cpp asserts the same)
+    _fields_ = [("n_paths", C.c_uint64), ("n_nodes", C.c_uint64), ("node_first", C.POINTER(C.c_uint64)),
+                ("record", C.POINTER(C.c_uint32)), ("start", C.POINTER(C.c_uint32)), ("end", C.POINTER(C.c_uint32)),
+                ("contig_size", C.POINTER(C.c_uint32)), ("reverse", C.POINTER(C.c_uint8)),
+                ("first_vertex", C.POINTER(C.c_uint32)), ("terminal_vertex", C.POINTER(C.c_uint32)),
+                ("gap_size", C.POINTER(C.c_int64)), ("raw_gap_size", C.POINTER(C.c_int64)), ("segment", C.POINTER(C.c_uint32))]
 
 
 class OverlapNode(C.Structure):
@@ -181,6 +193,10 @@ def load():
     L.mxg_path_segments.argtypes = [vp, i32, C.POINTER(SegmentsView)]
     L.mxg_path_segments_mk.argtypes = [vp, i32, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(u64)]
     L.mxg_mk_stats.argtypes = [vp, vp, vp, u64, vp, vp]
+    L.mxg_format_paths.argtypes = [vp, i32, C.POINTER(FormatParams), vp, C.POINTER(PathNodesView)]
+    L.mxg_vertex_hashes.argtypes = [vp, vp, u64, vp]
+    L.mxg_mk_orientation.argtypes = [u64, C.c_int64, u64]
+    L.mxg_mk_orientation.restype = C.c_char
     L.mxg_overlap_cuts.argtypes = [vp, i32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp]
     L.mxg_write_scaffolds.argtypes = [vp, i32, vp, vp, u64, i32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp]
     L.mxg_scaffold_strips.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64)]

@@ -1,6 +1,8 @@
 // api.cpp -- extern "C" entry points of libntjoin_mx.so (declared in include/ntjoin_mx.h).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <cstddef>
 #include <new>
 #include <thread>
 
@@ -870,6 +872,109 @@ int mxg_path_segments_mk(mxg_handle *h, int assembly, const int64_t **s, const u
     *tie_term = h->segs.mk_tie.data();
     *n_segments = h->segs.mk_s.size();
     return MXG_OK;
+}
+
+static_assert(sizeof(mxg_format_params) == 40, "mxg_format_params: ntjoin_amd/capi.py FormatParams mirrors this layout");
+static_assert(sizeof(mxg_path_nodes_view) == 104, "mxg_path_nodes_view: ntjoin_amd/capi.py PathNodesView mirrors this layout");
+
+int mxg_format_paths(mxg_handle *h, int assembly, const mxg_format_params *p, const uint32_t *record_length, mxg_path_nodes_view *out)
+{
+    if (!h) return MXG_EINVAL;
+    if (!p || !out) return set_err(h, MXG_EINVAL, "mxg_format_paths: null argument");
+    if (p->struct_size < offsetof(mxg_format_params, mkt) + sizeof(uint32_t))
+        return set_err(h, MXG_EINVAL, "mxg_format_paths: struct_size %u is too small", p->struct_size);
+    if (!h->graph.valid || !h->paths.valid) return set_err(h, MXG_EINVAL, "mxg_format_paths: call mxg_find_paths first");
+    if (assembly < 0 || (uint32_t)assembly >= h->graph.n_asm || (size_t)assembly >= h->asms.size())
+        return set_err(h, MXG_EINVAL, "mxg_format_paths: assembly index %d out of range", assembly);
+    int rc = MXG_OK;
+    try {
+        const Assembly *a = h->asms[assembly];
+        std::vector<uint32_t> own;
+        if (!record_length) {
+            bool any = false;
+            own.reserve(a->recs.size());
+            for (const Record &r : a->recs) {
+                if (r.len > 0xFFFFFFFFull)
+                    return set_err(h, MXG_ELIMIT, "mxg_format_paths: record %s is longer than 2^32 - 1 bases", r.id.c_str());
+                any = any || r.len != 0;
+                own.push_back((uint32_t)r.len);
+            }
+            if (!any && !own.empty())
+                return set_err(h, MXG_EINVAL, "mxg_format_paths: assembly %d holds no record lengths (minimizer input); pass record_length",
+                               assembly);
+            record_length = own.data();
+        }
+        bool overhang = false;  // a negative overhang: MXG_EINVAL, but the view is filled all the same
+        rc = format_paths(h, (uint32_t)assembly, *p, record_length, &overhang);
+        if (rc != MXG_OK && !overhang) return rc;
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_format_paths");
+    }
+    const PathNodes &N = h->nodes;
+    out->n_paths = N.node_first.size() - 1;
+    out->n_nodes = N.n_nodes;
+    out->node_first = N.node_first.data();
+    out->record = N.record;
+    out->start = N.start;
+    out->end = N.end;
+    out->contig_size = N.contig_size;
+    out->reverse = N.reverse;
+    out->first_vertex = N.first_vertex;
+    out->terminal_vertex = N.terminal_vertex;
+    out->gap_size = N.gap;
+    out->raw_gap_size = N.raw;
+    out->segment = N.segment;
+    return rc;
+}
+
+int mxg_vertex_hashes(mxg_handle *h, const uint32_t *vertices, uint64_t n, uint64_t *out)
+{
+    if (!h) return MXG_EINVAL;
+    if (n && (!vertices || !out)) return set_err(h, MXG_EINVAL, "mxg_vertex_hashes: null argument");
+    try {
+        return vertex_hashes(h, vertices, n, out);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_vertex_hashes");
+    }
+}
+
+// the quotient x / 18 of an exact integer, rounded once to the nearest double (ties to even), as CPython's int / int is
+static double div18_exact(unsigned __int128 x)
+{
+    if (x < ((unsigned __int128)1 << 53)) return (double)(uint64_t)x / 18.0;  // exact operand, one IEEE rounding
+    const int shift_in = 24;  // x < 2^100 (n < 2^32): x << 24 fits, and the quotient has more than 55 bits
+    const unsigned __int128 xs = x << shift_in, q = xs / 18;
+    const bool sticky = xs % 18 != 0;
+    int nb = 0;
+    for (unsigned __int128 t = q; t; t >>= 1) ++nb;
+    const int sh = nb - 53;
+    const unsigned __int128 half = (unsigned __int128)1 << (sh - 1), rem = q & ((half << 1) - 1);
+    uint64_t top = (uint64_t)(q >> sh);
+    if (rem > half || (rem == half && (sticky || (top & 1)))) ++top;
+    return std::ldexp((double)top, sh - shift_in);
+}
+
+#pragma STDC FP_CONTRACT OFF
+char mxg_mk_orientation(uint64_t n, int64_t s, uint64_t tie_term)
+{
+    // pymannkendall.original_test as determine_orientation reads it (reference bin/ntjoin_assemble.py:37-40): variance, z, the
+    // two-sided p on scipy's ndtr (erf below 1/sqrt 2, erfc above), h = |z| > ppf(0.975); '+' / '-' when h and p <= 0.05
+    if (n >= (1ull << 32)) return '?';
+    const unsigned __int128 full = (unsigned __int128)n * (n ? n - 1 : 0) * (2 * (unsigned __int128)n + 5);
+    if (s == 0 || tie_term >= full) return '?';  // z = 0: p = 1 (no variance left: every value equal, s is 0 as well)
+    const double var = div18_exact(full - tie_term);
+    const double z = (s > 0 ? (double)(s - 1) : (double)(s + 1)) / std::sqrt(var);
+    const double az = std::fabs(z), x = az * 0.7071067811865476;
+    double cdf;
+    if (x < 0.7071067811865476) {
+        cdf = 0.5 + 0.5 * std::erf(x);
+    } else {
+        const double y = 0.5 * std::erfc(x);
+        cdf = x > 0 ? 1.0 - y : y;
+    }
+    const double pv = 2 * (1 - cdf);
+    if (az > 1.959963984540054 && pv <= 0.05) return z > 0 ? '+' : '-';
+    return '?';
 }
 
 int mxg_mk_stats(mxg_handle *h, const uint32_t *values, const uint64_t *run_first, uint64_t n_runs, int64_t *s,

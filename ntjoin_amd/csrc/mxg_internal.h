@@ -196,6 +196,16 @@ struct Segments {  // results of mxg_path_segments / mxg_mx_extremes / mxg_path_
     std::vector<uint32_t> ext_min, ext_max;     // per record of the assembly last asked for
 };
 
+struct PathNodes {  // result of mxg_format_paths (host copies)
+    std::vector<uint64_t> node_first;  // [n_paths + 1]
+    std::vector<uint64_t> block;       // the node arrays as the device holds them (one copy); the pointers below look into it
+    size_t n_nodes = 0;
+    const uint32_t *record = nullptr, *start = nullptr, *end = nullptr, *contig_size = nullptr, *first_vertex = nullptr,
+                   *terminal_vertex = nullptr, *segment = nullptr;
+    const uint8_t *reverse = nullptr;
+    const int64_t *gap = nullptr, *raw = nullptr;
+};
+
 struct Timers {
     double ms_hash = 0, ms_resolve = 0, ms_graph = 0;
     // MXG_FLAG_TIMING_FINE: one span per kernel (ms_resolve stays the sum of the three behind the hash kernel)
@@ -252,12 +262,13 @@ struct mxg_handle {
     mxg::DevBuf dg_ghost;           // ... {record, global vertex id} of the shared minimizer before this rank's first, per assembly
     bool dg_ghost_on = false;
     mxg::Paths paths;
-    mxg::DevBuf pbuf[48];  // scratch of paths.hip
+    mxg::DevBuf pbuf[56];  // scratch of paths.hip
     mxg::DevBuf mkbuf[8];  // scratch of mk.hip
     mxg::DevBuf ovbuf[16];  // scratch of overlap.hip
     mxg::DevBuf scbuf[8];   // scratch of scaffold.hip
     std::vector<uint32_t> scaf_lead, scaf_tail;  // N/n stripped from either end of every unassigned interval by the last mxg_write_scaffolds
     mxg::Segments segs;
+    mxg::PathNodes nodes;
     mxg::Timers tm;
     mxg::HashTab tab{};
     mxg::DevBuf d_init_tab;  // byte table of the direct hash formula (256 x 16 B), built by the first sketch
@@ -482,6 +493,11 @@ int dg_edges_slots(mxg_handle *h, const void *d_recv, uint32_t world, uint32_t M
 int path_segments(mxg_handle *h, uint32_t assembly);
 int mx_extremes(mxg_handle *h, uint32_t assembly);
 int path_segments_mk(mxg_handle *h, uint32_t assembly);
+// the path stage in one call (mxg_format_paths): fills h->nodes; record_length = one entry per record of the assembly;
+// *overhang = the error returned is the negative overhang (h->nodes is complete all the same)
+int format_paths(mxg_handle *h, uint32_t assembly, const mxg_format_params &p, const uint32_t *record_length, bool *overhang);
+// the minimizer hashes of the given graph vertices, gathered on the device (mxg_vertex_hashes)
+int vertex_hashes(mxg_handle *h, const uint32_t *vertices, uint64_t n, uint64_t *out);
 // mk.hip: Mann-Kendall S and tie term of the runs [d_first[r], d_first[r + 1]) of d_x (device arrays, d_first with n_runs + 1
 // entries; d_x is sorted in place run by run), len[r] = the runs' lengths on the host
 int mk_runs(mxg_handle *h, uint32_t *d_x, const uint32_t *d_first, uint32_t n_runs, uint32_t n_total,

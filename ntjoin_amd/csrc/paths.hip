@@ -21,11 +21,12 @@
 namespace mxg {
 
 static constexpr uint32_t NIL = 0xFFFFFFFFu;
-// scratch buffers of this file (mxg_handle::pbuf); PV / PF / PC keep the paths on the device after find_paths
+// scratch buffers of this file (mxg_handle::pbuf); PV / PF / PC keep the paths on the device after find_paths, NB / NBE the
+// two neighbour slots of every vertex with their edge (format_paths looks the path's edges up there)
 enum { ALIVE, COMP, SUB, DEG, NONLIN, FLAG, CNTV, CNTE, CNTD1, MAXDEG, FILL, NB, NBE, KEY0, KEY1, KEY2, SUCC0, CNT0, END0,
        SUCC1, CNT1, END1, SIZE, ISSRC, FIRST, RANK, BSUM, TOTAL, PV, PF, PC, SG_FLAG, SG_EXCL, SG_FIRST, SG_REC, SG_PATH,
-       SG_STAT, XT_MIN, XT_MAX, SG_MKX, PBUF_COUNT };
-static_assert(PBUF_COUNT <= 48, "mxg_handle::pbuf too small");
+       SG_STAT, XT_MIN, XT_MAX, SG_MKX, FM_ORI, FM_KEEP, FM_KEXCL, FM_NODES, FM_NFIRST, FM_LEN, FM_ERR, VH_IDX, VH_OUT, PBUF_COUNT };
+static_assert(PBUF_COUNT <= 56, "mxg_handle::pbuf too small");
 
 __device__ __forceinline__ uint32_t find_root(uint32_t *parent, uint32_t v)
 {
@@ -613,12 +614,10 @@ __global__ __launch_bounds__(256) void ks_stats(const uint32_t *__restrict__ seg
     }
 }
 
-int mx_extremes(mxg_handle *h, uint32_t a)
+// phase of mx_extremes: the kernel and the copies to S.ext_min / S.ext_max are on the stream when this returns (no sync)
+static int extremes_enqueue(mxg_handle *h, uint32_t a)
 {
     Graph &g = h->graph;
-    if (!g.valid) return set_err(h, MXG_EINVAL, "mxg_mx_extremes: call mxg_build_graph first");
-    if (a >= g.n_asm) return set_err(h, MXG_EINVAL, "assembly index %u out of range", a);
-    MXG_HIP(h, hipSetDevice(h->device));
     const size_t nr = h->asms[a]->recs.size();
     Segments &S = h->segs;
     S.ext_min.assign(nr, 0xFFFFFFFFu);
@@ -636,25 +635,33 @@ int mx_extremes(mxg_handle *h, uint32_t a)
     MXG_HIP(h, hipGetLastError());
     MXG_HIP(h, hipMemcpyAsync(S.ext_min.data(), B[XT_MIN].p, nr * 4, hipMemcpyDeviceToHost, h->stream));
     MXG_HIP(h, hipMemcpyAsync(S.ext_max.data(), B[XT_MAX].p, nr * 4, hipMemcpyDeviceToHost, h->stream));
+    return MXG_OK;
+}
+
+int mx_extremes(mxg_handle *h, uint32_t a)
+{
+    Graph &g = h->graph;
+    if (!g.valid) return set_err(h, MXG_EINVAL, "mxg_mx_extremes: call mxg_build_graph first");
+    if (a >= g.n_asm) return set_err(h, MXG_EINVAL, "assembly index %u out of range", a);
+    MXG_HIP(h, hipSetDevice(h->device));
+    int rc = extremes_enqueue(h, a);
+    if (rc != MXG_OK) return rc;
     MXG_HIP(h, hipStreamSynchronize(h->stream));
     return MXG_OK;
 }
 
-int path_segments(mxg_handle *h, uint32_t a)
+// phases of path_segments.  segments_device: the runs of assembly a on the device (SG_*), their number on the host (the one
+// sync of this phase); S is cleared.  segments_copy: the copies to S are on the stream when it returns (no sync).
+static int segments_device(mxg_handle *h, uint32_t a, uint32_t *n_seg_out)
 {
     Graph &g = h->graph;
     const Paths &P = h->paths;
-    if (!g.valid || !P.valid) return set_err(h, MXG_EINVAL, "mxg_path_segments: call mxg_find_paths first");
-    if (a >= g.n_asm) return set_err(h, MXG_EINVAL, "assembly index %u out of range", a);
-    MXG_HIP(h, hipSetDevice(h->device));
     Segments &S = h->segs;
     S.path.clear(); S.record.clear(); S.first.clear(); S.stat.clear(); S.mk_s.clear(); S.mk_tie.clear();
     S.assembly = -1;
+    *n_seg_out = 0;
     const uint32_t n = (uint32_t)P.vertex.size(), n_paths = (uint32_t)P.component.size();
-    if (n == 0) {
-        S.assembly = (int)a;
-        return MXG_OK;
-    }
+    if (n == 0) return MXG_OK;
     DevBuf *B = h->pbuf;
     const uint32_t *pv = B[PV].as<uint32_t>();
     const uint64_t *pf = B[PF].as<uint64_t>();
@@ -682,13 +689,36 @@ int path_segments(mxg_handle *h, uint32_t a)
     hipLaunchKernelGGL(ks_stats, dim3((n_seg + 3) / 4), b, 0, h->stream, B[SG_FIRST].as<uint32_t>(), n_seg, n, pv, vpos,
                        B[SG_STAT].as<uint32_t>());
     MXG_HIP(h, hipGetLastError());
+    *n_seg_out = n_seg;
+    return MXG_OK;
+}
+
+static int segments_copy(mxg_handle *h, uint32_t n_seg)
+{
+    Segments &S = h->segs;
+    DevBuf *B = h->pbuf;
     S.path.resize(n_seg); S.record.resize(n_seg); S.first.resize(n_seg); S.stat.resize((size_t)n_seg * 5);
+    if (n_seg == 0) return MXG_OK;
     MXG_HIP(h, hipMemcpyAsync(S.path.data(), B[SG_PATH].p, (size_t)n_seg * 4, hipMemcpyDeviceToHost, h->stream));
     MXG_HIP(h, hipMemcpyAsync(S.record.data(), B[SG_REC].p, (size_t)n_seg * 4, hipMemcpyDeviceToHost, h->stream));
     MXG_HIP(h, hipMemcpyAsync(S.first.data(), B[SG_FIRST].p, (size_t)n_seg * 4, hipMemcpyDeviceToHost, h->stream));
     MXG_HIP(h, hipMemcpyAsync(S.stat.data(), B[SG_STAT].p, (size_t)n_seg * 20, hipMemcpyDeviceToHost, h->stream));
+    return MXG_OK;
+}
+
+int path_segments(mxg_handle *h, uint32_t a)
+{
+    Graph &g = h->graph;
+    const Paths &P = h->paths;
+    if (!g.valid || !P.valid) return set_err(h, MXG_EINVAL, "mxg_path_segments: call mxg_find_paths first");
+    if (a >= g.n_asm) return set_err(h, MXG_EINVAL, "assembly index %u out of range", a);
+    MXG_HIP(h, hipSetDevice(h->device));
+    uint32_t n_seg = 0;
+    int rc = segments_device(h, a, &n_seg);
+    if (rc == MXG_OK) rc = segments_copy(h, n_seg);
+    if (rc != MXG_OK) return rc;
     MXG_HIP(h, hipStreamSynchronize(h->stream));
-    S.assembly = (int)a;
+    h->segs.assembly = (int)a;
     return MXG_OK;
 }
 
@@ -729,6 +759,308 @@ int path_segments_mk(mxg_handle *h, uint32_t a)
     std::vector<uint32_t> len(n_seg);
     for (uint32_t s = 0; s < n_seg; ++s) len[s] = S.stat[(size_t)s * 5];
     return mk_runs(h, B[SG_MKX].as<uint32_t>(), B[SG_FIRST].as<uint32_t>(), n_seg, n, len, S.mk_s.data(), S.mk_tie.data());
+}
+
+// ------------------------------------------------------------------------------------------------------
+// the path stage in one call (mxg_format_paths): what format_path (reference bin/ntjoin_assemble.py:175-218) makes of
+// every path with determine_orientation (:30-50), calc_start_coord / calc_end_coord (:52-65) and calculate_gap_size
+// (:67-113), on the runs of path_segments above
+//   kf_orient     per run: '+' / '-' / '?' (strictly monotone, then the m rule in fp64), or "ask Mann-Kendall" with mkt
+//   kf_apply_mk   the host's Mann-Kendall decisions (one byte per run) into the orientations
+//   (scan)        kept runs -> node index
+//   kf_nodes      per kept run: coordinates, endpoints; per path: its first node
+//   kf_junctions  one wave per node: AND of the support masks over the stretch to the next node, then the gap estimate
+// ------------------------------------------------------------------------------------------------------
+enum : uint8_t { ORI_FWD = 0, ORI_REV = 1, ORI_NONE = 2, ORI_ASK_MK = 3 };
+enum : uint32_t { FERR_OVERHANG = 1u, FERR_NO_EDGE = 2u };
+
+__global__ __launch_bounds__(256) void kf_orient(const uint32_t *__restrict__ stat, uint32_t n_seg, double m, int mkt,
+                                                 uint8_t *__restrict__ ori)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= n_seg) return;
+    const uint32_t n = stat[(size_t)s * 5], inc = stat[(size_t)s * 5 + 3], dec = stat[(size_t)s * 5 + 4];
+    uint8_t o = ORI_NONE;
+    if (n > 1) {
+        if (dec == 0 && inc == n - 1) o = ORI_FWD;
+        else if (inc == 0 && dec == n - 1) o = ORI_REV;
+        else if (mkt) o = ORI_ASK_MK;
+        else {
+            const double positive = (double)inc / (double)(n - 1) * 100.0;
+            if (positive >= m) o = ORI_FWD;
+            else if (100.0 - positive >= m) o = ORI_REV;
+        }
+    }
+    ori[s] = o;
+}
+
+__global__ __launch_bounds__(256) void kf_apply_mk(const uint8_t *__restrict__ decided, uint32_t n_seg, uint8_t *__restrict__ ori)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s < n_seg && ori[s] == ORI_ASK_MK) ori[s] = decided[s];
+}
+
+__global__ __launch_bounds__(256) void kf_keep(const uint8_t *__restrict__ ori, uint32_t n_seg, uint32_t *__restrict__ keep)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s < n_seg) keep[s] = ori[s] <= ORI_REV ? 1u : 0u;
+}
+
+struct FormatNodes {  // the node arrays on the device (one allocation, FM_NODES), cap entries each
+    uint32_t *record, *start, *end, *size, *first_vertex, *terminal_vertex, *segment, *path;
+    int64_t *gap, *raw;
+    uint8_t *reverse;
+    static size_t bytes(size_t cap) { return cap * (8 * 4 + 2 * 8 + 1) + 64; }
+    void place(unsigned char *p, size_t cap)
+    {
+        gap = reinterpret_cast<int64_t *>(p); raw = gap + cap;
+        record = reinterpret_cast<uint32_t *>(raw + cap); start = record + cap; end = start + cap; size = end + cap;
+        first_vertex = size + cap; terminal_vertex = first_vertex + cap; segment = terminal_vertex + cap; path = segment + cap;
+        reverse = reinterpret_cast<uint8_t *>(path + cap);
+    }
+};
+
+struct FormatIn {
+    const uint32_t *seg_first, *seg_rec, *seg_path, *stat;  // the runs (path_segments)
+    const uint8_t *ori;
+    const uint32_t *keep_excl;                              // kept runs before run s = node index
+    const uint64_t *n_nodes;                                // ... and their total
+    const uint32_t *seg_excl;                               // per path vertex: runs before it (SG_EXCL)
+    const uint64_t *path_first;
+    const uint32_t *pv;
+    const uint32_t *ext_min, *ext_max, *rec_len;
+    uint32_t n_seg, n_paths, k;
+};
+
+__global__ __launch_bounds__(256) void kf_nodes(const FormatIn in, FormatNodes nd, uint64_t *__restrict__ node_first)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s <= in.n_paths)  // the first node of path s = the kept runs before the path's first run
+        node_first[s] = s < in.n_paths ? (uint64_t)in.keep_excl[in.seg_excl[in.path_first[s]]] : *in.n_nodes;
+    if (s >= in.n_seg || in.ori[s] > ORI_REV) return;
+    const uint32_t j = in.keep_excl[s], rec = in.seg_rec[s], first = in.seg_first[s];
+    const uint32_t n = in.stat[(size_t)s * 5], mn = in.stat[(size_t)s * 5 + 1], mx = in.stat[(size_t)s * 5 + 2];
+    const uint32_t len = in.rec_len[rec];
+    nd.record[j] = rec;
+    nd.start[j] = mn == in.ext_min[rec] ? 0u : mn;
+    nd.end[j] = mx == in.ext_max[rec] ? len : mx + in.k;
+    nd.size[j] = len;
+    nd.reverse[j] = in.ori[s];
+    nd.first_vertex[j] = in.pv[first];
+    nd.terminal_vertex[j] = in.pv[first + n - 1];
+    nd.segment[j] = s;
+    nd.path[j] = in.seg_path[s];
+}
+
+struct JunctionIn {
+    const uint32_t *seg_first, *stat, *pv;
+    const uint32_t *nb, *nbe, *esup;  // neighbour slots of find_paths, support mask per edge
+    const uint32_t *vpos;             // [assembly * nv_stride + vertex]
+    const uint64_t *n_nodes;
+    uint64_t nv_stride, ne;
+    uint32_t n_asm, assembly, k;
+    int64_t g, G;
+};
+
+// One wave per node j; lanes stride over the path's edges between the last vertex of node j's run and the first vertex of node
+// j + 1's (one edge unless runs without orientation lie between: then up to the length of those runs), AND-reduced by shuffles.
+// err[0]: FERR_* bits; err64[1]: the smallest node index with a negative overhang.
+__global__ __launch_bounds__(256) void kf_junctions(const JunctionIn in, FormatNodes nd, uint32_t *err, unsigned long long *err_node)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n_nodes = *in.n_nodes;
+    if (j >= n_nodes) return;
+    if (j + 1 >= n_nodes || nd.path[j + 1] != nd.path[j]) {  // a path's last node
+        if (lane == 0) { nd.gap[j] = 0; nd.raw[j] = 0; }
+        return;
+    }
+    const uint32_t su = nd.segment[j], sv = nd.segment[j + 1];
+    const uint32_t iu = in.seg_first[su] + in.stat[(size_t)su * 5] - 1, iv = in.seg_first[sv];
+    uint32_t common = 0xFFFFFFFFu, bad = 0;
+    for (uint32_t i = iu + lane; i < iv; i += 64) {
+        const uint32_t x = in.pv[i], y = in.pv[i + 1];
+        uint32_t e = 0xFFFFFFFFu;
+        if (in.nb[2 * (size_t)x] == y) e = in.nbe[2 * (size_t)x];
+        else if (in.nb[2 * (size_t)x + 1] == y) e = in.nbe[2 * (size_t)x + 1];
+        if (e < in.ne) common &= in.esup[e];
+        else bad = 1;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        common &= (uint32_t)__shfl_xor((int)common, o, 64);
+        bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
+    }
+    if (lane != 0) return;
+    if (bad) {
+        atomicOr(err, FERR_NO_EDGE);
+        nd.gap[j] = 0; nd.raw[j] = 0;
+        return;
+    }
+    if (in.n_asm < 32) common &= (1u << in.n_asm) - 1u;
+    if (common == 0) {
+        nd.gap[j] = in.g; nd.raw[j] = in.g;
+        return;
+    }
+    const uint32_t u = in.pv[iu], v = in.pv[iv];
+    uint64_t sum = 0;
+    for (uint32_t b = 0; b < in.n_asm; ++b)
+        if (common >> b & 1u) {
+            const int64_t pu = in.vpos[b * in.nv_stride + u], pw = in.vpos[b * in.nv_stride + v];
+            sum += (uint64_t)(pw > pu ? pw - pu : pu - pw);
+        }
+    const int64_t k = in.k, mean = (int64_t)(sum / (uint64_t)__popc(common)) - k;
+    const int64_t upos = in.vpos[in.assembly * in.nv_stride + u], vpos = in.vpos[in.assembly * in.nv_stride + v];
+    const int64_t a = nd.reverse[j] == ORI_FWD ? (int64_t)nd.end[j] - upos - k : upos - (int64_t)nd.start[j];
+    const int64_t b = nd.reverse[j + 1] == ORI_FWD ? vpos - (int64_t)nd.start[j + 1] : (int64_t)nd.end[j + 1] - vpos - k;
+    if (a < 0 || b < 0) {  // the reference raises here; the rest of the call finishes
+        atomicOr(err, FERR_OVERHANG);
+        atomicMin(err_node, (unsigned long long)j);
+        nd.gap[j] = 0; nd.raw[j] = 0;
+        return;
+    }
+    const int64_t raw = mean - a - b;
+    int64_t gap = raw > in.g ? raw : in.g;
+    if (in.G > 0 && gap > in.G) gap = in.G;
+    nd.gap[j] = gap;
+    nd.raw[j] = raw;
+}
+
+int format_paths(mxg_handle *h, uint32_t a, const mxg_format_params &p, const uint32_t *record_length, bool *overhang)
+{
+    *overhang = false;
+    Graph &g = h->graph;
+    const Paths &P = h->paths;
+    Segments &S = h->segs;
+    PathNodes &N = h->nodes;
+    MXG_HIP(h, hipSetDevice(h->device));
+    N = PathNodes();
+    const uint32_t n_paths = (uint32_t)P.component.size(), nr = (uint32_t)h->asms[a]->recs.size();
+    N.node_first.assign((size_t)n_paths + 1, 0);
+    int rc = extremes_enqueue(h, a);
+    if (rc != MXG_OK) return rc;
+    uint32_t n_seg = 0;
+    if ((rc = segments_device(h, a, &n_seg)) != MXG_OK) return rc;  // (sync: the number of runs)
+    if ((rc = segments_copy(h, n_seg)) != MXG_OK) return rc;
+    if (n_seg == 0) {
+        MXG_HIP(h, hipStreamSynchronize(h->stream));
+        S.assembly = (int)a;
+        return MXG_OK;
+    }
+    DevBuf *B = h->pbuf;
+    const dim3 gs((n_seg + 255) / 256), b(256);
+    MXG_HIP(h, B[FM_ORI].ensure((size_t)n_seg * 2 + 16));  // orientations | the host's Mann-Kendall decisions
+    MXG_HIP(h, B[FM_KEEP].ensure((size_t)n_seg * 4 + 16));
+    MXG_HIP(h, B[FM_KEXCL].ensure((size_t)n_seg * 4 + 16));
+    MXG_HIP(h, B[FM_NODES].ensure(FormatNodes::bytes(n_seg)));
+    MXG_HIP(h, B[FM_NFIRST].ensure(((size_t)n_paths + 1) * 8));
+    MXG_HIP(h, B[FM_LEN].ensure((size_t)nr * 4 + 16));
+    MXG_HIP(h, B[FM_ERR].ensure(64));
+    uint8_t *ori = B[FM_ORI].as<uint8_t>();
+    hipLaunchKernelGGL(kf_orient, gs, b, 0, h->stream, B[SG_STAT].as<uint32_t>(), n_seg, p.m, p.mkt ? 1 : 0, ori);
+    MXG_HIP(h, hipGetLastError());
+    std::vector<uint8_t> decided;
+    if (p.mkt) {
+        // the statistics need the runs' lengths on the host (mk_runs sizes its launches by them): the copies above, then mk.hip's own
+        MXG_HIP(h, hipStreamSynchronize(h->stream));
+        S.assembly = (int)a;
+        if ((rc = path_segments_mk(h, a)) != MXG_OK) return rc;
+        decided.assign(n_seg, ORI_NONE);
+        for (uint32_t s = 0; s < n_seg; ++s) {
+            const uint32_t n = S.stat[(size_t)s * 5], inc = S.stat[(size_t)s * 5 + 3], dec = S.stat[(size_t)s * 5 + 4];
+            if (n < 2 || (dec == 0 && inc == n - 1) || (inc == 0 && dec == n - 1)) continue;
+            const char c = mxg_mk_orientation(n, S.mk_s[s], S.mk_tie[s]);
+            decided[s] = c == '+' ? ORI_FWD : c == '-' ? ORI_REV : ORI_NONE;
+        }
+        MXG_HIP(h, hipMemcpyAsync(ori + n_seg, decided.data(), n_seg, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(kf_apply_mk, gs, b, 0, h->stream, ori + n_seg, n_seg, ori);
+        MXG_HIP(h, hipGetLastError());
+    }
+    uint64_t *d_tot = B[TOTAL].as<uint64_t>() + 1;
+    hipLaunchKernelGGL(kf_keep, gs, b, 0, h->stream, ori, n_seg, B[FM_KEEP].as<uint32_t>());
+    MXG_HIP(h, hipGetLastError());
+    if ((rc = exclusive_scan_u32(h, B[FM_KEEP].as<uint32_t>(), n_seg, B[BSUM], B[FM_KEXCL].as<uint32_t>(), d_tot)) != MXG_OK) return rc;
+    MXG_HIP(h, hipMemcpyAsync(B[FM_LEN].p, record_length, (size_t)nr * 4, hipMemcpyHostToDevice, h->stream));
+    MXG_HIP(h, hipMemsetAsync(B[FM_ERR].p, 0, 8, h->stream));
+    MXG_HIP(h, hipMemsetAsync(B[FM_ERR].as<unsigned char>() + 8, 0xFF, 8, h->stream));
+    FormatNodes nd;
+    nd.place(B[FM_NODES].as<unsigned char>(), n_seg);
+    FormatIn fi;
+    fi.seg_first = B[SG_FIRST].as<uint32_t>(); fi.seg_rec = B[SG_REC].as<uint32_t>(); fi.seg_path = B[SG_PATH].as<uint32_t>();
+    fi.stat = B[SG_STAT].as<uint32_t>(); fi.ori = ori; fi.keep_excl = B[FM_KEXCL].as<uint32_t>(); fi.n_nodes = d_tot;
+    fi.seg_excl = B[SG_EXCL].as<uint32_t>(); fi.path_first = B[PF].as<uint64_t>(); fi.pv = B[PV].as<uint32_t>();
+    fi.ext_min = B[XT_MIN].as<uint32_t>(); fi.ext_max = B[XT_MAX].as<uint32_t>(); fi.rec_len = B[FM_LEN].as<uint32_t>();
+    fi.n_seg = n_seg; fi.n_paths = n_paths; fi.k = h->cfg.k;
+    const uint32_t n_fill = std::max(n_seg, n_paths + 1);
+    hipLaunchKernelGGL(kf_nodes, dim3((n_fill + 255) / 256), b, 0, h->stream, fi, nd, B[FM_NFIRST].as<uint64_t>());
+    MXG_HIP(h, hipGetLastError());
+    JunctionIn ji;
+    ji.seg_first = fi.seg_first; ji.stat = fi.stat; ji.pv = fi.pv;
+    ji.nb = B[NB].as<uint32_t>(); ji.nbe = B[NBE].as<uint32_t>(); ji.esup = h->g_esup.as<uint32_t>();
+    ji.vpos = h->g_vpos.as<uint32_t>(); ji.n_nodes = d_tot; ji.nv_stride = g.nv_stride; ji.ne = g.ne;
+    ji.n_asm = g.n_asm; ji.assembly = a; ji.k = h->cfg.k; ji.g = p.g; ji.G = p.G;
+    // (the grid covers every run: the number of nodes stays on the device until the copies below)
+    hipLaunchKernelGGL(kf_junctions, dim3((n_seg + 3) / 4), b, 0, h->stream, ji, nd, B[FM_ERR].as<uint32_t>(),
+                       B[FM_ERR].as<unsigned long long>() + 1);
+    MXG_HIP(h, hipGetLastError());
+    // host copies: the node arrays in one copy (n_seg entries each; the first n_nodes count, known behind the sync)
+    N.block.assign((FormatNodes::bytes(n_seg) + 7) / 8, 0);
+    MXG_HIP(h, hipMemcpyAsync(N.block.data(), B[FM_NODES].p, FormatNodes::bytes(n_seg), hipMemcpyDeviceToHost, h->stream));
+    MXG_HIP(h, hipMemcpyAsync(N.node_first.data(), B[FM_NFIRST].p, ((size_t)n_paths + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    uint64_t err[2] = {0, 0};
+    MXG_HIP(h, hipMemcpyAsync(err, B[FM_ERR].p, 16, hipMemcpyDeviceToHost, h->stream));
+    MXG_HIP(h, hipStreamSynchronize(h->stream));
+    S.assembly = (int)a;
+    FormatNodes hn;
+    hn.place(reinterpret_cast<unsigned char *>(N.block.data()), n_seg);
+    N.n_nodes = (size_t)N.node_first[n_paths];
+    N.record = hn.record; N.start = hn.start; N.end = hn.end; N.contig_size = hn.size; N.first_vertex = hn.first_vertex;
+    N.terminal_vertex = hn.terminal_vertex; N.segment = hn.segment; N.reverse = hn.reverse; N.gap = hn.gap; N.raw = hn.raw;
+    if ((uint32_t)err[0] & FERR_NO_EDGE)
+        return set_err(h, MXG_EDEVICE, "internal error: mxg_format_paths found two consecutive path vertices without an edge");
+    if ((uint32_t)err[0] & FERR_OVERHANG) {
+        const uint64_t j = err[1];
+        *overhang = true;
+        const uint64_t path = (uint64_t)(std::upper_bound(N.node_first.begin(), N.node_first.end(), j) - N.node_first.begin()) - 1;
+        return set_err(h, MXG_EINVAL, "mxg_format_paths: Gap distance estimation less than 0 between path %llu node %llu (record %u, "
+                       "%u-%u) and the next (record %u, %u-%u): the record lengths are shorter than the minimizers imply",
+                       (unsigned long long)path, (unsigned long long)(j - N.node_first[path]), N.record[j], N.start[j], N.end[j],
+                       N.record[j + 1], N.start[j + 1], N.end[j + 1]);
+    }
+    return MXG_OK;
+}
+
+// the minimizer hashes of a few graph vertices (the endpoints of format_paths' nodes) without the graph's host mirror
+__global__ __launch_bounds__(256) void kv_gather_hash(const uint64_t *__restrict__ vhash, uint64_t nv, const uint32_t *__restrict__ idx,
+                                                      uint64_t n, uint64_t *__restrict__ out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n) out[i] = idx[i] < nv ? vhash[idx[i]] : 0;
+}
+
+int vertex_hashes(mxg_handle *h, const uint32_t *vertices, uint64_t n, uint64_t *out)
+{
+    const Graph &g = h->graph;
+    if (!g.valid) return set_err(h, MXG_EINVAL, "mxg_vertex_hashes: call mxg_build_graph first");
+    for (uint64_t i = 0; i < n; ++i)
+        if (vertices[i] >= g.nv) return set_err(h, MXG_EINVAL, "mxg_vertex_hashes: vertex %u out of range", vertices[i]);
+    if (n == 0) return MXG_OK;
+    if (n >= (1ull << 31) * 256) return set_err(h, MXG_ELIMIT, "mxg_vertex_hashes: too many vertices");
+    if (g.host_valid) {  // the mirror is there already
+        for (uint64_t i = 0; i < n; ++i) out[i] = g.vhash[vertices[i]];
+        return MXG_OK;
+    }
+    MXG_HIP(h, hipSetDevice(h->device));
+    DevBuf *B = h->pbuf;
+    MXG_HIP(h, B[VH_IDX].ensure(n * 4));
+    MXG_HIP(h, B[VH_OUT].ensure(n * 8));
+    MXG_HIP(h, hipMemcpyAsync(B[VH_IDX].p, vertices, n * 4, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(kv_gather_hash, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, h->stream, h->g_vhash.as<uint64_t>(), g.nv,
+                       B[VH_IDX].as<uint32_t>(), n, B[VH_OUT].as<uint64_t>());
+    MXG_HIP(h, hipGetLastError());
+    MXG_HIP(h, hipMemcpyAsync(out, B[VH_OUT].p, n * 8, hipMemcpyDeviceToHost, h->stream));
+    MXG_HIP(h, hipStreamSynchronize(h->stream));
+    return MXG_OK;
 }
 
 }  // namespace mxg

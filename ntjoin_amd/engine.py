@@ -335,6 +335,14 @@ class MxEngine:
                 "edge_support": _np(g.edge_support, ne, np.uint32),
                 "edge_weight": _np(g.edge_weight, ne, np.float64)}
 
+    def vertex_hashes(self, vertices):
+        """mxg_vertex_hashes: the minimizer hashes (u64) of the given graph vertices, gathered on the device: the graph's host
+        mirror (get_graph) is not made for them"""
+        idx = np.ascontiguousarray(vertices, dtype=np.uint32)
+        out = np.zeros(len(idx), dtype=np.uint64)
+        self._check(self._lib.mxg_vertex_hashes(self._h, idx.ctypes.data, len(idx), out.ctypes.data))
+        return out
+
     def find_paths(self, n=1):
         """linear paths through the graph (ntJoin's -n = minimum edge weight): list of (component id, [vertex indices])"""
         v = capi.PathsView()
@@ -364,6 +372,37 @@ class MxEngine:
         s, t, n = C.POINTER(C.c_int64)(), C.POINTER(C.c_uint64)(), C.c_uint64()
         self._check(self._lib.mxg_path_segments_mk(self._h, int(a), C.byref(s), C.byref(t), C.byref(n)))
         return {"s": _np(s, n.value, np.int64), "tie_term": _np(t, n.value, np.uint64)}
+
+    def format_paths(self, a, g=20, G=0, m=90, mkt=False, lengths=None):
+        """mxg_format_paths: nodes, orientations and gap sizes of all paths of the last find_paths for assembly a, as a dict of
+        arrays: node_first u64[n_paths + 1], and per node record, start, end, contig_size, first_vertex, terminal_vertex,
+        segment (u32), reverse (u8: 0 '+', 1 '-'), gap_size, raw_gap_size (i64, to the next node of the path).  lengths = one
+        length per record of the assembly (None: those the handle holds).  A negative overhang ("Gap distance estimation less
+        than 0") raises MxError with the arrays as its .nodes."""
+        p = capi.FormatParams()
+        p.struct_size, p.g, p.G, p.m, p.mkt = C.sizeof(capi.FormatParams), int(g), int(G), float(m), int(bool(mkt))
+        ln = None
+        if lengths is not None:
+            ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+            if ln.ndim != 1 or (0 <= int(a) < self.n_assemblies and len(ln) != self.n_records(a)):
+                raise ValueError("format_paths: lengths needs one entry per record of the assembly")
+        v = capi.PathNodesView()
+        rc = self._lib.mxg_format_paths(self._h, int(a), C.byref(p), None if ln is None else ln.ctypes.data, C.byref(v))
+        if rc < 0:
+            err = MxError(rc, (self._lib.mxg_last_error(self._h) or b"").decode())
+            # the one error that fills the view is the negative overhang (include/ntjoin_mx.h): no other leaves node_first set
+            err.nodes = self._path_nodes(v) if rc == capi.MXG_EINVAL and v.node_first else None
+            raise err
+        return self._path_nodes(v)
+
+    @staticmethod
+    def _path_nodes(v):
+        n = int(v.n_nodes)
+        out = {"node_first": _np(v.node_first, int(v.n_paths) + 1, np.uint64), "reverse": _np(v.reverse, n, np.uint8),
+               "gap_size": _np(v.gap_size, n, np.int64), "raw_gap_size": _np(v.raw_gap_size, n, np.int64)}
+        for name in ("record", "start", "end", "contig_size", "first_vertex", "terminal_vertex", "segment"):
+            out[name] = _np(getattr(v, name), n, np.uint32)
+        return out
 
     def mk_stats(self, values, run_first):
         """the same statistics of caller-given runs: run r = values[run_first[r]:run_first[r + 1]] -> (s int64, tie_term uint64)"""

@@ -18,7 +18,7 @@ import sys
 import numpy as np
 
 from . import capi
-from .engine import MxEngine
+from .engine import MxEngine, MxError
 from .ntjoin_utils import MxGraph, sketch_views
 
 COLOURS = ["red", "green", "blue", "purple", "orange", "turquoise", "pink", "yellow", "orchid", "salmon"]
@@ -214,7 +214,61 @@ class Ntjoin:
             return mk_orientation(n, s, tie_term)
         return "?"
 
+    NO_LENGTHS = ("format_paths: the target was loaded from a minimizer TSV, which holds no contig lengths; "
+                  "pass lengths={contig: length}")
+
     def format_paths(self, lengths=None, g=20, G=0, m=90, mkt=False):
+        """format_path (:175-218) for every path of the last find_paths() and the target assembly: one list per path of
+        [contig, ori, start, end, contig_size, first_mx, terminal_mx, gap_size, raw_gap_size].  Runs, orientations (the m rule,
+        or with mkt=True the Mann-Kendall test), coordinates and the gap estimates of calculate_gap_size (:67-113) are the
+        library's (mxg_format_paths: one call for all paths, from what the graph and path stages left on the device); only the
+        rows are made here, with the minimizer hashes of the nodes' endpoints.  An engine without the call goes the host route
+        (_format_paths_host)."""
+        eng = self._engine
+        if not hasattr(eng, "format_paths"):
+            return self._format_paths_host(lengths, g, G, m, mkt)
+        tgt = len(self._order) - 1
+        ids = eng.record_ids(tgt, eng.n_records(tgt))
+        lens = None if lengths is None else [lengths.get(c, 0) for c in ids]
+        try:
+            nodes = eng.format_paths(tgt, g=g, G=G, m=m, mkt=mkt, lengths=lens)
+        except MxError as err:
+            nodes = getattr(err, "nodes", None)
+            if nodes is None:
+                if lengths is None and err.code == capi.MXG_EINVAL and ids and not any(eng.record_lengths(tgt)):
+                    raise ValueError(self.NO_LENGTHS) from None
+                raise
+            self._need_lengths(nodes, ids, lengths)
+            # the view is filled: the error is the negative overhang, whose message names the first such path and node
+            where = re.search(r"path (\d+) node (\d+)", str(err))
+            if not where:
+                raise
+            path = self._node_rows(nodes, ids)[int(where.group(1))]
+            u, v = path[int(where.group(2))], path[int(where.group(2)) + 1]
+            raise ValueError(f"Gap distance estimation less than 0 between {u} and {v}") from None
+        self._need_lengths(nodes, ids, lengths)
+        return self._node_rows(nodes, ids)
+
+    @staticmethod
+    def _need_lengths(nodes, ids, lengths):
+        "KeyError, as lengths[contig] of the host route gives, for a contig of some node that lengths does not hold"
+        if lengths is not None:
+            for r in np.unique(nodes["record"]).tolist():
+                if ids[r] not in lengths:
+                    raise KeyError(ids[r])
+
+    def _node_rows(self, nodes, ids):
+        "the rows of format_paths from the arrays of MxEngine.format_paths: one list per path"
+        first_mx = self._engine.vertex_hashes(nodes["first_vertex"])
+        terminal_mx = self._engine.vertex_hashes(nodes["terminal_vertex"])
+        rows = [list(r) for r in zip(
+            [ids[r] for r in nodes["record"].tolist()], ["-" if r else "+" for r in nodes["reverse"].tolist()],
+            nodes["start"].tolist(), nodes["end"].tolist(), nodes["contig_size"].tolist(), map(str, first_mx.tolist()),
+            map(str, terminal_mx.tolist()), nodes["gap_size"].tolist(), nodes["raw_gap_size"].tolist())]
+        at = nodes["node_first"].tolist()
+        return [rows[lo:hi] for lo, hi in zip(at, at[1:])]
+
+    def _format_paths_host(self, lengths=None, g=20, G=0, m=90, mkt=False):
         """format_path (:175-218) for every path of the last find_paths() and the target assembly: one list per path of
         [contig, ori, start, end, contig_size, first_mx, terminal_mx, gap_size, raw_gap_size].  The per-minimizer work
         (grouping by contig, min/max, orientation tallies) is the library's (mxg_path_segments, mxg_mx_extremes); the
