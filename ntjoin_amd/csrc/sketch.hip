@@ -39,7 +39,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
+#include <optional>
 #include <type_traits>
 
 #include "batch_ctrl.h"
@@ -1978,23 +1978,10 @@ struct Driver {
         fine = (h_->cfg.flags & MXG_FLAG_TIMING_FINE) != 0;
     }
     DevBuf &sc(int i) { return h->scratch[slot][i]; }
-    // stretches the device route's per-stretch arrays hold for the batch being enqueued, and the blocks at the front of k_emit's
-    // grid that place them, four stretches each (see gap_capacity)
-    uint32_t gcap = GAP_DEV_MAX, n_place = GAP_DEV_MAX / 4;
-    void set_gaps(uint32_t cap, uint32_t place, double expect = -1.0)
-    {
-        gcap = cap;
-        n_place = place;
-        gap_expect = expect;
-    }
-    double gap_expect = -1.0;  // stretches the plan expects of the batch for the stretch kernels (< 0: not known)
-
-    // SC_CTRL holds the device control block (CTRL_WORDS) followed by the two super-count arrays of the batch (scan_kernels.h):
-    // per hash-kernel wave, then per k_resolve block; ctrl_bytes() of it are zeroed by the batch's one memset
-    uint32_t n_wave_sup = 0;
-    uint32_t *wave_sup() { return sc(SC_CTRL).as<uint32_t>() + CTRL_WORDS; }
-    uint32_t *sel_sup(uint32_t) { return wave_sup() + n_wave_sup; }
-    static uint32_t n_sel_sup(uint32_t n_cap) { return sup_words((n_cap + RK - 1) / RK); }
+    // SC_CTRL: the device control block, then what the batch's route keeps behind it (batch_ctrl.h: CandCtrlLayout, SliceCtrlLayout)
+    uint32_t *ctrl_word(uint32_t w) { return sc(SC_CTRL).as<uint32_t>() + w; }
+    static CandCtrlLayout cand_layout(uint32_t n_waves, uint32_t n_cap) { return cand_ctrl_layout(sup_words(n_waves), sup_words((n_cap + RK - 1) / RK)); }
+    static SliceCtrlLayout slice_layout(const BsSelGeom &b) { return slice_ctrl_layout(sup_words(b.n_slices)); }
 
     bool fine = false;  // MXG_FLAG_TIMING_FINE: a span per kernel
     int ev_next(int kind)  // fine timing only: close the running span and open one of `kind`
@@ -2068,16 +2055,17 @@ struct Driver {
     }
 
     // sparse path: resolve + gap detection + per-256 counts (SC_CNT256 + super-counts behind the control block) in ONE
-    // launch; emit(..., true) turns them into offsets, places the minimizers and writes the total to CW_SELECTED
-    int resolve_count(const Tables &T, uint32_t n_cap, uint32_t ctg_lo, uint32_t ctg_hi, uint64_t tau, uint32_t n_likely)
+    // launch; emit from EmitSource::resolve turns them into offsets, places the minimizers and writes the total to CW_SELECTED
+    int resolve_count(const Tables &T, const BatchShape &shape, const CandCtrlLayout &layout, uint32_t n_cap, uint32_t ctg_lo,
+                      uint32_t ctg_hi, uint64_t tau, uint32_t n_likely)
     {
         if (!n_cap) return MXG_OK;
         MXG_HIP(h, sc(SC_SEL).ensure(std::max<uint32_t>(n_cap, 16)));
-        const uint32_t blocks = ((grid_cand ? std::min(grid_cand, n_cap) : n_cap) + RK - 1) / RK;
+        const uint32_t blocks = ((shape.grid_cand ? std::min(shape.grid_cand, n_cap) : n_cap) + RK - 1) / RK;
         MXG_HIP(h, sc(SC_CNT256).ensure((size_t)blocks * 4 + 64));
         ResolveParams rp = resolve_params(T, n_cap, ctg_lo, ctg_hi, tau);
         rp.cnt256 = sc(SC_CNT256).as<uint32_t>();
-        rp.sel_sup = sel_sup(n_cap);
+        rp.sel_sup = ctrl_word(layout.sel_sup);
         MXG_HIP(h, sc(SC_CS_H).ensure((size_t)blocks * RK * 8));
         MXG_HIP(h, sc(SC_CS_K).ensure((size_t)blocks * RK * 4));
         MXG_HIP(h, sc(SC_CS_C).ensure((size_t)blocks * RK * 4));
@@ -2092,7 +2080,7 @@ struct Driver {
             hipLaunchKernelGGL((k_resolve<true, true, 2>), dim3(blocks), dim3(RK), 0, st, rp);
         else if (abl == 3)
             hipLaunchKernelGGL((k_resolve<true, true, 3>), dim3(blocks), dim3(RK), 0, st, rp);
-        else if (env_u64(h, "MXG_RH", few_cand ? 32 : 64) == 32)  // halo of 32 candidates: enough for <= 12 per window (976 -> 985 Gbp/s)
+        else if (env_u64(h, "MXG_RH", shape.few_cand ? 32 : 64) == 32)  // halo of 32 candidates: enough for <= 12 per window (976 -> 985 Gbp/s)
             hipLaunchKernelGGL((k_resolve<true, true, 0, 32>), dim3(blocks), dim3(RK), 0, st, rp);
         else
             hipLaunchKernelGGL((k_resolve<true, true>), dim3(blocks), dim3(RK), 0, st, rp);
@@ -2119,29 +2107,14 @@ struct Driver {
         return MXG_OK;
     }
 
-    // offsets: SC_BSUM per 1024-tile (after resolve_and_count) or, fused = true, from SC_CNT256 (after resolve_count)
-    uint32_t *n_out = nullptr;  // see EmitParams::n_out (set by sketch_assemblies for the fused call)
-    bool few_cand = false;      // <= 12 candidates per window: smaller k_reorder blocks and k_resolve halos (set per batch)
-    // Batches enqueued without a host sync: k_resolve and k_emit are launched for the EXPECTED number of candidates (+ 30 %)
-    // instead of the arrays' capacity (about 2.7 x the expectation), so that half their blocks do not start just to find
-    // nothing to do -- blocks that each hold a wave slot for a memory round trip beside the other stream's hash kernel.  A batch
-    // with more candidates than that never reports (no tile holds its last candidate): the host redoes the assembly.
-    uint32_t grid_cand = 0;     // 0: the capacity
-    // how a batch hangs together with the batches before it and with the device-side stretch fix-up (see EmitParams)
-    struct ChainIO {
-        const uint64_t *base_in = nullptr;
-        uint64_t *base_out = nullptr;
-        bool dev_gaps = false;
-        hipEvent_t wait = nullptr;  // recorded behind the previous batch of the assembly when that ran on the other stream
-        uint32_t ecb = 0;           // slices per k_emit tile behind k_bs_select (0: the default)
-    };
-    int emit(const uint32_t *d_packed, const Tables &T, uint32_t n_cap, DevBuf &oh, DevBuf &op, DevBuf &orc, DevBuf &of,
-             uint64_t out_base, bool fused = false, uint32_t *host_ctrl = nullptr, const ChainIO *io = nullptr,
-             uint32_t rk = RK, uint32_t n_fixed = 0, const uint32_t *cand_spread = nullptr)
+    // k_emit over the batch's selection, as `src` left it in this driver's scratch, into `out` from `out_base` on; with
+    // `report`, the batch's last tile writes the host report there
+    int emit(const Tables &T, const BatchShape &shape, const EmitSource &src, uint32_t n_cap, const OutArrays &out, uint64_t out_base,
+             uint32_t *report)
     {
-        const uint64_t limit = OutArrays{&oh, &op, &orc, &of}.cap();
         if (!n_cap) return MXG_OK;
-        EmitParams ep;
+        const bool fused = src.route != EmitSource::TILE_SUMS;
+        EmitParams ep{};
         ep.sel = sc(SC_SEL).as<uint8_t>();
         ep.ch = sc(SC_CAND_H).as<uint64_t>();
         ep.ck = sc(SC_CAND_K).as<uint32_t>();
@@ -2151,46 +2124,40 @@ struct Driver {
         ep.n_cap = n_cap;
         ep.bsum = fused ? nullptr : sc(SC_BSUM).as<uint32_t>();
         ep.cnt256 = fused ? sc(SC_CNT256).as<uint32_t>() : nullptr;
-        ep.sel_sup = fused ? sel_sup(n_cap) : nullptr;
+        ep.sel_sup = fused ? ctrl_word(src.sup) : nullptr;
         ep.n_sel = sc(SC_CTRL).as<uint32_t>() + CW_SELECTED;
-        ep.host_ctrl = host_ctrl;
-        ep.n_out = host_ctrl ? n_out : nullptr;
+        ep.host_ctrl = report;
+        ep.n_out = report ? shape.n_out : nullptr;
         ep.runs = T.d_runs;
         ep.ctg_run0 = T.d_ctg_run0;
         ep.ctg_rec = T.d_ctg_rec;
         ep.ctg_info = T.d_ctg_info;
         ep.mult = 1ull ^ ((uint64_t)h->cfg.k * 0x90b45d39fb6da1faull);
-        (void)d_packed;
         ep.out_base = out_base;
-        ep.out_limit = limit;
-        ep.o_hash = oh.as<uint64_t>();
-        ep.o_pos = op.as<uint32_t>();
-        ep.o_rec = orc.as<uint32_t>();
-        ep.o_fwd = of.as<uint8_t>();
+        ep.out_limit = out.cap();
+        ep.o_hash = out.hash->as<uint64_t>();
+        ep.o_pos = out.pos->as<uint32_t>();
+        ep.o_rec = out.rec->as<uint32_t>();
+        ep.o_fwd = out.fwd->as<uint8_t>();
         ep.cs_h = fused ? sc(SC_CS_H).as<uint64_t>() : nullptr;  // (the sparse path's k_resolve laid the selected ones out per block)
         ep.cs_k = fused ? sc(SC_CS_K).as<uint32_t>() : nullptr;
         ep.cs_c = fused ? sc(SC_CS_C).as<uint32_t>() : nullptr;
-        ep.cs_aos = fused && n_fixed ? sc(SC_CS_H).as<uint4>() : nullptr;  // (n_fixed: the batch went through k_bs_select)
-        ep.base_in = io ? io->base_in : nullptr;
-        ep.base_out = io ? io->base_out : nullptr;
-        ep.dev_gaps = io && io->dev_gaps ? 1u : 0u;
-        ep.gcap = gcap;
-        ep.n_place = n_place;
-        ep.rk = rk;
-        ep.n_fixed = n_fixed;
-        ep.cand_spread = cand_spread;
-        const uint32_t n_grid = n_fixed ? n_fixed : (grid_cand ? std::min(grid_cand, n_cap) : n_cap);
+        ep.cs_aos = src.route == EmitSource::SLICES ? sc(SC_CS_H).as<uint4>() : nullptr;
+        ep.base_in = shape.base_in;
+        ep.base_out = shape.base_out;
+        ep.dev_gaps = shape.dev_gaps ? 1u : 0u;
+        ep.gcap = shape.gcap;
+        ep.n_place = shape.n_place;
+        ep.rk = src.rk;
+        ep.n_fixed = src.n_fixed;
+        ep.cand_spread = src.route == EmitSource::SLICES ? ctrl_word(src.cand_spread) : nullptr;
+        const uint32_t n_grid = src.n_fixed ? src.n_fixed : (shape.grid_cand ? std::min(shape.grid_cand, n_cap) : n_cap);
         ep.ecb = EMIT_COMPACT_BLOCKS;
-        if (rk < RK) {  // the slices of k_bs_select: ~18 minimizers each
-            const uint64_t e = env_u64(h, "MXG_EMIT_ECB", io && io->ecb ? io->ecb : 16);
+        if (src.rk < RK) {  // the slices of k_bs_select: ~18 minimizers each
+            const uint64_t e = env_u64(h, "MXG_EMIT_ECB", shape.ecb ? shape.ecb : 16);
             ep.ecb = e >= 64 ? 64u : e >= 32 ? 32u : 16u;
         }
-        ep.n_tiles = fused ? (n_grid + ep.ecb * rk - 1) / (ep.ecb * rk) : (n_grid + TILE - 1) / TILE;
-        ep.s_key = nullptr;
-        ep.s_off = ep.s_src = nullptr;
-        ep.gaps = nullptr;
-        ep.r_hash = nullptr;
-        ep.r_pos = ep.r_rec = ep.r_cnt = ep.r_start = nullptr;
+        ep.n_tiles = fused ? (n_grid + ep.ecb * src.rk - 1) / (ep.ecb * src.rk) : (n_grid + TILE - 1) / TILE;
         uint32_t grid = ep.n_tiles;
         if (ep.dev_gaps) {
             ep.s_key = sc(SC_GD_HASH).as<uint64_t>();
@@ -2201,8 +2168,8 @@ struct Driver {
             ep.r_pos = sc(SC_GR_POS).as<uint32_t>();
             ep.r_rec = sc(SC_GR_REC).as<uint32_t>();
             ep.r_cnt = sc(SC_GR_CNT).as<uint32_t>();
-            ep.r_start = ep.r_cnt + gcap;
-            grid += n_place;
+            ep.r_start = ep.r_cnt + shape.gcap;
+            grid += shape.n_place;
         }
         hipLaunchKernelGGL(k_emit, dim3(grid), dim3(256), 0, st, ep);
         MXG_HIP(h, hipGetLastError());
@@ -2263,7 +2230,7 @@ struct Driver {
             MXG_HIP(h, hipMemcpyAsync(&total, sc(SC_CTRL).as<uint32_t>() + CW_SELECTED, 8, hipMemcpyDeviceToHost, st));
             MXG_HIP(h, hipStreamSynchronize(st));
             if ((rc = out_reserve(h, out, out.n + total, st)) != MXG_OK) return rc;
-            if ((rc = emit(d_packed, T, n_cand, *out.hash, *out.pos, *out.rec, *out.fwd, out.n)) != MXG_OK) return rc;
+            if ((rc = emit(T, BatchShape{}, EmitSource::tile_sums(RK), n_cand, out, out.n, nullptr)) != MXG_OK) return rc;
             out.n += total;
             h->stat_dense_kmers += nk;
             c0 = c1;
@@ -2349,8 +2316,6 @@ struct Driver {
     }
 
     // ---- sparse pipeline -------------------------------------------------------------------------------------
-    // control block (u32 words): [0] max wave count if a wave overflowed its arena slice, [1] gap count,
-    // [2..3] number of selected candidates (u64), [4..5] number of candidates (u64)
     struct BatchGeom {
         size_t c0, c1;
         uint64_t nk;
@@ -2382,14 +2347,10 @@ struct Driver {
         if (h->arena_cap_hint == 0) wave_cap = env_u64(h, "MXG_WAVE_CAP", wave_cap);  // test knob
         return wave_cap;
     }
-    // Enqueue one batch completely (hash -> order -> resolve+count -> speculative emit at out.n); the last kernel writes
-    // the batch's report to `ctrl_host` (a pinned slot); NO host sync.  *n_cap_out = capacity the candidate arrays were sized for.
-    // grid of the hash kernel: one block per tile of 256 strips (a few persistent blocks per CU with an equal number of tiles each
-    // were an experiment of round 2, measured and dropped)
-    uint32_t sparse_grid(uint32_t n_tiles, uint64_t) const { return n_tiles; }
     // stretches sketched on the device, one block each (results wait in their regions for k_gap_post): reads SC_GAPS / CW_STRETCHES
-    int enqueue_dev_gaps(Assembly *a, const Tables &T, const uint32_t *ctrl_host)
+    int enqueue_dev_gaps(Assembly *a, const Tables &T, const BatchShape &shape, const uint32_t *ctrl_host)
     {
+        const uint32_t gcap = shape.gcap, n_place = shape.n_place;
         MXG_HIP(h, sc(SC_GR_HASH).ensure((size_t)GAP_DEV_POOL * 8));
         MXG_HIP(h, sc(SC_GR_POS).ensure((size_t)GAP_DEV_POOL * 4));
         MXG_HIP(h, sc(SC_GR_REC).ensure((size_t)GAP_DEV_POOL * 4));
@@ -2423,7 +2384,7 @@ struct Driver {
         // (no more blocks than the launch expects stretches -- what k_emit has placing blocks for: a block of 51 KB that finds
         // nothing to do still has to be brought to a CU, 22 us for 768 of them behind k_sel_stretch, which leaves few stretches over)
         const uint32_t gf_blocks = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::max<uint64_t>(env_u64(h, "MXG_GAP_FIX_BLOCKS", GAP_FIX_BLOCKS), 1), gcap),
-                                                                gap_expect >= 0.0 ? std::max<uint64_t>(32, (uint64_t)(2.0 * gap_expect) + 16) : 4ull * n_place);
+                                                                shape.gap_expect >= 0.0 ? std::max<uint64_t>(32, (uint64_t)(2.0 * shape.gap_expect) + 16) : 4ull * n_place);
         if (h->cfg.variant == MXG_VARIANT_V1_MIN)
             hipLaunchKernelGGL(k_gap_fix<MXG_VARIANT_V1_MIN>, dim3(gf_blocks), dim3(256), 0, st, gp);
         else
@@ -2442,83 +2403,100 @@ struct Driver {
         return MXG_OK;
     }
 
-    int enqueue_sparse(Assembly *a, const Tables &T, const BatchGeom &g, uint64_t wave_cap, uint32_t tau_hi,
-                       OutArrays &out, uint32_t *ctrl_host, uint32_t *n_cap_out, const ChainIO *io = nullptr,
-                       uint32_t cand_hint = 0xFFFFFFFFu, const uint32_t *bs_bitmap = nullptr)
+    // ---- candidate-array route: hash (or the k = 32 filter's bits) -> order -> resolve + count -> speculative emit at out_base;
+    // the last kernel writes the batch's report to `report` (a pinned slot); NO host sync
+    struct SparseBatch {  // what the phases of enqueue_sparse share
+        Assembly *a; const Tables &T; const BatchGeom &g; const BatchShape &shape;
+        uint32_t tau_hi, wave_cap;
+        uint32_t cand_hint;         // candidates the batch held last time (0xFFFFFFFF: not known)
+        const uint32_t *bs_bitmap;  // the k = 32 filter's bits, or null: the rolling-hash kernel
+        uint32_t *report;
+        uint32_t n_cap = 0;
+        CandCtrlLayout ctrl{};
+        uint32_t queue_cap = 0;  // entries of a slice's LDS queue in the reorder kernels (0: no queue)
+        bool r_wave = false;     // reorder with one wave per slice
+    };
+    // MXG_RING_SLACK=<percent> (test knob): the ring filter captures up to that many percent more k-mers than have
+    // hash < tau, i.e. entries that k_reorder finds to be >= tau and k_resolve must treat as absent.  On real runs
+    // such entries occur about once per 10^9 k-mers, so the tests force them.
+    uint32_t filter_tau(uint32_t tau_hi) const
     {
-        // MXG_TIMING_SAMPLE=n: event pairs around one batch in n only (four event records per batch cost 2 % of the step at
-        // 3 Gbp; bench.py asks for one in four and scales the sums by the bases they cover)
-        struct TimingGuard {
-            bool &t; bool saved;
-            TimingGuard(bool &t_, bool now) : t(t_), saved(t_) { t = now; }
-            ~TimingGuard() { t = saved; }
-        };
-        const uint64_t t_sample = timing && !fine && io ? env_u64(h, "MXG_TIMING_SAMPLE", 1) : 1;
-        TimingGuard timing_guard(timing, timing && (t_sample <= 1 || (h->timing_batches++ % t_sample) == 0));
-        const uint32_t S = a->S_sparse;
-        few_cand = (double)tau_hi / 4294967296.0 * (double)h->cfg.w <= 12.5;
+        const uint32_t ring_slack = (uint32_t)env_u64(h, "MXG_RING_SLACK", 0);
+        return ring_slack ? (uint32_t)std::min<uint64_t>(0x7FFFFFFEull, (uint64_t)tau_hi * (100 + ring_slack) / 100) & ~1u : tau_hi;
+    }
+    // the part of a batch's shape that this route decides: by the threshold, and by the candidates it expects where nobody waits
+    void shape_sparse(BatchShape &shape, const BatchGeom &g, uint64_t wave_cap, uint32_t tau_hi, uint32_t cand_hint) const
+    {
+        shape.few_cand = (double)tau_hi / 4294967296.0 * (double)h->cfg.w <= 12.5;
+        // (min(fwd, rev) < tau: either strand may pass)
+        shape.grid_cand = grid_by_estimate(shape.chained ? env_u64(h, "MXG_GRID_BY_ESTIMATE", 1) : 0, g.nk, filter_tau(tau_hi),
+                                           h->cfg.variant == MXG_VARIANT_V1_MIN, cand_hint != 0xFFFFFFFFu ? cand_hint : 0,
+                                           (uint32_t)std::min<uint64_t>((uint64_t)g.n_waves * wave_cap, 0xFFFFFFFFu), RK, EMIT_COMPACT_BLOCKS * RK);
+    }
+
+    // On return: the batch's scratch is reserved, and the fill that zeroes its control block and super-counts is on the stream.
+    int sparse_reserve(SparseBatch &b)
+    {
+        const BatchGeom &g = b.g;
         MXG_HIP(h, sc(SC_GAPS).ensure((size_t)GAP_CAP * 16));
         MXG_HIP(h, sc(SC_STRIP_CNT).ensure((size_t)g.n_strips * 4 + 16));
         MXG_HIP(h, sc(SC_STRIP_META).ensure((size_t)g.n_strips * 4 + 16));
         MXG_HIP(h, sc(SC_WAVE_CNT).ensure((size_t)g.n_waves * 4 + 16));
         MXG_HIP(h, sc(SC_WAVE_TOT).ensure((size_t)g.n_waves * 4 + 16));
-        const uint64_t n_cap64 = (uint64_t)g.n_waves * wave_cap;
+        const uint64_t n_cap64 = (uint64_t)g.n_waves * b.wave_cap;
         if (n_cap64 >= (1ull << 32))
             return set_err(h, MXG_ELIMIT, "candidate arena would exceed 2^32 entries; use MXG_FLAG_DENSE_ONLY");
-        const uint32_t n_cap = (uint32_t)n_cap64;
-        *n_cap_out = n_cap;
-        MXG_HIP(h, sc(SC_CAND_H).ensure((size_t)n_cap * 8));
-        MXG_HIP(h, sc(SC_CAND_K).ensure((size_t)n_cap * 4));
-        MXG_HIP(h, sc(SC_CAND_C).ensure((size_t)n_cap * 4));
-        n_wave_sup = sup_words(g.n_waves);
-        const size_t ctrl_bytes = ((size_t)CTRL_WORDS + n_wave_sup + n_sel_sup(n_cap)) * 4;
-        MXG_HIP(h, sc(SC_CTRL).ensure(ctrl_bytes));
-        MXG_HIP(h, hipMemsetAsync(sc(SC_CTRL).p, 0, ctrl_bytes, st));  // control block + both super-count arrays
+        b.n_cap = (uint32_t)n_cap64;
+        MXG_HIP(h, sc(SC_CAND_H).ensure((size_t)b.n_cap * 8));
+        MXG_HIP(h, sc(SC_CAND_K).ensure((size_t)b.n_cap * 4));
+        MXG_HIP(h, sc(SC_CAND_C).ensure((size_t)b.n_cap * 4));
+        b.ctrl = cand_layout(g.n_waves, b.n_cap);
+        MXG_HIP(h, sc(SC_CTRL).ensure(b.ctrl.bytes()));
+        MXG_HIP(h, hipMemsetAsync(sc(SC_CTRL).p, 0, b.ctrl.bytes(), st));  // control block + both super-count arrays
+        // reorder geometry (needed first: the k = 32 route's reorder kernel exists in the one-wave-per-slice form only):
+        // one wave per slice + position tables when the queues of a block fit beside the 32 KB of tables
+        b.queue_cap = b.wave_cap <= 8192 ? b.wave_cap : 0;
+        b.r_wave = b.queue_cap && reorder_w_lds(b) + 512 <= 65536 && env_u64(h, "MXG_REORDER_W", 1) != 0;
+        if (!b.r_wave || !b.T.d_strip_run) b.bs_bitmap = nullptr;  // (a batch whose slices outgrow the LDS queues takes the rolling-hash kernel)
+        if (!b.bs_bitmap) MXG_HIP(h, sc(SC_ARENA).ensure((size_t)b.n_cap * 8));
+        return MXG_OK;
+    }
+    static size_t reorder_w_lds(const SparseBatch &b) { return (size_t)2048 * 16 + (size_t)RW_WAVES * b.queue_cap * 4; }
+
+    // On return: the kernel that counts the batch's candidates per strip and wave is on the stream, in a timing span of its own
+    // (the hash span, or with the k = 32 filter's bits a span of the batch's rest).
+    int sparse_count(const SparseBatch &b)
+    {
+        const BatchGeom &g = b.g;
         SparseParams sp;
-        sp.packed = a->d_packed;
-        sp.runs = T.d_runs;
-        sp.run_strip0 = T.d_strip0_sparse;
+        sp.packed = b.a->d_packed;
+        sp.runs = b.T.d_runs;
+        sp.run_strip0 = b.T.d_strip0_sparse;
         sp.run_lo = g.r_lo;
         sp.run_hi = g.r_hi;
         sp.strip_lo = g.strip_lo;
         sp.strip_hi = g.strip_hi;
         sp.k = h->cfg.k;
-        sp.S = S;
+        sp.S = b.a->S_sparse;
         sp.five = env_u64(h, "MXG_HASH_FIVE", 1) != 0 ? 1u : 0u;
-        // MXG_RING_SLACK=<percent> (test knob): the ring filter captures up to that many percent more k-mers than have
-        // hash < tau, i.e. entries that k_reorder finds to be >= tau and k_resolve must treat as absent.  On real runs
-        // such entries occur about once per 10^9 k-mers, so the tests force them.
-        const uint32_t ring_slack = (uint32_t)env_u64(h, "MXG_RING_SLACK", 0);  // read per call, like the other knobs
-        sp.tau_hi = ring_slack ? (uint32_t)std::min<uint64_t>(0x7FFFFFFEull, (uint64_t)tau_hi * (100 + ring_slack) / 100) & ~1u
-                               : tau_hi;
-        sp.wave_cap = (uint32_t)wave_cap;
+        sp.tau_hi = filter_tau(b.tau_hi);
+        sp.wave_cap = b.wave_cap;
         sp.wave_cnt = sc(SC_WAVE_CNT).as<uint32_t>();
         sp.ctrl = sc(SC_CTRL).as<uint32_t>();
         sp.strip_cnt = sc(SC_STRIP_CNT).as<uint32_t>();
         sp.strip_meta = sc(SC_STRIP_META).as<uint32_t>();
         sp.wave_tot = sc(SC_WAVE_TOT).as<uint32_t>();
-        sp.wave_sup = wave_sup();
-        // reorder geometry (needed first: the k = 32 route's reorder kernel exists in the one-wave-per-slice form only)
-        const uint32_t queue_cap = sp.wave_cap <= 8192 ? sp.wave_cap : 0;
-        const size_t q_lds = (size_t)queue_cap * 4;
-        // slices per block of k_reorder: one (two to four, the block's byte table loaded once for all of them, measured slower in round 2)
-        const uint32_t r_g = 1;
-        const uint32_t r_grid = (g.n_waves + r_g - 1) / r_g;
-        // one wave per slice + position tables when the queues of a block fit beside the 32 KB of tables
-        const size_t w_lds = (size_t)2048 * 16 + (size_t)RW_WAVES * queue_cap * 4;
-        const bool r_wave = queue_cap && w_lds + 512 <= 65536 && env_u64(h, "MXG_REORDER_W", 1) != 0;
-        const uint32_t w_grid = std::min<uint32_t>((g.n_waves + RW_WAVES - 1) / RW_WAVES,
-                                                   (uint32_t)env_u64(h, "MXG_REORDER_W_GRID", 256 * 3));
-        if (!r_wave || !T.d_strip_run) bs_bitmap = nullptr;  // (a batch whose slices outgrow the LDS queues takes the rolling-hash kernel)
-        if (!bs_bitmap) MXG_HIP(h, sc(SC_ARENA).ensure((size_t)n_cap * 8));
+        sp.wave_sup = ctrl_word(b.ctrl.wave_sup);
         sp.arena = sc(SC_ARENA).as<uint2>();
-        int rc;
         sp.init_tab = h->d_init_tab.as<uint4>();
-        sp.strip_run = T.d_strip_run;
+        sp.strip_run = b.T.d_strip_run;
         sp.tab = h->tab;
-        if ((rc = bs_bitmap ? ev_begin(0, false) : ev_begin(batch_bases(T, g.c0, g.c1), true)) != MXG_OK) return rc;
+        int rc;
+        if ((rc = b.bs_bitmap ? ev_begin(0, false) : ev_begin(batch_bases(b.T, g.c0, g.c1), true)) != MXG_OK) return rc;
         sp.n_tiles = g.n_blocks;
-        dim3 grid(sparse_grid(g.n_blocks, g.nk)), block(256);
+        // grid of the hash kernel: one block per tile of 256 strips (a few persistent blocks per CU with an equal number of tiles
+        // each were an experiment of round 2, measured and dropped)
+        dim3 grid(g.n_blocks), block(256);
         static const int abl = getenv("MXG_ABLATE") ? atoi(getenv("MXG_ABLATE")) : 0;  // profiling only
         // Every lane keeps one 128-byte line of packed bases "open" for 32 block iterations (16 bases = 4 bytes per iteration),
         // so the waves resident on an XCD hold (waves x 64 x 128 B) of live lines.  At full occupancy that is more than the
@@ -2529,8 +2507,8 @@ struct Driver {
         // k = 32 the first 16 KB of it hold init32_half's tables.
         size_t pad = (size_t)env_u64(h, "MXG_HASH_LDS", g.nk >= (256ull << 20) ? 18000 : 0);
         if (sp.five && sp.k == 32) pad = std::max<size_t>(pad, 16384);
-        if (bs_bitmap)  // (k = 32 route: the filter has run over the whole assembly; only its bits are turned into entries)
-            hipLaunchKernelGGL(k_bs_count, dim3(g.n_blocks), block, 0, st, sp, bs_bitmap);
+        if (b.bs_bitmap)  // (k = 32 route: the filter has run over the whole assembly; only its bits are turned into entries)
+            hipLaunchKernelGGL(k_bs_count, dim3(g.n_blocks), block, 0, st, sp, b.bs_bitmap);
         else if (h->cfg.variant == MXG_VARIANT_V1_MIN)
             hipLaunchKernelGGL((k_hash_sparse<MXG_VARIANT_V1_MIN>), grid, block, pad, st, sp);
         else if (abl == 1)
@@ -2541,38 +2519,51 @@ struct Driver {
             hipLaunchKernelGGL((k_hash_sparse<MXG_VARIANT_V2_SUM>), grid, block, pad, st, sp);
         if ((rc = ev_end()) != MXG_OK) return rc;
         MXG_HIP(h, hipGetLastError());
-        // order the candidates: exclusive scan of per-strip counts (total = number of candidates), then scatter
+        return MXG_OK;
+    }
+
+    // On return: the kernel that orders the candidates (exclusive scan of the per-strip counts, total = CW_CAND, then scatter
+    // into SC_CAND_*) is on the stream, behind the opening of the span of the batch's rest.
+    int sparse_reorder(const SparseBatch &b)
+    {
+        const BatchGeom &g = b.g;
+        int rc;
         if ((rc = ev_begin(0, false)) != MXG_OK) return rc;
         ReorderParams op;
-        op.arena = sp.arena;
-        op.wave_cnt = sp.wave_cnt;
-        op.wave_cap = sp.wave_cap;
-        op.n_cap = n_cap;
+        op.arena = sc(SC_ARENA).as<uint2>();
+        op.wave_cnt = sc(SC_WAVE_CNT).as<uint32_t>();
+        op.wave_cap = b.wave_cap;
+        op.n_cap = b.n_cap;
         op.n_waves = g.n_waves;
-        op.strip_cnt = sp.strip_cnt;
+        op.strip_cnt = sc(SC_STRIP_CNT).as<uint32_t>();
         op.n_strips = g.n_strips;
-        op.wave_tot = sp.wave_tot;
-        op.wave_sup = sp.wave_sup;
-        op.n_cand = sp.ctrl + CW_CAND;
-        op.strip_meta = bs_bitmap ? T.d_strip_run : sp.strip_meta;
-        op.runs = sp.runs;
-        op.run_strip0 = sp.run_strip0;
-        op.strip_lo = sp.strip_lo;
-        op.S = sp.S;
-        op.packed = sp.packed;
-        op.init_tab = sp.init_tab;
-        op.k = sp.k;
+        op.wave_tot = sc(SC_WAVE_TOT).as<uint32_t>();
+        op.wave_sup = ctrl_word(b.ctrl.wave_sup);
+        op.n_cand = ctrl_word(CW_CAND);
+        op.strip_meta = b.bs_bitmap ? b.T.d_strip_run : sc(SC_STRIP_META).as<uint32_t>();
+        op.runs = b.T.d_runs;
+        op.run_strip0 = b.T.d_strip0_sparse;
+        op.strip_lo = g.strip_lo;
+        op.S = b.a->S_sparse;
+        op.packed = b.a->d_packed;
+        op.init_tab = h->d_init_tab.as<uint4>();
+        op.k = h->cfg.k;
         op.ch = sc(SC_CAND_H).as<uint64_t>();
         op.ck = sc(SC_CAND_K).as<uint32_t>();
         op.cc = sc(SC_CAND_C).as<uint32_t>();
         op.tab = h->tab;
-        op.bm = bs_bitmap;
-        op.queue_cap = queue_cap;
-        if (bs_bitmap)  // (bs_possible: V2, and enqueue_sparse's caller has checked that the queues fit)
+        op.bm = b.bs_bitmap;
+        op.queue_cap = b.queue_cap;
+        const size_t q_lds = (size_t)b.queue_cap * 4, w_lds = reorder_w_lds(b);
+        // slices per block of k_reorder: one (two to four, the block's byte table loaded once for all of them, measured slower in round 2)
+        const uint32_t r_grid = g.n_waves;
+        const uint32_t w_grid = std::min<uint32_t>((g.n_waves + RW_WAVES - 1) / RW_WAVES,
+                                                   (uint32_t)env_u64(h, "MXG_REORDER_W_GRID", 256 * 3));
+        if (b.bs_bitmap)  // (bs_possible: V2, and enqueue_sparse's caller has checked that the queues fit)
             hipLaunchKernelGGL(k_bs_reorder_w<MXG_VARIANT_V2_SUM>, dim3(w_grid), dim3(RW_WAVES * 64), w_lds, st, op);
-        else if (r_wave && h->cfg.variant == MXG_VARIANT_V1_MIN)
+        else if (b.r_wave && h->cfg.variant == MXG_VARIANT_V1_MIN)
             hipLaunchKernelGGL(k_reorder_w<MXG_VARIANT_V1_MIN>, dim3(w_grid), dim3(RW_WAVES * 64), w_lds, st, op);
-        else if (r_wave && !knob_set(h, "MXG_ABLATE_REORDER"))
+        else if (b.r_wave && !knob_set(h, "MXG_ABLATE_REORDER"))
             hipLaunchKernelGGL(k_reorder_w<MXG_VARIANT_V2_SUM>, dim3(w_grid), dim3(RW_WAVES * 64), w_lds, st, op);
         else if (h->cfg.variant == MXG_VARIANT_V1_MIN)
             hipLaunchKernelGGL(k_reorder<MXG_VARIANT_V1_MIN>, dim3(r_grid), dim3(RB), q_lds, st, op);
@@ -2581,39 +2572,61 @@ struct Driver {
             static const int rabl = getenv("MXG_ABLATE_REORDER") ? atoi(getenv("MXG_ABLATE_REORDER")) : 0;  // profiling only
             if (rabl == 1)
                 hipLaunchKernelGGL((k_reorder<MXG_VARIANT_V2_SUM, 1>), dim3(r_grid), dim3(RB), q_lds, st, op);
-            else if (env_u64(h, "MXG_RB", few_cand ? 256 : RB) == 256)  // ~205 candidates per slice at 10 per window: one pass of 256 threads
+            else if (env_u64(h, "MXG_RB", b.shape.few_cand ? 256 : RB) == 256)  // ~205 candidates per slice at 10 per window: one pass of 256 threads
                 hipLaunchKernelGGL((k_reorder<MXG_VARIANT_V2_SUM, 0, 256>), dim3(r_grid), dim3(256), q_lds, st, op);
             else
                 hipLaunchKernelGGL(k_reorder<MXG_VARIANT_V2_SUM>, dim3(r_grid), dim3(RB), q_lds, st, op);
         }
         MXG_HIP(h, hipGetLastError());
-        // resolve + speculative emit straight into the output arrays (guarded by their capacity): on the common path
-        // (no gap, no overflow) the batch then needs a single host sync
+        return MXG_OK;
+    }
+
+    // On return: k_resolve (selection, stretch detection and per-block counts in one launch) and, on the device route, the
+    // stretch kernels are on the stream (fine timing: in a span of kind 3).
+    int sparse_resolve(const SparseBatch &b)
+    {
+        int rc;
         if ((rc = ev_next(3)) != MXG_OK) return rc;
-        grid_cand = 0;
-        if (const uint64_t by_est = io ? env_u64(h, "MXG_GRID_BY_ESTIMATE", 1) : 0) {
-            // (min(fwd, rev) < tau: either strand may pass)
-            const uint64_t expect = (uint64_t)((double)g.nk * (double)sp.tau_hi / 4294967296.0) *
-                                    (h->cfg.variant == MXG_VARIANT_V1_MIN ? 2u : 1u);
-            const uint64_t hint = cand_hint != 0xFFFFFFFFu ? cand_hint : 0;
-            uint64_t gc = std::max(expect, hint) * 13 / 10 + 16384;
-            if (by_est == 2) gc = std::max<uint64_t>(RK, expect / 2);  // (test knob: too small on purpose)
-            // a whole number of k_emit tiles, so that k_resolve (256 candidates per block) and k_emit cover the same candidates:
-            // a tile that reports must have had all its blocks resolved
-            constexpr uint64_t ET = (uint64_t)EMIT_COMPACT_BLOCKS * RK;
-            grid_cand = (uint32_t)std::min<uint64_t>(n_cap, (gc + ET - 1) / ET * ET);
-        }
-        if ((rc = resolve_count(T, n_cap, (uint32_t)g.c0, (uint32_t)g.c1, (uint64_t)tau_hi << 32,
-                                cand_hint != 0xFFFFFFFFu ? cand_hint : a->cand_hint)) != MXG_OK) return rc;
-        const bool dev = io && io->dev_gaps;
-        if (dev && (rc = enqueue_dev_gaps(a, T, ctrl_host)) != MXG_OK) return rc;
+        if ((rc = resolve_count(b.T, b.shape, b.ctrl, b.n_cap, (uint32_t)b.g.c0, (uint32_t)b.g.c1, (uint64_t)b.tau_hi << 32,
+                                b.cand_hint != 0xFFFFFFFFu ? b.cand_hint : b.a->cand_hint)) != MXG_OK) return rc;
+        return b.shape.dev_gaps ? enqueue_dev_gaps(b.a, b.T, b.shape, b.report) : MXG_OK;
+    }
+
+    // On return: the speculative k_emit straight into the output arrays (guarded by their capacity) is on the stream, behind
+    // the wait for the batch before this one, and the batch's last span is closed: on the common path (no stretch, no
+    // overflow) the batch needs a single host sync.
+    int sparse_emit(const SparseBatch &b, const OutArrays &out)
+    {
+        int rc;
         if ((rc = ev_next(4)) != MXG_OK) return rc;
         // the batch before this one (same assembly, other stream) must have passed its count on
-        if (io && io->wait) MXG_HIP(h, hipStreamWaitEvent(st, io->wait, 0));
-        rc = emit(a->d_packed, T, n_cap, *out.hash, *out.pos, *out.rec, *out.fwd, out.n, true, ctrl_host, io);
-        grid_cand = 0;
-        if (rc != MXG_OK) return rc;
+        if (b.shape.wait) MXG_HIP(h, hipStreamWaitEvent(st, b.shape.wait, 0));
+        if ((rc = emit(b.T, b.shape, EmitSource::resolve(b.ctrl, RK), b.n_cap, out, out.n, b.report)) != MXG_OK) return rc;
         return ev_end();
+    }
+
+    // Enqueue one batch completely; *n_cap_out = capacity the candidate arrays were sized for.
+    int enqueue_sparse(Assembly *a, const Tables &T, const BatchGeom &g, const BatchShape &shape, uint64_t wave_cap, uint32_t tau_hi,
+                       const OutArrays &out, uint32_t *report, uint32_t *n_cap_out, uint32_t cand_hint = 0xFFFFFFFFu,
+                       const uint32_t *bs_bitmap = nullptr)
+    {
+        // MXG_TIMING_SAMPLE=n: event pairs around one batch in n only (four event records per batch cost 2 % of the step at
+        // 3 Gbp; bench.py asks for one in four and scales the sums by the bases they cover)
+        struct TimingGuard {
+            bool &t; bool saved;
+            TimingGuard(bool &t_, bool now) : t(t_), saved(t_) { t = now; }
+            ~TimingGuard() { t = saved; }
+        };
+        const uint64_t t_sample = timing && !fine && shape.chained ? env_u64(h, "MXG_TIMING_SAMPLE", 1) : 1;
+        TimingGuard timing_guard(timing, timing && (t_sample <= 1 || (h->timing_batches++ % t_sample) == 0));
+        SparseBatch b{a, T, g, shape, tau_hi, (uint32_t)wave_cap, cand_hint, bs_bitmap, report};
+        int rc;
+        if ((rc = sparse_reserve(b)) != MXG_OK) return rc;
+        *n_cap_out = b.n_cap;
+        if ((rc = sparse_count(b)) != MXG_OK) return rc;
+        if ((rc = sparse_reorder(b)) != MXG_OK) return rc;
+        if ((rc = sparse_resolve(b)) != MXG_OK) return rc;
+        return sparse_emit(b, out);
     }
 
     // ---- k = 32 route (sketch_bs.hip): the assembly's filter bitmap is in a->d_bs_out (bs_hash, enqueued by the caller on
@@ -2622,160 +2635,185 @@ struct Driver {
     {
         return bs_select_geom(a->S_sparse, a->sel_H, h->cfg.w, frac, g.n_strips, (uint32_t)env_u64(h, "MXG_SEL_QCAP", 0), (uint32_t)env_u64(h, "MXG_SEL_RK", 0));
     }
-    // The slice kernel's control block cleared ahead of the filter that precedes it on this stream (the filter does not touch it):
-    // filter and slice kernel then follow one another without a fill between them (two idle spells of ~6 us per assembly).
-    bool ctrl_cleared = false;
+    struct SelBatch {  // what the phases of enqueue_sel share
+        Assembly *a; const Tables &T; const BatchGeom &g; const BsSelGeom &b; const BatchShape &shape;
+        uint32_t tau_hi, *report;
+        SliceCtrlLayout ctrl;
+        uint32_t n_ent;  // entries the slices have room for: one per selected candidate
+        // the stretches between two candidates of a slice go to k_sel_stretch (MXG_SEL_INLINE=0: all stretches through k_gap_fix)
+        uint32_t inl_amax;
+        // (the upper part of the stretch array holds the requests for k_sel_stretch, two entries each)
+        static constexpr uint32_t gap_cap = GAP_CAP - SEL_IREQ_CAP;
+    };
+    // (pieces only where the host's route for what k_gap_fix hands over knows them: the tile kernel)
+    uint32_t sel_gap_nmax(const BatchShape &shape) const
+    {
+        return shape.dev_gaps && h->cfg.w <= ST_WMAX && !knob_set(h, "MXG_STRETCH_DENSE") && !knob_set(h, "MXG_GAP_WHOLE") ? GAP_DEV_NMAX : 0u;
+    }
+    // The slice kernel's control block (SliceCtrlLayout) cleared ahead of the filter that precedes it on this stream (the filter
+    // does not touch it): filter and slice kernel then follow one another without a fill between them (two idle spells of ~6 us
+    // per assembly).  sel_reserve skips its fill only for exactly these bytes.
+    size_t sel_ctrl_cleared = 0;  // bytes zeroed ahead (0: none)
     int clear_sel_ctrl(const BsSelGeom &b)
     {
         int rc;
         if ((rc = flush_emit(nullptr)) != MXG_OK) return rc;  // (this driver's scratch is about to be reused)
-        const size_t ctrl_bytes = ((size_t)CTRL_WORDS + sup_words(b.n_slices) + 2 * 64 * 32) * 4;
-        MXG_HIP(h, sc(SC_CTRL).ensure(ctrl_bytes));
-        MXG_HIP(h, hipMemsetAsync(sc(SC_CTRL).p, 0, ctrl_bytes, st));
-        ctrl_cleared = true;
+        const size_t bytes = slice_layout(b).bytes();
+        MXG_HIP(h, sc(SC_CTRL).ensure(bytes));
+        MXG_HIP(h, hipMemsetAsync(sc(SC_CTRL).p, 0, bytes, st));
+        sel_ctrl_cleared = bytes;
         return MXG_OK;
     }
-    int enqueue_sel(Assembly *a, const Tables &T, const BatchGeom &g, const BsSelGeom &b, uint32_t tau_hi, OutArrays &out,
-                    uint32_t *ctrl_host, const ChainIO *io)
+    // On return: an emit this driver held back is on the stream, the batch's scratch is reserved, and its control block with
+    // the super-counts, candidate counters and tickets is zero or the fill that zeroes it is on the stream.
+    int sel_reserve(const SelBatch &s)
     {
         int rc;
         if ((rc = flush_emit(nullptr)) != MXG_OK) return rc;  // (this driver's scratch is about to be reused)
         MXG_HIP(h, sc(SC_GAPS).ensure((size_t)GAP_CAP * 16));
-        n_wave_sup = 0;
-        const size_t ctrl_bytes = ((size_t)CTRL_WORDS + sup_words(b.n_slices) + 2 * 64 * 32) * 4;  // + the candidate counters
-        MXG_HIP(h, sc(SC_CTRL).ensure(ctrl_bytes));
-        MXG_HIP(h, sc(SC_CNT256).ensure((size_t)b.n_slices * 4 + 64));
-        const size_t n_ent = (size_t)b.n_slices * b.rk;
-        MXG_HIP(h, sc(SC_CS_H).ensure(n_ent * 16));  // (one 16-byte entry per selected candidate: EmitParams::cs_aos)
+        MXG_HIP(h, sc(SC_CTRL).ensure(s.ctrl.bytes()));
+        MXG_HIP(h, sc(SC_CNT256).ensure((size_t)s.b.n_slices * 4 + 64));
+        MXG_HIP(h, sc(SC_CS_H).ensure((size_t)s.n_ent * 16));  // (one 16-byte entry per selected candidate: EmitParams::cs_aos)
         // regions for the slices that outgrow their LDS queue (SC_CAND_H / SC_CAND_K: this route has no candidate arrays)
-        const size_t ovf_ent = (size_t)b.n_ovf * (b.ovf_cap + 2 * SEL_PAD);
+        const size_t ovf_ent = (size_t)s.b.n_ovf * (s.b.ovf_cap + 2 * SEL_PAD);
         MXG_HIP(h, sc(SC_CAND_H).ensure(ovf_ent * 8));
         MXG_HIP(h, sc(SC_CAND_K).ensure(ovf_ent * 4));
-        if (!ctrl_cleared) MXG_HIP(h, hipMemsetAsync(sc(SC_CTRL).p, 0, ctrl_bytes, st));
-        ctrl_cleared = false;
+        if (sel_ctrl_cleared != s.ctrl.bytes()) MXG_HIP(h, hipMemsetAsync(sc(SC_CTRL).p, 0, s.ctrl.bytes(), st));
+        sel_ctrl_cleared = 0;
+        return MXG_OK;
+    }
+    // On return: k_bs_select is on the stream in a span of its own (kind 2, in either timing mode: bench.py's roofline object
+    // times it inside the timed region), and behind it the record of ev_sel_done, where the next assembly's filter may start.
+    int sel_slices(const SelBatch &s)
+    {
+        int rc;
         // (fine timing: the slice kernel is booked where the other route books count + reorder, the stretch kernels where it books
         // resolve + stretches)
-        // (the slice kernel has a span of its own in either timing mode: bench.py's roofline object times it inside the timed region)
         if ((rc = ev_begin(0, false, 2)) != MXG_OK) return rc;
         BsSelParams bp{};
-        bp.bm = a->d_bs_out.as<uint32_t>() + 4;  // (BS_OUT_PAD)
-        bp.packed = a->d_packed;
-        bp.runx = a->d_runx.as<RunX>();
-        bp.strip_run = T.d_strip_run;
-        bp.ctg_drop = T.d_ctg_drop;
+        bp.bm = s.a->d_bs_out.as<uint32_t>() + 4;  // (BS_OUT_PAD)
+        bp.packed = s.a->d_packed;
+        bp.runx = s.a->d_runx.as<RunX>();
+        bp.strip_run = s.T.d_strip_run;
+        bp.ctg_drop = s.T.d_ctg_drop;
         bp.ptab = h->d_init_tab.as<uint4>() + 256;
-        bp.n_strips_asm = (*T.strip0_sparse)[T.runs->size()];
-        bp.strip_lo = g.strip_lo;
-        bp.strip_hi = g.strip_hi;
-        bp.S = a->S_sparse;
-        bp.H = b.H;
-        bp.T = b.T;
-        bp.n_slices = b.n_slices;
+        bp.n_strips_asm = (*s.T.strip0_sparse)[s.T.runs->size()];
+        bp.strip_lo = s.g.strip_lo;
+        bp.strip_hi = s.g.strip_hi;
+        bp.S = s.a->S_sparse;
+        bp.H = s.b.H;
+        bp.T = s.b.T;
+        bp.n_slices = s.b.n_slices;
         bp.w = h->cfg.w;
-        bp.tau = (uint64_t)tau_hi << 32;
-        bp.qcap = b.qcap;
+        bp.tau = (uint64_t)s.tau_hi << 32;
+        bp.qcap = s.b.qcap;
         bp.ovf_h = sc(SC_CAND_H).as<uint64_t>();
         bp.ovf_e = sc(SC_CAND_K).as<uint32_t>();
-        bp.ovf_cap = b.ovf_cap;
-        bp.n_ovf = b.n_ovf;
-        bp.ovf_next = sc(SC_CTRL).as<uint32_t>() + CW_REGION_TICKET;
-        bp.rk = b.rk;
+        bp.ovf_cap = s.b.ovf_cap;
+        bp.n_ovf = s.b.n_ovf;
+        bp.ovf_next = ctrl_word(CW_REGION_TICKET);
+        bp.rk = s.b.rk;
         bp.cs = sc(SC_CS_H).as<uint4>();
         bp.cnt = sc(SC_CNT256).as<uint32_t>();
-        bp.sup = sel_sup(0);
+        bp.sup = ctrl_word(s.ctrl.sup);
         bp.gaps = sc(SC_GAPS).as<uint4>();
-        // (the upper part of the stretch array holds the requests for k_sel_stretch, two entries each)
-        bp.gap_cap = GAP_CAP - SEL_IREQ_CAP;
-        bp.ireq = sc(SC_GAPS).as<uint4>() + bp.gap_cap;
+        bp.gap_cap = s.gap_cap;
+        bp.ireq = sc(SC_GAPS).as<uint4>() + s.gap_cap;
         bp.ireq_cap = sel_ireq_cap(h);  // (k_sel_stretch reads SEL_IREQ_SPARE entries from any request on: the array's layout does not move)
-        // (pieces only where the host's route for what k_gap_fix hands over knows them: the tile kernel)
-        bp.gap_nmax = (io && io->dev_gaps && h->cfg.w <= ST_WMAX && !knob_set(h, "MXG_STRETCH_DENSE") && !knob_set(h, "MXG_GAP_WHOLE")) ? GAP_DEV_NMAX : 0u;
+        bp.gap_nmax = sel_gap_nmax(s.shape);
         bp.ctrl = sc(SC_CTRL).as<uint32_t>();
-        bp.cand_spread = sel_sup(0) + sup_words(b.n_slices);
+        bp.cand_spread = ctrl_word(s.ctrl.cand_spread);
         bp.ablate = (uint32_t)env_u64(h, "MXG_SEL_ABLATE", 0);  // (profiling only: stop every slice after phase n)
-        // the stretches between two candidates of a slice go to k_sel_stretch (MXG_SEL_INLINE=0: all stretches through k_gap_fix)
-        bp.inl_amax = knob_u64(h, "MXG_SEL_INLINE", 1) && b.n_slices < (1u << 24) ? bs_select_inline_amax(h->cfg.w) : 0u;
-        if ((rc = launch_bs_select(h, bp, b, st)) != MXG_OK) return rc;
-        // (the next assembly's filter may start here; MXG_STAGGER=2, an experiment: behind this batch's emit instead, below)
-        const bool late = knob_u64(h, "MXG_STAGGER", 1) == 2;
-        if (h->ev_sel_done[slot] && !late) MXG_HIP(h, hipEventRecord(h->ev_sel_done[slot], st));
-        h->stat_sel_slices += b.n_slices;
-        const bool dev = io && io->dev_gaps;
-        if (timing && !fine) {  // the rest of the batch (stretches, emit) as one span
+        bp.inl_amax = s.inl_amax;
+        if ((rc = launch_bs_select(h, bp, s.b, st)) != MXG_OK) return rc;
+        // (the next assembly's filter may start here; MXG_STAGGER=2, an experiment: behind this batch's emit instead, sel_emit)
+        if (h->ev_sel_done[slot] && knob_u64(h, "MXG_STAGGER", 1) != 2) MXG_HIP(h, hipEventRecord(h->ev_sel_done[slot], st));
+        h->stat_sel_slices += s.b.n_slices;
+        return MXG_OK;
+    }
+    // On return: the span of the batch's rest is open (stretches and emit as one span; fine timing: kind 3, booked with the
+    // stretch kernels) and k_sel_stretch, if the batch takes stretches that way, is on the stream.
+    int sel_stretches(const SelBatch &s)
+    {
+        int rc;
+        if (timing && !fine) {
             if ((rc = ev_end()) != MXG_OK || (rc = ev_begin(0, false, 1)) != MXG_OK) return rc;
         }
         if ((rc = ev_next(3)) != MXG_OK) return rc;
-        // (booked with the stretch kernels: the slice kernel's span is its own)
-        if (bp.inl_amax) {
-            SelStretchParams sp{};
-            sp.packed = bp.packed;
-            sp.runs = T.d_runs;
-            sp.ctg_run0 = T.d_ctg_run0;
-            sp.ctg_drop = T.d_ctg_drop;
-            sp.byte_tab = h->d_init_tab.as<uint4>();
-            sp.tab = h->tab;
-            sp.w = bp.w;
-            sp.amax = bp.inl_amax;
-            sp.rk = bp.rk;
-            sp.cs = bp.cs;
-            sp.cnt = bp.cnt;
-            sp.sup = bp.sup;
-            sp.ireq = bp.ireq;
-            sp.ireq_cap = bp.ireq_cap;
-            sp.n_slices = bp.n_slices;
-            sp.ctrl = bp.ctrl;
-            sp.tickets = bp.cand_spread + 64 * 32;
-            sp.ablate = (uint32_t)env_u64(h, "MXG_SST_ABLATE", 0);
-            sp.gaps = bp.gaps;
-            sp.gap_cap = bp.gap_cap;
-            sp.gap_nmax = bp.gap_nmax;
-            if ((rc = launch_sel_stretch(h, sp, st)) != MXG_OK) return rc;
-        }
-        if (dev && (rc = enqueue_dev_gaps(a, T, ctrl_host)) != MXG_OK) return rc;
-        if (defer_emit && io && !io->wait && !io->base_in && !io->base_out) {
+        if (!s.inl_amax) return MXG_OK;
+        SelStretchParams sp{};
+        sp.packed = s.a->d_packed;
+        sp.runs = s.T.d_runs;
+        sp.ctg_run0 = s.T.d_ctg_run0;
+        sp.ctg_drop = s.T.d_ctg_drop;
+        sp.byte_tab = h->d_init_tab.as<uint4>();
+        sp.tab = h->tab;
+        sp.w = h->cfg.w;
+        sp.amax = s.inl_amax;
+        sp.rk = s.b.rk;
+        sp.cs = sc(SC_CS_H).as<uint4>();
+        sp.cnt = sc(SC_CNT256).as<uint32_t>();
+        sp.sup = ctrl_word(s.ctrl.sup);
+        sp.ireq = sc(SC_GAPS).as<uint4>() + s.gap_cap;
+        sp.ireq_cap = sel_ireq_cap(h);
+        sp.n_slices = s.b.n_slices;
+        sp.ctrl = sc(SC_CTRL).as<uint32_t>();
+        sp.tickets = ctrl_word(s.ctrl.tickets);
+        sp.ablate = (uint32_t)env_u64(h, "MXG_SST_ABLATE", 0);
+        sp.gaps = sc(SC_GAPS).as<uint4>();
+        sp.gap_cap = s.gap_cap;
+        sp.gap_nmax = sel_gap_nmax(s.shape);
+        return launch_sel_stretch(h, sp, st);
+    }
+    // On return: k_emit is on the stream behind the wait for the batch before this one, or held back for flush_emit; either
+    // way the span of the batch's rest is closed.
+    int sel_emit(const SelBatch &s, const OutArrays &out)
+    {
+        int rc;
+        const HeldEmit e{&s.T, s.shape, EmitSource::slices(s.ctrl, s.b.rk, s.n_ent), s.n_ent, out, out.n, s.report};
+        if (s.shape.may_hold_emit && !s.shape.wait && !s.shape.base_in && !s.shape.base_out) {
             // the emit is held back (flush_emit): the caller enqueues it behind the NEXT assembly's slice kernel -- enqueued here it
             // would start when that assembly's filter lets go of the GPU and land on its slice kernel, whose blocks need whole CUs
             // (rocprofv3, round 5: 529 us for the target's launch against 450 for the reference's) -- so that it runs beside that
             // assembly's stretch kernels instead, which leave the GPU idle
-            if ((rc = ev_end()) != MXG_OK) return rc;
-            const Tables *Tp = &T;
-            DevBuf *oh = out.hash, *op = out.pos, *orc = out.rec, *of = out.fwd;
-            const uint64_t on = out.n;
-            const ChainIO ioc = *io;
-            const uint32_t rk = b.rk, gc = gcap, np = n_place;
-            uint32_t *const no = n_out;
-            const uint32_t *cs = bp.cand_spread;
-            pending_emit = [=](hipEvent_t behind) -> int {
-                int rc2;
-                if (behind) MXG_HIP(h, hipStreamWaitEvent(st, behind, 0));
-                if ((rc2 = ev_begin(0, false, fine ? 4 : 1)) != MXG_OK) return rc2;
-                const uint32_t gc0 = gcap, np0 = n_place;
-                uint32_t *const no0 = n_out;
-                gcap = gc; n_place = np; n_out = no;
-                rc2 = emit(a->d_packed, *Tp, (uint32_t)n_ent, *oh, *op, *orc, *of, on, true, ctrl_host, &ioc, rk, (uint32_t)n_ent, cs);
-                gcap = gc0; n_place = np0; n_out = no0;
-                if (rc2 != MXG_OK) return rc2;
-                return ev_end();
-            };
-            return MXG_OK;
+            held_emit = e;
+            return ev_end();
         }
         if ((rc = ev_next(4)) != MXG_OK) return rc;
-        if (io && io->wait) MXG_HIP(h, hipStreamWaitEvent(st, io->wait, 0));
-        rc = emit(a->d_packed, T, (uint32_t)n_ent, *out.hash, *out.pos, *out.rec, *out.fwd, out.n, true, ctrl_host, io, b.rk,
-                  (uint32_t)n_ent, bp.cand_spread);
-        if (rc != MXG_OK) return rc;
-        if (h->ev_sel_done[slot] && late) MXG_HIP(h, hipEventRecord(h->ev_sel_done[slot], st));
+        if (s.shape.wait) MXG_HIP(h, hipStreamWaitEvent(st, s.shape.wait, 0));
+        if ((rc = emit(*e.T, e.shape, e.src, e.n_cap, e.out, e.out_base, e.report)) != MXG_OK) return rc;
+        if (h->ev_sel_done[slot] && knob_u64(h, "MXG_STAGGER", 1) == 2) MXG_HIP(h, hipEventRecord(h->ev_sel_done[slot], st));
         return ev_end();
     }
-    // the emit enqueue_sel held back, now: behind `behind` (an event of another stream) if given
-    std::function<int(hipEvent_t)> pending_emit;
-    bool defer_emit = false;
+    int enqueue_sel(Assembly *a, const Tables &T, const BatchGeom &g, const BsSelGeom &b, const BatchShape &shape, uint32_t tau_hi,
+                    const OutArrays &out, uint32_t *report)
+    {
+        const uint32_t inl_amax = knob_u64(h, "MXG_SEL_INLINE", 1) && b.n_slices < (1u << 24) ? bs_select_inline_amax(h->cfg.w) : 0u;
+        const SelBatch s{a, T, g, b, shape, tau_hi, report, slice_layout(b), b.n_slices * b.rk, inl_amax};
+        int rc;
+        if ((rc = sel_reserve(s)) != MXG_OK) return rc;
+        if ((rc = sel_slices(s)) != MXG_OK) return rc;
+        if ((rc = sel_stretches(s)) != MXG_OK) return rc;
+        if (shape.dev_gaps && (rc = enqueue_dev_gaps(a, T, shape, report)) != MXG_OK) return rc;
+        return sel_emit(s, out);
+    }
+    // The one call of emit that sel_emit held back, and the report slot it writes.  flush_emit enqueues it: behind `behind` (an
+    // event of another stream) if given, in a span of its own (kind 4 with fine timing, else 1).
+    struct HeldEmit {
+        const Tables *T; BatchShape shape; EmitSource src;
+        uint32_t n_cap; OutArrays out; uint64_t out_base; uint32_t *report;
+    };
+    std::optional<HeldEmit> held_emit;
     int flush_emit(hipEvent_t behind)
     {
-        if (!pending_emit) return MXG_OK;
-        auto f = std::move(pending_emit);
-        pending_emit = nullptr;
-        return f(behind);
+        if (!held_emit) return MXG_OK;
+        const HeldEmit e = *held_emit;
+        held_emit.reset();
+        int rc;
+        if (behind) MXG_HIP(h, hipStreamWaitEvent(st, behind, 0));
+        if ((rc = ev_begin(0, false, fine ? 4 : 1)) != MXG_OK) return rc;
+        if ((rc = emit(*e.T, e.shape, e.src, e.n_cap, e.out, e.out_base, e.report)) != MXG_OK) return rc;
+        return ev_end();
     }
 
     // Second half of a sparse batch, after the host has read the report `r` of a run that did not overflow:
@@ -2787,6 +2825,7 @@ struct Driver {
         const uint64_t n_cand = r.n_cand();
         uint32_t n_gaps = r.n_stretches();
         const uint64_t total = r.n_selected();
+        const EmitSource src = EmitSource::resolve(cand_layout(g.n_waves, n_cap), RK);  // (where enqueue_sparse left the batch)
         h->stat_candidates += n_cand;
         a->cand_hint = (uint32_t)std::min<uint64_t>(n_cand, 0xFFFFFFFFull);
         int rc;
@@ -2804,7 +2843,7 @@ struct Driver {
         if (n_gaps == 0) {
             if (out.n + total > out.cap()) {  // the speculative emit did not fit: grow, emit again
                 if ((rc = out_reserve(h, out, out.n + total, st)) != MXG_OK) return rc;
-                if ((rc = emit(a->d_packed, T, n_cap, *out.hash, *out.pos, *out.rec, *out.fwd, out.n, true)) != MXG_OK) return rc;
+                if ((rc = emit(T, BatchShape{}, src, n_cap, out, out.n, nullptr)) != MXG_OK) return rc;
             }
             out.n += total;
         } else {
@@ -2813,7 +2852,8 @@ struct Driver {
             MXG_HIP(h, sc(SC_ST_POS).ensure(std::max<uint64_t>(total * 4, 16)));
             MXG_HIP(h, sc(SC_ST_REC).ensure(std::max<uint64_t>(total * 4, 16)));
             MXG_HIP(h, sc(SC_ST_FWD).ensure(std::max<uint64_t>(total, 16)));
-            if ((rc = emit(a->d_packed, T, n_cap, sc(SC_ST_HASH), sc(SC_ST_POS), sc(SC_ST_REC), sc(SC_ST_FWD), 0, true)) != MXG_OK) return rc;
+            const OutArrays staging{&sc(SC_ST_HASH), &sc(SC_ST_POS), &sc(SC_ST_REC), &sc(SC_ST_FWD), 0};
+            if ((rc = emit(T, BatchShape{}, src, n_cap, staging, 0, nullptr)) != MXG_OK) return rc;
             uint64_t n_gap_mx = 0;
             if ((rc = process_gaps(a, T, gaps, &n_gap_mx)) != MXG_OK) return rc;
             if (total + n_gap_mx >= (1ull << 32)) return set_err(h, MXG_ELIMIT, "batch sketch too large to merge");
@@ -2980,7 +3020,9 @@ struct Driver {
             for (int attempt = 0;; ++attempt) {
                 uint32_t n_cap_now = 0;
                 std::fill_n(ctrl, REPORT_WORDS, REPORT_UNSET);
-                int rc = enqueue_sparse(a, T, g, wave_cap, tau_hi, out, ctrl, &n_cap_now);
+                BatchShape shape;  // (the host waits for the batch: its grids cover the arrays' capacity)
+                shape_sparse(shape, g, wave_cap, tau_hi, 0xFFFFFFFFu);
+                int rc = enqueue_sparse(a, T, g, shape, wave_cap, tau_hi, out, ctrl, &n_cap_now);
                 if (rc != MXG_OK) return rc;
                 n_cap64 = n_cap_now;
                 MXG_HIP(h, stream_wait(st));
@@ -3401,7 +3443,7 @@ struct AsmCut {
 // Every assembly is cut into batches of whole records (SPARSE_BATCH_KMERS) and EVERY batch of EVERY assembly is enqueued
 // completely -- hash -> order -> resolve (-> stretches on the device) -> emit -- alternating between the handle's two
 // streams with their own scratch, before the host waits once for both streams.  A batch starts in the assembly's sketch
-// where the batches before it end: that sum travels through a device word (ChainIO), and a batch whose predecessor ran on
+// where the batches before it end: that sum travels through a device word (BatchShape::base_in), and a batch whose predecessor ran on
 // the other stream waits for it just before its emit, so its hash / order / resolve kernels overlap the predecessor's
 // latency-bound tail.  What did not end the common way (arena overflow, stretches the device route could not hold,
 // output beyond its estimate) is redone afterwards: from the candidate arrays when they are still intact in the
@@ -3597,39 +3639,41 @@ struct SketchStep {
         }
         it.hc = report_slot(h, items.size());
         std::fill_n(it.hc, REPORT_WORDS, REPORT_UNSET);
-        Driver::ChainIO io;
-        io.dev_gaps = plan.dev_gaps;
-        {   // placing blocks for twice the stretches the plan expects of this batch (+ 256), at most for all the arrays hold; a
-            // batch that meets more than its launch can place reports so and is enqueued again with the density it met
-            const double expect = plan.gap_rate * (double)it.g.nk;
-            const uint32_t place4 = (uint32_t)std::min<double>((double)plan.gcap, 2.0 * expect + 256.0);
-            drv.set_gaps(plan.gcap, a->gap_rate_hint > 0 ? (place4 + 3u) / 4u : plan.gcap / 4u, a->gap_rate_hint > 0 ? expect : -1.0);
-            if (const uint64_t forced = knob_u64(h, "MXG_GAP_PLACE", 0))  // test knob: placing blocks for this many stretches
-                drv.set_gaps(plan.gcap, (uint32_t)std::min<uint64_t>((forced + 3u) / 4u, plan.gcap / 4u));
-            it.place4 = 4u * drv.n_place;
-        }
+        BatchShape shape;
+        shape.chained = true;
+        shape.dev_gaps = plan.dev_gaps;
+        // (a batch that meets more stretches than its launch can place reports so and is enqueued again with the density it met)
+        const GapPlacing gp = gap_placing(plan.gcap, plan.gap_rate, it.g.nk, a->gap_rate_hint, knob_u64(h, "MXG_GAP_PLACE", 0));
+        shape.gcap = plan.gcap;
+        shape.n_place = gp.n_place;
+        shape.gap_expect = gp.gap_expect;
+        it.place4 = gp.place4;
         // tiles of 32 slices in k_emit (0.18 against 0.21 ms per step at 3 Gbp + 3 Gbp) unless stretches are so dense that
         // most tiles of that size would hold one (the tile then searches the stretch keys per minimizer: repeat-rich
         // sequence is 2 % slower with 32, 6 % with 64; tools/sweep_emit_ecb.sh)
-        io.ecb = plan.gap_rate * 32.0 * 64.0 * a->S_sparse < 0.5 ? 32u : 16u;
+        shape.ecb = plan.gap_rate * 32.0 * 64.0 * a->S_sparse < 0.5 ? 32u : 16u;
         uint64_t *chain = h->d_chain.as<uint64_t>();
-        io.base_in = b == 0 ? nullptr : chain + (items.size() - 1);
-        io.base_out = c.gs.size() > 1 ? chain + items.size() : nullptr;
+        shape.base_in = b == 0 ? nullptr : chain + (items.size() - 1);
+        shape.base_out = c.gs.size() > 1 ? chain + items.size() : nullptr;
         if (b > 0 && drvs[items.back().slot] != &drv) {  // predecessor on the other stream: wait for its count before the emit
-            if ((rc = lazy_event_at(h, h->ev_sync, items.size(), &io.wait)) != MXG_OK) return rc;
-            MXG_HIP(h, hipEventRecord(io.wait, drvs[items.back().slot]->st));
+            if ((rc = lazy_event_at(h, h->ev_sync, items.size(), &shape.wait)) != MXG_OK) return rc;
+            MXG_HIP(h, hipEventRecord(shape.wait, drvs[items.back().slot]->st));
         }
-        drv.n_out = chain_modes ? h->d_nmx.as<uint32_t>() + i : nullptr;
+        shape.n_out = chain_modes ? h->d_nmx.as<uint32_t>() + i : nullptr;
         if (c.sel_ok) {
-            drv.defer_emit = defer_emits && !chain_modes && c.gs.size() == 1 && !one_stream;
-            if ((rc = drv.enqueue_sel(a, runs[i].T, it.g, c.bgs[b], plan.tau_hi, out, it.hc, &io)) != MXG_OK) return rc;
+            shape.may_hold_emit = defer_emits && !chain_modes && c.gs.size() == 1 && !one_stream;
+            if ((rc = drv.enqueue_sel(a, runs[i].T, it.g, c.bgs[b], shape, plan.tau_hi, out, it.hc)) != MXG_OK) return rc;
             // the emits other drivers hold back (the assembly before this one): behind this slice kernel
             for (Driver *od : drvs)
                 if (od != &drv && (rc = od->flush_emit(h->ev_sel_done[sl])) != MXG_OK) return rc;
             last_sel_slot = (int)sl;
-        } else if ((rc = drv.enqueue_sparse(a, runs[i].T, it.g, drv.default_wave_cap(a->S_sparse, plan.frac), plan.tau_hi, out, it.hc,
-                                            &it.n_cap, &io, a->cand_hints[b], c.use_bs ? a->d_bs_out.as<uint32_t>() + 4 : nullptr)) != MXG_OK)
-            return rc;
+        } else {
+            const uint64_t wave_cap = drv.default_wave_cap(a->S_sparse, plan.frac);
+            drv.shape_sparse(shape, it.g, wave_cap, plan.tau_hi, a->cand_hints[b]);
+            if ((rc = drv.enqueue_sparse(a, runs[i].T, it.g, shape, wave_cap, plan.tau_hi, out, it.hc, &it.n_cap, a->cand_hints[b],
+                                         c.use_bs ? a->d_bs_out.as<uint32_t>() + 4 : nullptr)) != MXG_OK)
+                return rc;
+        }
         last_on_slot[sl] = items.size();
         items.push_back(it);
         return MXG_OK;

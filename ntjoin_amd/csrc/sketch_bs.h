@@ -53,7 +53,7 @@ struct BsSelParams {
     uint4 *gaps;
     uint32_t gap_cap;
     uint32_t gap_nmax;           // k-mers of the longest stretch reported in one piece (0: any); see sel_push_gap
-    uint32_t *cand_spread;       // 64 counters, 32 words apart: the slices' own candidates (k_emit adds them up for the report)
+    uint32_t *cand_spread;       // a row of SPREAD_WORDS (batch_ctrl.h: 64 counters, 32 words apart; SliceCtrlLayout::cand_spread): the slices' own candidates (k_emit adds them up for the report)
     uint32_t *ctrl;              // CW_STRETCHES, CW_REDO, CW_SLICE_GAVE_UP, CW_SEL_REQS (batch_ctrl.h)
     uint32_t ablate;             // (profiling builds: every slice stops after phase n; 0 = run)
     // inl_amax != 0: a slice's stretches become requests for k_sel_stretch, {contig, first, last k-mer, slice | number in the
@@ -78,7 +78,7 @@ struct SelStretchParams {
     uint32_t ireq_cap;
     uint32_t n_slices;           // slices of the batch: an entry that names another one is stepped over (sel_req_is_first)
     uint32_t *ctrl;              // CW_SEL_REQS requests, CW_STRETCHES (what does not fit here goes on to k_gap_fix)
-    uint32_t *tickets;           // 64 counters, 32 words apart, zero: request 64 t + c is handed out by ticket t of counter c
+    uint32_t *tickets;           // a row of SPREAD_WORDS (SliceCtrlLayout::tickets), zero: request 64 t + c is handed out by ticket t of counter c
     uint4 *gaps;
     uint32_t gap_cap, gap_nmax;
     uint32_t ablate;             // (profiling only, MXG_SST_ABLATE: 1 no rolls, 2 no first hash, 4 no window scans, 8 nothing per request, 32 no row update)

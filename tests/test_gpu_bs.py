@@ -7,6 +7,8 @@
     same records, bit for bit, with the statistics saying which route ran;
   * slices that outgrow their LDS queue (MXG_SEL_QCAP) work in global memory, and a batch without a region left is redone;
   * inputs the filter does not take (k != 32, the min(fwd, rev) variant) still go the old way;
+  * the k_emit that a single-batch assembly holds back for the next assembly's slice kernel (MXG_DEFER_EMIT, MXG_STAGGER): the same
+    sketches as with every emit in its own place;
   * the request array of k_sel_stretch at its capacity (MXG_SEL_IREQ_CAP; csrc/sel_requests.h): every capacity from one request to
     one more than a small input makes, batches that walk what earlier batches and other assemblies left in the array, realistic
     records at a handful of capacities, the fused call -- no stale request is taken, no minimizer comes out twice.
@@ -23,7 +25,7 @@ from tests.test_gpu_scale_paths import _check, _records
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROUTE_KNOBS = ("MXG_GAP_POOL", "MXG_BS", "MXG_BS_SELECT", "MXG_SEL_QCAP", "MXG_SEL_RK", "MXG_GAP_WHOLE", "MXG_GAP_DEV_CAP", "MXG_SPARSE_BATCH_KMERS", "MXG_WAVE_CAP", "MXG_SPARSE_S", "MXG_DEV_GAPS", "MXG_SEL_INLINE",
-               "MXG_SEL_IREQ_CAP")
+               "MXG_SEL_IREQ_CAP", "MXG_DEFER_EMIT", "MXG_STAGGER")
 
 
 @pytest.fixture
@@ -308,6 +310,35 @@ def test_knobs_are_read_once_per_handle_and_reported(oracle, env):
         eng.add_records("x", 1.0, recs)
         eng.sketch()
         assert eng.stats()["select_slices"] > 0 and "MXG_BS_SELECT=1" in eng.knobs()
+
+
+def test_held_back_emit_places_what_an_emit_in_place_does(oracle, env):
+    """Three single-batch assemblies on the slice route: the first two emits are held back and enqueued behind the NEXT assembly's
+    slice kernel, the last one at the end of the step (MXG_DEFER_EMIT=0: every emit in its own place; MXG_STAGGER=0: no filter
+    waits for a slice kernel, and nothing is held back).  MXG_DEV_GAPS=1, so that the placing blocks and the stretch capacity of
+    a batch travel with its held emit; _records has N runs and low-complexity islands longer than the window, which make
+    candidate-free stretches.  _records at w = 1000 is the smallest input on which this file asserts select_slices > 0
+    (test_select_route_is_the_default_for_small_inputs).  Knobs are parsed once per handle: a fresh handle per setting."""
+    from ntjoin_amd.engine import MxEngine
+    w = 1000
+    asms = [_records(700 + a) for a in range(3)]
+    want = [_expected(oracle, recs, 32, w) for recs in asms]
+    env["MXG_DEV_GAPS"] = "1"
+    for knob, value in ((None, None), ("MXG_DEFER_EMIT", "0"), ("MXG_STAGGER", "0")):
+        env.pop("MXG_DEFER_EMIT", None)
+        env.pop("MXG_STAGGER", None)
+        if knob:
+            env[knob] = value
+        with MxEngine(k=32, w=w) as eng:
+            for a, recs in enumerate(asms):
+                eng.add_records(f"asm{a}", 1.0, recs)
+            eng.sketch()
+            for a in range(len(asms)):
+                _assert_sketch(eng.get_sketch(a), want[a], (knob, a))
+            st = eng.stats()
+            if knob:
+                assert f"{knob}={value}" in eng.knobs().split(), "the handle did not read the knob"
+        assert st["select_slices"] > 0, (knob, "k_bs_select did not run")
 
 
 # ---------------------------------------------------------------------------------------------------------------
