@@ -211,7 +211,10 @@ __global__ __launch_bounds__(256) void kp_cycle_break(uint32_t nv, const uint32_
     if (r >= nv || sub[r] != r || sub_kind(s, r) != 2) return;
     uint32_t mv = (uint32_t)key[r];
     uint32_t a = nb[2 * mv], b = nb[2 * mv + 1];
-    uint32_t slot = pos_first[b] > pos_first[a] ? 1u : 0u;  // ties: first neighbour (stable sort, reverse=True)
+    // equal positions: the lower vertex index, not "the first slot" -- the slots fill in the order in which kp_edge_stats'
+    // atomics land, which differs from run to run
+    const uint32_t pa = pos_first[a], pb = pos_first[b];
+    uint32_t slot = (pb > pa || (pb == pa && b < a)) ? 1u : 0u;
     uint32_t hn = nb[2 * mv + slot], e = nbe[2 * mv + slot];
     alive[e] = 0;
     nb[2 * mv + slot] = NIL;

@@ -46,10 +46,41 @@ def _degrees(vertices, edges):
     return deg
 
 
-def find_paths(state, n):
-    """-> list (one entry per component of the globally filtered graph) of lists of paths (vertex names, source->target)"""
+def _bucket(groups, edges):
+    """edges of every vertex group, in the order of `edges` (one pass, not one scan of `edges` per group)"""
+    where = {v: i for i, grp in enumerate(groups) for v in grp}
+    out = [[] for _ in groups]
+    for e in edges:
+        out[where[e[0]]].append(e)
+    return out
+
+
+def _note(trace, key):
+    if trace is not None:
+        trace[key] = trace.get(key, 0) + 1
+
+
+def find_paths(state, n, trace=None):
+    """-> list (one entry per component of the globally filtered graph) of lists of paths (vertex names, source->target)
+
+    Equal positions: the reference leaves them to python's set order, so any fixed rule restates it.  The rules here, with
+    "index" = place in the order of state["vertices"]:
+      the ring's minimum-position vertex      lowest index among equals
+      its neighbour whose edge is cut         highest position, lowest index among equals
+      source / target of a chain              smallest / largest position, the later index among equals (so two endpoints
+                                              of equal position give source == target and no path)
+
+    trace (a dict or Counter), when given, counts
+      ("rounds", k)              components whose branch-filter loop ran k times (the first round never removes an edge: the
+                                 global filter has taken every edge below n already)
+      "ring_opened"              sub-components opened as a ring (they are counted again under their verdict)
+      "rejected_branched"        sub-components that still hold a vertex of degree > 2
+      "rejected_same_endpoint"   chains whose endpoints have equal positions (source == target)
+      "rejected_other"           a single vertex
+      "accepted"                 paths"""
     weights = state["weights"]
     vertices = list(state["vertices"])
+    index = {v: i for i, v in enumerate(vertices)}
     edges = [(s, t, w) for s, t, _sup, w in state["edges"]]
     if not n <= min(weights.values()):                      # filter_graph_global
         edges = [e for e in edges if not e[2] < n]
@@ -57,11 +88,12 @@ def find_paths(state, n):
     first_max = [a for a, wt in weights.items() if wt == max_w][0]   # sorted(..., reverse=True)[0]: stable -> first
     last_max = [a for a, wt in weights.items() if wt == max_w][-1]   # [...].pop() -> last
     info = state["list_mx_info"]
+    pos_first, pos_last = info[first_max], info[last_max]
+    total_w = sum(weights.values())
     out = []
-    for comp in _components(vertices, edges):
-        cset = set(comp)
-        cedges = [e for e in edges if e[0] in cset]
-        min_w, total_w = n, sum(weights.values())
+    comps = _components(vertices, edges)
+    for comp, cedges in zip(comps, _bucket(comps, edges)):
+        min_w, rounds = n, 0
         while True:                                           # find_paths_process: branch filtering
             deg = _degrees(comp, cedges)
             if all(d < 3 for d in deg.values()) or not min_w <= total_w:
@@ -69,44 +101,46 @@ def find_paths(state, n):
             branch = {v for v, d in deg.items() if d > 2}
             cedges = [e for e in cedges if not ((e[0] in branch or e[1] in branch) and e[2] < min_w)]
             min_w += 1
+            rounds += 1
+        _note(trace, ("rounds", rounds))
         paths = []
-        for sub in _components(comp, cedges):
-            sset = set(sub)
-            sedges = [e for e in cedges if e[0] in sset]
+        subs = _components(comp, cedges)
+        for sub, sedges in zip(subs, _bucket(subs, cedges)):
             deg = _degrees(sub, sedges)
+            if any(d > 2 for d in deg.values()):
+                _note(trace, "rejected_branched")
+                continue
             sources = [v for v in sub if deg[v] == 1]
             if not sources:                                   # check_circularity
                 if all(d == 2 for d in deg.values()):
-                    mv = min(sub, key=lambda v: info[first_max][v][1])
+                    mv = min(sub, key=lambda v: (pos_first[v][1], index[v]))
                     nbrs = [t if s == mv else s for s, t, _w in sedges if mv in (s, t)]
-                    hn = max(nbrs, key=lambda v: info[first_max][v][1])
+                    hn = min(nbrs, key=lambda v: (-pos_first[v][1], index[v]))
                     sedges = [e for e in sedges if {e[0], e[1]} != {mv, hn}]
                     sources = [mv, hn]
+                    _note(trace, "ring_opened")
             if len(sources) != 2:
+                _note(trace, "rejected_other")
                 continue
-            pos = {v: info[last_max][v][1] for v in sources}  # determine_source_vertex
+            sources.sort(key=index.get)
+            pos = {v: pos_last[v][1] for v in sources}       # determine_source_vertex
             source = [v for v in sources if pos[v] == min(pos.values())][-1]
             target = [v for v in sources if pos[v] == max(pos.values())][-1]
+            if source == target:
+                _note(trace, "rejected_same_endpoint")
+                continue
             adj = defaultdict(list)
             for s, t, _w in sedges:
                 adj[s].append(t)
                 adj[t].append(s)
-            prev, dq = {source: None}, deque([source])        # shortest path
-            while dq:
-                u = dq.popleft()
-                for x in adj[u]:
-                    if x not in prev:
-                        prev[x] = u
-                        dq.append(x)
-            if target not in prev:
-                continue
-            path, u = [], target
-            while u is not None:
-                path.append(u)
-                u = prev[u]
-            path.reverse()
-            if len(path) == len(sub) and len(path) - 1 == len(sedges) and len(path) == len(set(path)):
-                paths.append(path)
+            path, before = [source], None                     # shortest path = the walk along the chain
+            while path[-1] != target:
+                step = [x for x in adj[path[-1]] if x != before]
+                before = path[-1]
+                path.append(step[0])
+            assert len(path) == len(sub) and len(path) - 1 == len(sedges) and len(path) == len(set(path))
+            _note(trace, "accepted")
+            paths.append(path)
         out.append(paths)
     return out
 
