@@ -993,7 +993,19 @@ int write_tsv(mxg_handle *h, Assembly *a, const char *path, int with_pos, int wi
     int rc = sync_sketch_to_host(h, a);
     if (rc != MXG_OK) return rc;
     const uint32_t k = h->cfg.k;
-    if (with_seq && !a->has_text) {
+    // text that the device ingest left in HBM: fetched, so that this writer too spells the k-mers as the file does.  (Host memory:
+    // the file's size for the copy plus a byte per base for the sequences, against a quarter byte per base of the packed bases.
+    // Paid only here, on the rare route -- k > 200 or MXG_HOST_TSV=1 behind the device parser, which never loads a shard.)
+    std::string dev_seq;
+    std::vector<uint64_t> dev_seq_off;
+    const bool from_dev_text = with_seq && !a->has_text && a->text_on_device;
+    if (from_dev_text) {
+        if ((rc = fetch_device_text(h, a, dev_seq, dev_seq_off)) != MXG_OK) return rc;
+        for (size_t r = 0; r < a->recs.size(); ++r)  // (checked before the file is opened: a refusal leaves nothing behind)
+            for (uint64_t i = a->rec_first[r]; i < a->rec_first[r + 1]; ++i)
+                if (dev_seq_off[r] + a->h_pos[i] + k > dev_seq_off[r + 1])
+                    return set_err(h, MXG_EINVAL, "minimizer %llu of '%s' lies outside its record's text", (unsigned long long)i, a->name.c_str());
+    } else if (with_seq && !a->has_text) {
         if (!a->has_bases)
             return set_err(h, MXG_EINVAL, "assembly '%s' has no bases: cannot print k-mer sequences", a->name.c_str());
         if (a->h_packed.empty()) {  // fetch the packed bases back from HBM
@@ -1025,6 +1037,8 @@ int write_tsv(mxg_handle *h, Assembly *a, const char *path, int with_pos, int wi
                 o.put(':');
                 if (a->has_text) {
                     o.put(a->text.data() + (size_t)(rec.text_off + a->h_pos[i]), k);
+                } else if (from_dev_text) {
+                    o.put(dev_seq.data() + (size_t)(dev_seq_off[r] + a->h_pos[i]), k);
                 } else {
                     uint64_t b0 = rec.base_off + a->h_pos[i];
                     for (uint32_t j = 0; j < k; ++j) {

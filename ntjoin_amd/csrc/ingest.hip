@@ -12,7 +12,7 @@
 // exist).  The raw text stays in HBM, so the k-mer column of the TSV is printed exactly as the file spells it.
 //
 // TSV: entry lengths -> exclusive scan -> every byte of the file has a known offset; the text is produced in windows of
-// TSV_WIN bytes (double-buffered: the device formats window c+1 while the host writes window c).
+// 64 MiB (MXG_TSV_WIN: fewer, a test knob) (double-buffered: the device formats window c+1 while the host writes window c).
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -651,6 +651,35 @@ __global__ __launch_bounds__(256) void k_tsv_ids(const TsvParams p)
     if (p.rec_first[r + 1] == f) put_win(p, at, '\n');
 }
 
+// The sequences of a device-ingested assembly as the file spells them, line breaks removed, for the host writer: record r's bases
+// are seq[rec_off[r]], seq[rec_off[r] + 1], ...  (The whole text comes over at once: host memory of the file's size next to `seq`.)
+int fetch_device_text(mxg_handle *h, Assembly *a, std::string &seq, std::vector<uint64_t> &rec_off)
+{
+    const size_t n_rec = a->recs.size();
+    rec_off.assign(n_rec + 1, 0);
+    seq.clear();
+    if (!a->text_on_device || a->ing_item0.size() != n_rec + 1)
+        return set_err(h, MXG_EINVAL, "assembly '%s' holds no text on the device", a->name.c_str());
+    const size_t n_items = a->ing_item0[n_rec];
+    std::vector<IngItem> items(n_items);
+    std::vector<unsigned char> text(a->text_bytes);
+    MXG_HIP(h, hipSetDevice(h->device));
+    if (n_items) MXG_HIP(h, hipMemcpyAsync(items.data(), a->d_ing_items.p, n_items * sizeof(IngItem), hipMemcpyDeviceToHost, h->stream));
+    if (!text.empty()) MXG_HIP(h, hipMemcpyAsync(text.data(), a->d_text.p, text.size(), hipMemcpyDeviceToHost, h->stream));
+    MXG_HIP(h, hipStreamSynchronize(h->stream));
+    seq.reserve(a->total_bases);
+    for (size_t r = 0; r < n_rec; ++r) {
+        rec_off[r] = seq.size();
+        for (uint64_t q = a->ing_item0[r]; q < a->ing_item0[r + 1]; ++q) {
+            if (items[q].lo + items[q].len > text.size()) return set_err(h, MXG_EDEVICE, "internal error: text item out of range");
+            for (uint64_t at = items[q].lo; at < items[q].lo + items[q].len; ++at)
+                if (text[at] != '\n' && text[at] != '\r') seq.push_back((char)text[at]);
+        }
+    }
+    rec_off[n_rec] = seq.size();
+    return MXG_OK;
+}
+
 int write_tsv_device(mxg_handle *h, Assembly *a, const char *path, int with_pos, int with_strand, int with_seq)
 {
     if (!a->has_sketch) return set_err(h, MXG_EINVAL, "assembly '%s' has no sketch yet (call mxg_sketch)", a->name.c_str());
@@ -764,7 +793,10 @@ int write_tsv_device(mxg_handle *h, Assembly *a, const char *path, int with_pos,
     const bool regular = f != stdout && fstat(ofd, &sb) == 0 && S_ISREG(sb.st_mode);
     // (the NAME may still be a symbolic link to a regular file -- /dev/stdout redirected into one -- and is then left alone too)
     const bool removable = regular && lstat(path, &sb) == 0 && S_ISREG(sb.st_mode);
-    constexpr uint64_t WIN = 64ull << 20;
+    // MXG_TSV_WIN (test knob): bytes of text per window, 1 .. WIN_MAX; the two device windows and their halves of the pinned pool
+    // keep WIN_MAX bytes whatever it says
+    constexpr uint64_t WIN_MAX = 64ull << 20;
+    const uint64_t WIN = std::max<uint64_t>(1, std::min<uint64_t>(knob_u64(h, "MXG_TSV_WIN", WIN_MAX), WIN_MAX));
     // the file, the pinned windows and their events are released on every way out; a file left incomplete is removed
     struct Out {
         FILE *f;
@@ -791,13 +823,13 @@ int write_tsv_device(mxg_handle *h, Assembly *a, const char *path, int with_pos,
     char **pin = out.pin;
     hipEvent_t *ev = out.ev;
     bool ok = true;
-    static_assert(2 * WIN <= PIN_POOL_BYTES && WIN % PIN_PIECE_BYTES == 0, "the windows come out of the handle's pinned pool, whole pieces each");
+    static_assert(2 * WIN_MAX <= PIN_POOL_BYTES && WIN_MAX % PIN_PIECE_BYTES == 0, "the windows come out of the handle's pinned pool, whole pieces each");
     {
         unsigned char *pool = nullptr;
         MXG_HIP(h, pin_pool_get(h, &pool));
         for (int b = 0; b < 2; ++b) {
-            MXG_HIP(h, h->tsv_win[b].ensure(WIN));
-            pin[b] = reinterpret_cast<char *>(pool) + (size_t)b * WIN;
+            MXG_HIP(h, h->tsv_win[b].ensure(WIN_MAX));
+            pin[b] = reinterpret_cast<char *>(pool) + (size_t)b * WIN_MAX;
             MXG_HIP(h, hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
         }
     }

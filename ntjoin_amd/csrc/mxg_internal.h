@@ -384,6 +384,7 @@ int write_tsv(mxg_handle *h, Assembly *a, const char *path, int with_pos, int wi
 // ingest.hip: FASTA -> packed bases + run table on the device (1: not for this route, use load_fasta); TSV text on the device
 int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_threads);
 int write_tsv_device(mxg_handle *h, Assembly *a, const char *path, int with_pos, int with_strand, int with_seq);
+int fetch_device_text(mxg_handle *h, Assembly *a, std::string &seq, std::vector<uint64_t> &rec_off);  // (for the host TSV writer)
 uint32_t host_threads(const mxg_handle *h);
 // n_parts byte ranges written to fd at consecutive offsets from `off` on, by that many threads (host_io.cpp)
 bool put_parallel(int fd, uint64_t off, const char *const *data, const size_t *len, uint32_t n_parts);
