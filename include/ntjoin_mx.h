@@ -501,6 +501,46 @@ int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *no
    handle's and hold until its next mxg_write_scaffolds. */
 int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals);
 
+/* ---- next row (f7): the paths adjusted for relocations, --no_cut and overlapping regions ------------------------------------
+   What the reference's main_scaffolder (bin/ntjoin_assemble.py:751-786) does to the PathNodes between format_path and the
+   trimming / printing of the scaffolds, for all paths in one call, in its order:
+     1  tally_incorporated_segments (:220-230): per contig the set of (start, end) of the nodes of every path with two nodes or more;
+     2  merge_relocations (:126-172) over all paths in path order: adjacent nodes of one contig, both '+' and ascending or both '-'
+        and descending, become one (the chain's head takes the end / start, terminal_mx / first_mx and gap of the node merged into
+        it) unless a segment of the contig's set that shares neither end with either node touches the joined region (:115-123);
+     3  with no_cut, adjust_paths (:266-305): subsumed nodes leave (:253-264), another merge_relocations, then per node: the
+        contig's best region (:233-244) or only node becomes the whole contig, any other node of a contig in several nodes leaves
+        and, strictly inside its path, adds its length to the gap of the last kept node (clamped to G when G > 0);
+     4  tally_intersecting_segments (:661-686): per contig the segments of its set that intersect another one (half-open:
+        max(starts) < min(ends)), ascending by (start, end), resolved by OverlapRegion.find_non_overlapping (bin/overlap_region.py);
+        equal start: the smaller end first -- bedtools' sort leaves that order open, the rule is this library's;
+     5  merge_relocations again (print_scaffolds :550);
+     6  remove_overlapping_regions (:451-466): a node whose exact (start, end) phase 4 resolved is dropped or takes the replacement;
+     7  check_terminal_node_gap_zero (:441-448): gap 0 on every path's last node whose ori is not '?'.
+   Node i of path p is nodes[path_first[p] + i] as format_path made it; `record` is any index below 2^28 that names the target
+   contig (nodes of one contig carry one index), first_mx / terminal_mx are opaque tags.  The result is what print_scaffolds holds
+   at :555: the nodes of every path (a path may come back with one node or none), and per node the index of the input node it is
+   (the head of its merged chain).  The arrays of `out` are host copies owned by the handle, valid until its next
+   mxg_adjust_paths.  Sketches, graph and paths of the handle are left as they are.
+   MXG_EINVAL: ori above 2, start >= end, path_first not increasing from 0; and, naming "path <p> node <i>" of the input, the merge
+   step at which the reference raises KeyError: a segment that an earlier merge already took out of its contig's set (two nodes with
+   the same contig, start and end, one of which merges).  MXG_ELIMIT: a record index of 2^28 or more, 2^31 nodes or paths or more. */
+typedef struct mxg_adjust_node {           /* one PathNode as format_path made it */
+    uint32_t record, start, end, contig_size;
+    uint64_t first_mx, terminal_mx;        /* opaque tags (the minimizer hashes); copied on merges, compared by is_best_region */
+    int64_t  gap_size, raw_gap_size;
+    uint8_t  ori, pad[7];                  /* 0 '+', 1 '-', 2 '?' */
+} mxg_adjust_node;
+typedef struct mxg_adjust_params { uint32_t struct_size; uint32_t no_cut; int64_t G; } mxg_adjust_params;
+typedef struct mxg_adjusted_view {         /* host copies owned by the handle, valid until the next call */
+    uint64_t n_paths, n_nodes;
+    const uint64_t *node_first;            /* [n_paths + 1]; a path may come back empty */
+    const mxg_adjust_node *nodes;          /* the paths as print_scaffolds holds them at :555 */
+    const uint64_t *source;                /* per output node: index of the input node it is (the head of its merged chain) */
+} mxg_adjusted_view;
+int mxg_adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *path_first /* n_paths + 1 */, uint64_t n_paths,
+                     const mxg_adjust_params *p, mxg_adjusted_view *out);
+
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------
    No counterpart in the reference (it is one process).  Uniqueness and intersection need every occurrence of a hash in
    one place: every minimizer travels to the rank that owns its hash, the owner runs the ordinary graph kernels on what it

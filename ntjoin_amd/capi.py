@@ -21,7 +21,7 @@ SYMBOLS = [
     "mxg_record_id", "mxg_record_length", "mxg_num_records", "mxg_assembly_weight",
     "mxg_sketch", "mxg_sketch_graph", "mxg_get_sketch", "mxg_get_sketch_device", "mxg_compute_strands", "mxg_set_sketch_device",
     "mxg_pack_sketch_device", "mxg_set_sketch_gathered", "mxg_set_sketch_gathered_strided", "mxg_write_tsv",
-    "mxg_build_graph", "mxg_get_mx_flags", "mxg_get_graph", "mxg_find_paths", "mxg_path_segments", "mxg_path_segments_mk", "mxg_mk_stats", "mxg_format_paths", "mxg_mk_orientation", "mxg_vertex_hashes", "mxg_overlap_cuts", "mxg_write_scaffolds", "mxg_scaffold_strips", "mxg_mx_extremes", "mxg_dg_owner_counts", "mxg_dg_pack_items", "mxg_dg_set_items", "mxg_dg_vertices", "mxg_dg_item_results", "mxg_dg_msg_counts", "mxg_dg_pack_msgs", "mxg_dg_edges", "mxg_dg_pack_slots", "mxg_dg_owner_slots", "mxg_dg_slot_results", "mxg_dg_pack_msg_slots", "mxg_dg_edges_slots", "mxg_write_dot", "mxg_write_outputs", "mxg_dot_part_format", "mxg_dot_part_write",
+    "mxg_build_graph", "mxg_get_mx_flags", "mxg_get_graph", "mxg_find_paths", "mxg_path_segments", "mxg_path_segments_mk", "mxg_mk_stats", "mxg_format_paths", "mxg_mk_orientation", "mxg_vertex_hashes", "mxg_overlap_cuts", "mxg_adjust_paths", "mxg_write_scaffolds", "mxg_scaffold_strips", "mxg_mx_extremes", "mxg_dg_owner_counts", "mxg_dg_pack_items", "mxg_dg_set_items", "mxg_dg_vertices", "mxg_dg_item_results", "mxg_dg_msg_counts", "mxg_dg_pack_msgs", "mxg_dg_edges", "mxg_dg_pack_slots", "mxg_dg_owner_slots", "mxg_dg_slot_results", "mxg_dg_pack_msg_slots", "mxg_dg_edges_slots", "mxg_write_dot", "mxg_write_outputs", "mxg_dot_part_format", "mxg_dot_part_write",
     "mxg_py_repr_double", "mxg_py_repr_str", "mxg_get_stats", "mxg_reset_timers", "mxg_knobs",
     "mxg_synth_fill_packed_device", "mxg_synth_fill_packed_host", "mxg_synth_write_fasta",
     "mxg_plan_split", "mxg_add_assembly_packed_device_pieces", "mxg_dg_last_shared", "mxg_dg_set_ghosts",
@@ -78,6 +78,15 @@ class PathNodesView(C.Structure):  # mxg_path_nodes_view: 104 bytes (api.cpp ass
 class OverlapNode(C.Structure):
     _fields_ = [("record", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("raw_gap", C.c_int32),
                 ("reverse", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+class AdjustParams(C.Structure):  # mxg_adjust_params: 16 bytes (api.cpp asserts the same)
+    _fields_ = [("struct_size", C.c_uint32), ("no_cut", C.c_uint32), ("G", C.c_int64)]
+
+
+class AdjustedView(C.Structure):  # mxg_adjusted_view: 40 bytes (api.cpp asserts the same); nodes = engine.MxEngine.ADJUST_NODE entries
+    _fields_ = [("n_paths", C.c_uint64), ("n_nodes", C.c_uint64), ("node_first", C.POINTER(C.c_uint64)), ("nodes", C.c_void_p),
+                ("source", C.POINTER(C.c_uint64))]
 
 
 class SynthSeg(C.Structure):
@@ -198,6 +207,7 @@ def load():
     L.mxg_mk_orientation.argtypes = [u64, C.c_int64, u64]
     L.mxg_mk_orientation.restype = C.c_char
     L.mxg_overlap_cuts.argtypes = [vp, i32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp]
+    L.mxg_adjust_paths.argtypes = [vp, vp, vp, u64, C.POINTER(AdjustParams), C.POINTER(AdjustedView)]
     L.mxg_write_scaffolds.argtypes = [vp, i32, vp, vp, u64, i32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp]
     L.mxg_scaffold_strips.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64)]
     L.mxg_mx_extremes.argtypes = [vp, i32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)),

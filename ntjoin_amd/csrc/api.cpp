@@ -1018,6 +1018,32 @@ int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *no
     }
 }
 
+static_assert(sizeof(mxg_adjust_node) == 56, "mxg_adjust_node: ntjoin_amd/engine.py ADJUST_NODE mirrors this layout");
+static_assert(sizeof(mxg_adjust_params) == 16, "mxg_adjust_params: ntjoin_amd/capi.py AdjustParams mirrors this layout");
+static_assert(sizeof(mxg_adjusted_view) == 40, "mxg_adjusted_view: ntjoin_amd/capi.py AdjustedView mirrors this layout");
+
+int mxg_adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *path_first, uint64_t n_paths, const mxg_adjust_params *p,
+                     mxg_adjusted_view *out)
+{
+    if (!h) return MXG_EINVAL;
+    if (!p || !out || !path_first || (n_paths && path_first[n_paths] && !nodes)) return set_err(h, MXG_EINVAL, "mxg_adjust_paths: null argument");
+    if (p->struct_size < sizeof(mxg_adjust_params))
+        return set_err(h, MXG_EINVAL, "mxg_adjust_paths: struct_size %u is too small", p->struct_size);
+    int rc;
+    try {
+        rc = adjust_paths(h, nodes, path_first, n_paths, *p);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_adjust_paths");
+    }
+    if (rc != MXG_OK) return rc;
+    out->n_paths = n_paths;
+    out->n_nodes = h->adj_nodes.size();
+    out->node_first = h->adj_first.data();
+    out->nodes = h->adj_nodes.data();
+    out->source = h->adj_source.data();
+    return MXG_OK;
+}
+
 int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals)
 {
     if (!h) return MXG_EINVAL;

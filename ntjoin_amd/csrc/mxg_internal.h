@@ -266,6 +266,9 @@ struct mxg_handle {
     mxg::DevBuf mkbuf[8];  // scratch of mk.hip
     mxg::DevBuf ovbuf[16];  // scratch of overlap.hip
     mxg::DevBuf scbuf[8];   // scratch of scaffold.hip
+    mxg::DevBuf adjbuf[32];  // scratch of adjust.hip
+    std::vector<mxg_adjust_node> adj_nodes;      // the last mxg_adjust_paths' result (what its view points into)
+    std::vector<uint64_t> adj_first, adj_source;
     std::vector<uint32_t> scaf_lead, scaf_tail;  // N/n stripped from either end of every unassigned interval by the last mxg_write_scaffolds
     mxg::Segments segs;
     mxg::PathNodes nodes;
@@ -511,6 +514,8 @@ int overlap_cuts(mxg_handle *h, Assembly *a, int assembly, uint32_t k, uint32_t 
 int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
                     int32_t overlap_gap, uint32_t flags, const char *assigned_fa, const char *unassigned_fa, const char *unassigned_bed,
                     uint32_t *lead_strip, uint32_t *tail_strip, uint64_t *n_unassigned);
+// adjust.hip: relocations, --no_cut and overlapping regions of the given paths (mxg_adjust_paths); fills h->adj_*
+int adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *path_first, uint64_t n_paths, const mxg_adjust_params &p);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm
 int flags_to_host(mxg_handle *h, Assembly *a);
 

@@ -436,6 +436,27 @@ class MxEngine:
                                                sa.ctypes.data, ea.ctypes.data, cf.ctypes.data))
         return {"start_adjust": sa, "end_adjust": ea, "cut_found": cf.astype(bool)}
 
+    ADJUST_NODE = np.dtype([("record", "<u4"), ("start", "<u4"), ("end", "<u4"), ("contig_size", "<u4"), ("first_mx", "<u8"),
+                            ("terminal_mx", "<u8"), ("gap_size", "<i8"), ("raw_gap_size", "<i8"), ("ori", "u1"), ("pad", "u1", (7,))])
+
+    def adjust_paths(self, nodes, path_first, no_cut=False, G=0):
+        """mxg_adjust_paths: nodes = array of ADJUST_NODE (ori: 0 '+', 1 '-', 2 '?'), path_first = n_paths + 1 offsets -> dict(nodes:
+        the adjusted paths' nodes (ADJUST_NODE), node_first u64[n_paths + 1], source u64[n]: the input node every output node is).
+        Merged relocations, --no_cut and the overlapping regions of all paths in the reference's order (include/ntjoin_mx.h)."""
+        nodes = np.ascontiguousarray(nodes, dtype=self.ADJUST_NODE)
+        pf = np.ascontiguousarray(path_first, dtype=np.uint64)
+        if pf.ndim != 1 or len(pf) < 1 or int(pf[0]) != 0 or int(pf[-1]) != len(nodes):
+            raise ValueError("adjust_paths: path_first needs n_paths + 1 offsets, the first one 0 and the last one len(nodes)")
+        p = capi.AdjustParams()
+        p.struct_size, p.no_cut, p.G = C.sizeof(capi.AdjustParams), int(bool(no_cut)), int(G)
+        v = capi.AdjustedView()
+        self._check(self._lib.mxg_adjust_paths(self._h, nodes.ctypes.data, pf.ctypes.data, len(pf) - 1, C.byref(p), C.byref(v)))
+        n = int(v.n_nodes)
+        out = np.zeros(n, dtype=self.ADJUST_NODE)
+        if n:
+            C.memmove(out.ctypes.data, v.nodes, n * self.ADJUST_NODE.itemsize)
+        return {"nodes": out, "node_first": _np(v.node_first, int(v.n_paths) + 1, np.uint64), "source": _np(v.source, n, np.uint64)}
+
     SCAFFOLD_NODE = np.dtype([("record", "<u4"), ("start", "<u4"), ("end", "<u4"), ("gap_size", "<u4"), ("start_adjust", "<u4"),
                               ("end_adjust", "<u4"), ("reverse", "u1"), ("pad", "u1", (3,))])
 

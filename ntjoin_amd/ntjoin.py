@@ -338,6 +338,46 @@ class Ntjoin:
                 u[7], u[8] = gap, mean_dist - a_over - b_over
         return out
 
+    def adjust_paths(self, paths, no_cut=False, G=0):
+        """What main_scaffolder does to the paths between format_path and the scaffolds (:775-784 and :549-553) for paths as
+        format_paths() returns them: relocated pieces of one contig merged (merge_relocations :126-172, before and after the rest),
+        with no_cut whole contigs instead of cut ones (adjust_paths :266-305; G clamps the gaps it accumulates), regions of one
+        contig that overlap resolved (tally_intersecting_segments :661-686, remove_overlapping_regions :451-466), the last
+        oriented node's gap zeroed.  One library call for all paths (mxg_adjust_paths); rows of the same shape come back, one list
+        per input path (a path may come back with one node or none), ready for trim_overlaps and print_scaffolds.  Where the
+        reference raises KeyError (two nodes with the same contig, start and end, one of which merges) MxError names the node."""
+        flat = [nd for path in paths for nd in path]
+        index, tags = {}, {}
+        nodes = np.zeros(len(flat), dtype=MxEngine.ADJUST_NODE)
+        nodes["record"] = [index.setdefault(nd[0], len(index)) for nd in flat]
+        nodes["ori"] = ["+-?".index(nd[1]) for nd in flat]
+        for col, name in ((2, "start"), (3, "end"), (4, "contig_size"), (7, "gap_size"), (8, "raw_gap_size")):
+            nodes[name] = [nd[col] for nd in flat]
+        for col, name in ((5, "first_mx"), (6, "terminal_mx")):  # opaque to the library: any hashable tag
+            nodes[name] = [tags.setdefault(nd[col], len(tags)) for nd in flat]
+        first = np.cumsum([0] + [len(path) for path in paths]).astype(np.uint64)
+        res = self._engine.adjust_paths(nodes, first, no_cut=no_cut, G=G)
+        contigs, tag_of, nd = list(index), list(tags), res["nodes"]
+        rows = [[contigs[r], "+-?"[o], s, e, size, tag_of[f], tag_of[t], gap, raw] for r, o, s, e, size, f, t, gap, raw in zip(
+            nd["record"].tolist(), nd["ori"].tolist(), nd["start"].tolist(), nd["end"].tolist(), nd["contig_size"].tolist(),
+            nd["first_mx"].tolist(), nd["terminal_mx"].tolist(), nd["gap_size"].tolist(), nd["raw_gap_size"].tolist())]
+        at = res["node_first"].tolist()
+        return [rows[lo:hi] for lo, hi in zip(at, at[1:])]
+
+    def scaffold(self, lengths=None):
+        """main_scaffolder (:751-786) behind load_minimizers_scaffold in one handle: make_minimizer_graph -> find_paths ->
+        format_paths -> adjust_paths -> trim_overlaps (when args.overlap) -> print_scaffolds.  Read from args, with ntJoin's
+        defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp.  Returns what
+        print_scaffolds returns (the written files by kind)."""
+        opt = lambda name, dflt: dflt if getattr(self.args, name, None) is None else getattr(self.args, name)  # noqa: E731
+        self.make_minimizer_graph(materialize=False)
+        self.find_paths()
+        G = int(opt("G", 0))
+        paths = self.format_paths(lengths, g=int(opt("g", 20)), G=G, m=opt("m", 90), mkt=bool(opt("mkt", False)))
+        paths = self.adjust_paths(paths, no_cut=bool(opt("no_cut", False)), G=G)
+        cuts = self.trim_overlaps(paths, opt("overlap_k", 15), opt("overlap_w", 10)) if opt("overlap", False) else None
+        return self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)))
+
     def trim_overlaps(self, paths, overlap_k=None, overlap_w=None):
         """The cut points of the reference's overlap stage (adjust_for_trimming, bin/ntjoin_assemble.py:468-516, and
         merge_overlapping, bin/ntjoin_overlap.py:20-88) for paths as format_paths() returns them.  Nodes of orientation '?'
