@@ -541,6 +541,37 @@ typedef struct mxg_adjusted_view {         /* host copies owned by the handle, v
 int mxg_adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *path_first /* n_paths + 1 */, uint64_t n_paths,
                      const mxg_adjust_params *p, mxg_adjusted_view *out);
 
+/* ---- next row (f8): the .path file and the AGP of all paths --------------------------------------------------------------
+   What the reference's print_scaffolds writes per path with Python strings (bin/ntjoin_assemble.py:605-610), what write_agp
+   (:346-376) parses back out of that string with two regular expressions per component, and write_agp_unassigned (:379-404).
+   Here: formatted on the device from the node array, in the state mxg_write_scaffolds takes it (orientation '+' / '-' only, at
+   least two nodes per path, the last node's gap already zero), and the strips that call returned; no sequence text is read and
+   `end` is not compared with the record's length (mxg_write_scaffolds has done that).
+   Per node, after the strips (the first node of a path loses lead_strip[p] at its start if '+', at its end if '-'; the last node
+   loses tail_strip[p] at its end if '+', at its start if '-'; join_sequences :413-436), with L = end - start and
+   e = end_adjust ? end_adjust : L, the adjusted interval [s, t) is (bin/path_node.py:41-61)
+     '+':  (start + start_adjust, end - (L - e))        '-':  (start + (L - e), end - start_adjust).
+   path_file: "first_line\n", then per path "ntJoin<p>\t<id><ori>:<s>-<t> <gap>N <id><ori>:<s>-<t> ... <id><ori>:<s>-<t>\n"; the
+   last node's gap is left out whatever its value (:607).  id = the record's id as the handle holds it, gap = gap_size.
+   agp_file (may be NULL): nine tab-separated columns per component in path order; a node gives
+   "ntJoin<p> at at+n-1 part W id s+1 t ori" with n = t - s, the gap behind every node but the last
+   "ntJoin<p> at at+n-1 part N n scaffold yes align_genus" with n = gap (a gap of 0 still has its line, ending at at - 1, as the
+   reference writes it); `at` starts at 1 per path and advances by n (a 64-bit sum), `part` counts the components from 1.
+   MXG_PATHS_AGP_UNASSIGNED: behind the last path, for every interval [lo, hi) of the handle's last mxg_write_scaffolds that
+   computed the unassigned side (of this assembly), in BED order, with n = hi - lo - lead - tail > 0:
+   "id:lo-hi 1 n 1 W id lo+1+lead lo+lead+n +".
+   MXG_EINVAL (nothing is written): a path of fewer than two nodes, start >= end, end_adjust > L, a record index outside the
+   assembly, path_first not increasing from 0, path_file == NULL, MXG_PATHS_AGP_UNASSIGNED without such an mxg_write_scaffolds
+   before it, and, naming "path <p> node <i>", an adjusted interval that is empty or inverted after the strips.  MXG_ELIMIT: 2^31
+   nodes or more.  n_paths == 0 is valid (path_file holds its first line, agp_file the unassigned lines or nothing).  Sketches,
+   graph and paths of the handle are left as they are.  MXG_PATH_WIN (test knob): bytes of text per device window. */
+#define MXG_PATHS_AGP_UNASSIGNED 0x1u
+int mxg_write_paths(mxg_handle *h, int assembly, const mxg_scaffold_node *nodes,
+                    const uint64_t *path_first /* n_paths + 1 */, uint64_t n_paths,
+                    const uint32_t *lead_strip, const uint32_t *tail_strip /* [n_paths]; NULL = all 0 */,
+                    const char *first_line /* the FASTA's name, written as line 1 of path_file */,
+                    const char *path_file, const char *agp_file /* may be NULL */, uint32_t flags);
+
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------
    No counterpart in the reference (it is one process).  Uniqueness and intersection need every occurrence of a hash in
    one place: every minimizer travels to the rank that owns its hash, the owner runs the ordinary graph kernels on what it

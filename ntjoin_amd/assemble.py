@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""
+Counterpart of the reference's bin/ntjoin_assemble.py as bin/ntjoin_run.py drives it: the whole scaffolder in one process on
+one handle.  Same command line as ntjoin_amd.run (its parser, imported): the references' sketches FILES, the target's sketch
+-s, all named <fasta>.k<k>.w<w>.tsv as ntJoin's makefile names them.
+
+The target is always sketched from <fasta> (the scaffolds are cut from its text) and its TSV written as a by-product; a
+reference is loaded from its TSV when that file exists and sketched from <fasta> otherwise.  Then Ntjoin.scaffold():
+graph -> find_paths -> format_paths -> adjust_paths -> trim_overlaps (--overlap) -> print_scaffolds.  Written, under the
+reference's names: <p>.mx.dot, <p>.path, <p>.agp (--agp), <fasta>.k<k>.w<w>.n<n>.assigned.scaffolds.fa,
+...unassigned.scaffolds.fa and <p>.<target tsv>.unassigned.bed.  -t and --btllib_t are accepted and unused.
+"""
+import os
+import re
+import sys
+
+from .run import parse_arguments, set_weights
+
+TSV_NAME = re.compile(r"^(.+)\.k(\d+)\.w(\d+)\.tsv$")
+
+
+def fail(message):
+    "one line on stdout and exit status 1, as the reference reports a bad command line (bin/ntjoin_assemble.py:788-797)"
+    sys.stdout.write("ERROR: " + message + "\n")
+    sys.exit(1)
+
+
+def derive_names(args):
+    "-> ({tsv name: fasta name} for -s and every FILES entry, w); ends the run when a name does not carry this run's k and one w"
+    fasta, ws = {}, set()
+    for tsv in [args.s] + list(args.FILES):
+        match = TSV_NAME.match(tsv)
+        if not match:
+            fail(f"{tsv!r} is not named <fasta>.k<k>.w<w>.tsv")
+        if int(match.group(2)) != args.k:
+            fail(f"{tsv!r} names k={int(match.group(2))} but -k is {args.k}")
+        fasta[tsv] = match.group(1)
+        ws.add(int(match.group(3)))
+    if len(ws) != 1:
+        fail(f"the sketches name different window sizes (w = {sorted(ws)}); one run has one w")
+    return fasta, ws.pop()
+
+
+def sources(args, fasta):
+    "-> {tsv name: fasta to sketch}: the target always, a reference only when its TSV does not exist yet"
+    sketch = {}
+    if not os.path.exists(fasta[args.s]):
+        fail(f"the target FASTA {fasta[args.s]!r} does not exist (the scaffolds are cut from its text)")
+    sketch[args.s] = fasta[args.s]
+    for tsv in args.FILES:
+        if os.path.exists(tsv):
+            continue
+        if not os.path.exists(fasta[tsv]):
+            fail(f"neither the sketch {tsv!r} nor the FASTA {fasta[tsv]!r} exists")
+        sketch[tsv] = fasta[tsv]
+    return sketch
+
+
+def main(argv=None):
+    args = parse_arguments(argv)
+    fasta, w = derive_names(args)
+    sketch = sources(args, fasta)
+    weights = set_weights(args)
+    from .ntjoin import Ntjoin  # (behind the checks: importing it loads the library)
+    nj = Ntjoin(args, fasta=sketch, w=w)
+    nj.weights_list = weights
+    try:
+        nj.load_minimizers_scaffold()
+        nj.scaffold()
+    finally:
+        nj.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1044,6 +1044,22 @@ int mxg_adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t
     return MXG_OK;
 }
 
+int mxg_write_paths(mxg_handle *h, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
+                    const uint32_t *lead_strip, const uint32_t *tail_strip, const char *first_line, const char *path_file, const char *agp_file,
+                    uint32_t flags)
+{
+    if (!h) return MXG_EINVAL;
+    if (assembly < 0 || (size_t)assembly >= h->asms.size()) return set_err(h, MXG_EINVAL, "mxg_write_paths: no assembly %d", assembly);
+    if (!path_first || !path_file || !first_line || (n_paths && path_first[n_paths] && !nodes))
+        return set_err(h, MXG_EINVAL, "mxg_write_paths: null argument");
+    try {
+        return write_paths(h, h->asms[assembly], assembly, nodes, path_first, n_paths, lead_strip, tail_strip, first_line, path_file, agp_file,
+                           flags);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_write_paths");
+    }
+}
+
 int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals)
 {
     if (!h) return MXG_EINVAL;

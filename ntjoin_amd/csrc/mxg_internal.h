@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <sys/stat.h>
 
 #include <atomic>
 #include <chrono>
@@ -270,6 +271,14 @@ struct mxg_handle {
     std::vector<mxg_adjust_node> adj_nodes;      // the last mxg_adjust_paths' result (what its view points into)
     std::vector<uint64_t> adj_first, adj_source;
     std::vector<uint32_t> scaf_lead, scaf_tail;  // N/n stripped from either end of every unassigned interval by the last mxg_write_scaffolds
+    struct ScafInterval {
+        uint32_t rec, lo, hi, lead, tail;
+    };
+    // the unassigned intervals, in BED order, with their strips, of the last mxg_write_scaffolds that computed the unassigned side,
+    // and their assembly (-1: no such call yet): what mxg_write_paths makes the AGP's unassigned lines of
+    std::vector<ScafInterval> scaf_iv;
+    int scaf_iv_asm = -1;
+    mxg::DevBuf ptbuf[16];  // scratch of pathtext.hip
     mxg::Segments segs;
     mxg::PathNodes nodes;
     mxg::Timers tm;
@@ -391,6 +400,35 @@ int fetch_device_text(mxg_handle *h, Assembly *a, std::string &seq, std::vector<
 uint32_t host_threads(const mxg_handle *h);
 // n_parts byte ranges written to fd at consecutive offsets from `off` on, by that many threads (host_io.cpp)
 bool put_parallel(int fd, uint64_t off, const char *const *data, const size_t *len, uint32_t n_parts);
+// a file that is removed again unless the call completes (only a regular file this call created or truncated):
+// what scaffold.hip and pathtext.hip write their outputs through
+struct OutFile {
+    FILE *f = nullptr;
+    std::string path;
+    bool regular = false, removable = false, complete = false;
+    bool open(const char *p)
+    {
+        path = p;
+        f = fopen(p, "w+b");  // (read access too: put_parallel maps the file)
+        if (!f) return false;
+        struct stat sb;
+        regular = fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode);
+        removable = regular && lstat(p, &sb) == 0 && S_ISREG(sb.st_mode);
+        return true;
+    }
+    bool close()
+    {
+        if (!f) return true;
+        const bool ok = fclose(f) == 0;
+        f = nullptr;
+        return ok;
+    }
+    ~OutFile()
+    {
+        (void)close();
+        if (!complete && removable) (void)remove(path.c_str());
+    }
+};
 int write_dot(mxg_handle *h, const char *path);
 int dot_part_format(mxg_handle *h, uint32_t part, uint32_t n_parts, uint64_t bytes[2]);
 int dot_part_write(mxg_handle *h, const char *path, uint64_t v_off, uint64_t e_off, int first, int last);
@@ -514,6 +552,10 @@ int overlap_cuts(mxg_handle *h, Assembly *a, int assembly, uint32_t k, uint32_t 
 int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
                     int32_t overlap_gap, uint32_t flags, const char *assigned_fa, const char *unassigned_fa, const char *unassigned_bed,
                     uint32_t *lead_strip, uint32_t *tail_strip, uint64_t *n_unassigned);
+// pathtext.hip: the .path and AGP text of the given paths (mxg_write_paths)
+int write_paths(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
+                const uint32_t *lead_strip, const uint32_t *tail_strip, const char *first_line, const char *path_file, const char *agp_file,
+                uint32_t flags);
 // adjust.hip: relocations, --no_cut and overlapping regions of the given paths (mxg_adjust_paths); fills h->adj_*
 int adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *path_first, uint64_t n_paths, const mxg_adjust_params &p);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm

@@ -194,35 +194,6 @@ __global__ __launch_bounds__(256) void k_scaf_emit(const ScafText t, const ScafP
 
 namespace {
 
-// a file that is removed again unless the call completes (only a regular file this call created or truncated)
-struct OutFile {
-    FILE *f = nullptr;
-    std::string path;
-    bool regular = false, removable = false, complete = false;
-    bool open(const char *p)
-    {
-        path = p;
-        f = fopen(p, "w+b");  // (read access too: put_parallel maps the file)
-        if (!f) return false;
-        struct stat sb;
-        regular = fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode);
-        removable = regular && lstat(p, &sb) == 0 && S_ISREG(sb.st_mode);
-        return true;
-    }
-    bool close()
-    {
-        if (!f) return true;
-        const bool ok = fclose(f) == 0;
-        f = nullptr;
-        return ok;
-    }
-    ~OutFile()
-    {
-        (void)close();
-        if (!complete && removable) (void)remove(path.c_str());
-    }
-};
-
 struct PieceTable {
     std::vector<ScafPiece> pieces;
     std::string lits;
@@ -511,6 +482,11 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
             pt.literal("\n");
         }
         if (unassigned_fa && (rc = scaf_emit_file(h, t, pt, 0u, ufa, WIN)) != MXG_OK) return rc;
+    }
+    if (want_un) {  // the intervals with their strips: what mxg_write_paths makes the AGP's unassigned lines of
+        h->scaf_iv.resize(gaps.size());
+        for (size_t g = 0; g < gaps.size(); ++g) h->scaf_iv[g] = {gaps[g].rec, gaps[g].lo, gaps[g].hi, h->scaf_lead[g], h->scaf_tail[g]};
+        h->scaf_iv_asm = assembly;
     }
     if (unassigned_bed) {
         for (const Iv &iv : gaps) fprintf(bed.f, "%s\t%u\t%u\n", a->recs[iv.rec].id.c_str(), iv.lo, iv.hi);

@@ -467,13 +467,7 @@ class MxEngine:
         tail_strip u32[n_paths]: N/n stripped from the scaffolds' ends, n_unassigned: records in the unassigned FASTA)"""
         if assigned is None:
             raise ValueError("write_scaffolds: assigned= names the scaffold FASTA to write")
-        nodes = rows
-        if not (isinstance(nodes, np.ndarray) and nodes.dtype == self.SCAFFOLD_NODE):
-            arr = np.asarray(rows, dtype=np.int64).reshape(-1, 7)
-            nodes = np.zeros(len(arr), dtype=self.SCAFFOLD_NODE)
-            for j, name in enumerate(("record", "start", "end", "gap_size", "start_adjust", "end_adjust", "reverse")):
-                nodes[name] = arr[:, j]
-        nodes = np.ascontiguousarray(nodes)
+        nodes = self._scaffold_nodes(rows)
         pf = np.ascontiguousarray(path_first, dtype=np.uint64)
         if len(pf) < 1 or int(pf[0]) != 0 or int(pf[-1]) != len(nodes):
             raise ValueError("write_scaffolds: path_first needs n_paths + 1 offsets, the first one 0 and the last one len(nodes)")
@@ -486,6 +480,44 @@ class MxEngine:
                                                   capi.SCAF_FOLD_CASE if fold_case else 0, enc(assigned), enc(unassigned), enc(bed),
                                                   lead.ctypes.data, tail.ctypes.data, C.byref(n_un)))
         return {"lead_strip": lead, "tail_strip": tail, "n_unassigned": int(n_un.value)}
+
+    def _scaffold_nodes(self, rows):
+        "rows (record, start, end, gap_size, start_adjust, end_adjust, reverse), or an array of SCAFFOLD_NODE -> that array"
+        nodes = rows
+        if not (isinstance(nodes, np.ndarray) and nodes.dtype == self.SCAFFOLD_NODE):
+            arr = np.asarray(rows, dtype=np.int64).reshape(-1, 7)
+            nodes = np.zeros(len(arr), dtype=self.SCAFFOLD_NODE)
+            for j, name in enumerate(("record", "start", "end", "gap_size", "start_adjust", "end_adjust", "reverse")):
+                nodes[name] = arr[:, j]
+        return np.ascontiguousarray(nodes)
+
+    def write_paths(self, assembly, rows, path_first, lead_strip=None, tail_strip=None, first_line="", path=None, agp=None,
+                    agp_unassigned=False):
+        """mxg_write_paths: the .path file `path` (line 1 = first_line, then one line per path) and, when named, the AGP `agp` of the
+        paths, formatted on the device.  rows / path_first as write_scaffolds takes them, lead_strip / tail_strip = what it
+        returned (None: no strips); agp_unassigned=True appends the AGP lines of the unassigned intervals the handle's last
+        write_scaffolds left behind."""
+        if path is None:
+            raise ValueError("write_paths: path= names the .path file to write")
+        nodes = self._scaffold_nodes(rows)
+        pf = np.ascontiguousarray(path_first, dtype=np.uint64)
+        if pf.ndim != 1 or len(pf) < 1:
+            raise ValueError("write_paths: path_first needs n_paths + 1 offsets")
+        n_paths = len(pf) - 1
+        if len(pf) and int(pf[-1]) > len(nodes):
+            raise ValueError("write_paths: path_first reaches beyond the nodes")
+        strips = []
+        for name, s in (("lead_strip", lead_strip), ("tail_strip", tail_strip)):
+            if s is not None:
+                s = np.ascontiguousarray(s, dtype=np.uint32)
+                if s.shape != (n_paths,):
+                    raise ValueError(f"write_paths: {name} needs one entry per path")
+            strips.append(s)
+        enc = lambda p: None if p is None else os.fsencode(str(p))  # noqa: E731
+        self._check(self._lib.mxg_write_paths(self._h, int(assembly), nodes.ctypes.data if len(nodes) else None, pf.ctypes.data, n_paths,
+                                              None if strips[0] is None else strips[0].ctypes.data,
+                                              None if strips[1] is None else strips[1].ctypes.data, str(first_line).encode("utf-8"),
+                                              enc(path), enc(agp), capi.PATHS_AGP_UNASSIGNED if agp_unassigned else 0))
 
     def scaffold_strips(self):
         """mxg_scaffold_strips: (lead u32[n], tail u32[n]) = N/n stripped from either end of every unassigned interval (the BED's

@@ -458,6 +458,38 @@ class Ntjoin:
                 start = int(lo) + 1 + lead
                 agp_fh.write("\t".join(str(c) for c in (f"{ctg}:{lo}-{hi}", 1, n, 1, "W", ctg, start, start + n - 1, "+")) + "\n")
 
+    def _write_path_host(self, files, assembly_fa, kept, leads, tails):
+        """The .path file and, when files names one, the AGP as a per-node loop on the host (:605-610, write_agp, write_agp_unassigned):
+        what print_scaffolds did before mxg_write_paths, kept for the inputs the library refuses.  kept = per written path its
+        (nodes, cuts), leads / tails = the strips mxg_write_scaffolds returned."""
+        agp_fh = None
+        if "agp" in files:
+            agp_fh = open(files["agp"], "w", encoding="utf-8")  # pylint: disable=consider-using-with
+        try:
+            with open(files["path"], "w", encoding="utf-8") as fh:
+                fh.write(assembly_fa + "\n")
+                for ct, ((nodes, cuts), lead, tail) in enumerate(zip(kept, leads, tails)):
+                    coords = [[nd[1], nd[2], nd[3]] for nd in nodes]
+                    for c, strip, left in ((coords[0], lead, True), (coords[-1], tail, False)):  # join_sequences :413-436
+                        if strip:
+                            if (c[0] == "+") == left:
+                                c[1] += strip
+                            else:
+                                c[2] -= strip
+                    parts = []
+                    for nd, (ori, start, end), (sa, ea) in zip(nodes, coords, cuts):
+                        a_start, a_end = self._path_coords(ori, start, end, sa, ea)
+                        parts.append(f"{nd[0]}{ori}:{a_start}-{a_end} {nd[7]}N")
+                    path_str = re.sub(r"\s+\d+N$", "", " ".join(parts))
+                    fh.write(f"ntJoin{ct}\t{path_str}\n")
+                    if agp_fh:
+                        self._write_agp(agp_fh, f"ntJoin{ct}", path_str)
+            if agp_fh:
+                self._write_agp_unassigned(agp_fh, files["bed"])
+        finally:
+            if agp_fh:
+                agp_fh.close()
+
     def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20):
         """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
         trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
@@ -500,34 +532,20 @@ class Ntjoin:
         print(datetime.datetime.today(), ": Printing output scaffolds", file=sys.stdout)
         res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
                                   assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"])
-        agp_fh = None
         if agp:
             files["agp"] = self.args.p + ".agp"
-            agp_fh = open(files["agp"], "w", encoding="utf-8")  # pylint: disable=consider-using-with
-        try:
-            with open(files["path"], "w", encoding="utf-8") as fh:
-                fh.write(assembly_fa + "\n")
-                for ct, ((nodes, cuts), lead, tail) in enumerate(zip(kept, res["lead_strip"].tolist(), res["tail_strip"].tolist())):
-                    coords = [[nd[1], nd[2], nd[3]] for nd in nodes]
-                    for c, strip, left in ((coords[0], lead, True), (coords[-1], tail, False)):  # join_sequences :413-436
-                        if strip:
-                            if (c[0] == "+") == left:
-                                c[1] += strip
-                            else:
-                                c[2] -= strip
-                    parts = []
-                    for nd, (ori, start, end), (sa, ea) in zip(nodes, coords, cuts):
-                        a_start, a_end = self._path_coords(ori, start, end, sa, ea)
-                        parts.append(f"{nd[0]}{ori}:{a_start}-{a_end} {nd[7]}N")
-                    path_str = re.sub(r"\s+\d+N$", "", " ".join(parts))
-                    fh.write(f"ntJoin{ct}\t{path_str}\n")
-                    if agp_fh:
-                        self._write_agp(agp_fh, f"ntJoin{ct}", path_str)
-            if agp_fh:
-                self._write_agp_unassigned(agp_fh, files["bed"])
-        finally:
-            if agp_fh:
-                agp_fh.close()
+        lead, tail = res["lead_strip"], res["tail_strip"]
+        if hasattr(eng, "write_paths"):
+            try:
+                eng.write_paths(tgt, rows, first, lead_strip=lead, tail_strip=tail, first_line=assembly_fa, path=files["path"],
+                                agp=files.get("agp"), agp_unassigned=agp)
+                return files
+            except MxError as err:
+                # a cut that leaves a node's interval empty or inverted: the library refuses it and has written nothing; such paths
+                # keep the text the host loop gives them
+                if err.code != capi.MXG_EINVAL or "empty or inverted" not in str(err):
+                    raise
+        self._write_path_host(files, assembly_fa, kept, lead.tolist(), tail.tolist())
         return files
 
     def print_graph(self, graph, out_prefix=None):
