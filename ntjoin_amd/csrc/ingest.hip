@@ -11,6 +11,11 @@
 // packs the bases, and reports where validity changes (the run table of SURVEY.md A.3: k-mers over invalid bases do not
 // exist).  The raw text stays in HBM, so the k-mer column of the TSV is printed exactly as the file spells it.
 //
+// A BGZF-compressed file (`bgzip`: bgzf_inflate.h) takes the same route with the compressed bytes: (2) uploads the file as it is,
+// k_bgzf_inflate (bgzf.hip) writes the text into the text buffer, and since the host never sees the text, (1) is done by kernels
+// here (k_hdr_*) whose header lines come back in one copy.  Plain gzip, and any file the walk or the decoder objects to, is left
+// to the host parser and zlib as before.
+//
 // TSV: entry lengths -> exclusive scan -> every byte of the file has a known offset; the text is produced in windows of
 // 64 MiB (MXG_TSV_WIN: fewer, a test knob) (double-buffered: the device formats window c+1 while the host writes window c).
 #include <fcntl.h>
@@ -25,6 +30,7 @@
 #include <cstring>
 #include <thread>
 
+#include "bgzf_inflate.h"
 #include "mxg_internal.h"
 #include "scan_kernels.h"
 #include "text_index.h"
@@ -149,6 +155,143 @@ template <class F> static void parallel_for(uint32_t n_threads, F f)
     for (auto &x : th) x.join();
 }
 
+// ---- header lines found on the device (the BGZF route: the text exists only in HBM) ----
+// thread t of a block owns text bytes [4096 b + 16 t, + 16): bit j set = byte j is a '>' at the start of a line
+__device__ __forceinline__ uint32_t hdr_flags16(const unsigned char *__restrict__ text, uint64_t n)
+{
+    const uint64_t a0 = (uint64_t)blockIdx.x * ING_TILE + 16u * threadIdx.x;
+    if (a0 >= n) return 0u;
+    const uint4 v = *reinterpret_cast<const uint4 *>(text + a0);  // (the text buffer is padded to whole tiles)
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t prev = a0 ? text[a0 - 1] : (uint32_t)'\n', f = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j) {
+        const uint32_t c = (w[j >> 2] >> (8u * (j & 3u))) & 255u;
+        if (c == (uint32_t)'>' && prev == (uint32_t)'\n' && a0 + j < n) f |= 1u << j;
+        prev = c;
+    }
+    return f;
+}
+__global__ __launch_bounds__(256) void k_hdr_count(const unsigned char *__restrict__ text, uint64_t n, uint32_t *__restrict__ bsum)
+{
+    __shared__ uint32_t sh[256];
+    (void)block_exclusive_256((uint32_t)__popc(hdr_flags16(text, n)), sh);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = sh[255];
+}
+// bsum: exclusive scan of the counts (k_scan_sums) -> the positions in text order
+__global__ __launch_bounds__(256) void k_hdr_emit(const unsigned char *__restrict__ text, uint64_t n, const uint32_t *__restrict__ bsum,
+                                                  uint64_t n_hdr, uint64_t *__restrict__ at)
+{
+    __shared__ uint32_t sh[256];
+    uint32_t f = hdr_flags16(text, n);
+    uint64_t i = (uint64_t)bsum[blockIdx.x] + block_exclusive_256((uint32_t)__popc(f), sh);
+    const uint64_t a0 = (uint64_t)blockIdx.x * ING_TILE + 16u * threadIdx.x;
+    while (f) {
+        const uint32_t j = (uint32_t)__ffs((int)f) - 1u;
+        f &= f - 1u;
+        if (i < n_hdr) at[i] = a0 + j;
+        ++i;
+    }
+}
+// one thread per header line: its '\n' (or the text's end)
+__global__ __launch_bounds__(256) void k_hdr_end(const unsigned char *__restrict__ text, uint64_t n, const uint64_t *__restrict__ at, uint64_t n_hdr,
+                                                 uint64_t *__restrict__ end)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_hdr) return;
+    uint64_t p = at[i] + 1;
+    while (p < n && text[p] != '\n') ++p;
+    end[i] = p;
+}
+// ... and its bytes behind the '>' into one buffer, line i at off[i]
+__global__ __launch_bounds__(256) void k_hdr_gather(const unsigned char *__restrict__ text, const uint64_t *__restrict__ at,
+                                                    const uint64_t *__restrict__ end, const uint64_t *__restrict__ off, uint64_t n_hdr,
+                                                    unsigned char *__restrict__ lines)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_hdr) return;
+    const uint64_t lo = at[i] + 1, len = end[i] - lo, o = off[i];
+    for (uint64_t u = 0; u < len; ++u) lines[o + u] = text[lo + u];
+}
+
+struct Hdr {
+    uint64_t at, end;  // '>' and its line's '\n' (or the text's end)
+};
+
+// The BGZF route between the upload and the work items: the members inflated into d_text, the header lines found there and brought
+// back (hdr; line r's bytes behind its '>' are lines[line_off[r] ...]).  MXG_OK, a negative error, or 1: a member's data or CRC is
+// not in order (the host parser and zlib then say what is wrong with the file).
+static int bgzf_text_and_headers(mxg_handle *h, const char *path, const BgzfPlan &plan, const unsigned char *d_comp, uint64_t comp_bytes,
+                                 unsigned char *d_text, hipStream_t st, bool dbg_io, std::vector<Hdr> &hdr, std::vector<unsigned char> &lines,
+                                 std::vector<uint64_t> &line_off)
+{
+    auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now_s();
+    const uint64_t usz = plan.usz;
+    const size_t n_mem = plan.members.size();
+    if (n_mem >= (1ull << 31)) return 1;
+    auto soft = [&](hipError_t e) {  // (no room on the device: the host parser takes the file)
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation;
+    };
+    DevBuf d_mem, d_status, d_bsum, d_total, d_at, d_end, d_off, d_lines;  // (scratch of this call: freed when it returns)
+    hipError_t e;
+    const uint64_t n_tiles = (usz + ING_TILE - 1) / ING_TILE;
+    if (n_tiles >= (1ull << 31)) return 1;
+    if ((e = d_mem.ensure(n_mem * sizeof(BgzfMember))) != hipSuccess || (e = d_status.ensure((n_mem + 1) * 4)) != hipSuccess ||
+        (e = d_bsum.ensure(n_tiles * 4)) != hipSuccess || (e = d_total.ensure(16)) != hipSuccess)
+        return soft(e) ? 1 : set_err(h, MXG_EDEVICE, "device allocation failed: %s", hipGetErrorString(e));
+    MXG_HIP(h, hipMemcpyAsync(d_mem.p, plan.members.data(), n_mem * sizeof(BgzfMember), hipMemcpyHostToDevice, st));
+    int rc = bgzf_inflate_device(h, d_comp, comp_bytes, d_mem.as<BgzfMember>(), (uint32_t)n_mem, d_text, usz, d_status.as<uint32_t>(), st);
+    if (rc != MXG_OK) return rc;
+    uint32_t fail = 0;
+    MXG_HIP(h, hipMemcpyAsync(&fail, d_status.p, 4, hipMemcpyDeviceToHost, st));
+    // (the header count does not wait for the verdict: a member that failed left bytes inside its own range of the text, no more)
+    hipLaunchKernelGGL(k_hdr_count, dim3((uint32_t)n_tiles), dim3(256), 0, st, d_text, usz, d_bsum.as<uint32_t>());
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, d_bsum.as<uint32_t>(), (uint32_t)n_tiles, d_total.as<uint64_t>());
+    MXG_HIP(h, hipGetLastError());
+    uint64_t n_hdr = 0;
+    MXG_HIP(h, hipMemcpyAsync(&n_hdr, d_total.p, 8, hipMemcpyDeviceToHost, st));
+    MXG_HIP(h, hipStreamSynchronize(st));
+    const double t_inf = now_s() - t0;  // (the kernel and, beside it, one pass over the text)
+    if (fail != 0) return 1;
+    if (dbg_io)
+        fprintf(stderr, "[mxg] bgzf_inflate members=%llu bytes_in=%llu bytes_out=%llu ms=%.3f\n", (unsigned long long)n_mem,
+                (unsigned long long)comp_bytes, (unsigned long long)usz, t_inf * 1e3);
+    if (n_hdr >= (1ull << 32)) return set_err(h, MXG_ELIMIT, "too many records in '%s'", path);
+    hdr.resize(n_hdr);
+    line_off.assign(n_hdr + 1, 0);
+    if (!n_hdr) return MXG_OK;
+    if ((e = d_at.ensure(n_hdr * 8)) != hipSuccess || (e = d_end.ensure(n_hdr * 8)) != hipSuccess || (e = d_off.ensure(n_hdr * 8)) != hipSuccess)
+        return soft(e) ? 1 : set_err(h, MXG_EDEVICE, "device allocation failed: %s", hipGetErrorString(e));
+    const uint32_t hb = (uint32_t)((n_hdr + 255) / 256);
+    hipLaunchKernelGGL(k_hdr_emit, dim3((uint32_t)n_tiles), dim3(256), 0, st, d_text, usz, d_bsum.as<uint32_t>(), n_hdr, d_at.as<uint64_t>());
+    hipLaunchKernelGGL(k_hdr_end, dim3(hb), dim3(256), 0, st, d_text, usz, d_at.as<uint64_t>(), n_hdr, d_end.as<uint64_t>());
+    MXG_HIP(h, hipGetLastError());
+    std::vector<uint64_t> at(n_hdr), end(n_hdr);
+    MXG_HIP(h, hipMemcpyAsync(at.data(), d_at.p, n_hdr * 8, hipMemcpyDeviceToHost, st));
+    MXG_HIP(h, hipMemcpyAsync(end.data(), d_end.p, n_hdr * 8, hipMemcpyDeviceToHost, st));
+    MXG_HIP(h, hipStreamSynchronize(st));
+    for (uint64_t r = 0; r < n_hdr; ++r) {
+        if (at[r] >= usz || end[r] <= at[r] || end[r] > usz || (r && at[r] <= end[r - 1]))
+            return set_err(h, MXG_EDEVICE, "internal error: header lines of '%s' out of order", path);
+        hdr[r] = Hdr{at[r], end[r]};
+        line_off[r + 1] = line_off[r] + (end[r] - at[r] - 1);
+    }
+    lines.resize(line_off[n_hdr]);
+    if (!lines.empty()) {
+        if ((e = d_lines.ensure(lines.size())) != hipSuccess)
+            return soft(e) ? 1 : set_err(h, MXG_EDEVICE, "device allocation failed: %s", hipGetErrorString(e));
+        MXG_HIP(h, hipMemcpyAsync(d_off.p, line_off.data(), n_hdr * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_hdr_gather, dim3(hb), dim3(256), 0, st, d_text, d_at.as<uint64_t>(), d_end.as<uint64_t>(), d_off.as<uint64_t>(), n_hdr,
+                           d_lines.as<unsigned char>());
+        MXG_HIP(h, hipGetLastError());
+        MXG_HIP(h, hipMemcpyAsync(lines.data(), d_lines.p, lines.size(), hipMemcpyDeviceToHost, st));
+        MXG_HIP(h, hipStreamSynchronize(st));
+    }
+    return MXG_OK;
+}
+
 // returns MXG_OK, a negative error, or 1: "not for this route" (the caller falls back to the host parser)
 int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_threads)
 {
@@ -168,7 +311,7 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
     const uint64_t fsz = (uint64_t)sb.st_size;
     unsigned char magic[2] = {0, 0};
     const bool gz = fsz >= 2 && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-    if (fsz == 0 || gz) {  // (the host parser produces the empty assembly / inflates gzip input)
+    if (fsz == 0) {  // (the host parser produces the empty assembly)
         close(fd);
         return 1;
     }
@@ -194,6 +337,15 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
             munmap(const_cast<unsigned char *>(p), n);
         }
     } unmap{txt, fsz, (h->cfg.flags & MXG_FLAG_ONE_SHOT) && !getenv("MXG_UNMAP_EARLY") ? h : nullptr};
+    // gzip magic: a chain of BGZF members is inflated on the device (the file below = the compressed bytes, the text = what the
+    // trailers add up to); plain gzip, a mixed file, a walk that misses the file's end, no text at all: the host parser and zlib
+    BgzfPlan plan;
+    const bool bgzf = gz;
+    if (gz && (!bgzf_plan(txt, fsz, plan) || plan.usz == 0)) {
+        unmap.keep = nullptr;
+        return 1;
+    }
+    const uint64_t tsz = bgzf ? plan.usz : fsz;  // bytes of text
     MXG_HIP(h, hipSetDevice(h->device));
 
     // ---- (2) raw text -> HBM through pinned staging buffers, started first so that it overlaps the header scan ----
@@ -203,12 +355,15 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
         (void)hipGetLastError();
         return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation;
     };
-    const uint64_t text_alloc = ((fsz + ING_TILE - 1) / ING_TILE + 1) * ING_TILE;
+    const uint64_t text_alloc = ((tsz + ING_TILE - 1) / ING_TILE + 1) * ING_TILE;
+    DevBuf d_comp;  // BGZF: the file's bytes, released as soon as the text is inflated (whole words: the decoder fetches aligned words)
     {
-        const hipError_t e = a->d_text.ensure(text_alloc);
+        hipError_t e = a->d_text.ensure(text_alloc);
+        if (e == hipSuccess && bgzf) e = d_comp.ensure((fsz + 3) & ~3ull);
         if (e != hipSuccess) return dev_fallback(e) ? 1 : set_err(h, MXG_EDEVICE, "device allocation failed: %s", hipGetErrorString(e));
     }
     unsigned char *d_text = a->d_text.as<unsigned char>();
+    unsigned char *d_up = bgzf ? d_comp.as<unsigned char>() : d_text;  // where the file's bytes go
     tp_alloc = now_s() - tp0;
     constexpr uint64_t STAGE = 32ull << 20;
     constexpr int NB = 4;
@@ -273,19 +428,31 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
             } catch (const std::exception &) {  // (no thread to be had: copy alone)
                 memcpy(stage[b], txt + off, n);
             }
-            if (uerr == hipSuccess) uerr = hipMemcpyAsync(d_text + off, stage[b], n, hipMemcpyHostToDevice, cs);
+            if (uerr == hipSuccess) uerr = hipMemcpyAsync(d_up + off, stage[b], n, hipMemcpyHostToDevice, cs);
             if (uerr == hipSuccess) uerr = hipEventRecord(sev[b], cs);
         }
-        if (uerr == hipSuccess) uerr = hipMemsetAsync(d_text + fsz, '\n', text_alloc - fsz, cs);
+        if (uerr == hipSuccess) uerr = hipMemsetAsync(d_text + tsz, '\n', text_alloc - tsz, cs);
         if (uerr == hipSuccess) uerr = hipStreamSynchronize(cs);
     });
 
     // ---- (1) header lines: '>' at the start of a line ----
-    struct Hdr {
-        uint64_t at, end;  // '>' and its line's '\n' (or the file's end)
-    };
-    std::vector<std::vector<Hdr>> found(n_threads);
-    parallel_for(n_threads, [&](uint32_t t) {
+    std::vector<Hdr> hdr;
+    std::vector<unsigned char> hdr_lines;  // BGZF: the header lines' bytes as the device gathered them
+    std::vector<uint64_t> hdr_line_off;
+    double tp_bgzf = 0;
+    if (bgzf) {  // (the text has to be there first: upload, inflate, then the header lines by kernels)
+        sg.finish();
+        if (uerr != hipSuccess) return set_err(h, MXG_EDEVICE, "text upload failed: %s", hipGetErrorString(uerr));
+        tp_bgzf = now_s() - tp0;
+        const int brc = bgzf_text_and_headers(h, path, plan, d_comp.as<unsigned char>(), fsz, d_text, h->stream, dbg_io, hdr, hdr_lines, hdr_line_off);
+        if (brc != MXG_OK) {
+            if (brc == 1) unmap.keep = nullptr;
+            return brc;
+        }
+        d_comp.release();
+    }
+    std::vector<std::vector<Hdr>> found(bgzf ? 0 : n_threads);
+    if (!bgzf) parallel_for(n_threads, [&](uint32_t t) {
         const uint64_t lo = fsz * t / n_threads, hi = fsz * (t + 1) / n_threads;
         uint64_t p = lo;
         while (p < hi) {
@@ -302,7 +469,6 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
             }
         }
     });
-    std::vector<Hdr> hdr;
     for (auto &v : found)
         for (auto &x : v)
             if (hdr.empty() || x.at > hdr.back().end) hdr.push_back(x);  // (a chunk border inside a header line)
@@ -313,8 +479,8 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
     std::vector<uint64_t> rec_item0(n_rec + 1);
     a->recs.resize(n_rec);
     for (size_t r = 0; r < n_rec; ++r) {
-        const uint64_t sb0 = std::min(hdr[r].end + 1, fsz), se = r + 1 < n_rec ? hdr[r + 1].at : fsz;
-        a->recs[r].id = header_token(txt + hdr[r].at + 1, hdr[r].end - hdr[r].at - 1);
+        const uint64_t sb0 = std::min(hdr[r].end + 1, tsz), se = r + 1 < n_rec ? hdr[r + 1].at : tsz;
+        a->recs[r].id = header_token(bgzf ? hdr_lines.data() + hdr_line_off[r] : txt + hdr[r].at + 1, hdr[r].end - hdr[r].at - 1);
         a->recs[r].text_off = sb0;
         rec_item0[r] = items.size();
         for (uint64_t p = sb0; p < se;) {
@@ -459,12 +625,12 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
     a->has_bases = true;
     a->has_text = false;
     a->text_on_device = true;
-    a->text_bytes = fsz;
+    a->text_bytes = tsz;
     a->ing_item0.assign(rec_item0.begin(), rec_item0.end());
     if (dbg_io)
         fprintf(stderr, "[mxg] load_fasta_device %s: %.3f s = open + map + text buffer %.3f, first pinned buffer at %.3f, headers + items (beside the "
                         "upload) until %.3f, upload done at %.3f, base counts at %.3f, packed at %.3f, run table at %.3f (%.2f GB)\n", path, now_s() - tp0,
-                tp_alloc, tp_pool, tp_hdr, tp_up, tp_count, tp_pack, now_s() - tp0, fsz / 1e9);
+                tp_alloc, tp_pool, tp_hdr, bgzf ? tp_bgzf : tp_up, tp_count, tp_pack, now_s() - tp0, tsz / 1e9);
     if (h->cfg.flags & MXG_FLAG_DROP_SEQ) {  // the caller does not want the text kept: k-mers are then printed from the packed bases
         a->d_text.release();
         a->d_ing_items.release();

@@ -398,6 +398,11 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
 int write_tsv_device(mxg_handle *h, Assembly *a, const char *path, int with_pos, int with_strand, int with_seq);
 int fetch_device_text(mxg_handle *h, Assembly *a, std::string &seq, std::vector<uint64_t> &rec_off);  // (for the host TSV writer)
 uint32_t host_threads(const mxg_handle *h);
+// bgzf.hip: the members of a BGZF file (bgzf_inflate.h) inflated by one launch on `st`; d_status: n_members + 1 words, word 0 ends as
+// 0 or the largest BgzfStatus of any member, word 1 + m as member m's
+struct BgzfMember;
+int bgzf_inflate_device(mxg_handle *h, const unsigned char *d_comp, uint64_t comp_bytes, const BgzfMember *d_members, uint32_t n_members,
+                        unsigned char *d_text, uint64_t text_bytes, uint32_t *d_status, hipStream_t st);
 // n_parts byte ranges written to fd at consecutive offsets from `off` on, by that many threads (host_io.cpp)
 bool put_parallel(int fd, uint64_t off, const char *const *data, const size_t *len, uint32_t n_parts);
 // a file that is removed again unless the call completes (only a regular file this call created or truncated):
