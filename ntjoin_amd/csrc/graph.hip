@@ -58,7 +58,6 @@ struct AsmSet {
     const uint64_t *hash[MXG_MAX_ASSEMBLIES];
     uint32_t *slot[MXG_MAX_ASSEMBLIES];
     uint8_t *flags[MXG_MAX_ASSEMBLIES];
-    uint8_t *shared[MXG_MAX_ASSEMBLIES];
     uint64_t *fol;                              // partitioned join: bit t of word 4 b + q = minimizer 64 q + t of block b is a follower
 };
 
@@ -126,7 +125,6 @@ __global__ __launch_bounds__(256) void k_flags(const AsmSet p, const Slot *__res
         const bool inall = seen == full;
         sh = inall && d == 0;
         p.flags[a][i] = (uint8_t)((uniq ? MXG_MX_UNIQUE : 0) | (sh ? MXG_MX_SHARED : 0) | (inall ? MXG_MX_INALL : 0));
-        p.shared[a][i] = sh ? 1 : 0;
     }
     const uint32_t c = (uint32_t)__syncthreads_count(sh ? 1 : 0);
     if (threadIdx.x == 0) count_publish(cnt + p.bstart[a], sup + sup_start(p, a), blockIdx.x - p.bstart[a], c);
@@ -774,48 +772,137 @@ __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint
     }
 }
 
-// k_flags for the partitioned join: the table state of minimizer i sits in recs[slot[a][i]]
-// mask0[w]: which of minimizers 64 w .. 64 w + 63 of assembly 0 are shared (k_vertices_pj ranks by it)
-__global__ __launch_bounds__(256) void k_flags_pj(const AsmSet p, uint32_t *cnt, uint32_t *sup, uint64_t *mask0)
+// ---- the tail's ordered passes: U consecutive 256-blocks per thread block ---------------------------------------------------
+// k_flags_pj, k_vertices_pj, k_adjacency, k_edge_flags and k_edges are plain ordered passes, one item per thread.  With one 256-block
+// per thread block a CU has 8 KB of loads in flight where an HBM round trip wants tens of KB, and every 256 items pay a block's
+// bookkeeping ("The tail's ordered passes").  Thread block j of <U> takes 256-blocks j U .. j U + U - 1
+// ("sub-blocks"); thread t keeps item t of each, so a wave still holds 64 consecutive items and the ballots, fol and mask0 words
+// and the per-256 counts are what they were.  Every sub-block's loads are requested before the first is used, the dependent
+// gathers follow for all U together, and the bookkeeping of sub-block u -- its count_prefix, its count_publish, the "last tile
+// reports the total" duty -- is done by wave u (U <= 4 = waves per block).  U by size: graph_tail_u (join_plan.h), MXG_GRAPH_U
+// forces it.  The global-table route's own passes (k_flags, k_vertices) stay at one 256-block per thread block.
+//
+// Ordered ranks of 0/1 flags inside the U sub-blocks with ONE barrier: a wave's ranks are a ballot and a popcount, the four wave
+// totals per sub-block go through LDS beside whatever else the caller publishes in front of the same barrier.
+template <uint32_t U>
+struct TailScan {
+    uint32_t tot[U][4];   // flags set per (sub-block, wave)
+    uint32_t before[U];   // what precedes the sub-block (count_prefix by wave u)
+};
+template <uint32_t U>
+__device__ __forceinline__ void tail_ballot(TailScan<U> &ts, uint32_t u, bool f, uint64_t &bm)
 {
-    const uint32_t a = asm_of_block(p, blockIdx.x);
-    const uint32_t i = (blockIdx.x - p.bstart[a]) * 256u + threadIdx.x;
-    bool sh = false;
-    {
-        // the verdict k_pj_join left here (k_vertices_pj reads the word's upper part) -- or a reference to the minimizer that
-        // went on for this one (k_pj2_bucket); a follower (pj_run_role) has neither: its leader, the last lane in front of it
-        // that is no follower, says whether the key is in every assembly
-        // (the verdict word is requested beside the follower bits, not behind them: a follower's word -- never written, whatever
-        // the buffer held -- is read and dropped)
-        const bool in = i < asm_n(p, a);
-        const uint32_t lane = threadIdx.x & 63u;
-        const uint64_t fb = p.fol[blockIdx.x * 4u + (threadIdx.x >> 6)];
-        const uint32_t v_raw = in ? p.slot[a][i] : 0u;
-        const bool isf = (fb >> lane) & 1ull;
-        uint32_t v = isf ? 0u : v_raw;
-        bool other = isf;
-        if ((v & 7u) == PJ_VERDICT_REF) {
-            v = p.slot[a][v >> 3];
-            other = true;
-        }
-        const uint32_t lead = 63u - (uint32_t)__clzll(~fb & ((2ull << lane) - 1ull));  // (lane 0 follows nobody; lane 63: the
-        const uint32_t vl = __shfl(v, lead);                                            //  shift wraps to 0, the mask to all ones)
-        if (isf) v = vl;
-        if (other) v &= MXG_MX_INALL;  // more than once in this assembly: neither unique nor shared
-        if (in) {
-            sh = (v & MXG_MX_SHARED) != 0;
-            p.flags[a][i] = (uint8_t)(v & 7u);
-            p.shared[a][i] = sh ? 1 : 0;
+    bm = __ballot(f);
+    if ((threadIdx.x & 63u) == 0) ts.tot[u][threadIdx.x >> 6] = (uint32_t)__popcll(bm);
+}
+// (behind the barrier) rank of this thread's flag of sub-block u among the sub-block's set flags
+template <uint32_t U>
+__device__ __forceinline__ uint32_t tail_rank(const TailScan<U> &ts, uint32_t u, uint64_t bm)
+{
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    uint32_t r = (uint32_t)__popcll(bm & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (uint32_t q = 0; q < 3; ++q) r += q < wv ? ts.tot[u][q] : 0u;
+    return r;
+}
+template <uint32_t U>
+__device__ __forceinline__ uint32_t tail_total(const TailScan<U> &ts, uint32_t u)
+{
+    return ts.tot[u][0] + ts.tot[u][1] + ts.tot[u][2] + ts.tot[u][3];
+}
+
+// The assemblies of a thread block's U sub-blocks [blk0, blk0 + U) of the concatenated 256-blocks: almost always one (its table
+// entries -- scalar loads from the argument block, dependent on one another -- are then fetched once, as in k_pj_bucket).
+// (The passes request their loads without branches around them -- an item that does not exist reads element 0 of an array that
+// does, and drops it -- so that the U sub-blocks' requests stay one run of instructions: behind a branch per sub-block the
+// compiler waits for each sub-block's flag before it requests the next one's.)
+struct TailAsm {
+    uint32_t a, n, b0;  // assembly, its minimizers, its first 256-block
+};
+__device__ __forceinline__ TailAsm tail_asm(const AsmSet &p, uint32_t a)
+{
+    return TailAsm{a, asm_n(p, a), p.bstart[a]};
+}
+template <uint32_t U>
+__device__ __forceinline__ bool tail_asms(const AsmSet &p, uint32_t blk0, uint32_t nb, TailAsm (&t)[U])
+{
+    const uint32_t a_first = asm_of_block(p, blk0), a_last = U > 1 ? asm_of_block(p, min(blk0 + U, nb) - 1u) : a_first;
+    t[0] = tail_asm(p, a_first);
+#pragma unroll
+    for (uint32_t u = 1; u < U; ++u) t[u] = t[0];
+    if (a_first != a_last) {
+#pragma unroll
+        for (uint32_t u = 1; u < U; ++u)
+            if (blk0 + u < nb) t[u] = tail_asm(p, asm_of_block(p, blk0 + u));
+    }
+    return a_first == a_last;
+}
+
+// k_flags for the partitioned join: the verdict of minimizer i sits in slot[a][i]
+// mask0[w]: which of minimizers 64 w .. 64 w + 63 of assembly 0 are shared (k_vertices_pj ranks by it)
+template <uint32_t U>
+__global__ __launch_bounds__(256) void k_flags_pj(const AsmSet p, uint32_t nb, uint32_t *cnt, uint32_t *sup, uint64_t *mask0)
+{
+    __shared__ TailScan<U> ts;
+    const uint32_t blk0 = blockIdx.x * U, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    TailAsm t[U];
+    tail_asms<U>(p, blk0, nb, t);
+    // the verdict k_pj_join left here (k_vertices_pj reads the word's upper part) -- or a reference to the minimizer that
+    // went on for this one (k_pj2_bucket); a follower (pj_run_role) has neither: its leader, the last lane in front of it
+    // that is no follower, says whether the key is in every assembly
+    // (the verdict word is requested beside the follower bits, not behind them: a follower's word -- never written, whatever
+    // the buffer held -- is read and dropped)
+    uint64_t fb[U];
+    uint32_t v[U], ia[U], ii[U];
+    bool in[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const bool there = blk0 + u < nb;  // (a sub-block beyond the last reads the first one's words)
+        const uint32_t blk = there ? blk0 + u : blk0;
+        ia[u] = t[u].a;
+        ii[u] = (blk - t[u].b0) * 256u + threadIdx.x;
+        in[u] = there && ii[u] < t[u].n;
+        fb[u] = p.fol[(size_t)blk * 4u + wv];
+        v[u] = p.slot[t[u].a][in[u] ? ii[u] : 0u];
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        if (blk0 + u >= nb) fb[u] = 0;
+        if (!in[u]) v[u] = 0;
+    }
+    bool other[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {  // (the references, rare, for all U together)
+        const bool isf = (fb[u] >> lane) & 1ull;
+        if (isf) v[u] = 0u;
+        other[u] = isf;
+        if ((v[u] & 7u) == PJ_VERDICT_REF) {
+            v[u] = p.slot[ia[u]][v[u] >> 3];
+            other[u] = true;
         }
     }
-    const uint64_t bm = __ballot(sh);
-    if (a == 0 && (threadIdx.x & 63u) == 0) mask0[(blockIdx.x - p.bstart[0]) * 4u + (threadIdx.x >> 6)] = bm;
-    const uint32_t c = (uint32_t)__syncthreads_count(sh ? 1 : 0);
-    if (threadIdx.x == 0) count_publish(cnt + p.bstart[a], sup + sup_start(p, a), blockIdx.x - p.bstart[a], c);
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const bool isf = (fb[u] >> lane) & 1ull;
+        const uint32_t lead = 63u - (uint32_t)__clzll(~fb[u] & ((2ull << lane) - 1ull));  // (lane 0 follows nobody; lane 63: the
+        const uint32_t vl = __shfl(v[u], lead);                                            //  shift wraps to 0, the mask to all ones)
+        uint32_t w = isf ? vl : v[u];
+        if (other[u]) w &= MXG_MX_INALL;  // more than once in this assembly: neither unique nor shared
+        const bool sh = in[u] && (w & MXG_MX_SHARED) != 0;
+        if (in[u]) p.flags[ia[u]][ii[u]] = (uint8_t)(w & 7u);
+        uint64_t bm;
+        tail_ballot(ts, u, sh, bm);
+        if (blk0 + u < nb && ia[u] == 0 && lane == 0) mask0[(size_t)(blk0 + u - p.bstart[0]) * 4u + wv] = bm;
+    }
+    __syncthreads();
+    if (wv < U && lane == 0 && blk0 + wv < nb) {  // wave u publishes the count of sub-block u
+        const uint32_t blk = blk0 + wv, a = asm_of_block(p, blk);
+        count_publish(cnt + p.bstart[a], sup + sup_start(p, a), blk - p.bstart[a], tail_total(ts, wv));
+    }
 }
 
 struct VertexParams {
-    const uint8_t *shared;
+    const uint8_t *flags;   // (MXG_MX_SHARED: a vertex)
     const uint32_t *cnt, *sup;  // shared minimizers per 256 elements of this assembly + super-counts (k_flags)
     uint64_t *n_shared;     // ctl[a]: total, written by the last tile
     const uint32_t *slot;
@@ -834,11 +921,10 @@ struct VertexParams {
 // ordered compaction of the shared minimizers of one assembly; rank r in filtered order
 __global__ __launch_bounds__(256) void k_vertices(const VertexParams p)
 {
-    // one minimizer per thread: a few hundred thousand items are too few for four per thread (196 blocks on 256 CUs,
-    // each thread walking four dependent gathers)
+    // (the global-table route, i.e. the fallback: one 256-block per thread block; the partitioned join's passes take U)
     __shared__ uint32_t sh[256];
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const bool f = i < (p.n_ptr ? min(*p.n_ptr, p.n) : p.n) && p.shared[i];
+    const bool f = i < (p.n_ptr ? min(*p.n_ptr, p.n) : p.n) && (p.flags[i] & MXG_MX_SHARED);
     __shared__ uint32_t sh_before;
     if (threadIdx.x < 64) {
         const uint32_t bef = count_prefix(p.cnt, p.sup, blockIdx.x);
@@ -904,69 +990,138 @@ struct VertexPjParams {
     uint32_t *ivid[MXG_MAX_ASSEMBLIES];  // (owner of a partitioned graph stage: item -> vertex id, NONE32 for an item that is no vertex)
 };
 
-__global__ __launch_bounds__(256) void k_vertices_pj(const VertexPjParams p)
+template <uint32_t U>
+__global__ __launch_bounds__(256) void k_vertices_pj(const VertexPjParams p, uint32_t nb)
 {
-    __shared__ uint32_t sh[256];
-    __shared__ uint32_t sh_before;
-    const uint32_t a = asm_of_block(p.as, blockIdx.x);
-    const uint32_t blk = blockIdx.x - p.as.bstart[a], nblk = p.as.bstart[a + 1] - p.as.bstart[a];
-    const uint32_t i = blk * 256u + threadIdx.x;
-    // (what the minimizer brings along first: its loads -- for a > 0 the chain verdict word -> mask words -> vertex id -- do not
-    // need its rank, and the block's prefix below is two dependent round trips every thread would otherwise wait for first.
-    // The shared flag, the verdict word, record, position and hash are requested together, whether the minimizer is shared or
-    // not (three in four are): one round trip where the flag came first and the rest behind it.)
-    const bool in = i < asm_n(p.as, a);
-    const uint8_t shf = in ? p.as.shared[a][i] : (uint8_t)0;
-    const uint32_t vw = in && a ? p.as.slot[a][i] : 0u;  // (the verdict word: flags in its three low bits)
-    const uint32_t rec = in ? p.rec[a][i] : 0u, pos = in ? p.pos[a][i] : 0u;
-    const uint64_t hsh = in && !a ? p.as.hash[0][i] : 0ull;
-    const bool f = shf != 0;
-    uint32_t v0 = 0;
-    if (f && a) {
-        const uint32_t i0 = vw >> 3, w = i0 >> 6;
-        const uint64_t *m = p.mask0 + (w & ~3u);
-        v0 = p.bpref0[i0 >> 8] + (uint32_t)__popcll(p.mask0[w] & ((1ull << (i0 & 63u)) - 1ull));
-        for (uint32_t q = 0; q < (w & 3u); ++q) v0 += (uint32_t)__popcll(m[q]);
+    __shared__ TailScan<U> ts;
+    const uint32_t blk0 = blockIdx.x * U, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    TailAsm t[U];
+    tail_asms<U>(p.as, blk0, nb, t);
+    // (what the minimizers bring along first: their loads -- for a > 0 the chain verdict word -> mask words -> vertex id -- do not
+    // need their rank, and a sub-block's prefix below is two dependent round trips every thread would otherwise wait for first.
+    // The flag byte, the verdict word, record, position and hash of all U sub-blocks are requested together, whether the
+    // minimizer is shared or not (three in four are): one round trip where the flag came first and the rest behind it.
+    // Assembly 0 needs no verdict word and the others no hash: their threads all read element 0 of it, one line.)
+    uint32_t ia[U], ii[U], vw[U], rec[U], pos[U];
+    uint64_t hsh[U];
+    bool in[U], f[U];
+    {
+        uint8_t fl[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            const bool there = blk0 + u < nb;
+            const uint32_t a = ia[u] = t[u].a, i = ii[u] = ((there ? blk0 + u : blk0) - t[u].b0) * 256u + threadIdx.x;
+            in[u] = there && i < t[u].n;
+            const uint32_t ic = in[u] ? i : 0u;
+            fl[u] = p.as.flags[a][ic];
+            vw[u] = p.as.slot[a][a ? ic : 0u];  // (the verdict word: flags in its three low bits)
+            rec[u] = p.rec[a][ic];
+            pos[u] = p.pos[a][ic];
+            hsh[u] = p.as.hash[0][a ? 0u : ic];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) f[u] = in[u] & ((fl[u] & MXG_MX_SHARED) != 0);  // (&: no branch around the flag)
     }
-    if (threadIdx.x < 64) {
+    // a > 0: the vertex id is the rank of the key's minimizer i0 in assembly 0.  The four mask words of i0's 256-block and the
+    // block's prefix are requested together (the words in front of i0's own were a loop of dependent length), for two sub-blocks
+    // at a time.  (<4> still takes 90 VGPRs, 5 waves per SIMD, and traced no faster than <2> with 58 and 8: by size the pass stops
+    // at U = 2, join_plan.h.)
+    uint32_t v0[U];
+#pragma unroll
+    for (uint32_t h = 0; h < U; h += 2) {
+        constexpr uint32_t G = U < 2 ? U : 2;
+        ulonglong2 mlo[G], mhi[G];
+        uint32_t bp[G];
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            const uint32_t u = h + g;
+            const uint32_t i0 = f[u] && ia[u] ? vw[u] >> 3 : 0u;  // (no vertex of an assembly > 0: block 0's words, dropped)
+            const ulonglong2 *m = reinterpret_cast<const ulonglong2 *>(p.mask0 + ((i0 >> 6) & ~3u));  // (32-byte aligned)
+            mlo[g] = m[0];
+            mhi[g] = m[1];
+            bp[g] = p.bpref0[i0 >> 8];
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            const uint32_t i0 = vw[h + g] >> 3, q = (i0 >> 6) & 3u;
+            const uint64_t own = q == 0 ? mlo[g].x : q == 1 ? mlo[g].y : q == 2 ? mhi[g].x : mhi[g].y;
+            v0[h + g] = bp[g] + (uint32_t)__popcll(own & ((1ull << (i0 & 63u)) - 1ull)) + (q > 0 ? (uint32_t)__popcll(mlo[g].x) : 0u) +
+                        (q > 1 ? (uint32_t)__popcll(mlo[g].y) : 0u) + (q > 2 ? (uint32_t)__popcll(mhi[g].x) : 0u);
+        }
+        if (U > 2) __builtin_amdgcn_sched_barrier(0);  // (or the scheduler requests the second pair's words beside the first's)
+    }
+    uint64_t bm[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) tail_ballot(ts, u, f[u], bm[u]);
+    if (wv < U && blk0 + wv < nb) {  // wave u: what precedes sub-block u in its assembly
+        const uint32_t blk_g = blk0 + wv, a = asm_of_block(p.as, blk_g);
+        const uint32_t blk = blk_g - p.as.bstart[a], nblk = p.as.bstart[a + 1] - p.as.bstart[a];
         const uint32_t *cnt = p.cnt + p.as.bstart[a], *sup = p.sup + sup_start(p.as, a);
         const uint32_t bef = count_prefix(cnt, sup, blk);
-        if (threadIdx.x == 0) sh_before = bef;
+        if (lane == 0) ts.before[wv] = bef;
         if (blk + 1 == nblk) {  // the assembly's last tile also reports its total
             const uint32_t all = count_prefix(cnt, sup, nblk);
-            if (threadIdx.x == 0) p.n_shared[a] = all;
+            if (lane == 0) p.n_shared[a] = all;
         }
     }
     __syncthreads();
-    const uint32_t r = sh_before + block_exclusive_256(f ? 1u : 0u, sh);
-    if (in && p.ivid[a]) p.ivid[a][i] = f ? (a ? v0 : r) : 0xFFFFFFFFu;
-    if (!f) return;
-    const uint32_t v = a ? v0 : r;
-    if (!a) p.vhash[v] = hsh;
-    const size_t o = (size_t)a * p.nvs;
-    p.vpos[o + v] = pos;
-    p.vrec[o + v] = rec;
-    p.fv[o + r] = v;
-    p.frec[o + r] = rec;
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        if (!in[u]) continue;
+        const uint32_t a = ia[u], i = ii[u];
+        const uint32_t r = ts.before[u] + tail_rank(ts, u, bm[u]);
+        const uint32_t v = a ? v0[u] : r;
+        if (p.ivid[a]) p.ivid[a][i] = f[u] ? v : NONE32;
+        if (!f[u]) continue;
+        if (!a) p.vhash[v] = hsh[u];
+        const size_t o = (size_t)a * p.nvs;
+        p.vpos[o + v] = pos[u];
+        p.vrec[o + v] = rec[u];
+        p.fv[o + r] = v;
+        p.frec[o + r] = rec[u];
+    }
 }
 
 // blockIdx.y = assembly; all arrays are [A][stride].  adj[a][u] = {successor, predecessor} of vertex u in assembly a's filtered
 // order (NONE32: none) -- one 8-byte entry, so that the kernels that ask "is v next to u in assembly b" touch one sector per
 // (b, u), not two.  Every vertex occurs exactly once in every assembly's filtered list (a shared minimizer is unique in each
 // assembly), so the thread of position r writes the whole entry of its vertex: nothing has to be cleared beforehand.
+// (Records and vertices of r and of both neighbours are requested together for all U sub-blocks, inside the rows' `stride`
+// words and beside the vertex count, not behind it: what lies beyond the count is read and dropped.)
+template <uint32_t U>
 __global__ __launch_bounds__(256) void k_adjacency(const uint32_t *__restrict__ fv0, const uint32_t *__restrict__ frec0,
                                                    const uint64_t *__restrict__ nv_ptr, uint2 *__restrict__ adj0, uint32_t stride)
 {
-    const uint32_t nv = (uint32_t)*nv_ptr;  // number of shared minimizers, still in HBM (no host sync before this stage)
     const size_t o = (size_t)blockIdx.y * stride;
     const uint32_t *fv = fv0 + o, *frec = frec0 + o;
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= nv) return;
-    const uint32_t rec = frec[r];
-    // consecutive surviving minimizers of the same contig (ntjoin_utils.py:98-99)
-    const uint32_t nx = (r + 1 < nv && frec[r + 1] == rec) ? fv[r + 1] : NONE32;
-    const uint32_t pv = (r > 0 && frec[r - 1] == rec) ? fv[r - 1] : NONE32;
-    adj0[o + fv[r]] = make_uint2(nx, pv);
+    uint32_t rc[U], rn[U], rp[U], vc[U], vn[U], vp[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t r = (blockIdx.x * U + u) * 256u + threadIdx.x;  // (< 2^32: the grid covers `stride` < 2^32 / A positions)
+        rc[u] = rn[u] = rp[u] = vc[u] = vn[u] = vp[u] = 0;
+        if (r < stride) {
+            rc[u] = frec[r];
+            vc[u] = fv[r];
+            if (r + 1 < stride) {
+                rn[u] = frec[r + 1];
+                vn[u] = fv[r + 1];
+            }
+            if (r > 0) {
+                rp[u] = frec[r - 1];
+                vp[u] = fv[r - 1];
+            }
+        }
+    }
+    const uint32_t nv = (uint32_t)*nv_ptr;  // number of shared minimizers, still in HBM (no host sync before this stage)
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t r = (blockIdx.x * U + u) * 256u + threadIdx.x;
+        if (r >= nv) continue;  // (nv <= stride)
+        // consecutive surviving minimizers of the same contig (ntjoin_utils.py:98-99)
+        const uint32_t nx = (r + 1 < nv && rn[u] == rc[u]) ? vn[u] : NONE32;
+        const uint32_t pv = (r > 0 && rp[u] == rc[u]) ? vp[u] : NONE32;
+        adj0[o + vc[u]] = make_uint2(nx, pv);
+    }
 }
 
 struct EdgeParams {
@@ -997,77 +1152,128 @@ __device__ __forceinline__ uint32_t edge_mask(const EdgeParams &p, uint32_t u, u
 // item = a*nv + r : the pair (filtered[a][r], filtered[a][r+1]); flagged iff assembly a is the first supporter
 // (up to eight assemblies the flag byte IS the edge's support mask: k_edges then has nothing to look up again -- 2 A random
 // reads per edge less)
-__global__ __launch_bounds__(256) void k_edge_flags(const EdgeParams p)
+// (n_items = n_asm * nv < 2^32; the row a = item / nv may change anywhere inside a thread block: it is the item's own)
+template <uint32_t U>
+__global__ __launch_bounds__(256) void k_edge_flags(const EdgeParams p, uint32_t n_items)
 {
-    uint64_t item = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    uint8_t f = 0;
-    if (item < (uint64_t)p.n_asm * p.nv) {
-        uint32_t a = (uint32_t)(item / p.nv);
-        uint32_t r = (uint32_t)(item % p.nv);
-        if (r < (uint32_t)*p.nv_ptr) {  // (beyond it: not a vertex)
-            const uint32_t u = p.fv[item];
-            // (up to four assemblies: their entries of u are requested together with this assembly's own -- the successor is
-            // then one of them -- instead of behind it)
-            uint32_t v, m = 0;
-            if (p.n_asm <= 4u) {
-                uint2 q[4];
+    __shared__ TailScan<U> ts;
+    const uint32_t blk0 = blockIdx.x * U, nblk = (n_items + 255u) / 256u, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    // the vertices of all U sub-blocks, beside the vertex count (what lies beyond it in a row is read and dropped)
+    uint32_t uu[U], ia[U];
+    bool live[U];
 #pragma unroll
-                for (uint32_t b = 0; b < 4u; ++b) q[b] = b < p.n_asm ? p.adj[(size_t)b * p.nv + u] : make_uint2(NONE32, NONE32);
-                v = a == 0 ? q[0].x : a == 1 ? q[1].x : a == 2 ? q[2].x : q[3].x;
-#pragma unroll
-                for (uint32_t b = 0; b < 4u; ++b)
-                    if (b < p.n_asm && (q[b].x == v || q[b].y == v)) m |= 1u << b;
-            } else {
-                v = p.adj[(size_t)a * p.nv + u].x;
-                if (v != NONE32) m = edge_mask(p, u, v);
-            }
-            if (v != NONE32) f = ((uint32_t)__builtin_ctz(m) == a) ? (p.n_asm <= 8u ? (uint8_t)m : (uint8_t)1) : (uint8_t)0;
-        }
-        p.eflag[item] = f;
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t item = (blk0 + u) * 256u + threadIdx.x;
+        uu[u] = p.fv[blk0 + u < nblk && item < n_items ? item : 0u];
     }
-    const uint32_t c = (uint32_t)__syncthreads_count(f);
-    if (threadIdx.x == 0) count_publish(p.bsum, p.bsuper, blockIdx.x, c);
+    const uint32_t nvc = (uint32_t)*p.nv_ptr;
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t item = (blk0 + u) * 256u + threadIdx.x;
+        const bool in = blk0 + u < nblk && item < n_items;
+        ia[u] = in ? item / p.nv : 0u;
+        live[u] = in && item - ia[u] * p.nv < nvc;  // (beyond the count: not a vertex)
+    }
+    uint8_t f[U];
+    if (p.n_asm <= 4u) {
+        // (up to four assemblies: their entries of u are requested together with this assembly's own -- the successor is
+        // then one of them -- instead of behind it; and all U sub-blocks' together)
+        uint2 q[U][4];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u)
+#pragma unroll
+            for (uint32_t b = 0; b < 4u; ++b)
+                q[u][b] = b < p.n_asm ? p.adj[(size_t)b * p.nv + (live[u] ? uu[u] : 0u)] : make_uint2(NONE32, NONE32);
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            const uint32_t a = ia[u];
+            const uint32_t v = a == 0 ? q[u][0].x : a == 1 ? q[u][1].x : a == 2 ? q[u][2].x : q[u][3].x;
+            uint32_t m = 0;
+#pragma unroll
+            for (uint32_t b = 0; b < 4u; ++b)
+                if (b < p.n_asm && (q[u][b].x == v || q[u][b].y == v)) m |= 1u << b;
+            f[u] = live[u] && v != NONE32 && (uint32_t)__builtin_ctz(m) == a ? (uint8_t)m : (uint8_t)0;
+        }
+    } else {
+        uint32_t v[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) v[u] = p.adj[(size_t)ia[u] * p.nv + (live[u] ? uu[u] : 0u)].x;
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u)
+            if (!live[u]) v[u] = NONE32;
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            f[u] = 0;
+            if (v[u] == NONE32) continue;
+            const uint32_t m = edge_mask(p, uu[u], v[u]);
+            if ((uint32_t)__builtin_ctz(m) == ia[u]) f[u] = p.n_asm <= 8u ? (uint8_t)m : (uint8_t)1;
+        }
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t item = (blk0 + u) * 256u + threadIdx.x;
+        if (blk0 + u < nblk && item < n_items) p.eflag[item] = f[u];
+        uint64_t bm;
+        tail_ballot(ts, u, f[u] != 0, bm);
+    }
+    __syncthreads();
+    if (wv < U && lane == 0 && blk0 + wv < nblk) count_publish(p.bsum, p.bsuper, blk0 + wv, tail_total(ts, wv));
 }
 
+// (U 256-blocks per thread block, one item per thread of each: see "the tail's ordered passes" above)
+template <uint32_t U>
 __global__ __launch_bounds__(256) void k_edges(const EdgeParams p, uint32_t n_items)
 {
-    __shared__ uint32_t sh[256];
-    const uint32_t item = blockIdx.x * 256u + threadIdx.x;  // (one per thread: see k_vertices)
-    const uint32_t fb = item < n_items ? p.eflag[item] : 0u;
-    const bool f = fb != 0;
-    // (the edge itself first: its chain of loads -- vertex, successor, the other assemblies' adjacency -- does not need the edge's
-    // place, and the block's prefix below is two dependent round trips every thread would otherwise wait for before starting)
-    uint32_t u = 0, v = 0, m = 0;
-    double wsum = 0.0;
-    if (f) {
-        const uint32_t a = item / p.nv;
-        u = p.fv[item];  // (fv is [A][nv] like the items; behind the flag: with many assemblies few items are edges)
-        v = p.adj[(size_t)a * p.nv + u].x;
-        m = p.n_asm <= 8u ? fb : edge_mask(p, u, v);
-        // python: sum(weights[f] for f in support) -- int 0 start, then float adds in support (= assembly) order
-        for (uint32_t b = 0; b < p.n_asm; ++b)
-            if (m & (1u << b)) wsum = wsum + p.weights[b];
+    __shared__ TailScan<U> ts;
+    const uint32_t blk0 = blockIdx.x * U, nblk = (n_items + 255u) / 256u, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    // (the edges themselves first: their chain of loads -- flag and vertex, successor, the other assemblies' adjacency -- does not
+    // need the edges' places, and a sub-block's prefix below is two dependent round trips every thread would otherwise wait for)
+    uint32_t fb[U], uu[U], v[U], m[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t item = (blk0 + u) * 256u + threadIdx.x;
+        const bool in = blk0 + u < nblk && item < n_items;
+        fb[u] = p.eflag[in ? item : 0u];
+        uu[u] = p.fv[in ? item : 0u];  // (fv is [A][nv] like the items; beside the flag, not behind it)
+        if (!in) fb[u] = 0;
     }
-    __shared__ uint32_t sh_before;
-    if (threadIdx.x < 64) {
-        const uint32_t bef = count_prefix(p.bsum, p.bsuper, blockIdx.x);
-        if (threadIdx.x == 0) sh_before = bef;
-        if (blockIdx.x + 1 == gridDim.x) {  // the last tile also reports the total
-            const uint32_t all = count_prefix(p.bsum, p.bsuper, (n_items + 255u) / 256u);
-            if (threadIdx.x == 0) {
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u)  // (no edge: entry 0, dropped)
+        v[u] = p.adj[fb[u] ? (size_t)(((blk0 + u) * 256u + threadIdx.x) / p.nv) * p.nv + uu[u] : (size_t)0].x;
+    uint64_t bm[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) tail_ballot(ts, u, fb[u] != 0, bm[u]);
+    if (wv < U && blk0 + wv < nblk) {  // wave u: edges in front of sub-block u
+        const uint32_t bef = count_prefix(p.bsum, p.bsuper, blk0 + wv);
+        if (lane == 0) ts.before[wv] = bef;
+        if (blk0 + wv + 1 == nblk) {  // the last tile also reports the total
+            const uint32_t all = count_prefix(p.bsum, p.bsuper, nblk);
+            if (lane == 0) {
                 *p.n_edges = all;
                 p.host_ctl[32] = all;  // CTL_EDGES
             }
-            if (threadIdx.x < p.n_asm) p.host_ctl[threadIdx.x] = p.nv_ptr[threadIdx.x];  // shared minimizers per assembly
+            if (lane < p.n_asm) p.host_ctl[lane] = p.nv_ptr[lane];  // shared minimizers per assembly
         }
     }
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        m[u] = fb[u];
+        if (fb[u] && p.n_asm > 8u) m[u] = edge_mask(p, uu[u], v[u]);
+    }
     __syncthreads();
-    const uint32_t e = sh_before + block_exclusive_256(f ? 1u : 0u, sh);
-    if (!f) return;
-    p.eu[e] = u;
-    p.ev[e] = v;
-    p.esup[e] = m;
-    p.ew[e] = wsum;
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        if (!fb[u]) continue;
+        // python: sum(weights[f] for f in support) -- int 0 start, then float adds in support (= assembly) order
+        double wsum = 0.0;
+        for (uint32_t b = 0; b < p.n_asm; ++b)
+            if (m[u] & (1u << b)) wsum = wsum + p.weights[b];
+        const uint32_t e = ts.before[u] + tail_rank(ts, u, bm[u]);
+        p.eu[e] = uu[u];
+        p.ev[e] = v[u];
+        p.esup[e] = m[u];
+        p.ew[e] = wsum;
+    }
 }
 
 // distributed graph, owner side (dgraph.hip): adjacency arrives as messages {kind << 8 | assembly, local vertex, other
@@ -1187,6 +1393,7 @@ static int plan_join(mxg_handle *h, int mode, const GraphBounds *gb, bool global
     const char *join_env = knob_raw(h, "MXG_GRAPH_JOIN");
     rq.join_global = join_env && !strcmp(join_env, "global");
     rq.force_two_level = knob_u64(h, "MXG_PJ_TWO_LEVEL", 0) != 0;
+    rq.graph_u = (uint32_t)std::min<uint64_t>(knob_u64(h, "MXG_GRAPH_U", 0), 8);  // 1 | 2 | 4 forces the tail passes' width
     switch (join_shape(rq, h->pj_learnt, pl)) {
     case JS_TOO_MANY_MINIMIZERS: return set_err(h, MXG_ELIMIT, "too many minimizers for one table (%llu)", (unsigned long long)pl.N);
     case JS_TOO_MANY_ITEMS: return set_err(h, MXG_ELIMIT, "graph too large for 32-bit item indices");
@@ -1216,20 +1423,18 @@ static int plan_join(mxg_handle *h, int mode, const GraphBounds *gb, bool global
         Assembly *as = h->asms[a];
         MXG_HIP(h, as->d_slot.ensure(std::max<uint64_t>(n_of[a] * 4, 16)));
         MXG_HIP(h, as->d_flags.ensure(std::max<uint64_t>(n_of[a], 16)));
-        MXG_HIP(h, as->d_shared.ensure(std::max<uint64_t>(n_of[a], 16)));
         as_all.n[a] = (uint32_t)n_of[a];
         as_all.n_ptr[a] = gb ? gb->n_ptr[a] : nullptr;
         as_all.hash[a] = as->d_hash.as<uint64_t>();
         as_all.slot[a] = as->d_slot.as<uint32_t>();
         as_all.flags[a] = as->d_flags.as<uint8_t>();
-        as_all.shared[a] = as->d_shared.as<uint8_t>();
     }
     for (uint32_t a = A; a < MXG_MAX_ASSEMBLIES; ++a) {
         as_all.n[a] = 0;
         as_all.n_ptr[a] = nullptr;
         as_all.hash[a] = nullptr;
         as_all.slot[a] = nullptr;
-        as_all.flags[a] = as_all.shared[a] = nullptr;
+        as_all.flags[a] = nullptr;
     }
     std::copy(pl.bstart, pl.bstart + MXG_MAX_ASSEMBLIES + 1, as_all.bstart);
     // per-256 counts of the two counting kernels and their super-counts (scan_kernels.h): [sup of k_flags, one run
@@ -1365,6 +1570,14 @@ static int take_or_make_plan(mxg_handle *h, const GraphCall &c, bool global_tabl
     return rc;
 }
 
+// a tail pass at its width (U = 1, 2 or 4: graph_tail_u)
+#define TAIL_LAUNCH(kernel, U, grid, stream, ...)                                                      \
+    do {                                                                                               \
+        if ((U) == 4) hipLaunchKernelGGL(kernel<4>, grid, dim3(256), 0, stream, __VA_ARGS__);          \
+        else if ((U) == 2) hipLaunchKernelGGL(kernel<2>, grid, dim3(256), 0, stream, __VA_ARGS__);     \
+        else hipLaunchKernelGGL(kernel<1>, grid, dim3(256), 0, stream, __VA_ARGS__);                   \
+    } while (0)
+
 // One attempt at the stage: the phases of build_graph_impl, in the order it enqueues them.
 struct GraphStage {
     mxg_handle *const h;
@@ -1427,6 +1640,10 @@ struct GraphStage {
             hipLaunchKernelGGL(narrow ? k_pj_join<true> : k_pj_join<false>, dim3(n_parts), dim3(256), 0, h->stream, recs, M, pl.P, n_rows,
                                pj_fail, pl.pj_force_fail, cursor, cap1, rows2, pl.as_all, pl.sc);
     }
+    void flags_pj()
+    {
+        TAIL_LAUNCH(k_flags_pj, pl.u_flags, dim3(graph_tail_grid(pl.nb, pl.u_flags)), h->stream, pl.as_all, pl.nb, pl.cnt, pl.fsup, pl.pj_mask0);
+    }
     int join_two_level()
     {
         if (!early) {  // (else: both levels ran behind every assembly's own k_emit, the cursors were cleared in front of the step)
@@ -1434,7 +1651,7 @@ struct GraphStage {
             launch_partition(h, pl, 0, pl.A, h->stream, pl.n_fsup + pl.n_esup);
         }
         launch_join(pl.recs2, pl.M, pl.P1 * pl.P, 0u, pl.cursor);
-        hipLaunchKernelGGL(k_flags_pj, dim3(pl.nb), dim3(256), 0, h->stream, pl.as_all, pl.cnt, pl.fsup, pl.pj_mask0);
+        flags_pj();
         return MXG_OK;
     }
     int join_one_level()
@@ -1447,7 +1664,7 @@ struct GraphStage {
         hipLaunchKernelGGL(k_pj_bucket, dim3(n_rows), dim3(PJ_BT), (size_t)pl.P * 8, h->stream, pl.as_all, pl.nb, pl.P - 1, M, recs, pl.fsup,
                            pl.n_fsup + pl.n_esup);
         launch_join(recs, M, pl.P, n_rows, nullptr);
-        hipLaunchKernelGGL(k_flags_pj, dim3(pl.nb), dim3(256), 0, h->stream, pl.as_all, pl.cnt, pl.fsup, pl.pj_mask0);
+        flags_pj();
         return MXG_OK;
     }
     int join_global()
@@ -1516,14 +1733,14 @@ struct GraphStage {
         if (rc != MXG_OK) return rc;
         hipLaunchKernelGGL(k_block_prefix, dim3((uint32_t)((pl.nb0 + 255) / 256)), dim3(256), 0, h->stream, pl.cnt + pl.as_all.bstart[0],
                            pl.fsup + sup_start(pl.as_all, 0), (uint32_t)pl.nb0, pl.pj_bpref0);
-        hipLaunchKernelGGL(k_vertices_pj, dim3(pl.nb), dim3(256), 0, h->stream, vp);
+        TAIL_LAUNCH(k_vertices_pj, pl.u_vertices, dim3(graph_tail_grid(pl.nb, pl.u_vertices)), h->stream, vp, pl.nb);
         return MXG_OK;
     }
     int fill(VertexParams &vp, uint32_t a)
     {
         Assembly *as = h->asms[a];
         const size_t row = (size_t)a * pl.nvs;
-        vp.shared = as->d_shared.as<uint8_t>();
+        vp.flags = as->d_flags.as<uint8_t>();
         vp.cnt = pl.cnt + pl.as_all.bstart[a];
         vp.sup = pl.fsup + sup_start(pl.as_all, a);
         vp.n_shared = ctl + CTL_SHARED + a;
@@ -1566,8 +1783,8 @@ struct GraphStage {
 
     void adjacency_own()  // GRAPH_FULL: from the handle's own record order
     {
-        hipLaunchKernelGGL(k_adjacency, dim3((uint32_t)((pl.nvs + 255) / 256), pl.A), dim3(256), 0, h->stream, h->g_fv.as<uint32_t>(),
-                           h->g_frec.as<uint32_t>(), ctl + CTL_SHARED, h->g_nxt.as<uint2>(), (uint32_t)pl.nvs);
+        TAIL_LAUNCH(k_adjacency, pl.u_edges, dim3(graph_tail_grid((pl.nvs + 255) / 256, pl.u_edges), pl.A), h->stream, h->g_fv.as<uint32_t>(),
+                    h->g_frec.as<uint32_t>(), ctl + CTL_SHARED, h->g_nxt.as<uint2>(), (uint32_t)pl.nvs);
     }
     // second half on the owner: every local vertex is an item (fv = identity), adjacency from messages (GRAPH_DG_EDGES) or in place
     void adjacency_of_owner()
@@ -1609,8 +1826,9 @@ struct GraphStage {
         MXG_HIP(h, h->g_ew.ensure((size_t)n_items * 8));
         EdgeParams ep;
         fill(ep);
-        hipLaunchKernelGGL(k_edge_flags, dim3(pl.e_blocks), dim3(256), 0, h->stream, ep);  // + per-256 counts
-        hipLaunchKernelGGL(k_edges, dim3(pl.e_blocks), dim3(256), 0, h->stream, ep, n_items);
+        const dim3 grid(graph_tail_grid(pl.e_blocks, pl.u_edges));
+        TAIL_LAUNCH(k_edge_flags, pl.u_edges, grid, h->stream, ep, n_items);  // + per-256 counts
+        TAIL_LAUNCH(k_edges, pl.u_edges, grid, h->stream, ep, n_items);
         MXG_HIP(h, hipGetLastError());
         return MXG_OK;
     }

@@ -67,6 +67,7 @@ struct JoinRequest {
     bool split = false;            // a sub-range of every coarse partition per assembly (the fused call's early partition)
     bool force_two_level = false;  // MXG_PJ_TWO_LEVEL
     bool join_global = false;      // MXG_GRAPH_JOIN=global
+    uint32_t graph_u = 0;          // MXG_GRAPH_U: 1, 2 or 4 forces the width of the tail's ordered passes (anything else: by size)
 };
 
 enum JoinShapeError { JS_OK = 0, JS_TOO_MANY_MINIMIZERS, JS_TOO_MANY_ITEMS };
@@ -87,7 +88,32 @@ struct JoinShape {
     size_t nb0 = 0;                                // assembly 0's
     uint32_t n_items = 0, e_blocks = 0;            // A * nvs items of the edge kernels, in blocks of 256
     size_t n_cur = 0;  // split: words of the sub-ranges' cursors that lie between the super-counts and the counts
+    // 256-blocks per thread block of the ordered passes (graph_tail_u): k_flags_pj and k_vertices_pj over nb, the adjacency and
+    // edge passes over e_blocks
+    uint32_t u_flags = 1, u_vertices = 1, u_edges = 1;
 };
+
+// The tail's ordered passes (k_flags_pj, k_vertices_pj over nb 256-blocks; k_adjacency, k_edge_flags, k_edges over e_blocks) give
+// every thread block U consecutive 256-blocks whose loads are all requested before the first is used: a pass of one 256-block per
+// thread block keeps 8 KB of loads in flight per CU, where an HBM round trip wants tens of KB ("The tail's
+// ordered passes").  Wider blocks are fewer blocks: the pass must still fill the chip's 256 CUs x 8 resident thread blocks several
+// times over, or its last round of blocks runs on a half-empty chip.  The thresholds lie between the sizes measured at forced
+// U = 1 / 2 / 4 (profiles/r08/graph_tail_ab.txt; traced time of the five passes together, us):
+//   100 + 100 Mbp    (nb ~ 1 560, e_blocks ~ 1 170)    27.8 / 29.4 / 31.3   the wider, the slower
+//   300 + 300 Mbp    (nb ~ 4 670, e_blocks ~ 3 520)    45.5 / 44.2 / 42.9   U = 2 not slower than 1; 4 against 2 inside the spread
+//   1000 + 1000 Mbp  (nb ~ 15 560, e_blocks ~ 11 720)  105.5 / 97.3 / 92.6  U = 4 fastest
+//   3000 + 3000 Mbp  (nb = 46 700, e_blocks ~ 35 200)  298.9 / 255.5 / 237.2
+// The vertex pass stops at U = 2 by size: <4> takes 90 VGPRs (5 waves per SIMD where <2> keeps 8) and traced 91.9 us against
+// <2>'s 91.8 at 3 Gbp + 3 Gbp, 31.0 against 30.9 at 1 Gbp + 1 Gbp.
+constexpr uint32_t GRAPH_TAIL_U2 = 3072, GRAPH_TAIL_U4 = 8192;
+constexpr uint32_t GRAPH_TAIL_U_VERTICES = 2;  // the widest vertex pass the size rule picks
+inline uint32_t graph_tail_u(uint64_t blocks, uint32_t forced = 0)
+{
+    if (forced == 1 || forced == 2 || forced == 4) return forced;
+    return blocks >= GRAPH_TAIL_U4 ? 4u : blocks >= GRAPH_TAIL_U2 ? 2u : 1u;
+}
+// thread blocks of a pass over `blocks` 256-blocks, U to each
+inline uint32_t graph_tail_grid(uint64_t blocks, uint32_t U) { return (uint32_t)((blocks + U - 1) / U); }
 
 inline JoinShapeError join_shape(const JoinRequest &rq, const JoinLearnt &learnt, JoinShape &pl)
 {
@@ -165,6 +191,10 @@ inline JoinShapeError join_shape(const JoinRequest &rq, const JoinLearnt &learnt
     pl.n_items = (uint32_t)((size_t)A * pl.nvs);
     pl.e_blocks = (pl.n_items + 255) / 256;
     if (pl.split && pl.pj && pl.two_level) pl.n_cur = (size_t)P1 * A * PJ1_CS;
+    pl.u_flags = graph_tail_u(pl.nb, rq.graph_u);
+    // (by size the vertex pass stops at GRAPH_TAIL_U_VERTICES; MXG_GRAPH_U=4 still runs it at 4)
+    pl.u_vertices = graph_tail_u(0, rq.graph_u) == rq.graph_u ? rq.graph_u : std::min(pl.u_flags, GRAPH_TAIL_U_VERTICES);
+    pl.u_edges = graph_tail_u(pl.e_blocks, rq.graph_u);
     return JS_OK;
 }
 

@@ -162,7 +162,7 @@ struct Assembly {
     std::vector<uint8_t> h_fwd;
     std::vector<uint64_t> rec_first;
     // graph stage
-    DevBuf d_flags, d_slot, d_shared, d_ivid;
+    DevBuf d_flags, d_slot, d_ivid;
     DevBuf d_perm, d_fg, d_frec, d_dgtmp;  // distributed graph stage (dgraph.hip), sender side
     std::vector<uint8_t> h_flags;
     bool flags_valid = false;   // device flags computed
