@@ -483,6 +483,10 @@ int mxg_overlap_cuts(mxg_handle *h, int assembly, uint32_t k, uint32_t w, const 
    beyond the record, a path of fewer than two nodes, end_adjust > L, a first or last piece whose text part is empty or N/n
    throughout (the reference asserts there).  MXG_ELIMIT: 2^31 nodes or more.  Sketches, graph and paths are left as they are. */
 #define MXG_SCAF_FOLD_CASE 0x1u
+/* MXG_SCAF_BGZF: assigned_fa and unassigned_fa are BGZF files (what `bgzip` writes: a chain of gzip members of at most 65 280 bytes
+   of text each, the 28-byte end marker behind the last) of exactly the bytes the call writes without the flag, deflated on the
+   device (literals only: about 2.25 bits a base); the BED, the strips and every return value are as without it. */
+#define MXG_SCAF_BGZF 0x2u
 typedef struct mxg_scaffold_node {
     uint32_t record, start, end;       /* [start, end) of the record */
     uint32_t gap_size;                 /* Ns behind the node (PathNode.gap_size) */
@@ -500,6 +504,11 @@ int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *no
    (bin/ntjoin_assemble.py:379-404) recomputes from the text of every record (len_diff_start, len_diff_end).  The arrays are the
    handle's and hold until its next mxg_write_scaffolds. */
 int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals);
+
+/* The n bytes at data (host memory) written to `path` as a BGZF file, deflated on the device as the scaffold files of
+   MXG_SCAF_BGZF are: member j holds bytes [j P, j P + P) with P = 65 280 (the environment's MXG_BGZF_PAYLOAD, 1 .. 65 280, if set),
+   the end marker follows; n = 0 gives the end marker alone.  MXG_EINVAL: a null argument; MXG_EIO: the file. */
+int mxg_bgzf_write(mxg_handle *h, const void *data, uint64_t n, const char *path);
 
 /* ---- next row (f7): the paths adjusted for relocations, --no_cut and overlapping regions ------------------------------------
    What the reference's main_scaffolder (bin/ntjoin_assemble.py:751-786) does to the PathNodes between format_path and the

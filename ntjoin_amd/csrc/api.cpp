@@ -1018,6 +1018,17 @@ int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *no
     }
 }
 
+int mxg_bgzf_write(mxg_handle *h, const void *data, uint64_t n, const char *path)
+{
+    if (!h) return MXG_EINVAL;
+    if (!path || (n && !data)) return set_err(h, MXG_EINVAL, "mxg_bgzf_write: null argument");
+    try {
+        return bgzf_write(h, data, n, path);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_bgzf_write");
+    }
+}
+
 static_assert(sizeof(mxg_adjust_node) == 56, "mxg_adjust_node: ntjoin_amd/engine.py ADJUST_NODE mirrors this layout");
 static_assert(sizeof(mxg_adjust_params) == 16, "mxg_adjust_params: ntjoin_amd/capi.py AdjustParams mirrors this layout");
 static_assert(sizeof(mxg_adjusted_view) == 40, "mxg_adjusted_view: ntjoin_amd/capi.py AdjustedView mirrors this layout");

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <thread>
@@ -336,6 +337,7 @@ struct mxg_handle {
     bool pin_registered = false;          // the pool is mmap'ed memory registered piece by piece (else: hipHostMalloc)
     std::vector<std::pair<void *, size_t>> kept_maps;  // MXG_FLAG_ONE_SHOT: file mappings left for mxg_destroy / the process's end
     mxg::DevBuf tsv_win[2];
+    mxg::DevBuf zbuf[4];  // scratch of bgzf_deflate.hip: the members' slots, their sizes and places, the packed window
 };
 
 namespace mxg {
@@ -403,6 +405,15 @@ uint32_t host_threads(const mxg_handle *h);
 struct BgzfMember;
 int bgzf_inflate_device(mxg_handle *h, const unsigned char *d_comp, uint64_t comp_bytes, const BgzfMember *d_members, uint32_t n_members,
                         unsigned char *d_text, uint64_t text_bytes, uint32_t *d_status, hipStream_t st);
+// bgzf_deflate.hip: text on the device -> a BGZF file (bgzf_deflate.h).  bgzf_payload: text bytes a member (MXG_BGZF_PAYLOAD);
+// bgzf_window_bytes: text bytes a window, whole units of lcm(tile, P); bgzf_write_windows: the file, window by window -- fill(c, d_win,
+// lo, hi) enqueues on the handle's stream what puts text bytes [lo, hi) of the file at d_win; bgzf_write: host bytes (mxg_bgzf_write)
+struct OutFile;
+using BgzfFill = std::function<int(uint64_t c, unsigned char *d_win, uint64_t lo, uint64_t hi)>;
+uint32_t bgzf_payload(const mxg_handle *h);
+uint64_t bgzf_window_bytes(uint64_t want, uint32_t tile, uint32_t P);
+int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint32_t P, const BgzfFill &fill, const char *who);
+int bgzf_write(mxg_handle *h, const void *data, uint64_t n, const char *path);
 // n_parts byte ranges written to fd at consecutive offsets from `off` on, by that many threads (host_io.cpp)
 bool put_parallel(int fd, uint64_t off, const char *const *data, const size_t *len, uint32_t n_parts);
 // a file that is removed again unless the call completes (only a regular file this call created or truncated):

@@ -20,7 +20,8 @@
 //                complement, each with or without case folding) into the tile's image in LDS.  The reverse direction reads the
 //                chunks mirrored.  The image leaves with 16-byte stores.
 // Output leaves through two device windows and the pinned pool, as the TSV text does (ingest.hip): the device fills window
-// c + 1 while the host writes window c at its offset of the file.  MXG_SCAF_WIN sets the window size.
+// c + 1 while the host writes window c at its offset of the file.  MXG_SCAF_WIN sets the window size.  With MXG_SCAF_BGZF the windows
+// are deflated on the device into BGZF members on their way out (bgzf_deflate.hip) and the host writes the compressed bytes.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -214,19 +215,29 @@ struct PieceTable {
 }  // namespace
 
 // the table's bytes into `of`, window by window
-static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint32_t fold, OutFile &of, uint64_t WIN)
+// (bgzf_P: 0, or the file is a BGZF file of that many text bytes a member, deflated on the device: bgzf_deflate.hip)
+static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint32_t fold, OutFile &of, uint64_t WIN, uint32_t bgzf_P)
 {
     hipStream_t st = h->stream;
     DevBuf *B = h->scbuf;
     const uint64_t total = pt.total;
     const size_t n_pieces = pt.pieces.size();
     if (n_pieces >= 0xFFFFFFFFull) return set_err(h, MXG_ELIMIT, "mxg_write_scaffolds: too many pieces of output for one call");
-    if (!total) return MXG_OK;
+    if (!total) return bgzf_P ? bgzf_write_windows(h, of, 0, WIN, bgzf_P, BgzfFill(), "mxg_write_scaffolds") : MXG_OK;
     pt.pieces.push_back(ScafPiece{total, 0, 0, SP_LIT});  // (the end of the last piece)
     MXG_HIP(h, B[SC_PIECES].ensure((n_pieces + 1) * sizeof(ScafPiece)));
     MXG_HIP(h, B[SC_LITS].ensure(pt.lits.size() + 16));
     MXG_HIP(h, hipMemcpyAsync(B[SC_PIECES].p, pt.pieces.data(), (n_pieces + 1) * sizeof(ScafPiece), hipMemcpyHostToDevice, st));
     if (!pt.lits.empty()) MXG_HIP(h, hipMemcpyAsync(B[SC_LITS].p, pt.lits.data(), pt.lits.size(), hipMemcpyHostToDevice, st));
+    if (bgzf_P) {
+        const BgzfFill fill = [&](uint64_t, unsigned char *d_win, uint64_t lo, uint64_t hi) -> int {
+            hipLaunchKernelGGL(k_scaf_emit, dim3((uint32_t)((hi - lo + SCAF_TILE - 1) / SCAF_TILE)), dim3(256), 0, st, t, B[SC_PIECES].as<ScafPiece>(),
+                               (uint32_t)n_pieces, B[SC_LITS].as<unsigned char>(), fold, d_win, lo, hi);
+            MXG_HIP(h, hipGetLastError());
+            return MXG_OK;
+        };
+        return bgzf_write_windows(h, of, total, bgzf_window_bytes(WIN, SCAF_TILE, bgzf_P), bgzf_P, fill, "mxg_write_scaffolds");
+    }
     struct Events {
         hipStream_t st;
         hipEvent_t ev[2] = {nullptr, nullptr};
@@ -432,6 +443,7 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
     // ---- nothing is refused from here on: the files
     const uint64_t WIN = std::max<uint64_t>(SCAF_TILE, std::min<uint64_t>(knob_u64(h, "MXG_SCAF_WIN", PIN_POOL_BYTES / 2), PIN_POOL_BYTES / 2) /
                                                            SCAF_TILE * SCAF_TILE);
+    const uint32_t bgzf_P = flags & MXG_SCAF_BGZF ? bgzf_payload(h) : 0u;
     OutFile fa, ufa, bed;
     if (!fa.open(assigned_fa)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", assigned_fa);
     if (unassigned_fa && !ufa.open(unassigned_fa)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", unassigned_fa);
@@ -462,7 +474,7 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
             pt.literal("\n");
             if (lead_strip) lead_strip[p] = lead;
         }
-        if ((rc = scaf_emit_file(h, t, pt, flags & MXG_SCAF_FOLD_CASE ? 1u : 0u, fa, WIN)) != MXG_OK) return rc;
+        if ((rc = scaf_emit_file(h, t, pt, flags & MXG_SCAF_FOLD_CASE ? 1u : 0u, fa, WIN, bgzf_P)) != MXG_OK) return rc;
     }
     uint64_t n_un = 0;
     h->scaf_lead.assign(gaps.size(), 0);  // what mxg_scaffold_strips hands out: per interval of the BED
@@ -481,7 +493,7 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
             pt.add(SP_FWD, len - lead - tail, (uint64_t)iv.lo + lead, iv.rec);
             pt.literal("\n");
         }
-        if (unassigned_fa && (rc = scaf_emit_file(h, t, pt, 0u, ufa, WIN)) != MXG_OK) return rc;
+        if (unassigned_fa && (rc = scaf_emit_file(h, t, pt, 0u, ufa, WIN, bgzf_P)) != MXG_OK) return rc;
     }
     if (want_un) {  // the intervals with their strips: what mxg_write_paths makes the AGP's unassigned lines of
         h->scaf_iv.resize(gaps.size());

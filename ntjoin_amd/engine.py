@@ -460,11 +460,13 @@ class MxEngine:
     SCAFFOLD_NODE = np.dtype([("record", "<u4"), ("start", "<u4"), ("end", "<u4"), ("gap_size", "<u4"), ("start_adjust", "<u4"),
                               ("end_adjust", "<u4"), ("reverse", "u1"), ("pad", "u1", (3,))])
 
-    def write_scaffolds(self, assembly, rows, path_first, overlap_gap=None, fold_case=False, assigned=None, unassigned=None, bed=None):
+    def write_scaffolds(self, assembly, rows, path_first, overlap_gap=None, fold_case=False, assigned=None, unassigned=None, bed=None,
+                        bgzf=False):
         """mxg_write_scaffolds: rows = array of SCAFFOLD_NODE (or rows (record, start, end, gap_size, start_adjust, end_adjust,
         reverse)), path_first = n_paths + 1 offsets; overlap_gap=None: the overlap stage is off (the adjustments are not read).
         Writes the scaffold FASTA `assigned` and, when named, the unassigned FASTA and BED -> dict(lead_strip u32[n_paths],
-        tail_strip u32[n_paths]: N/n stripped from the scaffolds' ends, n_unassigned: records in the unassigned FASTA)"""
+        tail_strip u32[n_paths]: N/n stripped from the scaffolds' ends, n_unassigned: records in the unassigned FASTA).
+        bgzf=True: the two FASTA files are BGZF files of the same bytes, deflated on the device (MXG_SCAF_BGZF)"""
         if assigned is None:
             raise ValueError("write_scaffolds: assigned= names the scaffold FASTA to write")
         nodes = self._scaffold_nodes(rows)
@@ -477,9 +479,15 @@ class MxEngine:
         enc = lambda p: None if p is None else os.fsencode(str(p))  # noqa: E731
         self._check(self._lib.mxg_write_scaffolds(self._h, int(assembly), nodes.ctypes.data, pf.ctypes.data, n_paths,
                                                   -1 if overlap_gap is None else int(overlap_gap),
-                                                  capi.SCAF_FOLD_CASE if fold_case else 0, enc(assigned), enc(unassigned), enc(bed),
+                                                  (capi.SCAF_FOLD_CASE if fold_case else 0) | (capi.SCAF_BGZF if bgzf else 0), enc(assigned), enc(unassigned), enc(bed),
                                                   lead.ctypes.data, tail.ctypes.data, C.byref(n_un)))
         return {"lead_strip": lead, "tail_strip": tail, "n_unassigned": int(n_un.value)}
+
+    def bgzf_write(self, data, path):
+        """mxg_bgzf_write: the bytes of `data` (bytes, bytearray, or a contiguous uint8 array) written to `path` as a BGZF file,
+        deflated on the device"""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        self._check(self._lib.mxg_bgzf_write(self._h, buf.ctypes.data if buf.size else None, int(buf.size), os.fsencode(str(path))))
 
     def _scaffold_nodes(self, rows):
         "rows (record, start, end, gap_size, start_adjust, end_adjust, reverse), or an array of SCAFFOLD_NODE -> that array"

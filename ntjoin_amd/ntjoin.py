@@ -367,7 +367,7 @@ class Ntjoin:
     def scaffold(self, lengths=None):
         """main_scaffolder (:751-786) behind load_minimizers_scaffold in one handle: make_minimizer_graph -> find_paths ->
         format_paths -> adjust_paths -> trim_overlaps (when args.overlap) -> print_scaffolds.  Read from args, with ntJoin's
-        defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp.  Returns what
+        defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz.  Returns what
         print_scaffolds returns (the written files by kind)."""
         opt = lambda name, dflt: dflt if getattr(self.args, name, None) is None else getattr(self.args, name)  # noqa: E731
         self.make_minimizer_graph(materialize=False)
@@ -376,7 +376,8 @@ class Ntjoin:
         paths = self.format_paths(lengths, g=int(opt("g", 20)), G=G, m=opt("m", 90), mkt=bool(opt("mkt", False)))
         paths = self.adjust_paths(paths, no_cut=bool(opt("no_cut", False)), G=G)
         cuts = self.trim_overlaps(paths, opt("overlap_k", 15), opt("overlap_w", 10)) if opt("overlap", False) else None
-        return self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)))
+        return self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)),
+                                    gz=bool(opt("gz", False)))
 
     def trim_overlaps(self, paths, overlap_k=None, overlap_w=None):
         """The cut points of the reference's overlap stage (adjust_for_trimming, bin/ntjoin_assemble.py:468-516, and
@@ -490,13 +491,14 @@ class Ntjoin:
             if agp_fh:
                 agp_fh.close()
 
-    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20):
+    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False):
         """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
         trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
         than two nodes are dropped (:585-594), the last kept node's gap is zeroed (check_terminal_node_gap_zero :441-448), and the
         library cuts the sequences from the text it holds (mxg_write_scaffolds): the target FASTA is not read again and no
         bedtools runs.  Written: <fasta>.k<k>.w<w>.n<n>.assigned.scaffolds.fa, ...unassigned.scaffolds.fa,
-        <p>.<target tsv>.unassigned.bed, <p>.path and, with agp=True, <p>.agp.  Returns the file names by kind."""
+        <p>.<target tsv>.unassigned.bed, <p>.path and, with agp=True, <p>.agp.  gz=True: the two FASTA files are BGZF files
+        (`bgzip`'s format, deflated on the device) named ...scaffolds.fa.gz.  Returns the file names by kind."""
         eng, tgt = self._engine, len(self._order) - 1
         if tgt < 0:
             raise ValueError("print_scaffolds: no target assembly has been loaded")
@@ -527,11 +529,12 @@ class Ntjoin:
             first.append(len(rows))
             kept.append((nodes, cuts))
         prefix = assembly_fa + params + ".n" + str(n)
-        files = {"assigned": prefix + ".assigned.scaffolds.fa", "unassigned": prefix + ".unassigned.scaffolds.fa",
+        ext = ".fa.gz" if gz else ".fa"
+        files = {"assigned": prefix + ".assigned.scaffolds" + ext, "unassigned": prefix + ".unassigned.scaffolds" + ext,
                  "bed": self.args.p + "." + target + ".unassigned.bed", "path": self.args.p + ".path"}
         print(datetime.datetime.today(), ": Printing output scaffolds", file=sys.stdout)
         res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
-                                  assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"])
+                                  assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz))
         if agp:
             files["agp"] = self.args.p + ".agp"
         lead, tail = res["lead_strip"], res["tail_strip"]

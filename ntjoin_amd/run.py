@@ -36,6 +36,8 @@ def parse_arguments(argv=None):
     parser.add_argument("--overlap_k", type=int, default=15)
     parser.add_argument("--overlap_w", type=int, default=10)
     parser.add_argument("--btllib_t", type=int, default=4)
+    # ours (the reference has no such flag): the scaffold FASTA files as BGZF, ...scaffolds.fa.gz (ntjoin_amd.assemble)
+    parser.add_argument("--gz", action="store_true", default=False)
     parser.add_argument("-v", "--version", action="version", version="ntjoin_amd hot path (ntJoin v1.1.5 compatible)")
     return parser.parse_args(argv)
 
