@@ -1,8 +1,11 @@
 """Inputs of the path adjustment stage's tests: the hand-made cases that tests/golden/make_golden_adjust.py records, the goldens
-as the restatement and the library take them, and the seeded fuzz cases.  Test infrastructure only.
+as the restatement and the library take them, and the seeded generators (fuzz, ladder, strided, large) whose inputs are re-made
+here while tests/golden/adjust/families holds what the reference answered on them.  Test infrastructure only.
 
 A row is [contig, ori, start, end, contig_size, first_mx, terminal_mx, gap_size, raw_gap_size] (Ntjoin.format_paths)."""
+import functools
 import glob
+import hashlib
 import json
 import os
 import random
@@ -80,7 +83,7 @@ def hand_cases():
             [n("G", "+", 0, 700), n("D", "-", 500, 800, size=800, gap=45), n("H", "+", 0, 80, size=80)],   # D: equal lengths, the first is best
             [n("H", "-", 10, 40, size=80), n("C", "-", 300, 900, size=900), n("I", "+", 5, 95, size=100)],  # C: the longer one is best
             [n("J", "+", 0, 40, size=90), n("K", "+", 0, 10, size=10), n("J", "-", 50, 90, size=90), n("L", "+", 0, 5)],  # other orientation
-            [n("M", "+", 0, 40, size=90), n("N", "+", 0, 10, size=10), n("M", "+", 50, 90, size=90), n("M", "+", 95, 99, size=90)],  # 3 regions
+            [n("M", "+", 0, 40, size=90), n("N", "+", 0, 10, size=10), n("M", "+", 50, 90, size=90), n("M", "+", 42, 48, size=90)],  # 3 regions
             [n("O", "+", 0, 40, size=90), n("P", "+", 0, 10, size=10), n("Q", "+", 2, 8, size=10), n("O", "+", 50, 90, size=90)],
             [n("P", "+", 2, 5, size=10), n("Q", "+", 0, 3, size=10), n("R", "+", 0, 10, size=10)],
         ])
@@ -235,13 +238,90 @@ def strided_case(no_cut=False):
     paths.append([n("CH", "+", 100 * i, 100 * i + 60 + (i % 3) * 20, size=7000, gap=i) for i in range(70)] + [n("Z", "+", 0, 10)])
     for i in range(40):  # MIX: 80 singles, then chains between them
         paths.append([n("MIX", "-", 100000 - 1000 * i - 300, 100000 - 1000 * i - 200, size=100000),
-                      n("MIX", "-", 100000 - 1000 * i - 600, 100000 - 1000 * i - 500, size=100000), n(f"m{i}", "+", 0, 50, size=50)])
+                      n("MIX", "-", 100000 - 1000 * i - 600, 100000 - 1000 * i - 500, size=100000), n(f"m{i}", "+", 0, 50, size=100)])
         paths.append([n(f"m{i}", "-", 60, 90, size=100), n("MIX", "+", 1000 * i + 450, 1000 * i + 480 + (40 if i % 5 == 0 else 0), size=100000)])
     return dict(no_cut=no_cut, G=50 if no_cut else 0, paths=paths)
 
 
+def check_case(case):
+    """What every input must keep, since ntJoin holds one length per contig (from the FASTA) and neither the library nor the
+    restatement checks it: one contig_size per contig, 0 <= start < end <= contig_size, an orientation of + - ?"""
+    sizes = {}
+    for p, path in enumerate(case["paths"]):
+        for i, row in enumerate(path):
+            contig, ori, start, end, size = row[:5]
+            assert sizes.setdefault(contig, size) == size, (p, i, contig, sizes[contig], size)
+            assert 0 <= start < end <= size, (p, i, row)
+            assert ori in ("+", "-", "?"), (p, i, row)
+    return case
+
+
+LADDER_L = [2, 3, 63, 64, 65, 127, 128, 129, 200, 257]  # around the wave (64, 128) and the block (256)
+LADDER_PATHS = [(255, False), (256, True), (257, False)]  # (paths, no_cut): around the block of the per-path kernels, which run P + 1 threads
+
+
+def ladder_case(L, no_cut=False, n_paths=None):
+    """Contigs X and Y in exactly L nodes each.  X: chains of 1 to 3 nodes in walking order, 0, 5, 10 or 40 bases apart, in both
+    orientations, and single nodes hooked into the segment before them (begun 25 to 29 bases before its end, or inside it); all
+    starts differ, so the order of equal starts stays out.  Y: triples Y+ (a, a+50), Y+ (a+100, a+150) in one path and
+    Y- (a+60, a+90) in another, which blocks the chain, then singles of 70 bases, two and two sharing 25 of them; the path that
+    comes last holds such a single, so that Y's list ends in a segment that counts.  Every path ends in a contig of its own, some
+    begin with one.  n_paths: two-node paths of contigs of their own are added up to that many paths."""
+    rng = random.Random(1000 + 2 * L + int(no_cut) + (0 if n_paths is None else 7 * n_paths))
+    size, tag, own = 1000 * L + 1000, [1], [0]
+
+    def row(contig, ori, start, end, csize):
+        tag[0] += 2
+        return [contig, ori, start, end, csize, str(tag[0]), str(tag[0] + 1), rng.choice([0, 20, 137]), rng.choice([-30, 0, 20, 137])]
+
+    def close(nodes):
+        own[0] += 1
+        lead = [row(f"lead{own[0]}", rng.choice("+-"), 10, 90, 100)] if rng.random() < 0.3 else []
+        return lead + nodes + [row(f"own{own[0]}", rng.choice("+-"), 0, 100, 100)]
+
+    paths, left, at, last, can_hook = [], L, 100, None, False
+    while left:  # X
+        kind = rng.random()
+        if can_hook and kind < 0.3:  # reaches 25 to 29 bases back into the segment before it
+            start = last[1] - rng.randint(25, 29)
+            spans = [(start, start + rng.choice([50, 100, 200]))]
+            can_hook = False
+        elif can_hook and kind < 0.4:  # inside the segment before it
+            spans, can_hook = [(last[0] + 10, last[1] - 10)], False
+        else:
+            spans = []
+            for _ in range(min(left, rng.choice([1, 1, 1, 2, 3]))):
+                spans.append((at, at + rng.choice([50, 100, 200])))
+                at = spans[-1][1] + rng.choice([0, 5, 10, 40])
+            can_hook = True
+        last = spans[-1] if can_hook else last
+        at = max(at, spans[-1][1]) + rng.choice([10, 60])
+        ori = rng.choice("+-")
+        paths.append(close([row("X", ori, s, e, size) for s, e in (spans if ori == "+" else spans[::-1])]))
+        left -= len(spans)
+    a = 100
+    for _ in range(L // 5):  # Y: the '-' node of another path lies between the two '+' nodes
+        paths.append(close([row("Y", "+", a, a + 50, size), row("Y", "+", a + 100, a + 150, size)]))
+        paths.append(close([row("Y", "-", a + 60, a + 90, size)]))
+        a += 200
+    tail = None
+    for j in range(L - 3 * (L // 5)):  # ... then singles, two and two sharing 25 bases
+        paths.append(close([row("Y", rng.choice("+-"), a + 45 * (j % 2), a + 45 * (j % 2) + 70, size)]))
+        tail = paths[-1] if j % 2 else tail
+        a += 200 * (j % 2)
+    while n_paths is not None and len(paths) < n_paths:
+        k = len(paths)
+        paths.append([row(f"pad{k}a", rng.choice("+-"), 10, 90, 100), row(f"pad{k}b", rng.choice("+-"), 0, 100, 100)])
+    assert n_paths is None or len(paths) == n_paths
+    rng.shuffle(paths)
+    paths.remove(tail)  # the last entry of Y's list and of its set of segments is one that intersects another
+    paths.append(tail)
+    return dict(paths=paths, no_cut=no_cut, G=rng.choice([0, 100]))
+
+
+@functools.lru_cache(maxsize=None)
 def large_case(n_nodes=100000, n_contigs=30000, seed=5):
-    "10^5 nodes over 3 * 10^4 contigs in paths of up to 8 nodes; no (contig, start, end) twice"
+    "10^5 nodes over 3 * 10^4 contigs of 11000 bases (a run ends before 10800) in paths of up to 8 nodes; no (contig, start, end) twice.  Cached: read it, do not change it"
     rng = random.Random(seed)
     paths, seen, total, tag = [], set(), 0, 1
     while total < n_nodes:
@@ -262,7 +342,7 @@ def large_case(n_nodes=100000, n_contigs=30000, seed=5):
                     continue
                 seen.add((c, s, e))
                 tag += 2
-                path.append([f"c{c}", ori, s, e, 10000, str(tag), str(tag + 1), rng.choice([0, 20, 137]), rng.choice([-30, 20, 137])])
+                path.append([f"c{c}", ori, s, e, 11000, str(tag), str(tag + 1), rng.choice([0, 20, 137]), rng.choice([-30, 20, 137])])
         paths.append(path[:want])
         total += len(paths[-1])
     from tests import _adjust_restatement as rs
@@ -271,3 +351,85 @@ def large_case(n_nodes=100000, n_contigs=30000, seed=5):
             return dict(paths=paths, no_cut=False, G=0, expected=rs.adjust(paths, False, 0))
         except KeyError as err:
             paths[err.args[0][0]] = paths[err.args[0][0]][:1]
+
+
+# ---- families: seeded inputs re-made here, the reference's answers under tests/golden/adjust/families ------------------------------
+GENERATORS = {"fuzz_case": fuzz_case, "ladder_case": ladder_case, "strided_case": strided_case, "large_case": large_case}
+LARGE_HEAD = 50  # output paths of the large case that its golden holds verbatim
+
+
+def family_specs():
+    "family -> [(case name, generator, arguments)]: what make_golden_adjust.py records and the tests read back"
+    ladder = [(f"L{L}" + ("_no_cut" if no_cut else ""), "ladder_case", dict(L=L, no_cut=no_cut)) for L in LADDER_L for no_cut in (False, True)]
+    ladder += [(f"paths{P}", "ladder_case", dict(L=3, no_cut=no_cut, n_paths=P)) for P, no_cut in LADDER_PATHS]
+    return {
+        "fuzz": [(f"seed{seed:03d}", "fuzz_case", dict(seed=seed)) for seed in FUZZ_SEEDS],
+        "ladder": ladder,
+        "strided": [("strided" + ("_no_cut" if no_cut else ""), "strided_case", dict(no_cut=no_cut)) for no_cut in (False, True)],
+        "large": [("large", "large_case", {})],
+    }
+
+
+def case_digest(case):
+    return hashlib.sha256(json.dumps([case["paths"], case["no_cut"], case["G"]], separators=(",", ":")).encode("ascii")).hexdigest()
+
+
+def json_digest(value):
+    return hashlib.sha256(json.dumps(value, separators=(",", ":")).encode("ascii")).hexdigest()
+
+
+def summarise_large(result, source):
+    "what the large case's golden holds in place of its rows"
+    lists = lambda v: json.loads(json.dumps(v))
+    assert all(len(path) <= 9 for path in result)  # counts: one digit per output path
+    return dict(result_sha256=json_digest(lists(result)), source_sha256=json_digest(lists(source)), counts="".join(str(len(path)) for path in result),
+                result_head=lists(result[:LARGE_HEAD]), source_head=lists(source[:LARGE_HEAD]))
+
+
+def pack_result(case, result, source):
+    """The reference's answer next to the input it was given, without loss: per output path, per node either i, the input node of
+    the same path that it is, unchanged, or [i, column, value, ...] with the columns of the row that differ.  The stage never
+    moves a node to another path; asserted here, when the golden is recorded"""
+    packed = []
+    for p, (path, where) in enumerate(zip(result, source)):
+        nodes = []
+        for row, (q, i) in zip(path, where):
+            was = case["paths"][p][i]
+            assert q == p and len(row) == len(was), (p, i, row, was)
+            nodes.append(i if row == was else [i] + [x for j in range(len(row)) if row[j] != was[j] for x in (j, row[j])])
+        packed.append(nodes)
+    assert unpack_result(case, packed) == (result, source)
+    return packed
+
+
+def unpack_result(case, packed):
+    "-> (result, source) as the reference returned them"
+    result, source = [], []
+    for p, nodes in enumerate(packed):
+        rows = []
+        for node in nodes:
+            row = list(case["paths"][p][node if isinstance(node, int) else node[0]])
+            for j, value in ([] if isinstance(node, int) else zip(node[1::2], node[2::2])):
+                row[j] = value
+            rows.append(row)
+        result.append(rows)
+        source.append([[p, node if isinstance(node, int) else node[0]] for node in nodes])
+    return result, source
+
+
+@functools.lru_cache(maxsize=None)
+def load_family(family):
+    """-> {case name: golden document with "case" (the input, re-made and checked against the recorded digest) and, from its
+    packed "nodes", "result" and "source"}.  Cached: read it, do not change it"""
+    with open(os.path.join(GOLDEN, "families", family + ".json"), encoding="ascii") as fh:
+        doc = json.load(fh)
+    out = {}
+    for entry in doc["cases"]:
+        meta = entry["meta"]
+        case = GENERATORS[meta["generator"]](**meta["args"])
+        assert case_digest(case) == meta["sha256"], f"{family}/{meta['name']}: the generator no longer gives the input the golden was recorded on"
+        entry = dict(entry, case=case)
+        if "nodes" in entry:
+            entry["result"], entry["source"] = unpack_result(case, entry.pop("nodes"))
+        out[meta["name"]] = entry
+    return out

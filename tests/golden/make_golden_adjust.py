@@ -10,7 +10,15 @@ check_terminal_node_gap_zero per path.  Recorded per case: the input rows, no_cu
 node the (path, node) of the input row it is.
 
 Cases: the format_by_n rows of four fixtures under tests/golden/cases (regions-ff-rr at n = 1 with and without no_cut,
-regions-fr-rf at n = 2, gap-dist and f-f-f at n = 1) and the hand-made cases of tests/_adjust_cases.py."""
+regions-fr-rf at n = 2, gap-dist and f-f-f at n = 1) and the hand-made cases of tests/_adjust_cases.py.
+
+Families (tests/golden/adjust/families/<family>.json): the seeded inputs of tests/_adjust_cases.py family_specs() (fuzz, ladder,
+strided, large).  Their inputs are not written: a case holds its generator's arguments and the sha256 of the input, its result
+and source packed against that input without loss (_adjust_cases.pack_result; for the large case their digests, the node counts
+and the first paths), or the KeyError the reference raised as
+{"error": {"path", "contig", "start", "end"}}: the path whose merge_relocations call raised and the Bed that was not in the set.
+Every case runs under both orders of equal starts (pybedtools_standin.py); meta.tie_independent says whether the two agree, and
+the recorded answer is the one under the project's rule (the smaller end first)."""
 import json
 import os
 import sys
@@ -57,6 +65,59 @@ def run_reference(asm_mod, path_node, ntjoin_utils, rows, no_cut, G):
     return result, [[nd.where for nd in path] for path in paths]
 
 
+def run_family_case(asm_mod, path_node, ntjoin_utils, case):
+    "-> {'result', 'source'} or {'error'}: run_reference, with the per-path merge_relocations calls wrapped to learn which path raised"
+    plain, raised = asm_mod.NtjoinScaffolder.merge_relocations, []
+
+    def wrapped(self, path, incorporated_segments):
+        try:
+            return plain(self, path, incorporated_segments)
+        except KeyError:
+            raised.append(path[0].where[0])
+            raise
+
+    asm_mod.NtjoinScaffolder.merge_relocations = wrapped
+    try:
+        result, source = run_reference(asm_mod, path_node, ntjoin_utils, json.loads(json.dumps(case["paths"])), case["no_cut"], case["G"])
+    except KeyError as err:
+        bed = err.args[0]
+        return {"error": {"path": raised[0], "contig": bed.contig, "start": bed.start, "end": bed.end}}
+    finally:
+        asm_mod.NtjoinScaffolder.merge_relocations = plain
+    return {"result": result, "source": source}
+
+
+def record_families(asm_mod, path_node, ntjoin_utils):
+    os.makedirs(os.path.join(OUT, "families"), exist_ok=True)
+    for family, specs in _adjust_cases.family_specs().items():
+        entries, tied = [], []
+        for name, generator, args in specs:
+            case = _adjust_cases.check_case(_adjust_cases.GENERATORS[generator](**args))
+            answers = []
+            for larger_end_first in (False, True):
+                pybedtools_standin.EQUAL_START_LARGER_END_FIRST = larger_end_first
+                try:
+                    answers.append(run_family_case(asm_mod, path_node, ntjoin_utils, case))
+                finally:
+                    pybedtools_standin.EQUAL_START_LARGER_END_FIRST = False
+            answer = answers[0]
+            if family == "large":
+                answer = _adjust_cases.summarise_large(answer["result"], answer["source"])
+            elif "error" not in answer:
+                answer = {"nodes": _adjust_cases.pack_result(case, answer["result"], answer["source"])}
+            if answers[0] != answers[1]:
+                tied.append(name)
+            entries.append({"meta": {"name": name, "generator": generator, "args": args, "sha256": _adjust_cases.case_digest(case),
+                                     "tie_independent": answers[0] == answers[1]}, **answer})
+        doc = {"meta": {"generator": "tests/golden/make_golden_adjust.py", "family": family,
+                        "inputs_from": "tests/_adjust_cases.py family_specs()"}, "cases": entries}
+        path = os.path.join(OUT, "families", family + ".json")
+        with open(path, "w", encoding="ascii") as fh:
+            json.dump(doc, fh, separators=(",", ":"))
+            fh.write("\n")
+        print(family, len(entries), "cases,", sum("error" in e for e in entries), "errors,", len(tied), "tie-dependent", tied, os.path.getsize(path), "bytes")
+
+
 def main():
     if not os.path.isdir(mg.REF):
         sys.exit("make_golden_adjust.py needs the reference tree (build container only)")
@@ -84,6 +145,7 @@ def main():
                f"format_path as recorded in tests/golden/cases/{case} (n={n})")
     for name, case in _adjust_cases.hand_cases().items():
         record("hand_" + name, case["paths"], case["no_cut"], case["G"], "tests/_adjust_cases.py hand_cases()")
+    record_families(asm_mod, path_node, ntjoin_utils)
 
 
 if __name__ == "__main__":

@@ -7,11 +7,15 @@ Contract: sort() orders the lines by chromosome, then start, then end (bedtools'
 undefined: ascending end is this project's rule, see tests/golden/adjust/README.md); intersect(c=True, wa=True) yields every line of
 a, in a's order, with the number of lines of b on the same chromosome that share at least one base with it, half-open:
 max(starts) < min(ends).  Intervals are taken to hold at least one base.  tests/test_adjust_cpu.py checks the counts against a
-brute-force count."""
+brute-force count.
+
+EQUAL_START_LARGER_END_FIRST (off by default) makes sort() put the larger end first among equal starts: the generator of the
+adjustment goldens runs every case under both orders and records whether the answer depends on the order."""
 import bisect
 import collections
 
 Interval = collections.namedtuple("Interval", "chrom start end count")
+EQUAL_START_LARGER_END_FIRST = False
 
 
 class BedTool:
@@ -27,6 +31,8 @@ class BedTool:
                 self.rows.append((chrom, int(start), int(end)))
 
     def sort(self):
+        if EQUAL_START_LARGER_END_FIRST:
+            return BedTool(sorted(self.rows, key=lambda row: (row[0], row[1], -row[2])), from_string=True)
         return BedTool(sorted(self.rows), from_string=True)
 
     def intersect(self, b, c=False, wa=False):

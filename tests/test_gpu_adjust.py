@@ -1,6 +1,8 @@
 """GPU tests of the path adjustment stage (mxg_adjust_paths, csrc/adjust.hip; reference main_scaffolder,
 bin/ntjoin_assemble.py:751-786): every golden exactly, the reference's fixtures end to end from FASTA through Ntjoin.scaffold(),
-seeded fuzz, the strided lists, one large call and the refusals against the restatement (tests/_adjust_restatement.py)."""
+seeded fuzz, the strided lists, one large call and the refusals against the restatement (tests/_adjust_restatement.py), and the
+same seeded inputs plus the ladder of list lengths around the wave and the block against what the reference answered on them
+(tests/golden/adjust/families)."""
 import argparse
 import collections
 import os
@@ -124,6 +126,64 @@ def test_lists_longer_than_a_wave(eng, no_cut):
     if not no_cut:
         chain = [row for path in want[0] for row in path if row[0] == "CH"]
         assert len(chain) == 1 and (chain[0][2], chain[0][3]) == (0, 6960)
+
+
+def check_against_golden(eng, doc, note=""):
+    "the library on a family's case against the reference's recorded answer: rows and sources, or the refusal of the path and contig"
+    case, name = doc["case"], doc["meta"]["name"]
+    note = f"{name}{note}" + ("" if doc["meta"]["tie_independent"] else
+                              ": tie-dependent, the reference's answer changes with the order of two segments of equal start")
+    if "error" in doc:
+        with pytest.raises(MxError) as err:
+            run(eng, case)
+        assert err.value.code == capi.MXG_EINVAL, note
+        where = re.search(r"path (\d+) node (\d+)", str(err.value))
+        assert where and int(where.group(1)) == doc["error"]["path"], note
+        assert case["paths"][int(where.group(1))][int(where.group(2))][0] == doc["error"]["contig"], note
+        return
+    rows, source, res = run(eng, case)
+    source = [[list(w) for w in path] for path in source]
+    if "counts" in doc:  # the large case: digests, node counts and the first paths
+        got = cases.summarise_large(rows, source)
+        assert got["result_head"] == doc["result_head"] and got["source_head"] == doc["source_head"], note
+        assert got["counts"] == doc["counts"], note
+        assert (got["result_sha256"], got["source_sha256"]) == (doc["result_sha256"], doc["source_sha256"]), note
+        return
+    assert rows == doc["result"], note
+    assert source == doc["source"], note
+    assert res["node_first"].tolist() == np.cumsum([0] + [len(p) for p in doc["result"]]).tolist(), note
+
+
+def test_fuzz_against_golden(eng):
+    fuzz = cases.load_family("fuzz")
+    assert len(fuzz) == 200 and sum("error" in doc for doc in fuzz.values()) == 4
+    for doc in fuzz.values():
+        check_against_golden(eng, doc)
+
+
+LADDER = [f"L{L}" + ("_no_cut" if no_cut else "") for L in cases.LADDER_L for no_cut in (False, True)] + [f"paths{P}" for P, _n in cases.LADDER_PATHS]
+
+
+@pytest.mark.parametrize("name", LADDER)
+def test_ladder_against_golden(eng, name):
+    "per-contig lists of 2 to 257 nodes, around the wave's strides (64, 128) and the block (256); 255, 256 and 257 paths"
+    check_against_golden(eng, cases.load_family("ladder")[name])
+
+
+@pytest.mark.parametrize("name", ["strided", "strided_no_cut"])
+def test_lists_longer_than_a_wave_against_golden(eng, name):
+    check_against_golden(eng, cases.load_family("strided")[name])
+
+
+def test_one_large_call_against_golden(eng):
+    check_against_golden(eng, cases.load_family("large")["large"])
+
+
+def test_one_handle_changing_sizes(eng):
+    "large, then the smallest and the longest ladder, then large again: nothing of a larger call's scratch shows in a smaller one"
+    ladder, large = cases.load_family("ladder"), cases.load_family("large")["large"]
+    for step, doc in enumerate((large, ladder["L2"], ladder["L257"], large, ladder["L2_no_cut"], ladder["L257_no_cut"])):
+        check_against_golden(eng, doc, note=f" (step {step} of the sequence)")
 
 
 def test_duplicate_segment_is_refused(eng):
