@@ -530,15 +530,6 @@ __global__ __launch_bounds__(64) void k_adj_rec_last(Adj A)
 
 uint32_t blocks_of(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + 255) / 256); }
 
-// out[0 .. n] = exclusive prefix sums of in[0 .. n] (n + 1 entries; in[n] is not counted)
-void scan_u32(mxg_handle *h, const uint32_t *in, uint32_t n1, uint32_t *bsum, uint64_t *total, uint32_t *out)
-{
-    const uint32_t tiles = (n1 + TILE - 1) / TILE;
-    hipLaunchKernelGGL(k_tile_sum_u32, dim3(tiles), dim3(256), 0, h->stream, in, n1, bsum);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, h->stream, bsum, tiles, total);
-    hipLaunchKernelGGL(k_tile_excl_u32, dim3(tiles), dim3(256), 0, h->stream, in, n1, bsum, out);
-}
-
 }  // namespace
 
 int adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *path_first, uint64_t n_paths, const mxg_adjust_params &p)
@@ -636,7 +627,7 @@ int adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *pa
     hipLaunchKernelGGL(k_adj_init, dim3(blocks_of(P)), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_adj_link, dim3(blocks_of(P)), dim3(256), 0, st, A, (const uint8_t *)nullptr);
     hipLaunchKernelGGL(k_adj_count, dim3(blocks_of(N)), dim3(256), 0, st, A);
-    scan_u32(h, A.rec_cnt, R + 1u, bsum, scan_total, A.rec_first);
+    launch_scan_u32(st, A.rec_cnt, R + 1u, bsum, A.rec_first, scan_total);  // (R + 1 entries: the last is the total)
     hipLaunchKernelGGL(k_adj_scatter, dim3(blocks_of(N)), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_adj_active, dim3(blocks_of(R)), dim3(256), 0, st, A);
     MXG_HIP(h, hipGetLastError());
@@ -666,7 +657,7 @@ int adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *pa
     hipLaunchKernelGGL(k_adj_lookup, dim3(blocks_of(N)), dim3(256), 0, st, A);
     uint32_t *out_cnt = A.path_len, *out_first = B[AJ_OUT_FIRST].as<uint32_t>();
     hipLaunchKernelGGL(k_adj_final, dim3(blocks_of(P + 1ull)), dim3(256), 0, st, A, out_cnt);
-    scan_u32(h, out_cnt, P + 1u, bsum, scan_total, out_first);
+    launch_scan_u32(st, out_cnt, P + 1u, bsum, out_first, scan_total);
     hipLaunchKernelGGL(k_adj_emit, dim3(blocks_of(P)), dim3(256), 0, st, A, (const uint32_t *)out_first, B[AJ_OUT_NODES].as<mxg_adjust_node>(),
                        B[AJ_OUT_SRC].as<uint64_t>());
     MXG_HIP(h, hipGetLastError());

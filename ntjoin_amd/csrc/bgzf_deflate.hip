@@ -15,9 +15,7 @@
 //   k_bgzf_pack     the members' sizes are scanned (scan_kernels.h) and every member is copied to its place in the packed chain,
 //               as aligned words of the destination put together from two words of the slot.
 // The packed window starts with 16 bytes {u64 bytes, u32 stored members, u32 0} that travel to the host in front of the data.
-#include <fcntl.h>
-#include <unistd.h>
-
+// The host side (bgzf_write_windows) is a sequence of its own made of the parts of the window protocol (win_out.hip).
 #include <algorithm>
 #include <numeric>
 
@@ -217,9 +215,7 @@ __global__ __launch_bounds__(256) void k_bgzf_pack(const unsigned char *__restri
 
 namespace {
 enum { ZB_SLOTS, ZB_SIZES, ZB_OUT };
-constexpr size_t PIN_HALF = PIN_POOL_BYTES / 2;
 constexpr size_t PIN_DATA = PIN_HALF - 4096;  // a half's last 4 KiB take the window's head
-static_assert(PIN_HALF % PIN_PIECE_BYTES == 0, "a half is whole pieces");
 }  // namespace
 
 uint32_t bgzf_payload(const mxg_handle *h)
@@ -238,37 +234,19 @@ uint64_t bgzf_window_bytes(uint64_t want, uint32_t tile, uint32_t P)
     return std::max<uint64_t>(unit, want / unit * unit);
 }
 
-// A BGZF file of `total` bytes of text through `of`, window by window: fill(c, d_win, lo, hi) enqueues on the handle's stream
-// whatever puts text bytes [lo, hi) of the file at d_win (h->tsv_win[c & 1], room for WIN bytes); the members of the window are
-// then deflated and packed on the device, their bytes and head go to one half of the pinned pool, and the host writes them at the
+// A BGZF file of `total` bytes of text through `of`, window by window, from the parts of the plain window loop (win_out.hip: the
+// fill, WinBufs, copy_pieces, OutFile::put) in a sequence of its own: the members of a window are deflated and packed on the
+// device behind the fill, the window's head comes over first and says how many bytes to fetch, and the host writes them at the
 // running offset while the device forms the next window.  The end-of-file marker follows the last member.
-int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint32_t P, const BgzfFill &fill, const char *who)
+int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint32_t P, const WinFill &fill, const char *who)
 {
     hipStream_t st = h->stream;
     DevBuf *Z = h->zbuf;
     const bool dbg_io = getenv("MXG_DEBUG_IO") != nullptr;
-    const int ofd = fileno(of.f);
     uint64_t file_off = 0, n_members = 0, n_stored = 0;
     double ms = 0;
-    auto put = [&](const char *p, uint64_t bytes) -> bool {
-        bool ok = true;
-        if (!of.regular) {  // (a pipe or a device: in order, at the descriptor's own position)
-            for (uint64_t done = 0; done < bytes && ok;) {
-                const ssize_t wr = write(ofd, p + done, bytes - done);
-                ok = wr > 0;
-                if (ok) done += (uint64_t)wr;
-            }
-        } else if (bytes) {
-            const uint32_t T = (uint32_t)std::min<uint64_t>(std::min(16u, std::max(1u, host_threads(h))), (bytes + (1u << 20) - 1) >> 20);
-            const char *src[16];
-            size_t len[16];
-            for (uint32_t u = 0; u < T; ++u) {
-                const uint64_t lo = bytes * u / T, hi = bytes * (u + 1) / T;
-                src[u] = p + lo;
-                len[u] = hi - lo;
-            }
-            ok = put_parallel(ofd, file_off, src, len, T);
-        }
+    auto put = [&](const char *p, uint64_t bytes) -> bool {  // ... at the running offset
+        const bool ok = of.put(p, bytes, file_off, host_threads(h));
         file_off += bytes;
         return ok;
     };
@@ -282,30 +260,11 @@ int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN,
         MXG_HIP(h, Z[ZB_SLOTS].ensure(out_room));
         MXG_HIP(h, Z[ZB_SIZES].ensure((2 * win_members + n_tiles + 4) * 4));
         MXG_HIP(h, Z[ZB_OUT].ensure(sizeof(BgzfWinHead) + out_room + 16));
-        struct Events {
-            hipStream_t st;
-            hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-            ~Events()
-            {
-                (void)hipStreamSynchronize(st);
-                for (hipEvent_t e : ev)
-                    if (e) (void)hipEventDestroy(e);
-            }
-        } evs{st};
-        hipEvent_t *ev_head = evs.ev, *ev_t0 = evs.ev + 2, *ev_t1 = evs.ev + 4, *ev_data = evs.ev + 6;
-        char *pin[2];
-        unsigned char *pool = nullptr;
-        MXG_HIP(h, pin_pool_get(h, &pool));
-        for (int b = 0; b < 2; ++b) {
-            MXG_HIP(h, h->tsv_win[b].ensure(win_bytes + 16));
-            pin[b] = reinterpret_cast<char *>(pool) + (size_t)b * PIN_HALF;
-            MXG_HIP(h, hipEventCreateWithFlags(&ev_head[b], hipEventDisableTiming));
-            MXG_HIP(h, hipEventCreateWithFlags(&ev_data[b], hipEventDisableTiming));
-            if (dbg_io) {
-                MXG_HIP(h, hipEventCreate(&ev_t0[b]));
-                MXG_HIP(h, hipEventCreate(&ev_t1[b]));
-            }
-        }
+        WinBufs wb(h);
+        int rc = wb.init(win_bytes + 16, 4, dbg_io ? 4 : 0);
+        if (rc != MXG_OK) return rc;
+        char **pin = wb.pin;
+        hipEvent_t *ev_head = wb.ev, *ev_data = wb.ev + 2, *ev_t0 = wb.ev + 4, *ev_t1 = wb.ev + 6;  // (the last four: MXG_DEBUG_IO)
         unsigned char *d_out = Z[ZB_OUT].as<unsigned char>();
         uint32_t *d_sizes = Z[ZB_SIZES].as<uint32_t>(), *d_offs = d_sizes + win_members, *d_bsum = d_offs + win_members;
         const uint64_t n_win = (total + WIN - 1) / WIN;
@@ -313,7 +272,7 @@ int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN,
         auto enqueue = [&](uint64_t c) -> int {  // window c: text, members, packed chain, its head on the way to the host
             const int b = (int)(c & 1);
             const uint64_t lo = c * WIN, hi = std::min(total, lo + WIN);
-            const uint32_t m = members_of(c), tiles = (m + TILE - 1) / TILE;
+            const uint32_t m = members_of(c);
             unsigned char *d_win = h->tsv_win[b].as<unsigned char>();
             const int rc = fill(c, d_win, lo, hi);
             if (rc != MXG_OK) return rc;
@@ -322,9 +281,7 @@ int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN,
             hipLaunchKernelGGL(k_bgzf_deflate, dim3(m), dim3(256), 0, st, d_win, hi - lo, P, Z[ZB_SLOTS].as<unsigned char>(), slot, d_sizes,
                                reinterpret_cast<BgzfWinHead *>(d_out));
             MXG_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(k_tile_sum_u32, dim3(tiles), dim3(256), 0, st, d_sizes, m, d_bsum);
-            hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, d_bsum, tiles, reinterpret_cast<uint64_t *>(d_out));
-            hipLaunchKernelGGL(k_tile_excl_u32, dim3(tiles), dim3(256), 0, st, d_sizes, m, d_bsum, d_offs);
+            launch_scan_u32(st, d_sizes, m, d_bsum, d_offs, reinterpret_cast<uint64_t *>(d_out));
             hipLaunchKernelGGL(k_bgzf_pack, dim3(m), dim3(256), 0, st, Z[ZB_SLOTS].as<unsigned char>(), slot, d_sizes, d_offs,
                                d_out + sizeof(BgzfWinHead), out_room);
             MXG_HIP(h, hipGetLastError());
@@ -333,15 +290,9 @@ int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN,
             MXG_HIP(h, hipEventRecord(ev_head[b], st));
             return MXG_OK;
         };
-        // bytes [at, at + n) of the packed chain to the half's start (n <= PIN_DATA); no copy reaches across two pieces of the pool
-        auto fetch = [&](int b, uint64_t at, uint64_t n) -> int {
-            for (uint64_t done = 0; done < n; done += PIN_PIECE_BYTES)
-                MXG_HIP(h, hipMemcpyAsync(pin[b] + done, d_out + sizeof(BgzfWinHead) + at + done, std::min<uint64_t>(PIN_PIECE_BYTES, n - done),
-                                          hipMemcpyDeviceToHost, st));
-            return MXG_OK;
-        };
-        int rc = enqueue(0);
-        if (rc != MXG_OK) return rc;
+        // bytes [at, at + n) of the packed chain to the half's start (n <= PIN_DATA)
+        auto fetch = [&](int b, uint64_t at, uint64_t n) { return copy_pieces(h, pin[b], d_out + sizeof(BgzfWinHead) + at, n); };
+        if ((rc = enqueue(0)) != MXG_OK) return rc;
         for (uint64_t c = 0; c < n_win; ++c) {
             const int b = (int)(c & 1);
             if (hipEventSynchronize(ev_head[b]) != hipSuccess) return set_err(h, MXG_EDEVICE, "%s: the device failed while forming '%s'", who, of.path.c_str());
@@ -391,7 +342,7 @@ int bgzf_write(mxg_handle *h, const void *data, uint64_t n, const char *path)
     OutFile of;
     if (!of.open(path)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", path);
     hipStream_t st = h->stream;
-    const BgzfFill fill = [&](uint64_t, unsigned char *d_win, uint64_t lo, uint64_t hi) -> int {
+    const WinFill fill = [&](uint64_t, unsigned char *d_win, uint64_t lo, uint64_t hi) -> int {
         // (pageable memory: the copy returns when the bytes have left `data`)
         MXG_HIP(h, hipMemcpyAsync(d_win, static_cast<const unsigned char *>(data) + lo, hi - lo, hipMemcpyHostToDevice, st));
         return MXG_OK;

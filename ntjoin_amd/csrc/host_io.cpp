@@ -911,37 +911,6 @@ std::string py_repr_float(double v)
 }
 
 // ---- writers ---------------------------------------------------------------------------------------------
-// Several byte ranges -> consecutive places of one file, each by its own thread (pwrite; optionally copies into a shared mapping
-// of the file's new range).
-bool put_parallel(int fd, uint64_t off, const char *const *data, const size_t *len, uint32_t n_parts)
-{
-    std::vector<uint64_t> at(n_parts + 1, off);
-    for (uint32_t t = 0; t < n_parts; ++t) at[t + 1] = at[t] + len[t];
-    const uint64_t total = at[n_parts] - off;
-    if (!total) return true;
-    // (a shared mapping of the file filled by the workers was measured on the GPU boxes' /tmp and dropped: 1.2-1.35 s against
-    // 0.8-0.9 s of pwrite for 1.9 GB of outputs -- write faults on a shared file mapping are no cheaper than the inode lock)
-    std::atomic<bool> good{true};
-    auto put = [&](uint32_t t) {
-        size_t done = 0;
-        while (done < len[t]) {
-            const ssize_t wr = pwrite(fd, data[t] + done, len[t] - done, (off_t)(at[t] + done));
-            if (wr <= 0) {
-                good = false;
-                return;
-            }
-            done += (size_t)wr;
-        }
-    };
-    {
-        std::vector<std::thread> th;
-        for (uint32_t t = 1; t < n_parts; ++t) th.emplace_back(put, t);
-        put(0);
-        for (auto &x : th) x.join();
-    }
-    return good;
-}
-
 struct OutBuf {
     FILE *f;
     std::vector<char> b;

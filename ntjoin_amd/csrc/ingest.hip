@@ -17,7 +17,7 @@
 // to the host parser and zlib as before.
 //
 // TSV: entry lengths -> exclusive scan -> every byte of the file has a known offset; the text is produced in windows of
-// 64 MiB (MXG_TSV_WIN: fewer, a test knob) (double-buffered: the device formats window c+1 while the host writes window c).
+// 64 MiB (MXG_TSV_WIN: fewer, a test knob) that leave through write_windows (win_out.hip); decimals through WinSink (text_dev.h).
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -33,6 +33,7 @@
 #include "bgzf_inflate.h"
 #include "mxg_internal.h"
 #include "scan_kernels.h"
+#include "text_dev.h"
 #include "text_index.h"
 
 namespace mxg {
@@ -645,16 +646,6 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
 // ======================================================================================================
 // TSV text on the device
 // ======================================================================================================
-__device__ __forceinline__ uint32_t dec_digits(uint64_t v)
-{
-    uint32_t d = 1;
-    while (v >= 10u) {
-        v /= 10u;
-        ++d;
-    }
-    return d;
-}
-
 struct TsvParams {
     uint64_t n;               // minimizers
     const uint64_t *hash;
@@ -744,20 +735,6 @@ __global__ __launch_bounds__(256) void k_tsv_offsets(const uint8_t *__restrict__
     if (blockIdx.x == 0 && threadIdx.x == 0) off[n] = *total;
 }
 
-__device__ __forceinline__ void put_win(const TsvParams &p, uint64_t at, char c)
-{
-    if (at >= p.win_lo && at < p.win_hi) p.out[at - p.win_lo] = c;
-}
-__device__ __forceinline__ uint64_t put_dec(const TsvParams &p, uint64_t at, uint64_t v)
-{
-    const uint32_t d = dec_digits(v);
-    for (uint32_t u = 0; u < d; ++u) {
-        put_win(p, at + d - 1u - u, (char)('0' + (uint32_t)(v % 10u)));
-        v /= 10u;
-    }
-    return at + d;
-}
-
 // the tile index as text_of_base (text_index.h) reads it
 __device__ __forceinline__ TextIndex tsv_text_index(const TsvParams &p)
 {
@@ -770,37 +747,38 @@ __global__ __launch_bounds__(256) void k_tsv_entries(const TsvParams p)
     if (i >= p.n) return;
     const uint32_t r = p.rec[i];
     // global offset = everything the id columns before and including this record's take + the entries before this one
-    uint64_t at = p.rec_prefix[r] + (p.id_off[r + 1] - p.id_off[r]) + 1u + p.off[i];
+    const uint64_t at = p.rec_prefix[r] + (p.id_off[r + 1] - p.id_off[r]) + 1u + p.off[i];
     const uint64_t end = at + p.len[i];
     if (end <= p.win_lo || at >= p.win_hi) return;
-    at = put_dec(p, at, p.hash[i]);
+    WinSink o{at, p.win_lo, p.win_hi, p.out};
+    o.num(p.hash[i]);
     if (p.with_pos) {
-        put_win(p, at++, ':');
-        at = put_dec(p, at, p.pos[i]);
+        o.ch(':');
+        o.num(p.pos[i]);
     }
     if (p.with_strand) {
-        put_win(p, at++, ':');
-        put_win(p, at++, p.fwd[i] ? '+' : '-');
+        o.ch(':');
+        o.ch(p.fwd[i] ? '+' : '-');
     }
     if (p.with_seq) {
-        put_win(p, at++, ':');
+        o.ch(':');
         if (p.text) {
             uint64_t a = text_of_base(tsv_text_index(p), r, p.pos[i]);
             for (uint32_t u = 0; u < p.k; ++a) {
                 const unsigned char b = p.text[a];
                 if (b == '\n' || b == '\r') continue;
-                put_win(p, at++, (char)b);
+                o.ch((char)b);
                 ++u;
             }
         } else {
             const uint64_t b0 = p.rec_base[r] + p.pos[i];
             for (uint32_t u = 0; u < p.k; ++u) {
                 const uint64_t g = b0 + u;
-                put_win(p, at++, "ACGT"[(p.packed[g >> 4] >> (2u * ((uint32_t)g & 15u))) & 3u]);
+                o.ch("ACGT"[(p.packed[g >> 4] >> (2u * ((uint32_t)g & 15u))) & 3u]);
             }
         }
     }
-    put_win(p, at, i + 1 == p.rec_first[r + 1] ? '\n' : ' ');
+    o.ch(i + 1 == p.rec_first[r + 1] ? '\n' : ' ');
 }
 
 // one thread per record: its id, the tab, and the line break of a record without minimizers
@@ -809,12 +787,13 @@ __global__ __launch_bounds__(256) void k_tsv_ids(const TsvParams p)
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (r >= p.n_rec) return;
     const uint64_t f = p.rec_first[r];
-    uint64_t at = p.rec_prefix[r] + p.off[f];
+    const uint64_t at = p.rec_prefix[r] + p.off[f];
     const uint32_t l = p.id_off[r + 1] - p.id_off[r];
     if (at + l + 2u <= p.win_lo || at >= p.win_hi) return;
-    for (uint32_t u = 0; u < l; ++u) put_win(p, at++, p.ids[p.id_off[r] + u]);
-    put_win(p, at++, '\t');
-    if (p.rec_first[r + 1] == f) put_win(p, at, '\n');
+    WinSink o{at, p.win_lo, p.win_hi, p.out};
+    for (uint32_t u = 0; u < l; ++u) o.ch(p.ids[p.id_off[r] + u]);
+    o.ch('\t');
+    if (p.rec_first[r + 1] == f) o.ch('\n');
 }
 
 // The sequences of a device-ingested assembly as the file spells them, line breaks removed, for the host writer: record r's bases
@@ -853,7 +832,7 @@ int write_tsv_device(mxg_handle *h, Assembly *a, const char *path, int with_pos,
     const bool dbg_io = getenv("MXG_DEBUG_IO") != nullptr;  // timings on stderr
     auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_begin = now_s();
-    double t_tables = 0, t_alloc = 0, t_dev_wait = 0, t_put = 0;
+    double t_tables = 0;
     MXG_HIP(h, hipSetDevice(h->device));
     hipStream_t st = h->stream;
     int rc;
@@ -949,120 +928,29 @@ int write_tsv_device(mxg_handle *h, Assembly *a, const char *path, int with_pos,
     }
     const uint64_t total = pre + total_entries;
     t_tables = now_s() - t_begin;
-    FILE *f = strcmp(path, "-") == 0 ? stdout : fopen(path, "w+b");  // (read access too: put_parallel maps the file)
-    if (!f) return set_err(h, MXG_EIO, "cannot open '%s' for writing", path);
-    const int ofd = fileno(f);
-    fflush(f);
-    // a regular file takes the windows in parallel parts at absolute offsets (pwrite); anything else -- a FIFO, /dev/stdout, a
-    // process substitution -- has no offsets: it is written in order at the descriptor's own position, and is never removed
-    struct stat sb;
-    const bool regular = f != stdout && fstat(ofd, &sb) == 0 && S_ISREG(sb.st_mode);
-    // (the NAME may still be a symbolic link to a regular file -- /dev/stdout redirected into one -- and is then left alone too)
-    const bool removable = regular && lstat(path, &sb) == 0 && S_ISREG(sb.st_mode);
-    // MXG_TSV_WIN (test knob): bytes of text per window, 1 .. WIN_MAX; the two device windows and their halves of the pinned pool
-    // keep WIN_MAX bytes whatever it says
-    constexpr uint64_t WIN_MAX = 64ull << 20;
-    const uint64_t WIN = std::max<uint64_t>(1, std::min<uint64_t>(knob_u64(h, "MXG_TSV_WIN", WIN_MAX), WIN_MAX));
-    // the file, the pinned windows and their events are released on every way out; a file left incomplete is removed
-    struct Out {
-        FILE *f;
-        const char *path;
-        hipStream_t st;
-        bool removable;
-        char *pin[2] = {nullptr, nullptr};
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        bool complete = false, closed = false;
-        bool close()
-        {
-            closed = true;
-            return f == stdout ? fflush(f) == 0 : fclose(f) == 0;
-        }
-        ~Out()
-        {
-            (void)hipStreamSynchronize(st);
-            for (int b = 0; b < 2; ++b)
-                if (ev[b]) (void)hipEventDestroy(ev[b]);  // (the windows are the handle's: pin_pool, tsv_win)
-            if (!closed) (void)close();
-            if (!complete && removable) (void)remove(path);  // (only a regular file this call created or truncated)
-        }
-    } out{f, path, st, removable};
-    char **pin = out.pin;
-    hipEvent_t *ev = out.ev;
-    bool ok = true;
-    static_assert(2 * WIN_MAX <= PIN_POOL_BYTES && WIN_MAX % PIN_PIECE_BYTES == 0, "the windows come out of the handle's pinned pool, whole pieces each");
-    {
-        unsigned char *pool = nullptr;
-        MXG_HIP(h, pin_pool_get(h, &pool));
-        for (int b = 0; b < 2; ++b) {
-            MXG_HIP(h, h->tsv_win[b].ensure(WIN_MAX));
-            pin[b] = reinterpret_cast<char *>(pool) + (size_t)b * WIN_MAX;
-            MXG_HIP(h, hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
-        }
-    }
-    t_alloc = now_s() - t_begin - t_tables;
-    auto enqueue = [&](uint64_t c) -> int {
-        const int b = (int)(c & 1);
-        p.out = h->tsv_win[b].as<char>();
-        p.win_lo = c * WIN;
-        p.win_hi = std::min(total, p.win_lo + WIN);
+    OutFile of;
+    if (!of.open(path)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", path);
+    // MXG_TSV_WIN (test knob): bytes of text per window, 1 .. a half of the pinned pool
+    const uint64_t WIN = std::max<uint64_t>(1, std::min<uint64_t>(knob_u64(h, "MXG_TSV_WIN", PIN_HALF), PIN_HALF));
+    const WinFill fill = [&](uint64_t, unsigned char *d_win, uint64_t lo, uint64_t hi) -> int {
+        p.out = reinterpret_cast<char *>(d_win);
+        p.win_lo = lo;
+        p.win_hi = hi;
         if (n) hipLaunchKernelGGL(k_tsv_entries, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, p);
         if (n_rec) hipLaunchKernelGGL(k_tsv_ids, dim3((uint32_t)((n_rec + 255) / 256)), dim3(256), 0, st, p);
         MXG_HIP(h, hipGetLastError());
-        // (the pool is pinned in pieces, each registered with HIP on its own: no copy may reach across two of them)
-        for (uint64_t done = 0, n = p.win_hi - p.win_lo; done < n; done += PIN_PIECE_BYTES)
-            MXG_HIP(h, hipMemcpyAsync(pin[b] + done, h->tsv_win[b].as<char>() + done, std::min<uint64_t>(PIN_PIECE_BYTES, n - done),
-                                      hipMemcpyDeviceToHost, st));
-        MXG_HIP(h, hipEventRecord(ev[b], st));
         return MXG_OK;
     };
-    const uint64_t n_win = (total + WIN - 1) / WIN;
-    rc = MXG_OK;
-    if (n_win) rc = enqueue(0);
-    for (uint64_t c = 0; c < n_win && rc == MXG_OK; ++c) {
-        if (c + 1 < n_win) rc = enqueue(c + 1);  // the device formats the next window while this one is written out
-        if (rc != MXG_OK) break;
-        const int b = (int)(c & 1);
-        const double tw0 = now_s();
-        if (hipEventSynchronize(ev[b]) != hipSuccess) {
-            rc = set_err(h, MXG_EDEVICE, "TSV formatting failed on the device");
-            break;
-        }
-        const double tw1 = now_s();
-        t_dev_wait += tw1 - tw0;
-        const uint64_t bytes = std::min(total, (c + 1) * WIN) - c * WIN;
-        if (!regular) {  // (a pipe, a FIFO, a device or the shell's redirection: in order, at the descriptor's own position)
-            uint64_t done = 0;
-            while (done < bytes) {
-                const ssize_t wr = write(ofd, pin[b] + done, bytes - done);
-                if (wr <= 0) {
-                    ok = false;
-                    break;
-                }
-                done += (uint64_t)wr;
-            }
-        } else {  // the window in `-t` parts, copied into the file's pages side by side
-            const uint32_t T = (uint32_t)std::min<uint64_t>(std::min(16u, std::max(1u, host_threads(h))), (bytes + (1u << 20) - 1) >> 20);
-            const char *src[16];
-            size_t len[16];
-            for (uint32_t t = 0; t < T; ++t) {
-                const uint64_t lo = bytes * t / T, hi = bytes * (t + 1) / T;
-                src[t] = pin[b] + lo;
-                len[t] = hi - lo;
-            }
-            ok = put_parallel(ofd, c * WIN, src, len, T);
-        }
-        t_put += now_s() - tw1;
-        if (!ok) break;
-    }
-    (void)hipStreamSynchronize(st);
-    ok = out.close() && ok;
+    WinTimes tw;
+    rc = write_windows(h, of, total, WIN, 0, fill, "mxg_write_tsv", &tw);
+    const bool closed = of.close();
     if (dbg_io)
         fprintf(stderr, "[mxg] write_tsv_device %s: %.3f s = tables %.3f (record column to the host %.3f, record tables %.3f, uploads + allocations %.3f, lengths + offsets %.3f) + buffers %.3f + waiting for the device %.3f + writing %.3f (%llu MB)\n",
-                a->name.c_str(), now_s() - t_begin, t_tables, t_rec, t_host, t_up, t_tables - t_rec - t_host - t_up, t_alloc, t_dev_wait, t_put,
+                a->name.c_str(), now_s() - t_begin, t_tables, t_rec, t_host, t_up, t_tables - t_rec - t_host - t_up, tw.buffers, tw.dev_wait, tw.put,
                 (unsigned long long)(total >> 20));
     if (rc != MXG_OK) return rc;
-    if (!ok) return set_err(h, MXG_EIO, "write error on '%s'", path);
-    out.complete = true;
+    if (!closed) return set_err(h, MXG_EIO, "write error on '%s'", path);
+    of.complete = true;
     return MXG_OK;
 }
 

@@ -20,6 +20,7 @@
 
 #include "join_plan.h"
 #include "ntjoin_mx.h"
+#include "out_file.h"
 
 namespace mxg {
 
@@ -405,46 +406,39 @@ uint32_t host_threads(const mxg_handle *h);
 struct BgzfMember;
 int bgzf_inflate_device(mxg_handle *h, const unsigned char *d_comp, uint64_t comp_bytes, const BgzfMember *d_members, uint32_t n_members,
                         unsigned char *d_text, uint64_t text_bytes, uint32_t *d_status, hipStream_t st);
+// win_out.hip: how text formed on the device reaches a file.  The file is cut into windows of WIN bytes; window c is formed in
+// h->tsv_win[c & 1], copied into half c & 1 of the pinned pool and put into the file while the device forms window c + 1.
+// fill(c, d_win, lo, hi) enqueues on the handle's stream what puts bytes [lo, hi) of the text at d_win.
+using WinFill = std::function<int(uint64_t c, unsigned char *d_win, uint64_t lo, uint64_t hi)>;
+constexpr size_t PIN_HALF = PIN_POOL_BYTES / 2;
+static_assert(PIN_HALF % PIN_PIECE_BYTES == 0, "a half is whole pieces");
+// the two halves of the pinned pool, the two device windows and the events of one writer; all the handle's but the events
+struct WinBufs {
+    mxg_handle *h;
+    char *pin[2] = {nullptr, nullptr};
+    hipEvent_t ev[8] = {};
+    explicit WinBufs(mxg_handle *h_) : h(h_) {}
+    WinBufs(const WinBufs &) = delete;
+    WinBufs &operator=(const WinBufs &) = delete;
+    // the pool, win_bytes <= PIN_HALF a device window, ev[0, n_plain) without timing and ev[n_plain, n_plain + n_timed) with
+    int init(size_t win_bytes, uint32_t n_plain, uint32_t n_timed = 0);
+    ~WinBufs();  // waits for the stream: nothing is in flight into the pool or out of the windows when the caller goes on
+};
+// n bytes of device memory to the START of a half of the pool (n <= PIN_HALF), enqueued on the handle's stream
+int copy_pieces(mxg_handle *h, char *dst_pinned, const void *src_dev, uint64_t n);
+struct WinTimes {  // seconds: taking the buffers, waiting for the device, putting
+    double buffers = 0, dev_wait = 0, put = 0;
+};
+// `total` bytes into `of` behind its first `base` bytes, window by window (nothing at all for total = 0)
+int write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint64_t base, const WinFill &fill, const char *who,
+                  WinTimes *times = nullptr);
 // bgzf_deflate.hip: text on the device -> a BGZF file (bgzf_deflate.h).  bgzf_payload: text bytes a member (MXG_BGZF_PAYLOAD);
-// bgzf_window_bytes: text bytes a window, whole units of lcm(tile, P); bgzf_write_windows: the file, window by window -- fill(c, d_win,
-// lo, hi) enqueues on the handle's stream what puts text bytes [lo, hi) of the file at d_win; bgzf_write: host bytes (mxg_bgzf_write)
-struct OutFile;
-using BgzfFill = std::function<int(uint64_t c, unsigned char *d_win, uint64_t lo, uint64_t hi)>;
+// bgzf_window_bytes: text bytes a window, whole units of lcm(tile, P); bgzf_write_windows: the file, window by window, deflated
+// between fill and copy; bgzf_write: host bytes (mxg_bgzf_write)
 uint32_t bgzf_payload(const mxg_handle *h);
 uint64_t bgzf_window_bytes(uint64_t want, uint32_t tile, uint32_t P);
-int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint32_t P, const BgzfFill &fill, const char *who);
+int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint32_t P, const WinFill &fill, const char *who);
 int bgzf_write(mxg_handle *h, const void *data, uint64_t n, const char *path);
-// n_parts byte ranges written to fd at consecutive offsets from `off` on, by that many threads (host_io.cpp)
-bool put_parallel(int fd, uint64_t off, const char *const *data, const size_t *len, uint32_t n_parts);
-// a file that is removed again unless the call completes (only a regular file this call created or truncated):
-// what scaffold.hip and pathtext.hip write their outputs through
-struct OutFile {
-    FILE *f = nullptr;
-    std::string path;
-    bool regular = false, removable = false, complete = false;
-    bool open(const char *p)
-    {
-        path = p;
-        f = fopen(p, "w+b");  // (read access too: put_parallel maps the file)
-        if (!f) return false;
-        struct stat sb;
-        regular = fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode);
-        removable = regular && lstat(p, &sb) == 0 && S_ISREG(sb.st_mode);
-        return true;
-    }
-    bool close()
-    {
-        if (!f) return true;
-        const bool ok = fclose(f) == 0;
-        f = nullptr;
-        return ok;
-    }
-    ~OutFile()
-    {
-        (void)close();
-        if (!complete && removable) (void)remove(path.c_str());
-    }
-};
 int write_dot(mxg_handle *h, const char *path);
 int dot_part_format(mxg_handle *h, uint32_t part, uint32_t n_parts, uint64_t bytes[2]);
 int dot_part_write(mxg_handle *h, const char *path, uint64_t v_off, uint64_t e_off, int first, int last);

@@ -29,6 +29,7 @@
 
 #include "mxg_internal.h"
 #include "nthash_dev.h"
+#include "text_dev.h"
 
 namespace mxg {
 
@@ -279,22 +280,12 @@ __global__ __launch_bounds__(256) void ov_node(const OvNode *__restrict__ nodes,
     if (tid == 0) o_cnt[2 * blockIdx.x] = n_fin;
 }
 
-__device__ __forceinline__ uint32_t ov_digits(uint64_t v)
-{
-    uint32_t d = 1;
-    while (v >= 10) {
-        v /= 10;
-        ++d;
-    }
-    return d;
-}
-
 // python's str(a) < str(b) for the decimal strings of two hashes (the reference names vertices by str(out_hash) and
 // compares the names: "9" > "10")
 __device__ __forceinline__ bool ov_str_less(uint64_t a, uint64_t b)
 {
     if (a == b) return false;
-    uint32_t da = ov_digits(a), db = ov_digits(b);
+    uint32_t da = dec_digits(a), db = dec_digits(b);
     if (da == db) return a < b;
     if (da < db) {
         uint64_t t = b;

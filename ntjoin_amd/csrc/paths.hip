@@ -344,16 +344,8 @@ __global__ __launch_bounds__(256) void kp_write_sources(uint32_t nv, const uint8
 }
 
 // ------------------------------------------------------------------------------------------------------
-static int exclusive_scan_u32(mxg_handle *h, const uint32_t *in, uint32_t n, DevBuf &bsum, uint32_t *out, uint64_t *d_total)
-{
-    const uint32_t tiles = (n + TILE - 1) / TILE;
-    MXG_HIP(h, bsum.ensure((size_t)tiles * 4 + 16));
-    hipLaunchKernelGGL(k_tile_sum_u32, dim3(tiles), dim3(256), 0, h->stream, in, n, bsum.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, h->stream, bsum.as<uint32_t>(), tiles, d_total);
-    hipLaunchKernelGGL(k_tile_excl_u32, dim3(tiles), dim3(256), 0, h->stream, in, n, bsum.as<uint32_t>(), out);
-    MXG_HIP(h, hipGetLastError());
-    return MXG_OK;
-}
+// bytes of launch_scan_u32's scratch (scan_kernels.h) for n entries
+static size_t scan_scratch_bytes(uint32_t n) { return (size_t)((n + TILE - 1) / TILE) * 4 + 16; }
 
 static int components(mxg_handle *h, const uint32_t *eu, const uint32_t *ev, const uint8_t *alive, uint32_t ne, uint32_t nv,
                       uint32_t *parent, uint32_t *d_flag)
@@ -496,11 +488,13 @@ int find_paths(mxg_handle *h, int64_t n_min)
                        B[KEY2].as<unsigned long long>(), B[SIZE].as<uint32_t>(), B[ISSRC].as<uint8_t>());
     MXG_HIP(h, B[TOTAL].ensure(64));
     uint64_t *d_tot = B[TOTAL].as<uint64_t>();
-    if ((rc = exclusive_scan_u32(h, B[SIZE].as<uint32_t>(), nv, B[BSUM], B[FIRST].as<uint32_t>(), d_tot)) != MXG_OK) return rc;
+    MXG_HIP(h, B[BSUM].ensure(scan_scratch_bytes(nv)));
+    launch_scan_u32(h->stream, B[SIZE].as<uint32_t>(), nv, B[BSUM].as<uint32_t>(), B[FIRST].as<uint32_t>(), d_tot);
     // path index = exclusive scan of is_src (as u32): reuse SIZE? keep it simple: widen is_src into FILL
     MXG_HIP(h, hipMemsetAsync(B[FILL].p, 0, (size_t)nv * 4, h->stream));
     hipLaunchKernelGGL(kp_widen, gv, b, 0, h->stream, B[ISSRC].as<uint8_t>(), nv, B[FILL].as<uint32_t>());
-    if ((rc = exclusive_scan_u32(h, B[FILL].as<uint32_t>(), nv, B[BSUM], B[RANK].as<uint32_t>(), d_tot + 1)) != MXG_OK) return rc;
+    launch_scan_u32(h->stream, B[FILL].as<uint32_t>(), nv, B[BSUM].as<uint32_t>(), B[RANK].as<uint32_t>(), d_tot + 1);
+    MXG_HIP(h, hipGetLastError());
     uint64_t tot[2] = {0, 0};
     MXG_HIP(h, hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, h->stream));
     MXG_HIP(h, hipStreamSynchronize(h->stream));
@@ -677,8 +671,9 @@ static int segments_device(mxg_handle *h, uint32_t a, uint32_t *n_seg_out)
     const dim3 gn((n + 255) / 256), b(256);
     hipLaunchKernelGGL(ks_mark_starts, dim3((n_paths + 255) / 256), b, 0, h->stream, pf, n_paths, B[SG_FLAG].as<uint32_t>());
     hipLaunchKernelGGL(ks_flags, gn, b, 0, h->stream, pv, n, vrec, B[SG_FLAG].as<uint32_t>());
-    int rc = exclusive_scan_u32(h, B[SG_FLAG].as<uint32_t>(), n, B[BSUM], B[SG_EXCL].as<uint32_t>(), B[TOTAL].as<uint64_t>());
-    if (rc != MXG_OK) return rc;
+    MXG_HIP(h, B[BSUM].ensure(scan_scratch_bytes(n)));
+    launch_scan_u32(h->stream, B[SG_FLAG].as<uint32_t>(), n, B[BSUM].as<uint32_t>(), B[SG_EXCL].as<uint32_t>(), B[TOTAL].as<uint64_t>());
+    MXG_HIP(h, hipGetLastError());
     uint64_t n_seg64 = 0;
     MXG_HIP(h, hipMemcpyAsync(&n_seg64, B[TOTAL].p, 8, hipMemcpyDeviceToHost, h->stream));
     MXG_HIP(h, hipStreamSynchronize(h->stream));
@@ -982,7 +977,9 @@ int format_paths(mxg_handle *h, uint32_t a, const mxg_format_params &p, const ui
     uint64_t *d_tot = B[TOTAL].as<uint64_t>() + 1;
     hipLaunchKernelGGL(kf_keep, gs, b, 0, h->stream, ori, n_seg, B[FM_KEEP].as<uint32_t>());
     MXG_HIP(h, hipGetLastError());
-    if ((rc = exclusive_scan_u32(h, B[FM_KEEP].as<uint32_t>(), n_seg, B[BSUM], B[FM_KEXCL].as<uint32_t>(), d_tot)) != MXG_OK) return rc;
+    MXG_HIP(h, B[BSUM].ensure(scan_scratch_bytes(n_seg)));
+    launch_scan_u32(h->stream, B[FM_KEEP].as<uint32_t>(), n_seg, B[BSUM].as<uint32_t>(), B[FM_KEXCL].as<uint32_t>(), d_tot);
+    MXG_HIP(h, hipGetLastError());
     MXG_HIP(h, hipMemcpyAsync(B[FM_LEN].p, record_length, (size_t)nr * 4, hipMemcpyHostToDevice, h->stream));
     MXG_HIP(h, hipMemsetAsync(B[FM_ERR].p, 0, 8, h->stream));
     MXG_HIP(h, hipMemsetAsync(B[FM_ERR].as<unsigned char>() + 8, 0xFF, 8, h->stream));

@@ -6,8 +6,8 @@
 //
 // The unit of work is a node.  Its text is a FRAGMENT of either file: in the .path file `[ntJoin<p>\t]id ori:s-e` and ` <gap>N ` or,
 // behind a path's last node, the line end; in the AGP its W line and, unless it is the last node, the N line of the gap behind it.
-// One formatter per fragment (pt_path_frag, pt_agp_frag) runs twice over a sink: PtCount adds up the bytes, PtWrite stores those
-// that fall into the window at hand -- the two passes cannot disagree about a length.
+// One formatter per fragment (pt_path_frag, pt_agp_frag) runs twice over a sink (text_dev.h): CountSink adds up the bytes, WinSink
+// stores those that fall into the window at hand -- the two passes cannot disagree about a length.
 //
 //   k_pt_nodes   per node: its path (bisection over path_first), the strips of an end node, the adjusted interval [s, e), the
 //                refusals (the lowest offending node wins, through one atomicMin), and the length of its components e - s + gap.
@@ -18,17 +18,14 @@
 //                two more scans turn them into file offsets.
 //   k_pt_bounds  per window: the node that holds the window's first byte (bisection over the offsets).
 //   k_pt_emit    per node of a window: the fragment's bytes that fall into [lo, hi).  A long id is a loop of one lane.
-// Output leaves through the two device windows and the pinned pool of the TSV writer (ingest.hip): the device formats window c + 1
-// while the host writes window c at its offset of the file.  MXG_PATH_WIN sets the bytes per window.
+// Output leaves window by window through write_windows (win_out.hip); MXG_PATH_WIN sets the bytes per window.
 // The first line of the .path file and the AGP's unassigned lines (one per interval, from the handle's copy of the last
 // mxg_write_scaffolds' intervals) are the host's.
-#include <fcntl.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <string>
 
 #include "mxg_internal.h"
+#include "text_dev.h"
 
 namespace mxg {
 
@@ -88,45 +85,11 @@ __device__ __forceinline__ PtNode pt_node(const PtParams &q, uint32_t i)
     return nd;
 }
 
-__device__ __forceinline__ uint32_t pt_digits(uint64_t v)
+// a record's id into either sink (text_dev.h)
+template <class Sink> __device__ __forceinline__ void pt_id(const PtParams &q, uint32_t r, Sink &o)
 {
-    uint32_t d = 1;
-    for (uint64_t lim = 10; d < 20 && v >= lim; lim *= 10) ++d;  // (10^19 < 2^64: lim does not wrap while d < 20)
-    return d;
+    o.bytes(q.ids + q.id_off[r], q.id_off[r + 1] - q.id_off[r]);
 }
-
-struct PtCount {
-    uint64_t bytes = 0;
-    __device__ __forceinline__ void ch(char) { ++bytes; }
-    __device__ __forceinline__ void lit(const char *, uint32_t n) { bytes += n; }
-    __device__ __forceinline__ void num(uint64_t v) { bytes += pt_digits(v); }
-    __device__ __forceinline__ void id(const PtParams &q, uint32_t r) { bytes += q.id_off[r + 1] - q.id_off[r]; }
-};
-
-struct PtWrite {
-    uint64_t pos, lo, hi;  // the next byte's offset; the window
-    char *out;             // the window's image
-    __device__ __forceinline__ void ch(char c)
-    {
-        if (pos >= lo && pos < hi) out[pos - lo] = c;
-        ++pos;
-    }
-    __device__ __forceinline__ void bytes(const char *src, uint64_t n)
-    {
-        const uint64_t a = max(pos, lo), b = min(pos + n, hi);  // (the part inside the window)
-        for (uint64_t u = a; u < b; ++u) out[u - lo] = src[u - pos];
-        pos += n;
-    }
-    __device__ __forceinline__ void lit(const char *s, uint32_t n) { bytes(s, n); }
-    __device__ __forceinline__ void num(uint64_t v)
-    {
-        char buf[20];
-        const uint32_t d = pt_digits(v);
-        for (uint32_t u = d; u-- > 0; v /= 10) buf[u] = (char)('0' + v % 10);
-        for (uint32_t u = 0; u < d; ++u) ch(buf[u]);
-    }
-    __device__ __forceinline__ void id(const PtParams &q, uint32_t r) { bytes(q.ids + q.id_off[r], q.id_off[r + 1] - q.id_off[r]); }
-};
 
 #define PT_LIT(o, s) (o).lit(s, (uint32_t)sizeof(s) - 1u)
 
@@ -137,7 +100,7 @@ template <class Sink> __device__ __forceinline__ void pt_path_frag(const PtParam
         o.num(nd.p);
         o.ch('\t');
     }
-    o.id(q, nd.rec);
+    pt_id(q, nd.rec, o);
     o.ch(nd.reverse ? '-' : '+');
     o.ch(':');
     o.num((uint64_t)nd.s);
@@ -164,7 +127,7 @@ template <class Sink> __device__ __forceinline__ void pt_agp_frag(const PtParams
     o.ch('\t');
     o.num(part);
     PT_LIT(o, "\tW\t");
-    o.id(q, nd.rec);
+    pt_id(q, nd.rec, o);
     o.ch('\t');
     o.num((uint64_t)nd.s + 1);
     o.ch('\t');
@@ -204,14 +167,14 @@ __global__ __launch_bounds__(256) void k_pt_len(const PtParams q)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i > q.n) return;
-    PtCount pc, ac;
+    CountSink pc, ac;
     if (i < q.n) {
         const PtNode nd = pt_node(q, i);
         pt_path_frag(q, nd, pc);
         pt_agp_frag(q, nd, 1 + q.sum[i] - q.sum[i - nd.j], ac);
     }
-    q.poff[i] = pc.bytes;
-    q.aoff[i] = ac.bytes;
+    q.poff[i] = pc.n;
+    q.aoff[i] = ac.n;
 }
 
 // exclusive prefix of per-thread sums `c` inside a block of 256; *total = the block's sum (all threads call)
@@ -300,21 +263,9 @@ __global__ __launch_bounds__(256) void k_pt_emit(const PtParams q, uint32_t agp,
     const uint64_t f_lo = off[i], f_hi = off[i + 1];
     if (f_hi <= lo || f_lo >= hi) return;
     const PtNode nd = pt_node(q, i);
-    PtWrite w{f_lo, lo, hi, out};
+    WinSink w{f_lo, lo, hi, out};
     if (agp) pt_agp_frag(q, nd, 1 + q.sum[i] - q.sum[i - nd.j], w);
     else pt_path_frag(q, nd, w);
-}
-
-// `bytes` bytes to the file: at offset `off` of a regular file, else at the descriptor's own position
-static bool pt_put(const OutFile &of, const char *src, uint64_t bytes, uint64_t off)
-{
-    const int fd = fileno(of.f);
-    for (uint64_t done = 0; done < bytes;) {
-        const ssize_t wr = of.regular ? pwrite(fd, src + done, bytes - done, (off_t)(off + done)) : write(fd, src + done, bytes - done);
-        if (wr <= 0) return false;
-        done += (uint64_t)wr;
-    }
-    return true;
 }
 
 static int pt_scan(mxg_handle *h, uint64_t *d_a, uint32_t n)  // d_a[0 .. n) -> exclusive sums, in place
@@ -342,49 +293,14 @@ static int pt_emit_file(mxg_handle *h, const PtParams &q, uint32_t agp, uint64_t
     MXG_HIP(h, hipGetLastError());
     MXG_HIP(h, hipMemcpyAsync(bounds.data(), h->ptbuf[PT_BOUNDS].p, n_win * 4, hipMemcpyDeviceToHost, st));
     MXG_HIP(h, hipStreamSynchronize(st));
-    struct Events {
-        hipStream_t st;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        ~Events()
-        {
-            (void)hipStreamSynchronize(st);
-            for (int b = 0; b < 2; ++b)
-                if (ev[b]) (void)hipEventDestroy(ev[b]);
-        }
-    } evs{st};
-    char *pin[2];
-    {
-        unsigned char *pool = nullptr;
-        MXG_HIP(h, pin_pool_get(h, &pool));
-        for (int b = 0; b < 2; ++b) {
-            MXG_HIP(h, h->tsv_win[b].ensure(WIN));
-            pin[b] = reinterpret_cast<char *>(pool) + (size_t)b * (PIN_POOL_BYTES / 2);
-            MXG_HIP(h, hipEventCreateWithFlags(&evs.ev[b], hipEventDisableTiming));
-        }
-    }
-    auto enqueue = [&](uint64_t c) -> int {
-        const int b = (int)(c & 1);
-        const uint64_t lo = c * WIN, hi = std::min(total, lo + WIN), n = hi - lo;
+    const WinFill fill = [&](uint64_t c, unsigned char *d_win, uint64_t lo, uint64_t hi) -> int {
         // (the node that holds byte hi holds byte hi - 1 or follows the node that does)
         const uint32_t i0 = bounds[c], i1 = c + 1 < n_win ? std::min(q.n, bounds[c + 1] + 1) : q.n;
-        hipLaunchKernelGGL(k_pt_emit, dim3((i1 - i0 + 255) / 256), dim3(256), 0, st, q, agp, i0, i1, lo, hi, h->tsv_win[b].as<char>());
+        hipLaunchKernelGGL(k_pt_emit, dim3((i1 - i0 + 255) / 256), dim3(256), 0, st, q, agp, i0, i1, lo, hi, reinterpret_cast<char *>(d_win));
         MXG_HIP(h, hipGetLastError());
-        // (the pool is pinned in pieces, each registered with HIP on its own: no copy may reach across two of them)
-        for (uint64_t done = 0; done < n; done += PIN_PIECE_BYTES)
-            MXG_HIP(h, hipMemcpyAsync(pin[b] + done, h->tsv_win[b].as<char>() + done, std::min<uint64_t>(PIN_PIECE_BYTES, n - done),
-                                      hipMemcpyDeviceToHost, st));
-        MXG_HIP(h, hipEventRecord(evs.ev[b], st));
         return MXG_OK;
     };
-    int rc = enqueue(0);
-    for (uint64_t c = 0; c < n_win && rc == MXG_OK; ++c) {
-        if (c + 1 < n_win && (rc = enqueue(c + 1)) != MXG_OK) break;  // the device fills the next window while this one is written
-        if (hipEventSynchronize(evs.ev[c & 1]) != hipSuccess)
-            return set_err(h, MXG_EDEVICE, "mxg_write_paths: the device failed while forming '%s'", of.path.c_str());
-        const uint64_t bytes = std::min(total, (c + 1) * WIN) - c * WIN;
-        if (!pt_put(of, pin[c & 1], bytes, base + c * WIN)) return set_err(h, MXG_EIO, "write error on '%s'", of.path.c_str());
-    }
-    return rc;
+    return write_windows(h, of, total, WIN, base, fill, "mxg_write_paths");
 }
 
 int write_paths(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
@@ -482,13 +398,12 @@ int write_paths(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_nod
         MXG_HIP(h, hipStreamSynchronize(st));
     }
     // ---- nothing is refused from here on: the files
-    const uint64_t WIN_MAX = PIN_POOL_BYTES / 2;
-    const uint64_t WIN = std::max<uint64_t>(1, std::min<uint64_t>(knob_u64(h, "MXG_PATH_WIN", WIN_MAX), WIN_MAX));
+    const uint64_t WIN = std::max<uint64_t>(1, std::min<uint64_t>(knob_u64(h, "MXG_PATH_WIN", PIN_HALF), PIN_HALF));
     OutFile pf, af;
     if (!pf.open(path_file)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", path_file);
     if (agp_file && !af.open(agp_file)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", agp_file);
     const std::string head = std::string(first_line ? first_line : "") + "\n";
-    if (!pt_put(pf, head.data(), head.size(), 0)) return set_err(h, MXG_EIO, "write error on '%s'", path_file);
+    if (!pf.put(head.data(), head.size(), 0, host_threads(h))) return set_err(h, MXG_EIO, "write error on '%s'", path_file);
     int rc;
     if ((rc = pt_emit_file(h, q, 0u, path_bytes, pf, head.size(), WIN)) != MXG_OK) return rc;
     if (agp_file) {
@@ -503,7 +418,7 @@ int write_paths(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_nod
                 un += id + ":" + std::to_string(iv.lo) + "-" + std::to_string(iv.hi) + "\t1\t" + std::to_string(len) + "\t1\tW\t" + id + "\t" +
                       std::to_string(first) + "\t" + std::to_string(first + (uint64_t)len - 1) + "\t+\n";
             }
-            if (!pt_put(af, un.data(), un.size(), agp_bytes)) return set_err(h, MXG_EIO, "write error on '%s'", agp_file);
+            if (!af.put(un.data(), un.size(), agp_bytes, host_threads(h))) return set_err(h, MXG_EIO, "write error on '%s'", agp_file);
         }
     }
     const bool c_pf = pf.close(), c_af = af.close();

@@ -19,13 +19,8 @@
 //                thread, an exclusive scan over the group), and the bytes go through a 256-entry table in LDS (identity,
 //                complement, each with or without case folding) into the tile's image in LDS.  The reverse direction reads the
 //                chunks mirrored.  The image leaves with 16-byte stores.
-// Output leaves through two device windows and the pinned pool, as the TSV text does (ingest.hip): the device fills window
-// c + 1 while the host writes window c at its offset of the file.  MXG_SCAF_WIN sets the window size.  With MXG_SCAF_BGZF the windows
-// are deflated on the device into BGZF members on their way out (bgzf_deflate.hip) and the host writes the compressed bytes.
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
+// Output leaves window by window through write_windows (win_out.hip); MXG_SCAF_WIN sets the window size.  With MXG_SCAF_BGZF the
+// windows are deflated on the device into BGZF members on their way out (bgzf_deflate.hip) and the host writes the compressed bytes.
 #include <algorithm>
 #include <string>
 
@@ -223,83 +218,21 @@ static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint
     const uint64_t total = pt.total;
     const size_t n_pieces = pt.pieces.size();
     if (n_pieces >= 0xFFFFFFFFull) return set_err(h, MXG_ELIMIT, "mxg_write_scaffolds: too many pieces of output for one call");
-    if (!total) return bgzf_P ? bgzf_write_windows(h, of, 0, WIN, bgzf_P, BgzfFill(), "mxg_write_scaffolds") : MXG_OK;
+    const char *who = "mxg_write_scaffolds";
+    if (!total) return bgzf_P ? bgzf_write_windows(h, of, 0, WIN, bgzf_P, WinFill(), who) : MXG_OK;
     pt.pieces.push_back(ScafPiece{total, 0, 0, SP_LIT});  // (the end of the last piece)
     MXG_HIP(h, B[SC_PIECES].ensure((n_pieces + 1) * sizeof(ScafPiece)));
     MXG_HIP(h, B[SC_LITS].ensure(pt.lits.size() + 16));
     MXG_HIP(h, hipMemcpyAsync(B[SC_PIECES].p, pt.pieces.data(), (n_pieces + 1) * sizeof(ScafPiece), hipMemcpyHostToDevice, st));
     if (!pt.lits.empty()) MXG_HIP(h, hipMemcpyAsync(B[SC_LITS].p, pt.lits.data(), pt.lits.size(), hipMemcpyHostToDevice, st));
-    if (bgzf_P) {
-        const BgzfFill fill = [&](uint64_t, unsigned char *d_win, uint64_t lo, uint64_t hi) -> int {
-            hipLaunchKernelGGL(k_scaf_emit, dim3((uint32_t)((hi - lo + SCAF_TILE - 1) / SCAF_TILE)), dim3(256), 0, st, t, B[SC_PIECES].as<ScafPiece>(),
-                               (uint32_t)n_pieces, B[SC_LITS].as<unsigned char>(), fold, d_win, lo, hi);
-            MXG_HIP(h, hipGetLastError());
-            return MXG_OK;
-        };
-        return bgzf_write_windows(h, of, total, bgzf_window_bytes(WIN, SCAF_TILE, bgzf_P), bgzf_P, fill, "mxg_write_scaffolds");
-    }
-    struct Events {
-        hipStream_t st;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        ~Events()
-        {
-            (void)hipStreamSynchronize(st);
-            for (int b = 0; b < 2; ++b)
-                if (ev[b]) (void)hipEventDestroy(ev[b]);
-        }
-    } evs{st};
-    char *pin[2];
-    {
-        unsigned char *pool = nullptr;
-        MXG_HIP(h, pin_pool_get(h, &pool));
-        for (int b = 0; b < 2; ++b) {
-            MXG_HIP(h, h->tsv_win[b].ensure(WIN));
-            pin[b] = reinterpret_cast<char *>(pool) + (size_t)b * (PIN_POOL_BYTES / 2);
-            MXG_HIP(h, hipEventCreateWithFlags(&evs.ev[b], hipEventDisableTiming));
-        }
-    }
-    auto enqueue = [&](uint64_t c) -> int {
-        const int b = (int)(c & 1);
-        const uint64_t lo = c * WIN, hi = std::min(total, lo + WIN), n = hi - lo;
-        hipLaunchKernelGGL(k_scaf_emit, dim3((uint32_t)((n + SCAF_TILE - 1) / SCAF_TILE)), dim3(256), 0, st, t, B[SC_PIECES].as<ScafPiece>(),
-                           (uint32_t)n_pieces, B[SC_LITS].as<unsigned char>(), fold, h->tsv_win[b].as<unsigned char>(), lo, hi);
+    const WinFill fill = [&](uint64_t, unsigned char *d_win, uint64_t lo, uint64_t hi) -> int {
+        hipLaunchKernelGGL(k_scaf_emit, dim3((uint32_t)((hi - lo + SCAF_TILE - 1) / SCAF_TILE)), dim3(256), 0, st, t, B[SC_PIECES].as<ScafPiece>(),
+                           (uint32_t)n_pieces, B[SC_LITS].as<unsigned char>(), fold, d_win, lo, hi);
         MXG_HIP(h, hipGetLastError());
-        // (the pool is pinned in pieces, each registered with HIP on its own: no copy may reach across two of them)
-        for (uint64_t done = 0; done < n; done += PIN_PIECE_BYTES)
-            MXG_HIP(h, hipMemcpyAsync(pin[b] + done, h->tsv_win[b].as<char>() + done, std::min<uint64_t>(PIN_PIECE_BYTES, n - done),
-                                      hipMemcpyDeviceToHost, st));
-        MXG_HIP(h, hipEventRecord(evs.ev[b], st));
         return MXG_OK;
     };
-    const uint64_t n_win = (total + WIN - 1) / WIN;
-    const int ofd = fileno(of.f);
-    int rc = enqueue(0);
-    for (uint64_t c = 0; c < n_win && rc == MXG_OK; ++c) {
-        if (c + 1 < n_win && (rc = enqueue(c + 1)) != MXG_OK) break;  // the device fills the next window while this one is written
-        const int b = (int)(c & 1);
-        if (hipEventSynchronize(evs.ev[b]) != hipSuccess) return set_err(h, MXG_EDEVICE, "mxg_write_scaffolds: the device failed while forming '%s'", of.path.c_str());
-        const uint64_t bytes = std::min(total, (c + 1) * WIN) - c * WIN;
-        bool ok = true;
-        if (!of.regular) {  // (a pipe or a device: in order, at the descriptor's own position)
-            for (uint64_t done = 0; done < bytes && ok;) {
-                const ssize_t wr = write(ofd, pin[b] + done, bytes - done);
-                ok = wr > 0;
-                if (ok) done += (uint64_t)wr;
-            }
-        } else {
-            const uint32_t T = (uint32_t)std::min<uint64_t>(std::min(16u, std::max(1u, host_threads(h))), (bytes + (1u << 20) - 1) >> 20);
-            const char *src[16];
-            size_t len[16];
-            for (uint32_t u = 0; u < T; ++u) {
-                const uint64_t lo = bytes * u / T, hi = bytes * (u + 1) / T;
-                src[u] = pin[b] + lo;
-                len[u] = hi - lo;
-            }
-            ok = put_parallel(ofd, c * WIN, src, len, T);
-        }
-        if (!ok) return set_err(h, MXG_EIO, "write error on '%s'", of.path.c_str());
-    }
-    return rc;
+    if (bgzf_P) return bgzf_write_windows(h, of, total, bgzf_window_bytes(WIN, SCAF_TILE, bgzf_P), bgzf_P, fill, who);
+    return write_windows(h, of, total, WIN, 0, fill, who);
 }
 
 int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
@@ -441,7 +374,7 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
                                (unsigned long long)p, side ? "last" : "first");
         }
     // ---- nothing is refused from here on: the files
-    const uint64_t WIN = std::max<uint64_t>(SCAF_TILE, std::min<uint64_t>(knob_u64(h, "MXG_SCAF_WIN", PIN_POOL_BYTES / 2), PIN_POOL_BYTES / 2) /
+    const uint64_t WIN = std::max<uint64_t>(SCAF_TILE, std::min<uint64_t>(knob_u64(h, "MXG_SCAF_WIN", PIN_HALF), PIN_HALF) /
                                                            SCAF_TILE * SCAF_TILE);
     const uint32_t bgzf_P = flags & MXG_SCAF_BGZF ? bgzf_payload(h) : 0u;
     OutFile fa, ufa, bed;

@@ -126,6 +126,15 @@ static __global__ __launch_bounds__(256) void k_tile_excl_u32(const uint32_t *__
     }
 }
 
+// out[0 .. n) = exclusive prefix sums of in[0 .. n), *total = their sum; bsum: (n + TILE - 1) / TILE words of scratch
+static inline void launch_scan_u32(hipStream_t stream, const uint32_t *in, uint32_t n, uint32_t *bsum, uint32_t *out, uint64_t *total)
+{
+    const uint32_t tiles = (n + TILE - 1) / TILE;
+    hipLaunchKernelGGL(k_tile_sum_u32, dim3(tiles), dim3(256), 0, stream, in, n, bsum);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, stream, bsum, tiles, total);
+    hipLaunchKernelGGL(k_tile_excl_u32, dim3(tiles), dim3(256), 0, stream, in, n, bsum, out);
+}
+
 // ---- ordered offsets without count / scan launches: two-level counts ------------------------------------------------
 // A producer kernel whose block b yields c items stores cnt[b] = c and adds c to sup[b >> 8] (one fire-and-forget atomic
 // per block: nobody waits for it).  The consumer kernel's block that needs "items before producer block q" sums

@@ -12,7 +12,8 @@ the text.
  3. the scaffold cases of tests/test_gpu_scaffolds.py with MXG_SCAF_BGZF: the decompressed files, the BED, the strips and the counts
     are the plain call's; small windows and small members give the bytes of one window;
  4. the compressed scaffolds go back in through add_fasta on the device inflate route and sketch to the same minimizers;
- 5. without the flag nothing changes and no witness line appears."""
+ 5. without the flag nothing changes and no witness line appears;
+ 6. the compressed file into a FIFO, in several windows: the bytes of the regular file."""
 import glob
 import gzip
 import os
@@ -23,7 +24,7 @@ import numpy as np
 import pytest
 
 from ntjoin_amd.engine import MxEngine
-from tests import _bgzf, _bgzf_deflate_host as host, _oracle, _scaffold_cases as cases
+from tests import _bgzf, _bgzf_deflate_host as host, _fifo, _oracle, _scaffold_cases as cases
 from tests.test_bgzf_deflate_cpu import P_MAX, check_file, deep_text, fibonacci_text
 
 pytestmark = pytest.mark.gpu
@@ -180,6 +181,28 @@ def test_scaffolds_compressed_equal_plain(kind, which, env, capfd, program, tmp_
     for f in (0, 1):
         want, _ = host.deflate(program, 1000, plain[f], tmp_path, f"want1000_{f}")
         assert got[0][f] == want
+
+
+def test_a_fifo_takes_the_compressed_windows_in_order(env, tmp_path):
+    """the assigned FASTA with MXG_SCAF_BGZF into a FIFO (no offsets: the windows' members and the end-of-file marker are written in
+    order at the descriptor's own position): the bytes of the same call into a regular file.  Members of 4096 bytes make a window of
+    one emit tile a whole number of members, so the knob gives the fuzz case's assigned file three windows."""
+    records, paths, gap, fold, fasta = scaffold_inputs("fuzz", 46, tmp_path)
+    index = {rid: r for r, (rid, _) in enumerate(records)}
+    rows, first = cases.rows_of(paths, index)
+    env["MXG_BGZF_PAYLOAD"] = "4096"
+    env["MXG_SCAF_WIN"] = str(cases.TILE)
+    with MxEngine(k=15, w=10) as eng:
+        a = eng.add_fasta("t", 1.0, fasta)
+        plain, _ = scaffolds(eng, a, records, paths, tmp_path / "plain", gap, fold, False)
+        want, _ = scaffolds(eng, a, records, paths, tmp_path / "comp", gap, fold, True)
+        assert len(plain[0]) > 2 * cases.TILE and gzip.decompress(want[0]) == plain[0]  # three windows
+        assert "MXG_BGZF_PAYLOAD=4096" in eng.knobs() and f"MXG_SCAF_WIN={cases.TILE}" in eng.knobs()
+        names = [str(tmp_path / f) for f in ("f.assigned.fa.gz", "f.unassigned.fa.gz", "f.bed")]
+        with _fifo.fifo_reader(names[0], len(want[0])) as drain:
+            eng.write_scaffolds(a, rows, first, overlap_gap=gap, fold_case=fold, assigned=names[0], unassigned=names[1], bed=names[2], bgzf=True)
+            assert drain() == want[0]
+        assert [read(n) for n in names[1:]] == want[1:]
 
 
 def test_round_trip_through_the_device_inflate_route(env, capfd, tmp_path):

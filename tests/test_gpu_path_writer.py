@@ -1,6 +1,6 @@
 """GPU tests of the .path / AGP writer (mxg_write_paths, csrc/pathtext.hip; reference print_scaffolds :605-610, write_agp :346-376,
 write_agp_unassigned :379-404): the goldens, paths that span lanes, waves and blocks, every digit border, orientations, cuts and
-strips, small output windows, the unassigned lines, every refusal, one larger call, and the routing inside Ntjoin.print_scaffolds.
+strips, small output windows, either file into a FIFO, the unassigned lines, every refusal, one larger call, and the routing inside Ntjoin.print_scaffolds.
 The writer never reads the bases, so the assemblies are a handful of short records.  Every comparison is byte for byte against
 the restatement (tests/_path_text_restatement.py)."""
 import argparse
@@ -14,7 +14,7 @@ import pytest
 
 from ntjoin_amd.engine import MxEngine, MxError
 from ntjoin_amd.ntjoin import Ntjoin
-from tests import _oracle, _path_text_restatement as pt, _scaffold_cases as cases, _scaffold_restatement as rs
+from tests import _fifo, _oracle, _path_text_restatement as pt, _scaffold_cases as cases, _scaffold_restatement as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -168,6 +168,28 @@ def test_small_windows_equal_the_default(win, tmp_path, monkeypatch):
         got = write(e, a, paths, leads, tails, tmp_path / "o", index)
         assert f"MXG_PATH_WIN={win}" in e.knobs()
     assert got == (text.encode("ascii"), agp.encode("ascii"))
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["path", "agp"])
+def test_a_fifo_takes_the_windows_in_order(which, tmp_path, monkeypatch):
+    """either file into a FIFO (no offsets: the first line and the windows are written in order at the descriptor's own position),
+    in windows of 7 bytes: the bytes of the same call into a regular file"""
+    paths, leads, tails = cut_and_strip_paths()
+    paths, leads, tails = paths[:4] + paths[-4:], leads[:4] + leads[-4:], tails[:4] + tails[-4:]  # (ids of 1 to 300 bytes)
+    index = {rid: r for r, rid in enumerate(NAMES)}
+    rows, first = cases.rows_of(paths, index)
+    text, agp = pt.by_regex(paths, leads, tails, "t.fa")
+    monkeypatch.setenv("MXG_PATH_WIN", "7")
+    with MxEngine(k=4, w=2) as e:
+        a = e.add_records("t", 1.0, RECORDS)
+        want = write(e, a, paths, leads, tails, tmp_path / "o", index)
+        assert want == (text.encode("ascii"), agp.encode("ascii")) and "MXG_PATH_WIN=7" in e.knobs()
+        assert all(3 * 7 < len(w) < 4096 for w in want)  # three windows or more; far below any pipe's capacity
+        names = [str(tmp_path / "f.path"), str(tmp_path / "f.agp")]
+        with _fifo.fifo_reader(names[which], len(want[which])) as drain:
+            e.write_paths(a, rows, first, lead_strip=leads, tail_strip=tails, first_line="t.fa", path=names[0], agp=names[1])
+            assert drain() == want[which]
+        assert read(names[1 - which]) == want[1 - which]
 
 
 def test_unassigned_lines_follow_the_last_path(tmp_path):

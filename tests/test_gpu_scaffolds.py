@@ -1,6 +1,6 @@
 """GPU tests of the scaffold stage (mxg_write_scaffolds, csrc/scaffold.hip; reference print_scaffolds and print_unassigned,
 bin/ntjoin_assemble.py:580-658): the goldens (the reference's own output) end to end through Ntjoin, seeded fuzz and one large call
-against the restatement (tests/_scaffold_restatement.py), both text layouts, small output windows, and every refusal.  Text only:
+against the restatement (tests/_scaffold_restatement.py), both text layouts, small output windows, the assigned file into a FIFO, and every refusal.  Text only:
 every comparison is byte for byte."""
 import argparse
 import glob
@@ -14,7 +14,7 @@ import pytest
 from ntjoin_amd import synth
 from ntjoin_amd.engine import MxEngine, MxError
 from ntjoin_amd.ntjoin import Ntjoin
-from tests import _oracle, _scaffold_cases as cases, _scaffold_restatement as rs
+from tests import _fifo, _oracle, _scaffold_cases as cases, _scaffold_restatement as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -160,6 +160,28 @@ def test_small_windows_equal_the_default(tmp_path, monkeypatch):
             assert win is None or f"MXG_SCAF_WIN={win}" in eng.knobs()
     assert len(got[0][0]) > 5 * 8192 and len(got[0][1]) > 8192  # several windows of either FASTA
     assert got[1:] == [got[0]] * 3
+
+
+def test_a_fifo_takes_the_windows_in_order(tmp_path, monkeypatch):
+    """the assigned FASTA into a FIFO (no offsets: the windows are written in order at the descriptor's own position), one emit tile
+    per window: the bytes of the same call into a regular file.  The fuzz case with the smallest assigned file of three windows."""
+    case = cases.fuzz_case(46)
+    fasta = str(tmp_path / "t.fa")
+    cases.write_fasta(fasta, case["records"], case["width"], case["final_newline"])
+    index = {rid: r for r, (rid, _) in enumerate(case["records"])}
+    rows, first = cases.rows_of(case["paths"], index)
+    monkeypatch.setenv("MXG_SCAF_WIN", str(cases.TILE))
+    with MxEngine(k=15, w=10) as eng:
+        a = eng.add_fasta("t", 1.0, fasta)
+        want = check_against_restatement(eng, a, case["records"], case["paths"], tmp_path / "o", case["overlap_gap"], case["fold"])
+        assert f"MXG_SCAF_WIN={cases.TILE}" in eng.knobs() and len(want[0]) > 2 * cases.TILE  # three windows
+        names = [str(tmp_path / f) for f in ("f.assigned.fa", "f.unassigned.fa", "f.bed")]
+        with _fifo.fifo_reader(names[0], len(want[0])) as drain:
+            res = eng.write_scaffolds(a, rows, first, overlap_gap=case["overlap_gap"], fold_case=case["fold"], assigned=names[0],
+                                      unassigned=names[1], bed=names[2])
+            assert drain() == want[0]
+        assert (read(names[1]), read(names[2])) == want[1:3]
+        assert res["lead_strip"].tolist() == want[3]["lead_strip"].tolist() and res["n_unassigned"] == want[3]["n_unassigned"]
 
 
 def test_refusals_write_nothing(tmp_path):
