@@ -30,6 +30,20 @@ constexpr uint32_t BS_EDGE_WORDS = 4100;    // a padded copy of a chunk's words:
 constexpr uint32_t BS_OUT_WORDS = 2048;     // u32 words of OUT per chunk
 constexpr uint32_t BS_OUT_PAD = 4;          // words in front of OUT[0] (slot 0 of the first lane writes OUT[-1])
 
+// The threshold as k_hash_bs takes it.  The test accepts the k-mers whose top-plane sum St (formed without the carry from below, so
+// it may be one short) lies in [-2, tt] mod 2^planes, and the kernel takes tt itself.  A stream generated with the carry-in
+// (gen/bs_gen.py --carry-in: HASH_BS_CARRY_IN, not the shipped one) accepts [-1, tt]: it adds one in its adder and compares St + 1
+// with tt + 1; from tt = 2^planes - 2 on every sum passes.  (Gen.kernel_tt)
+inline uint32_t bs_kernel_tt(uint32_t tt)
+{
+#if HASH_BS_CARRY_IN
+    const uint32_t top = (1u << HASH_BS_PLANES) - 1u;
+    return tt < top ? tt + 1u : top;
+#else
+    return tt;
+#endif
+}
+
 // The filter.  Blocks of 256 threads = one wave per SIMD; the grid is sized for TWO waves per SIMD (an even number of waves
 // per SIMD issues at 2.05 cycles per instruction, an odd one at 2.5-2.7: profiles/ubench), every wave takes the chunks
 // c0, c0 + stride, ...  The body is generated (gen/bs_gen.py) and owns v8..v247 and s36..s87; the few values around it
@@ -37,7 +51,7 @@ constexpr uint32_t BS_OUT_PAD = 4;          // words in front of OUT[0] (slot 0 
 // more words lie in front of it).
 __global__ __launch_bounds__(256) void k_hash_bs(const uint32_t *__restrict__ packed, const uint32_t *__restrict__ head,
                                                  const uint32_t *__restrict__ tail, uint32_t *__restrict__ OUT, uint32_t c_lo,
-                                                 uint32_t c_hi, uint32_t tt, uint32_t c_tail)
+                                                 uint32_t c_hi, uint32_t tt /* bs_kernel_tt(tt) */, uint32_t c_tail)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));

@@ -46,6 +46,19 @@ v_add_u32) into position order and go out as a plain bitmap, one bit per base po
 The words of the next chunk are requested into the registers of the current one as soon as the steps have read them (a load
 fills the planes of steps k and 16 + k: it goes out after step 16 + k).
 
+The test and what it reads.  The test of productive step t (n = 32 + t) adds the top B_PLANES = 14 planes of the two rings,
+FP[(j - n) % 31] + RP[(j + n) % 31] for j = 17 .. 30, without the carry from below, and accepts the sums St in [-2, tt] mod 2^14:
+St <= tt by a bit-sliced compare from the lowest plane up, -1 because the unknown carry may turn all-ones into 0, -2 because the
+all-ones chain beside the compare leaves the lowest plane out.  (Gen(carry_in=True) / --carry-in takes the unknown carry into
+the adder instead -- lowest plane s = ~(f ^ r), cy = f | r, compare against tt + 1 -- and needs no chain: 480 instructions
+fewer, [-1, tt]; measured in round 10 and not shipped, profiles/r10/filter_liveness_ab.txt.)
+So a test reads 14 of the 31 registers of each strand, and over a chunk every register is read by 14 or 15 of the 32 tests
+(Gen.reads).  Ring terms that no test reads are not made: the term of a base that comes in at warm-up step n and the term with
+which it leaves in the roll of productive step n are the same function of that base in a given register (rotl31^32 = rotl31), so
+where no test reads the register in between both are left out; a roll writes nothing into a register that no later test
+reads; the first term a register receives in a chunk writes it.  Per chunk: 7 349 VALU instructions, 3 164 of them v_bitop3_b32
+(7 840 / 3 706 with every term made, --ablate allterms: the same bitmap); making the planes is 1 670 of them, transposing the results 736.
+
 The same instruction list is (1) printed as gfx950 assembly for one inline-asm block with fixed registers (the chunk loop
 included) and (2) executed by a numpy model (class VM): tests/test_bs_gen_cpu.py runs the model against the direct ntHash
 formula, so renaming, truth tables and address arithmetic are checked without a GPU.
@@ -235,14 +248,20 @@ S_RS = 92
 
 
 class Gen:
-    def __init__(self, k=32, b_planes=B_PLANES, ablate=(), lds16=(), perm16=()):
+    def __init__(self, k=32, b_planes=B_PLANES, ablate=(), lds16=(), perm16=(), carry_in=False):
         """ablate (timing experiments only, tools/bs_ablate.sh -- the results are wrong on purpose): 'loads' = no vector loads in the
-        chunk loop (every chunk works on the first one's words) and no waits for them, 'stores' = no result stores"""
+        chunk loop (every chunk works on the first one's words) and no waits for them, 'stores' = no result stores.
+        Streams that the shipped one replaced, with correct results (each can be generated and timed on its own): 'nowarmpairs' = one
+        warm-up step per pass over the ring, 'allterms' = every ring register gets every term, read or not (the bitmap is the same).
+        carry_in (measured and not shipped, profiles/r10/filter_liveness_ab.txt): the wrap test as a carry into the adder, 480
+        instructions fewer; accepts [-1, tt] instead of [-2, tt] and takes its threshold as kernel_tt(tt)"""
         assert k == 32, "strips of 32 k-mers: k = 32 only (other k: k_hash_sparse)"
         self.ablate = set(ablate)
         self.lds16 = set(lds16) if not isinstance(lds16, bool) else ({'in', 'out'} if lds16 else set())
         self.perm16 = set(perm16)
         self.warm_pairs = 'nowarmpairs' not in self.ablate
+        self.live_terms = 'allterms' not in self.ablate    # ring terms that no test reads are left out ('allterms': every one is made)
+        self.carry_in = bool(carry_in)                     # the wrap test as a carry into the adder instead of the all-ones chain
         self.lds_slot = 0
         self.k = k
         self.b = b_planes
@@ -267,6 +286,7 @@ class Gen:
         self.le, self.ones = f"v{X0 + 44}", f"v{X0 + 45}"
         self.TT = [f"v{X0 + 48 + i}" for i in range(4)]  # temporaries of the transpose, one per bank
         self.neg = {}
+        self.started = set()   # ring registers that the chunk has written
 
     def e(self, *t):
         self.ins.append(t)
@@ -294,30 +314,51 @@ class Gen:
         e('xor', m['c2'], b1, m['a'])
         return m
 
-    def plane_update(self, dst, tvA, mA, tvB, mB, first=False):
-        """dst ^= A(out) ^ B(in)   (tvA None: no outgoing base; first: dst is zero before).  The constant terms are not
-        computed: self.neg[dst] says whether the register holds the complement of the logical plane; whoever reads the
-        plane folds the flag into its truth table."""
+    def plane_update(self, dst, terms):
+        """dst ^= the xor of `terms`, a list of at most two (truth vector, masks of the base it is a function of).  The first
+        term(s) a register receives in a chunk write it (what the chunk before left there is not read), whichever pass that is.
+        The constant terms are not computed: self.neg[dst] says whether the register holds the complement of the logical
+        plane; whoever reads the plane folds the flag into its truth table.  A term that the caller leaves out leaves its
+        constant out with it: this is the only place that touches the flags."""
         e = self.e
-        sa, ca = norm(tvA) if tvA is not None else (None, 0)
-        sb, cb = norm(tvB)
-        c = ca ^ cb
-        ra = mA[sa] if sa else None
-        rb = mB[sb] if sb else None
-        if first:
-            if ra is not None and rb is not None:
-                e('xor', dst, ra, rb)
+        if not terms:
+            return
+        regs, c = [], 0
+        for tv, m in terms:
+            sel, c1 = norm(tv)
+            c ^= c1
+            if sel:
+                regs.append(m[sel])
+        if dst not in self.started:
+            self.started.add(dst)
+            if len(regs) == 2:
+                e('xor', dst, regs[0], regs[1])
             else:
-                e('mov', dst, ra or rb or 0)
+                e('mov', dst, regs[0] if regs else 0)
             self.neg[dst] = c
             return
         self.neg[dst] ^= c
-        if ra is None and rb is None:
-            pass
-        elif ra is None or rb is None:
-            e('xor', dst, dst, ra or rb)
-        else:
-            e('bitop3', dst, dst, ra, rb, 0x96)
+        if len(regs) == 1:
+            e('xor', dst, dst, regs[0])
+        elif len(regs) == 2:
+            e('bitop3', dst, dst, regs[0], regs[1], 0x96)
+
+    def reads(self):
+        """(rf, rr): per ring register r of the forward / reverse strand, the set of productive steps whose test reads it.  The
+        test of step t (n = 32 + t) adds the planes j = 31 - b .. 30: FP[(j - n) % 31] and RP[(j + n) % 31]."""
+        rf = [set() for _ in range(RING)]
+        rr = [set() for _ in range(RING)]
+        for t in range(32):
+            n = 32 + t
+            for j in range(RING - self.b, RING):
+                rf[(j - n) % RING].add(t)
+                rr[(j + n) % RING].add(t)
+        return rf, rr
+
+    def kernel_tt(self, tt):
+        """the threshold as the generated code takes it (operand %[tt]; VM does the same): with the carry-in the adder forms
+        St + 1, so the compare is against tt + 1, and every sum passes from tt = 2^b - 2 on"""
+        return min(tt + 1, (1 << self.b) - 1) if self.carry_in else tt
 
     def o_stream(self, t, dst=None):
         """dst[0], dst[1] (default: A) <- the two bit planes of the outgoing base of step t: W[t] moved up by one slot, bit t of
@@ -345,17 +386,30 @@ class Gen:
         # ---- warm-up: steps n = 0..31: the slot's own strip, i.e. the o-stream (W shifted up by one slot)
         # Two steps per pass over the ring: a roll has room for two masks (the productive steps' outgoing and incoming base),
         # the warm-up has no outgoing base, so steps n and n + 1 share one instruction per plane (masks of n in the A set,
-        # of n + 1 in the B set, which nothing else uses before the first productive step).  The first pair writes the ring
-        # (dst = m1 ^ m2), the others add to it.
+        # of n + 1 in the B set, which nothing else uses before the first productive step).  A pair of which one term is left is a
+        # two-source xor, one with none disappears; the first term(s) of a register write it (plane_update).
+        # Terms that no test reads are not made.  A base that comes in at warm-up step n goes out in the roll of productive step
+        # n, and in one register the two terms are the same function of it (fo[j + 1] == fi[j], ro[j - 1] == ri[j], asserted
+        # below): if no test reads register r in between, i.e. at a step <= n, neither is made.  A base that comes in with the
+        # roll of step t stays: its term is needed iff a test after t reads r.  (live[r]: the steps that read r.)
+        for j in range(RING):
+            assert self.fo[(j + 1) % RING] == self.fi[j] and self.ro[(j - 1) % RING] == self.ri[j]
+        every = set(range(32))
+        lf, lr = self.reads() if self.live_terms else ([every] * RING, [every] * RING)
+        self.started = set()
+
+        def warm_terms(live, tv, n_, m_):
+            return [(tv, m_)] if min(live) <= n_ else []
+
         n = 0
         while n < 32:
             if not self.warm_pairs:
                 self.o_stream(n)
                 m1 = self.masks(A)
                 for r in range(31):
-                    self.plane_update(FP[r], None, None, self.fi[(r + n + 1) % 31], m1, first=(n == 0))
+                    self.plane_update(FP[r], warm_terms(lf[r], self.fi[(r + n + 1) % 31], n, m1))
                 for r in range(31):
-                    self.plane_update(RP[r], None, None, self.ri[(r - n) % 31], m1, first=(n == 0))
+                    self.plane_update(RP[r], warm_terms(lr[r], self.ri[(r - n) % 31], n, m1))
                 n += 1
                 continue
             self.o_stream(n)
@@ -363,9 +417,11 @@ class Gen:
             self.o_stream(n + 1, B)
             m2 = self.masks(B)
             for r in range(31):
-                self.plane_update(FP[r], self.fi[(r + n + 1) % 31], m1, self.fi[(r + n + 2) % 31], m2, first=(n == 0))
+                self.plane_update(FP[r], warm_terms(lf[r], self.fi[(r + n + 1) % 31], n, m1) +
+                                  warm_terms(lf[r], self.fi[(r + n + 2) % 31], n + 1, m2))
             for r in range(31):
-                self.plane_update(RP[r], self.ri[(r - n) % 31], m1, self.ri[(r - n - 1) % 31], m2, first=(n == 0))
+                self.plane_update(RP[r], warm_terms(lr[r], self.ri[(r - n) % 31], n, m1) +
+                                  warm_terms(lr[r], self.ri[(r - n - 1) % 31], n + 1, m2))
             n += 2
         # ---- productive steps t = 0..31 (n = 32 + t): test the k-mer, then roll
         s, cy, le, ones = self.s, self.cy, self.le, self.ones
@@ -385,32 +441,56 @@ class Gen:
                 mB = self.masks(B)
             # test: top b planes of F + R.  s (sum plane), cy (carry), le, ones hold true values; the planes' complement
             # flags go into the truth tables.  Banks: f 0, r 1, cy 2, s 3, le 0, ones 1.
+            # The carry from below is unknown, so the sum St of the top planes may be one short: St = -1 must pass
+            # (it may be 0).  carry_in: the adder takes a carry of one into its lowest plane (s = ~(f ^ r), cy = f | r) and the compare is
+            # against tt + 1 (kernel_tt): St + 1 <= tt + 1 accepts St in [-1, tt].  The first compare needs no le before it
+            # (le = ~s | Cm), the last one writes the step's result.
+            # Without it (the shipped stream): St <= tt, or all planes but the lowest are ones: St in [-2, tt].
             jlo = 31 - b
-            e('mov', le, -1)
+            assert b >= 2
+            if not self.carry_in:
+                e('mov', le, -1)
             for j in range(jlo, 31):
                 f, r = FP[(j - n) % 31], RP[(j + n) % 31]
                 nf, nr = self.neg[f], self.neg[r]
+                idx = j - jlo
                 if j == jlo:  # (third source: ignored by the truth table)
-                    e('bitop3', s, f, r, cy, self.tt3(lambda a, b2, c: a ^ b2, nf, nr, 0))
-                    e('bitop3', cy, f, r, cy, self.tt3(lambda a, b2, c: a & b2, nf, nr, 0))
+                    if self.carry_in:
+                        e('bitop3', s, f, r, cy, self.tt3(lambda a, b2, c: a ^ b2 ^ 1, nf, nr, 0))
+                        e('bitop3', cy, f, r, cy, self.tt3(lambda a, b2, c: a | b2, nf, nr, 0))
+                    else:
+                        e('bitop3', s, f, r, cy, self.tt3(lambda a, b2, c: a ^ b2, nf, nr, 0))
+                        e('bitop3', cy, f, r, cy, self.tt3(lambda a, b2, c: a & b2, nf, nr, 0))
                 else:
                     e('bitop3', s, f, r, cy, self.tt3(lambda a, b2, c: a ^ b2 ^ c, nf, nr, 0))
                     if j < 30:
                         e('bitop3', cy, f, r, cy, self.tt3(lambda a, b2, c: (a & b2) | (a & c) | (b2 & c), nf, nr, 0))
-                e('bitop3', le, s, le, f"s{S_CM + (j - jlo)}", 0x8E)
-                idx = j - jlo  # all-ones over planes jlo+1 .. 30
-                if idx == 1:
+                cm = f"s{S_CM + idx}"
+                if self.carry_in:
+                    dst = self.M[t] if j == 30 else le
+                    if idx == 0:  # (second source: ignored by the truth table)
+                        e('bitop3', dst, s, le, cm, self.tt3(lambda a, b2, c: (a ^ 1) | c))
+                    else:
+                        e('bitop3', dst, s, le, cm, 0x8E)
+                    continue
+                e('bitop3', le, s, le, cm, 0x8E)
+                if idx == 1:  # all-ones over planes jlo+1 .. 30
                     e('mov', ones, s)
                 elif idx >= 2:
                     e('and', ones, ones, s)
-            e('or', self.M[t], le, ones)
+            if not self.carry_in:
+                e('or', self.M[t], le, ones)
             if t < 31:
+                def roll_terms(live, tv_out, tv_in):
+                    if max(live) <= t:   # no test reads the register any more
+                        return []
+                    return ([(tv_out, mA)] if min(live) <= t else []) + [(tv_in, mB)]   # (out-term: iff its in-term was made)
                 for r in range(31):
                     jf = (r + n + 1) % 31
-                    self.plane_update(FP[r], self.fo[jf], mA, self.fi[jf], mB)
+                    self.plane_update(FP[r], roll_terms(lf[r], self.fo[jf], self.fi[jf]))
                 for r in range(31):
                     jr = (r - n) % 31
-                    self.plane_update(RP[r], self.ro[jr], mA, self.ri[jr], mB)
+                    self.plane_update(RP[r], roll_terms(lr[r], self.ro[jr], self.ri[jr]))
         self.transpose_out()
         # M[s] = the 32 positions of strip 32 lane + s - 1: slots 1..31 at bytes 0..123 of the lane's 128, slot 0 in front.
         # They stay in their registers (nothing touches M before the next chunk's first productive step) and are stored by
@@ -702,7 +782,8 @@ class VM:
         self.packed = packed
         self.c, self.cn = c, c_next
         self.vr = {}
-        self.sr = {S_CM + i: (0xFFFFFFFF if (tt >> i) & 1 else 0) for i in range(B_PLANES)}
+        self.tt = tt     # the threshold of reference_bits; run() converts it to what the stream takes (Gen.kernel_tt)
+        self.sr = {}
         self.sr.update({S_M16: 0x0000FFFF, S_M8: 0x00FF00FF, S_M4: 0x0F0F0F0F, S_M2: 0x33333333, S_M1: 0x55555555,
                         S_PA: 0x05040100, S_PB: 0x07060302})
         self.out = np.zeros(2048 + 1, dtype=np.uint32)  # word index + 1 (slot 0 of lane 0 lies in front of the chunk)
@@ -733,6 +814,8 @@ class VM:
 
     def run(self, g):
         U = np.uint32
+        ktt = g.kernel_tt(self.tt)
+        self.sr.update({S_CM + i: (0xFFFFFFFF if (ktt >> i) & 1 else 0) for i in range(B_PLANES)})
         for k in range(16):
             for j, wds in enumerate(self.lane_words(self.c, k)):
                 self.vr[f"v{W0 + 4 * k + j}"] = wds
@@ -815,9 +898,12 @@ def pack_chunks(codes, n_chunks):
     return (codes.reshape(-1, 16) << sh).sum(axis=1, dtype=np.uint32).reshape(n_chunks, 4096)
 
 
-def reference_bits(codes, k, tt, b_planes=B_PLANES):
+def reference_bits(codes, k, tt, b_planes=B_PLANES, carry_in=False):
     """codes: base codes (0..3) of n + k - 1 bases -> bool[n]: the ring test of the k-mer starting at each position.
-    St = top b bits of (F + R) mod 2^31 without any carry from below; accepted iff St in [-2, tt] (mod 2^b)."""
+    St = top b bits of (F + R) mod 2^31 without any carry from below; accepted iff St in [-2, tt] (mod 2^b).  The true top-b sum
+    is St or St + 1 (top31(hash) = F + R + c, c in {0, 1}, and the carry out of the low 31 - b bits of that is again 0 or 1), so
+    St = -1 may stand for 0 and must pass; -2 passes because the all-ones chain leaves the lowest plane out.
+    carry_in=True: the set of a stream generated with carry_in, [-1, tt], and every St once tt >= 2^b - 2."""
     codes = np.asarray(codes, dtype=np.int64)
     n = len(codes) - k + 1
     tf = np.array([top31(SEED[c]) for c in range(4)], dtype=np.uint64)
@@ -838,7 +924,10 @@ def reference_bits(codes, k, tt, b_planes=B_PLANES):
         R ^= rot(tr[c], j)
     low = 31 - b_planes
     St = ((F >> np.uint64(low)) + (R >> np.uint64(low))) & np.uint64((1 << b_planes) - 1)
-    return (St <= np.uint64(tt)) | (St >= np.uint64((1 << b_planes) - 2))
+    top = (1 << b_planes) - 1
+    if not carry_in:
+        return (St <= np.uint64(tt)) | (St >= np.uint64(top - 1))
+    return ((St + np.uint64(1)) & np.uint64(top)) <= np.uint64(min(tt + 1, top))
 
 
 def out_position(c, t, lane, s):
@@ -846,8 +935,8 @@ def out_position(c, t, lane, s):
     return c * CHUNK + (32 * lane + s - 1) * 32 + t
 
 
-def emit_inc(path, k, ablate=(), lds16=(), perm16=()):
-    g = Gen(k, ablate=ablate, lds16=lds16, perm16=perm16)
+def emit_inc(path, k, ablate=(), lds16=(), perm16=(), carry_in=False):
+    g = Gen(k, ablate=ablate, lds16=lds16, perm16=perm16, carry_in=carry_in)
     lines = g.asm()
     n_valu = sum(1 for i in g.ins if i[0] in ('xor', 'and', 'or', 'mov', 'bitop3', 'add', 'lshr', 'perm'))
     with open(path, 'w') as fh:
@@ -857,6 +946,7 @@ def emit_inc(path, k, ablate=(), lds16=(), perm16=()):
         fh.write(f"#define HASH_BS_VGPR_END {VEND}\n")
         fh.write(f"#define HASH_BS_VALU_PER_CHUNK {n_valu}\n")
         fh.write(f"#define HASH_BS_PLANES {B_PLANES}\n")
+        fh.write(f"#define HASH_BS_CARRY_IN {int(g.carry_in)}  // 1: operand [tt] is min(tt + 1, 2^planes - 1) (bs_kernels.h: bs_kernel_tt)\n")
         fh.write(f"#define HASH_BS_LDS_PER_WAVE {18 * 1024 if LDSLOADS_ABLATION else LDS_SLOTS * LDS_SLOT if g.lds16 else 0}\n")
         fh.write("#define HASH_BS_ASM \\\n")
         for ln in lines:
@@ -870,13 +960,14 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('-k', type=int, default=32)
     ap.add_argument('-o', default='hash_bs_k32.inc')
-    ap.add_argument('--ablate', default='', help="comma-separated: loads, stores, coalesced (timing experiments: tools/bs_ablate.sh; coalesced = every load's 64 lanes read 1 KB in a row, wrong words)")
+    ap.add_argument('--ablate', default='', help="comma-separated: loads, stores, coalesced (timing experiments: tools/bs_ablate.sh; coalesced = every load's 64 lanes read 1 KB in a row, wrong words); nowarmpairs, allterms (correct streams that the shipped one replaced: see Gen)")
     ap.add_argument('--perm16', default='', help="which transposes' stage 16 is two v_perm_b32 and a move per pair instead of twenty fast-class instructions: in, out, in,out")
     ap.add_argument('--lds16', default='', help="which transposes' stage 16 goes through LDS instead of registers: in, out, in,out (round 6: 944 VALU instructions fewer per chunk for 288 LDS operations, and no faster -- profiles/r06/filter_lds16_ab.txt)")
+    ap.add_argument('--carry-in', action='store_true', help="the wrap test as a carry into the adder: 480 VALU instructions fewer per chunk, accepts [-1, tt] (measured in round 10 and not shipped: inside the step's run-to-run spread -- profiles/r10/filter_liveness_ab.txt)")
     a = ap.parse_args()
     COALESCED_ABLATION = 'coalesced' in a.ablate.split(',')
     LDSLOADS_ABLATION = 'ldsloads' in a.ablate.split(',')
     COSTORES_ABLATION = 'costores' in a.ablate.split(',')
     n, nv = emit_inc(a.o, a.k, tuple(x for x in a.ablate.split(',') if x), lds16=tuple(x for x in a.lds16.split(',') if x),
-                     perm16=tuple(x for x in a.perm16.split(',') if x))
+                     perm16=tuple(x for x in a.perm16.split(',') if x), carry_in=a.carry_in)
     print(f"{a.o}: {n} lines, {nv} VALU per chunk", file=sys.stderr)

@@ -1185,7 +1185,7 @@ int bs_edges(mxg_handle *h, Assembly *a, hipStream_t st)
 int bs_hash(mxg_handle *h, Assembly *a, uint32_t tau_hi, hipStream_t st)
 {
     // tau = T * 2^33 with T = tau_hi / 2 on the top ring; the filter compares the top HASH_BS_PLANES bits of F + R with
-    // tt = (T - 1) >> (31 - planes) (gen/bs_gen.py: reference_bits)
+    // tt = (T - 1) >> (31 - planes) (gen/bs_gen.py: reference_bits); the kernel takes it as bs_kernel_tt(tt)
     const uint32_t T = tau_hi >> 1;
     const uint32_t tt = T ? (T - 1u) >> (31 - HASH_BS_PLANES) : 0u;
     // (alone on the GPU 1024 blocks over the 512 resident ones even out the tail: 478 us against 500 us at 3 Gbp; beside the other
@@ -1194,7 +1194,7 @@ int bs_hash(mxg_handle *h, Assembly *a, uint32_t tau_hi, hipStream_t st)
     const uint32_t blocks = std::min<uint32_t>((uint32_t)env_blocks, (a->bs_chunks + 3u) / 4u);  // two waves per SIMD are resident (see k_hash_bs)
     const uint32_t *head = a->d_bs_tail.as<uint32_t>() + 2, *tail = a->bs_chunks > 1 ? head + BS_EDGE_WORDS : head;
     hipLaunchKernelGGL(k_hash_bs, dim3(blocks), dim3(256), 0, st, a->d_packed, head, tail, a->d_bs_out.as<uint32_t>() + BS_OUT_PAD, 0u,
-                       a->bs_chunks, tt, a->bs_chunks - 1u);
+                       a->bs_chunks, bs_kernel_tt(tt), a->bs_chunks - 1u);
     MXG_HIP(h, hipGetLastError());
     return MXG_OK;
 }

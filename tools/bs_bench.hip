@@ -26,6 +26,16 @@ static uint32_t rotl31(uint32_t x, unsigned n)
     return n ? ((x << n) | (x >> (31 - n))) & 0x7FFFFFFFu : x;
 }
 static inline uint32_t base_at(const std::vector<uint32_t> &w, uint64_t p) { return (p >> 4) < w.size() ? (w[p >> 4] >> (2 * (p & 15))) & 3u : 0u; }
+// St = the sum of the top b planes without the carry from below (the true sum is St or St + 1), top = 2^b - 1: the shipped stream
+// accepts St in [-2, tt] mod 2^b; a stream generated with --carry-in accepts [-1, tt], and everything from tt = 2^b - 2 on
+static bool accept(uint32_t St, uint32_t tt, uint32_t top)
+{
+#if HASH_BS_CARRY_IN
+    return ((St + 1u) & top) <= (tt < top ? tt + 1u : top);
+#else
+    return St <= tt || St >= top - 1u;
+#endif
+}
 static bool ref_bit(const std::vector<uint32_t> &w, uint64_t p, uint32_t tt, int b)
 {
     uint32_t F = 0, R = 0;
@@ -34,8 +44,8 @@ static bool ref_bit(const std::vector<uint32_t> &w, uint64_t p, uint32_t tt, int
         F ^= rotl31((uint32_t)(SEED[c] >> 33), 31 - j);
         R ^= rotl31((uint32_t)(SEED[3 - c] >> 33), j);
     }
-    const uint32_t low = 31 - b, St = ((F >> low) + (R >> low)) & ((1u << b) - 1u);
-    return St <= tt || St >= (1u << b) - 2u;
+    const uint32_t low = 31 - b, top = (1u << b) - 1u, St = ((F >> low) + (R >> low)) & top;
+    return accept(St, tt, top);
 }
 
 // one wave that sleeps `iters` times 127 x 64 shader clocks and reports how long that took on the constant 100 MHz counter: the
@@ -52,6 +62,7 @@ int main(int argc, char **argv)
 {
     const double mbp = argc > 1 ? atof(argv[1]) : 3000.0;
     const uint32_t tt = argc > 2 ? (uint32_t)atoi(argv[2]) : 164u;
+    const uint32_t ktt = mxg::bs_kernel_tt(tt);
     const uint32_t n_chunks = (uint32_t)(mbp * 1e6 / 65536.0) + 1;
     const uint64_t n_words = (uint64_t)n_chunks * 4096 - 1000;  // (the last chunk is ragged)
     std::vector<uint32_t> hp(n_words);
@@ -73,7 +84,7 @@ int main(int argc, char **argv)
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    hipLaunchKernelGGL(mxg::k_hash_bs, dim3(512), dim3(256), 0, 0, dp, dHead, dTail, dO, 0u, n_chunks, tt, n_chunks - 1);
+    hipLaunchKernelGGL(mxg::k_hash_bs, dim3(512), dim3(256), 0, 0, dp, dHead, dTail, dO, 0u, n_chunks, ktt, n_chunks - 1);
     CK(hipDeviceSynchronize());
     CK(hipGetLastError());
     // ---- verify chunks 0, 1, the middle one and the last one
@@ -105,7 +116,7 @@ int main(int argc, char **argv)
             hipLaunchKernelGGL(k_clock_probe, dim3(8), dim3(64), 0, s2, dW, iters);
             if (with)
                 for (int r = 0; r < 12; ++r)
-                    hipLaunchKernelGGL(mxg::k_hash_bs, dim3(512), dim3(256), 0, 0, dp, dHead, dTail, dO, 0u, n_chunks, tt, n_chunks - 1);
+                    hipLaunchKernelGGL(mxg::k_hash_bs, dim3(512), dim3(256), 0, 0, dp, dHead, dTail, dO, 0u, n_chunks, ktt, n_chunks - 1);
             CK(hipDeviceSynchronize());
             CK(hipMemcpy(hW, dW, sizeof(hW), hipMemcpyDeviceToHost));
             double lo = 1e30, hi = 0;
@@ -118,11 +129,11 @@ int main(int argc, char **argv)
         }
     }
     for (int blocks : {256, 512, 768, 1024}) {
-        hipLaunchKernelGGL(mxg::k_hash_bs, dim3(blocks), dim3(256), 0, 0, dp, dHead, dTail, dO, 0u, n_chunks, tt, n_chunks - 1);
+        hipLaunchKernelGGL(mxg::k_hash_bs, dim3(blocks), dim3(256), 0, 0, dp, dHead, dTail, dO, 0u, n_chunks, ktt, n_chunks - 1);
         CK(hipDeviceSynchronize());
         CK(hipEventRecord(e0));
         const int reps = 5;
-        for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(mxg::k_hash_bs, dim3(blocks), dim3(256), 0, 0, dp, dHead, dTail, dO, 0u, n_chunks, tt, n_chunks - 1);
+        for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(mxg::k_hash_bs, dim3(blocks), dim3(256), 0, 0, dp, dHead, dTail, dO, 0u, n_chunks, ktt, n_chunks - 1);
         CK(hipEventRecord(e1));
         CK(hipEventSynchronize(e1));
         float ms = 0;
