@@ -487,6 +487,12 @@ int mxg_overlap_cuts(mxg_handle *h, int assembly, uint32_t k, uint32_t w, const 
    of text each, the 28-byte end marker behind the last) of exactly the bytes the call writes without the flag, deflated on the
    device (literals only: about 2.25 bits a base); the BED, the strips and every return value are as without it. */
 #define MXG_SCAF_BGZF 0x2u
+/* MXG_SCAF_FAI: beside assigned_fa write <assigned_fa>.fai and beside unassigned_fa, when given, <unassigned_fa>.fai: the index
+   `samtools faidx` makes of the file (the reference's `%.fai: %` rule, ntJoin:152-153, 207-208; format under mxg_write_fai).  Every
+   record of these files is one line: "name\tlen\toffset\tlen\tlen+1\n", name = ntJoin<p> or id:start-end, len = the bases written,
+   offset = where they start in the (uncompressed) file; an interval dropped from the FASTA has no line.  With MXG_SCAF_BGZF also
+   <...>.gzi for each (format under mxg_write_fai).  FASTA, BED, strips and return values are as without the flag. */
+#define MXG_SCAF_FAI 0x4u
 typedef struct mxg_scaffold_node {
     uint32_t record, start, end;       /* [start, end) of the record */
     uint32_t gap_size;                 /* Ns behind the node (PathNode.gap_size) */
@@ -504,6 +510,26 @@ int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *no
    (bin/ntjoin_assemble.py:379-404) recomputes from the text of every record (len_diff_start, len_diff_end).  The arrays are the
    handle's and hold until its next mxg_write_scaffolds. */
 int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals);
+
+/* ---- next row (f9): FASTA indexes -----------------------------------------------------------------------------------------------
+   <fasta>.fai as `samtools faidx` writes it (the reference's `%.fai: %` rule, ntJoin:152-153, 207-208: `$(target).fai` and one per
+   reference), from the text the handle holds.  One line per record, in file order: "NAME\tLENGTH\tOFFSET\tLINEBASES\tLINEWIDTH\n".
+   With T = the record's sequence text (from behind its header line to the next header's '>' or the end of the text) split at '\n':
+   NAME = the record's id; OFFSET = where T starts (for BGZF input: in the inflated text); LINEWIDTH = bytes of the first line with its
+   line end ("\n" or "\r\n"; the last line of the file may have none); LINEBASES = its bytes in 0x21 .. 0x7E; LENGTH = the bytes of T
+   in 0x21 .. 0x7E; empty T: "NAME\t0\tOFFSET\t0\t0".  A later record of a name already seen is left out (one line on stderr).
+   Accepted: every line but the last non-empty one has exactly the first line's bytes; the last non-empty line has 1 .. LINEBASES
+   bases and the same kind of line end, or none at the end of the text; empty lines follow only behind the last record of the file;
+   every byte of a line is in 0x21 .. 0x7E but a '\r' directly in front of the '\n'.  Anything else is MXG_EINVAL (samtools'
+   "different line length in sequence", taken conservatively): nothing is left at fai_path, and the message names the record and the
+   byte offset of the first offending line.
+   gzi_path (may be NULL): the .gzi of a BGZF input -- little-endian, a uint64 count N, then N pairs {compressed offset, uncompressed
+   offset}, one for every member that holds text except the first, in file order.
+   MXG_EINVAL also: an assembly whose text the handle does not hold on the device (TSV / side-car / minimizer / packed input,
+   MXG_HOST_INGEST=1, plain gzip, a pipe, MXG_FLAG_DROP_SEQ, text released by a one-shot handle, a shard or pieces of a file);
+   gzi_path for an assembly that did not come from BGZF.  MXG_FAI_WIN: bytes of the index formed per window (default and at most
+   64 Mi). */
+int mxg_write_fai(mxg_handle *h, int assembly, const char *fai_path, const char *gzi_path);
 
 /* The n bytes at data (host memory) written to `path` as a BGZF file, deflated on the device as the scaffold files of
    MXG_SCAF_BGZF are: member j holds bytes [j P, j P + P) with P = 65 280 (the environment's MXG_BGZF_PAYLOAD, 1 .. 65 280, if set),

@@ -9,6 +9,9 @@ reference is loaded from its TSV when that file exists and sketched from <fasta>
 graph -> find_paths -> format_paths -> adjust_paths -> trim_overlaps (--overlap) -> print_scaffolds.  Written, under the
 reference's names: <p>.mx.dot, <p>.path, <p>.agp (--agp), <fasta>.k<k>.w<w>.n<n>.assigned.scaffolds.fa,
 ...unassigned.scaffolds.fa and <p>.<target tsv>.unassigned.bed.  -t and --btllib_t are accepted and unused.
+--fai: also <fasta>.fai of the target and of every reference sketched from FASTA in this run (what the reference's `%.fai: %` rule
+makes with `samtools faidx`, ntJoin:152-153, 207-208), <fasta>.gzi of a BGZF input, and the .fai (with --gz: and .gzi) of the two
+scaffold files; a reference loaded from its TSV gets a line on stderr instead.
 """
 import os
 import re

@@ -12,6 +12,7 @@ FLAG_DENSE_ONLY, FLAG_DROP_SEQ, FLAG_TIMING, FLAG_TIMING_FINE, FLAG_ONE_SHOT = 0
 MX_UNIQUE, MX_SHARED, MX_INALL = 0x1, 0x2, 0x4
 SCAF_FOLD_CASE = 0x1
 SCAF_BGZF = 0x2
+SCAF_FAI = 0x4
 PATHS_AGP_UNASSIGNED = 0x1
 ABI_VERSION = 3
 
@@ -23,7 +24,7 @@ SYMBOLS = [
     "mxg_record_id", "mxg_record_length", "mxg_num_records", "mxg_assembly_weight",
     "mxg_sketch", "mxg_sketch_graph", "mxg_get_sketch", "mxg_get_sketch_device", "mxg_compute_strands", "mxg_set_sketch_device",
     "mxg_pack_sketch_device", "mxg_set_sketch_gathered", "mxg_set_sketch_gathered_strided", "mxg_write_tsv",
-    "mxg_build_graph", "mxg_get_mx_flags", "mxg_get_graph", "mxg_find_paths", "mxg_path_segments", "mxg_path_segments_mk", "mxg_mk_stats", "mxg_format_paths", "mxg_mk_orientation", "mxg_vertex_hashes", "mxg_overlap_cuts", "mxg_adjust_paths", "mxg_write_scaffolds", "mxg_scaffold_strips", "mxg_bgzf_write", "mxg_write_paths", "mxg_mx_extremes", "mxg_dg_owner_counts", "mxg_dg_pack_items", "mxg_dg_set_items", "mxg_dg_vertices", "mxg_dg_item_results", "mxg_dg_msg_counts", "mxg_dg_pack_msgs", "mxg_dg_edges", "mxg_dg_pack_slots", "mxg_dg_owner_slots", "mxg_dg_slot_results", "mxg_dg_pack_msg_slots", "mxg_dg_edges_slots", "mxg_write_dot", "mxg_write_outputs", "mxg_dot_part_format", "mxg_dot_part_write",
+    "mxg_build_graph", "mxg_get_mx_flags", "mxg_get_graph", "mxg_find_paths", "mxg_path_segments", "mxg_path_segments_mk", "mxg_mk_stats", "mxg_format_paths", "mxg_mk_orientation", "mxg_vertex_hashes", "mxg_overlap_cuts", "mxg_adjust_paths", "mxg_write_scaffolds", "mxg_scaffold_strips", "mxg_bgzf_write", "mxg_write_fai", "mxg_write_paths", "mxg_mx_extremes", "mxg_dg_owner_counts", "mxg_dg_pack_items", "mxg_dg_set_items", "mxg_dg_vertices", "mxg_dg_item_results", "mxg_dg_msg_counts", "mxg_dg_pack_msgs", "mxg_dg_edges", "mxg_dg_pack_slots", "mxg_dg_owner_slots", "mxg_dg_slot_results", "mxg_dg_pack_msg_slots", "mxg_dg_edges_slots", "mxg_write_dot", "mxg_write_outputs", "mxg_dot_part_format", "mxg_dot_part_write",
     "mxg_py_repr_double", "mxg_py_repr_str", "mxg_get_stats", "mxg_reset_timers", "mxg_knobs",
     "mxg_synth_fill_packed_device", "mxg_synth_fill_packed_host", "mxg_synth_write_fasta",
     "mxg_plan_split", "mxg_add_assembly_packed_device_pieces", "mxg_dg_last_shared", "mxg_dg_set_ghosts",
@@ -213,6 +214,7 @@ def load():
     L.mxg_write_scaffolds.argtypes = [vp, i32, vp, vp, u64, i32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp]
     L.mxg_write_paths.argtypes = [vp, i32, vp, vp, u64, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32]
     L.mxg_bgzf_write.argtypes = [vp, vp, u64, C.c_char_p]
+    L.mxg_write_fai.argtypes = [vp, i32, C.c_char_p, C.c_char_p]
     L.mxg_scaffold_strips.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64)]
     L.mxg_mx_extremes.argtypes = [vp, i32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)),
                                   C.POINTER(C.c_uint64)]

@@ -1018,6 +1018,18 @@ int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *no
     }
 }
 
+int mxg_write_fai(mxg_handle *h, int assembly, const char *fai_path, const char *gzi_path)
+{
+    if (!h) return MXG_EINVAL;
+    if (assembly < 0 || (size_t)assembly >= h->asms.size()) return set_err(h, MXG_EINVAL, "mxg_write_fai: no assembly %d", assembly);
+    if (!fai_path) return set_err(h, MXG_EINVAL, "mxg_write_fai: null argument");
+    try {
+        return write_fai(h, h->asms[assembly], assembly, fai_path, gzi_path);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_write_fai");
+    }
+}
+
 int mxg_bgzf_write(mxg_handle *h, const void *data, uint64_t n, const char *path)
 {
     if (!h) return MXG_EINVAL;

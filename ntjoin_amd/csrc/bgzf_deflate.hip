@@ -238,7 +238,8 @@ uint64_t bgzf_window_bytes(uint64_t want, uint32_t tile, uint32_t P)
 // fill, WinBufs, copy_pieces, OutFile::put) in a sequence of its own: the members of a window are deflated and packed on the
 // device behind the fill, the window's head comes over first and says how many bytes to fetch, and the host writes them at the
 // running offset while the device forms the next window.  The end-of-file marker follows the last member.
-int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint32_t P, const WinFill &fill, const char *who)
+int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint32_t P, const WinFill &fill, const char *who,
+                       std::vector<uint64_t> *member_off)
 {
     hipStream_t st = h->stream;
     DevBuf *Z = h->zbuf;
@@ -302,6 +303,13 @@ int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN,
             if (dbg_io) {
                 float t = 0;
                 if (hipEventElapsedTime(&t, ev_t0[b], ev_t1[b]) == hipSuccess) ms += t;
+            }
+            if (member_off) {  // (the .gzi: where the window's members lie in its chain, in front of the next window's scan)
+                const uint32_t m = members_of(c);
+                std::vector<uint32_t> offs(m);
+                MXG_HIP(h, hipMemcpyAsync(offs.data(), d_offs, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+                MXG_HIP(h, hipStreamSynchronize(st));
+                for (uint32_t j = 0; j < m; ++j) member_off->push_back(file_off + offs[j]);
             }
             n_members += members_of(c);
             n_stored += wh.stored;

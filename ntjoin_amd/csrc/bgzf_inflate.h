@@ -32,7 +32,7 @@ struct BgzfMember {    // one non-empty member
     uint32_t in_len;
     uint32_t isize;    // bytes of text, 1 .. 65536
     uint32_t crc;      // CRC-32 of the text
-    uint32_t pad;
+    uint32_t head;     // bytes of the member's header in front of in_off
 };
 
 enum BgzfStatus : uint32_t {
@@ -377,7 +377,7 @@ inline bool bgzf_plan(const unsigned char *p, uint64_t n, BgzfPlan &plan)
         m.crc = le32(at + total - 8);
         m.isize = le32(at + total - 4);
         m.out_off = plan.usz;
-        m.pad = 0;
+        m.head = (uint32_t)(12 + xlen);
         if (m.isize > BGZF_MAX_ISIZE) return false;
         if (m.isize) {
             plan.members.push_back(m);

@@ -627,6 +627,11 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
     a->has_text = false;
     a->text_on_device = true;
     a->text_bytes = tsz;
+    a->from_bgzf = bgzf;
+    for (const BgzfMember &m : plan.members) {
+        a->bgzf_comp_off.push_back(m.in_off - m.head);
+        a->bgzf_text_off.push_back(m.out_off);
+    }
     a->ing_item0.assign(rec_item0.begin(), rec_item0.end());
     if (dbg_io)
         fprintf(stderr, "[mxg] load_fasta_device %s: %.3f s = open + map + text buffer %.3f, first pinned buffer at %.3f, headers + items (beside the "

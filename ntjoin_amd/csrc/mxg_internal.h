@@ -120,6 +120,9 @@ struct Assembly {
     bool flat_text_on_device = false;  // host ingest: Assembly::text copied to d_text by the first mxg_write_scaffolds (no line ends, no index)
     DevBuf d_text, d_ing_items, d_ing_cnt, d_ing_sub, d_ing_pbase, d_ing_item0;
     std::vector<uint64_t> ing_item0;  // [n_records + 1] first tile of every record
+    // the members of a BGZF input that hold text: where each starts in the file and in the text (what its .gzi is made of, fai.hip)
+    bool from_bgzf = false;
+    std::vector<uint64_t> bgzf_comp_off, bgzf_text_off;
     DevBuf d_packed_own;
     const uint32_t *d_packed = nullptr;  // owned (above) or borrowed
     uint64_t packed_words = 0;
@@ -281,6 +284,7 @@ struct mxg_handle {
     std::vector<ScafInterval> scaf_iv;
     int scaf_iv_asm = -1;
     mxg::DevBuf ptbuf[16];  // scratch of pathtext.hip
+    mxg::DevBuf faibuf[16];  // scratch of fai.hip
     mxg::Segments segs;
     mxg::PathNodes nodes;
     mxg::Timers tm;
@@ -437,7 +441,9 @@ int write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint
 // between fill and copy; bgzf_write: host bytes (mxg_bgzf_write)
 uint32_t bgzf_payload(const mxg_handle *h);
 uint64_t bgzf_window_bytes(uint64_t want, uint32_t tile, uint32_t P);
-int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint32_t P, const WinFill &fill, const char *who);
+// (member_off, if given: where every member that holds text starts in the file)
+int bgzf_write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint32_t P, const WinFill &fill, const char *who,
+                       std::vector<uint64_t> *member_off = nullptr);
 int bgzf_write(mxg_handle *h, const void *data, uint64_t n, const char *path);
 int write_dot(mxg_handle *h, const char *path);
 int dot_part_format(mxg_handle *h, uint32_t part, uint32_t n_parts, uint64_t bytes[2]);
@@ -566,6 +572,17 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
 int write_paths(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
                 const uint32_t *lead_strip, const uint32_t *tail_strip, const char *first_line, const char *path_file, const char *agp_file,
                 uint32_t flags);
+// fai.hip: the .fai of a loaded assembly and, for a BGZF input, its .gzi (mxg_write_fai)
+int write_fai(mxg_handle *h, Assembly *a, int assembly, const char *fai_path, const char *gzi_path);
+// ... the .fai of a file mxg_write_scaffolds writes, every record one line: ntJoin<i>, or id:lo-hi of the assembly's record
+struct FaiOutRec {
+    uint64_t len;           // bases written
+    uint32_t header_bytes;  // its header line with the line end
+    uint32_t rec, lo, hi;   // the unassigned interval
+};
+int write_fai_records(mxg_handle *h, const Assembly *a, OutFile &of, const std::vector<FaiOutRec> &recs, bool ntjoin_names);
+// ... and a .gzi: the members that hold text, in file order, each with its place in the file and in the text
+int write_gzi(mxg_handle *h, OutFile &of, const std::vector<uint64_t> &comp_off, const std::vector<uint64_t> &text_off);
 // adjust.hip: relocations, --no_cut and overlapping regions of the given paths (mxg_adjust_paths); fills h->adj_*
 int adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *path_first, uint64_t n_paths, const mxg_adjust_params &p);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm

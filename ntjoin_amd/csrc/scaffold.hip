@@ -211,7 +211,9 @@ struct PieceTable {
 
 // the table's bytes into `of`, window by window
 // (bgzf_P: 0, or the file is a BGZF file of that many text bytes a member, deflated on the device: bgzf_deflate.hip)
-static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint32_t fold, OutFile &of, uint64_t WIN, uint32_t bgzf_P)
+// (member_off, if given: where every BGZF member that holds text starts in the file)
+static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint32_t fold, OutFile &of, uint64_t WIN, uint32_t bgzf_P,
+                          std::vector<uint64_t> *member_off = nullptr)
 {
     hipStream_t st = h->stream;
     DevBuf *B = h->scbuf;
@@ -231,7 +233,7 @@ static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint
         MXG_HIP(h, hipGetLastError());
         return MXG_OK;
     };
-    if (bgzf_P) return bgzf_write_windows(h, of, total, bgzf_window_bytes(WIN, SCAF_TILE, bgzf_P), bgzf_P, fill, who);
+    if (bgzf_P) return bgzf_write_windows(h, of, total, bgzf_window_bytes(WIN, SCAF_TILE, bgzf_P), bgzf_P, fill, who, member_off);
     return write_windows(h, of, total, WIN, 0, fill, who);
 }
 
@@ -377,18 +379,43 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
     const uint64_t WIN = std::max<uint64_t>(SCAF_TILE, std::min<uint64_t>(knob_u64(h, "MXG_SCAF_WIN", PIN_HALF), PIN_HALF) /
                                                            SCAF_TILE * SCAF_TILE);
     const uint32_t bgzf_P = flags & MXG_SCAF_BGZF ? bgzf_payload(h) : 0u;
+    // MXG_SCAF_FAI: <file>.fai beside either FASTA and, for BGZF files, <file>.gzi (fai.hip)
+    const bool with_fai = (flags & MXG_SCAF_FAI) != 0;
+    struct IndexFiles {
+        OutFile fai, gzi;
+        std::vector<FaiOutRec> recs;
+        std::vector<uint64_t> member_off;
+    } ix_fa, ix_ufa;
+    auto open_index = [&](IndexFiles &ix, const char *fasta) -> int {
+        const std::string fai = std::string(fasta) + ".fai", gzi = std::string(fasta) + ".gzi";
+        if (!ix.fai.open(fai.c_str())) return set_err(h, MXG_EIO, "cannot open '%s' for writing", fai.c_str());
+        if (bgzf_P && !ix.gzi.open(gzi.c_str())) return set_err(h, MXG_EIO, "cannot open '%s' for writing", gzi.c_str());
+        return MXG_OK;
+    };
+    // the index of a FASTA written: its rows, and the .gzi from where the members went (member j holds text [j P, j P + P))
+    auto write_index = [&](IndexFiles &ix, bool ntjoin_names) -> int {
+        int rc = write_fai_records(h, a, ix.fai, ix.recs, ntjoin_names);
+        if (rc != MXG_OK || !bgzf_P) return rc;
+        std::vector<uint64_t> text_off(ix.member_off.size());
+        for (size_t j = 0; j < text_off.size(); ++j) text_off[j] = (uint64_t)j * bgzf_P;
+        return write_gzi(h, ix.gzi, ix.member_off, text_off);
+    };
     OutFile fa, ufa, bed;
     if (!fa.open(assigned_fa)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", assigned_fa);
     if (unassigned_fa && !ufa.open(unassigned_fa)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", unassigned_fa);
     if (unassigned_bed && !bed.open(unassigned_bed)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", unassigned_bed);
     int rc;
+    if (with_fai && (rc = open_index(ix_fa, assigned_fa)) != MXG_OK) return rc;
+    if (with_fai && unassigned_fa && (rc = open_index(ix_ufa, unassigned_fa)) != MXG_OK) return rc;
     {
         PieceTable pt;
         pt.pieces.reserve(2 * n_nodes + 2 * n_paths + 1);
         for (uint64_t p = 0; p < n_paths; ++p) {
             const uint64_t lo = path_first[p], hi = path_first[p + 1];
             const uint32_t lead = cnt[2 * p], tail_text = cnt[2 * p + 1];
+            const uint64_t head0 = pt.total;
             pt.literal(">ntJoin" + std::to_string(p) + "\n");
+            const uint64_t seq0 = pt.total;
             for (uint64_t i = lo; i < hi; ++i) {
                 const mxg_scaffold_node &in = nodes[i];
                 uint32_t x = part[i].x, y = part[i].y, fill = part[i].fill;
@@ -404,10 +431,13 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
                 }
                 pt.add(SP_FILL, fill);
             }
+            if (with_fai) ix_fa.recs.push_back(FaiOutRec{pt.total - seq0, (uint32_t)(seq0 - head0), 0u, 0u, 0u});
             pt.literal("\n");
             if (lead_strip) lead_strip[p] = lead;
         }
-        if ((rc = scaf_emit_file(h, t, pt, flags & MXG_SCAF_FOLD_CASE ? 1u : 0u, fa, WIN, bgzf_P)) != MXG_OK) return rc;
+        if ((rc = scaf_emit_file(h, t, pt, flags & MXG_SCAF_FOLD_CASE ? 1u : 0u, fa, WIN, bgzf_P, with_fai ? &ix_fa.member_off : nullptr)) != MXG_OK)
+            return rc;
+        if (with_fai && (rc = write_index(ix_fa, true)) != MXG_OK) return rc;
     }
     uint64_t n_un = 0;
     h->scaf_lead.assign(gaps.size(), 0);  // what mxg_scaffold_strips hands out: per interval of the BED
@@ -422,11 +452,14 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
             if (lead >= len) continue;  // N throughout: in the BED only
             ++n_un;
             if (!unassigned_fa) continue;
+            const uint64_t head0 = pt.total;
             pt.literal(">" + a->recs[iv.rec].id + ":" + std::to_string(iv.lo) + "-" + std::to_string(iv.hi) + "\n");
+            if (with_fai) ix_ufa.recs.push_back(FaiOutRec{(uint64_t)len - lead - tail, (uint32_t)(pt.total - head0), iv.rec, iv.lo, iv.hi});
             pt.add(SP_FWD, len - lead - tail, (uint64_t)iv.lo + lead, iv.rec);
             pt.literal("\n");
         }
-        if (unassigned_fa && (rc = scaf_emit_file(h, t, pt, 0u, ufa, WIN, bgzf_P)) != MXG_OK) return rc;
+        if (unassigned_fa && (rc = scaf_emit_file(h, t, pt, 0u, ufa, WIN, bgzf_P, with_fai ? &ix_ufa.member_off : nullptr)) != MXG_OK) return rc;
+        if (with_fai && unassigned_fa && (rc = write_index(ix_ufa, false)) != MXG_OK) return rc;
     }
     if (want_un) {  // the intervals with their strips: what mxg_write_paths makes the AGP's unassigned lines of
         h->scaf_iv.resize(gaps.size());
@@ -439,8 +472,11 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
     }
     MXG_HIP(h, hipStreamSynchronize(st));
     const bool c_fa = fa.close(), c_ufa = ufa.close(), c_bed = bed.close();
-    if (!(c_fa && c_ufa && c_bed)) return set_err(h, MXG_EIO, "mxg_write_scaffolds: write error while closing the output files");
+    const bool c_fai = ix_fa.fai.close(), c_gzi = ix_fa.gzi.close(), c_ufai = ix_ufa.fai.close(), c_ugzi = ix_ufa.gzi.close();
+    const bool c_ix = c_fai && c_gzi && c_ufai && c_ugzi;
+    if (!(c_fa && c_ufa && c_bed && c_ix)) return set_err(h, MXG_EIO, "mxg_write_scaffolds: write error while closing the output files");
     fa.complete = ufa.complete = bed.complete = true;
+    ix_fa.fai.complete = ix_fa.gzi.complete = ix_ufa.fai.complete = ix_ufa.gzi.complete = true;
     if (n_unassigned) *n_unassigned = n_un;
     return MXG_OK;
 }

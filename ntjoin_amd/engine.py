@@ -461,12 +461,13 @@ class MxEngine:
                               ("end_adjust", "<u4"), ("reverse", "u1"), ("pad", "u1", (3,))])
 
     def write_scaffolds(self, assembly, rows, path_first, overlap_gap=None, fold_case=False, assigned=None, unassigned=None, bed=None,
-                        bgzf=False):
+                        bgzf=False, fai=False):
         """mxg_write_scaffolds: rows = array of SCAFFOLD_NODE (or rows (record, start, end, gap_size, start_adjust, end_adjust,
         reverse)), path_first = n_paths + 1 offsets; overlap_gap=None: the overlap stage is off (the adjustments are not read).
         Writes the scaffold FASTA `assigned` and, when named, the unassigned FASTA and BED -> dict(lead_strip u32[n_paths],
         tail_strip u32[n_paths]: N/n stripped from the scaffolds' ends, n_unassigned: records in the unassigned FASTA).
-        bgzf=True: the two FASTA files are BGZF files of the same bytes, deflated on the device (MXG_SCAF_BGZF)"""
+        bgzf=True: the two FASTA files are BGZF files of the same bytes, deflated on the device (MXG_SCAF_BGZF); fai=True: beside
+        either FASTA its <name>.fai and, with bgzf, its <name>.gzi (MXG_SCAF_FAI)"""
         if assigned is None:
             raise ValueError("write_scaffolds: assigned= names the scaffold FASTA to write")
         nodes = self._scaffold_nodes(rows)
@@ -479,9 +480,16 @@ class MxEngine:
         enc = lambda p: None if p is None else os.fsencode(str(p))  # noqa: E731
         self._check(self._lib.mxg_write_scaffolds(self._h, int(assembly), nodes.ctypes.data, pf.ctypes.data, n_paths,
                                                   -1 if overlap_gap is None else int(overlap_gap),
-                                                  (capi.SCAF_FOLD_CASE if fold_case else 0) | (capi.SCAF_BGZF if bgzf else 0), enc(assigned), enc(unassigned), enc(bed),
+                                                  (capi.SCAF_FOLD_CASE if fold_case else 0) | (capi.SCAF_BGZF if bgzf else 0) | (capi.SCAF_FAI if fai else 0),
+                                                  enc(assigned), enc(unassigned), enc(bed),
                                                   lead.ctypes.data, tail.ctypes.data, C.byref(n_un)))
         return {"lead_strip": lead, "tail_strip": tail, "n_unassigned": int(n_un.value)}
+
+    def write_fai(self, assembly, path, gzi=None):
+        """mxg_write_fai: the index `samtools faidx` makes of the assembly's FASTA, from the text the handle holds, written to `path`;
+        gzi= names the .gzi to write for an assembly that came from a BGZF file"""
+        enc = lambda p: None if p is None else os.fsencode(str(p))  # noqa: E731
+        self._check(self._lib.mxg_write_fai(self._h, int(assembly), enc(path), enc(gzi)))
 
     def bgzf_write(self, data, path):
         """mxg_bgzf_write: the bytes of `data` (bytes, bytearray, or a contiguous uint8 array) written to `path` as a BGZF file,

@@ -367,9 +367,12 @@ class Ntjoin:
     def scaffold(self, lengths=None):
         """main_scaffolder (:751-786) behind load_minimizers_scaffold in one handle: make_minimizer_graph -> find_paths ->
         format_paths -> adjust_paths -> trim_overlaps (when args.overlap) -> print_scaffolds.  Read from args, with ntJoin's
-        defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz.  Returns what
-        print_scaffolds returns (the written files by kind)."""
+        defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz, fai.  Returns what
+        print_scaffolds returns (the written files by kind).  With args.fai the inputs read from FASTA get their <fasta>.fai first
+        (write_input_indexes)."""
         opt = lambda name, dflt: dflt if getattr(self.args, name, None) is None else getattr(self.args, name)  # noqa: E731
+        if opt("fai", False):
+            self.write_input_indexes()
         self.make_minimizer_graph(materialize=False)
         self.find_paths()
         G = int(opt("G", 0))
@@ -377,7 +380,30 @@ class Ntjoin:
         paths = self.adjust_paths(paths, no_cut=bool(opt("no_cut", False)), G=G)
         cuts = self.trim_overlaps(paths, opt("overlap_k", 15), opt("overlap_w", 10)) if opt("overlap", False) else None
         return self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)),
-                                    gz=bool(opt("gz", False)))
+                                    gz=bool(opt("gz", False)), fai=bool(opt("fai", False)))
+
+    def write_input_indexes(self):
+        """<fasta>.fai of every loaded assembly that was read from FASTA (the reference's `%.fai: %` rule, ntJoin:152-153, 207-208:
+        `$(target).fai` and one per reference) from the text the handle holds, and <fasta>.gzi of a BGZF input.  An assembly loaded
+        from its TSV has no text in the handle: one line on stderr, and the run goes on.  Returns the files written."""
+        written = []
+        for a, assembly in enumerate(self._order):
+            fasta = self._fasta.get(assembly)
+            if fasta is None:
+                print(f"ntjoin_amd: {assembly} was loaded from its TSV: no FASTA index is written for it", file=sys.stderr)
+                continue
+            with open(fasta, "rb") as fh:
+                gzip_magic = fh.read(2) == b"\x1f\x8b"
+            try:
+                self._engine.write_fai(a, fasta + ".fai", gzi=fasta + ".gzi" if gzip_magic else None)
+            except MxError as err:
+                if err.code != capi.MXG_EINVAL or "does not hold the file's text" not in str(err) and "did not come from a BGZF" not in str(err):
+                    raise
+                # (plain gzip, or a file the device parser left to the host's: the text is not in HBM)
+                print(f"ntjoin_amd: no FASTA index is written for {fasta}: {err}", file=sys.stderr)
+                continue
+            written += [fasta + ".fai"] + ([fasta + ".gzi"] if gzip_magic else [])
+        return written
 
     def trim_overlaps(self, paths, overlap_k=None, overlap_w=None):
         """The cut points of the reference's overlap stage (adjust_for_trimming, bin/ntjoin_assemble.py:468-516, and
@@ -491,14 +517,15 @@ class Ntjoin:
             if agp_fh:
                 agp_fh.close()
 
-    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False):
+    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False):
         """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
         trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
         than two nodes are dropped (:585-594), the last kept node's gap is zeroed (check_terminal_node_gap_zero :441-448), and the
         library cuts the sequences from the text it holds (mxg_write_scaffolds): the target FASTA is not read again and no
         bedtools runs.  Written: <fasta>.k<k>.w<w>.n<n>.assigned.scaffolds.fa, ...unassigned.scaffolds.fa,
         <p>.<target tsv>.unassigned.bed, <p>.path and, with agp=True, <p>.agp.  gz=True: the two FASTA files are BGZF files
-        (`bgzip`'s format, deflated on the device) named ...scaffolds.fa.gz.  Returns the file names by kind."""
+        (`bgzip`'s format, deflated on the device) named ...scaffolds.fa.gz.  fai=True: beside either FASTA its .fai ("assigned_fai",
+        "unassigned_fai") and, with gz, its .gzi ("assigned_gzi", "unassigned_gzi").  Returns the file names by kind."""
         eng, tgt = self._engine, len(self._order) - 1
         if tgt < 0:
             raise ValueError("print_scaffolds: no target assembly has been loaded")
@@ -534,7 +561,13 @@ class Ntjoin:
                  "bed": self.args.p + "." + target + ".unassigned.bed", "path": self.args.p + ".path"}
         print(datetime.datetime.today(), ": Printing output scaffolds", file=sys.stdout)
         res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
-                                  assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz))
+                                  assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz),
+                                  **({"fai": True} if fai else {}))
+        if fai:
+            for kind in ("assigned", "unassigned"):
+                files[kind + "_fai"] = files[kind] + ".fai"
+                if gz:
+                    files[kind + "_gzi"] = files[kind] + ".gzi"
         if agp:
             files["agp"] = self.args.p + ".agp"
         lead, tail = res["lead_strip"], res["tail_strip"]

@@ -38,6 +38,9 @@ def parse_arguments(argv=None):
     parser.add_argument("--btllib_t", type=int, default=4)
     # ours (the reference has no such flag): the scaffold FASTA files as BGZF, ...scaffolds.fa.gz (ntjoin_amd.assemble)
     parser.add_argument("--gz", action="store_true", default=False)
+    # ours: <fasta>.fai of the target, of every reference read from FASTA and of the scaffold files, .gzi for the BGZF ones
+    # (what the reference's `%.fai: %` rule makes with samtools faidx, ntJoin:152-153, 207-208; ntjoin_amd.assemble)
+    parser.add_argument("--fai", action="store_true", default=False)
     parser.add_argument("-v", "--version", action="version", version="ntjoin_amd hot path (ntJoin v1.1.5 compatible)")
     return parser.parse_args(argv)
 
