@@ -19,6 +19,7 @@
 #include <unordered_map>
 
 #include "mxg_internal.h"
+#include "nthash_tab.h"
 
 namespace mxg {
 
@@ -144,56 +145,13 @@ const char *knob_raw(const mxg_handle *h, const char *name)
     return k.set ? k.raw.c_str() : nullptr;
 }
 
-// ---- ntHash constants ---------------------------------------------------
-static const uint64_t SEED[4] = {0x3c8bfbb395c60474ULL, 0x3193c18562a02b4cULL, 0x20323ed082572324ULL,
-                                 0x295549f54be24456ULL};  // A C G T
+// ---- ntHash tables (constants and formulas: nthash_tab.h) -------------------------------------------
+void make_hash_tab(uint32_t k, HashTab *t) { nttab::hash_tab(k, t->e); }
 
-static uint64_t srol_n(uint64_t x, unsigned n)
-{
-    const uint64_t LO = 0x1FFFFFFFFULL;
-    uint64_t lo = x & LO, hi = x >> 33;
-    unsigned a = n % 33, b = n % 31;
-    if (a) lo = ((lo << a) | (lo >> (33 - a))) & LO;
-    if (b) hi = ((hi << b) | (hi >> (31 - b))) & 0x7FFFFFFFULL;
-    return (hi << 33) | lo;
-}
-
-void make_hash_tab(uint32_t k, HashTab *t)
-{
-    for (int o = 0; o < 5; ++o)
-        for (int i = 0; i < 4; ++i) {
-            uint64_t f = SEED[i], r = srol_n(SEED[3 - i], k);
-            if (o < 4) {
-                f ^= srol_n(SEED[o], k);
-                r ^= SEED[3 - o];
-            }
-            t->e[o * 4 + i] = make_uint4((uint32_t)f, (uint32_t)(f >> 32), (uint32_t)r, (uint32_t)(r >> 32));
-        }
-}
-
-// Byte table of the direct hash formula (sketch.hip init_direct): the "warm-up state" after the first m = 4*(k/4) bases
-// is  F = XOR_j srol^{m-1-j}(seed[c_j]),  R = XOR_j srol^{k-m+j}(seed'[c_j]).  Entry v (one packed byte = bases 4q..4q+3,
-// base i in bits 2i..2i+1) holds the four terms of a byte at position 0: f4 = XOR_i srol^{3-i} seed[c_i],
-// r4 = XOR_i srol^{i} seed'[c_i]; the byte's position enters through Horner rotations by 4 on the device.
 void make_init_tab(uint32_t k, std::vector<uint4> &out)
 {
     (void)k;  // the byte table does not depend on k: position enters through the Horner rotations on the device
-    out.assign(256 + 8 * 256, make_uint4(0, 0, 0, 0));
-    for (uint32_t v = 0; v < 256; ++v) {
-        uint64_t f = 0, r = 0;
-        for (uint32_t i = 0; i < 4; ++i) {
-            const uint32_t c = (v >> (2 * i)) & 3u;
-            f ^= srol_n(SEED[c], 3 - i);
-            r ^= srol_n(SEED[3 - c], i);
-        }
-        out[v] = make_uint4((uint32_t)f, (uint32_t)(f >> 32), (uint32_t)r, (uint32_t)(r >> 32));
-        // position tables (sketch.hip init_pos): byte j of a group of 8 bytes (32 bases) contributes srol^{4(7-j)} f4 to the
-        // forward hash and srol^{4j} r4 to the reverse-complement hash -- one lookup and four XORs per byte, no rotation
-        for (uint32_t j = 0; j < 8; ++j) {
-            const uint64_t fj = srol_n(f, 4 * (7 - j)), rj = srol_n(r, 4 * j);
-            out[256 + j * 256 + v] = make_uint4((uint32_t)fj, (uint32_t)(fj >> 32), (uint32_t)rj, (uint32_t)(rj >> 32));
-        }
-    }
+    nttab::init_tab(out);
 }
 
 // ---- base code table -------------------------------------------------------------------------------

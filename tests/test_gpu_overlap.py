@@ -229,6 +229,19 @@ def test_long_overlaps():
     assert got["cut_found"].tolist() == [True, True, False, True, False]
 
 
+def test_accepted_maxima_of_k_and_w():
+    """k = 256 and w = 4096, the largest the call takes (257 and 4097 are refused: test_errors_and_state_untouched): one junction
+    of two contigs that overlap by 30 000 bases, against the restatement"""
+    rng = random.Random(256)
+    g = "".join(rng.choice("ACGT") for _ in range(90_000))
+    records = [("a", g[:60_000]), ("b", g[30_000:])]
+    paths = [[("a", "+", 0, 60_000, -30_000), ("b", "+", 0, 60_000, 0)]]
+    with MxEngine(k=32, w=100) as eng:
+        a = eng.add_records("t", 1.0, records)
+        got = check_against_restatement(eng, a, records, paths, 256, 4096)
+    assert got["cut_found"].tolist() == [True, False]
+
+
 def test_pieces_are_refused(tmp_path):
     fasta = str(tmp_path / "two.fa")
     rng = random.Random(5)

@@ -70,8 +70,12 @@ def test_overlap_shared_minimizer_k15_w10(oracle):
 
 def test_rolling_equals_direct(oracle):
     rng = random.Random(7)
-    for k in (1, 2, 15, 31, 32, 33, 64, 100):
+    # (37, 70, 103 and 128, 996: k - 4 and k are multiples of 33 and of 31, the zero branches of srol_n; 255..257: byte border of k;
+    # 1023 = lcm(33, 31), the period; 1024: the largest k the library accepts)
+    for k in (1, 2, 15, 31, 32, 33, 64, 100, 37, 70, 103, 128, 255, 256, 257, 996, 1023, 1024):
         seq = "".join(rng.choice("ACGTacgtNU") for _ in range(400))
+        if k > 100:  # (400 bases of this alphabet hold no valid k-mer that long: N every 700 or so, and room for k-mers)
+            seq = "".join(rng.choice("ACGTacgtU") if rng.random() > 1 / 700 else "N" for _ in range(k + 400))
         mh, oh, fw, ok = oracle.kmer_hashes(seq, k)
         import ctypes
         for i in range(len(seq) - k + 1):
@@ -90,7 +94,7 @@ def test_srol_identities(oracle):
         x = rng.getrandbits(64)
         assert oracle.lib.mxo_sror(oracle.lib.mxo_srol(x)) == x
         y = x
-        for n in range(0, 70):
+        for n in range(0, 1101):  # past the period 1023: every residue of n % 33 and n % 31, both zero branches together
             assert oracle.lib.mxo_srol_n(x, n) == y
             y = oracle.lib.mxo_srol(y)
     assert oracle.lib.mxo_srol_n(12345, 1023) == 12345  # period lcm(33,31)
