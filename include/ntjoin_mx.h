@@ -493,6 +493,11 @@ int mxg_overlap_cuts(mxg_handle *h, int assembly, uint32_t k, uint32_t w, const 
    offset = where they start in the (uncompressed) file; an interval dropped from the FASTA has no line.  With MXG_SCAF_BGZF also
    <...>.gzi for each (format under mxg_write_fai).  FASTA, BED, strips and return values are as without the flag. */
 #define MXG_SCAF_FAI 0x4u
+/* MXG_SCAF_REPORT: every window of assigned_fa and unassigned_fa goes through the report's two passes once it is formed in device
+   memory and before it leaves (plain and BGZF alike); mxg_scaffold_report hands the reports out.  The record lengths the piece
+   table knows are checked against the bases the device counts (MXG_EDEVICE on a mismatch).  Every file is byte for byte what the
+   call writes without the flag; without it nothing more is launched. */
+#define MXG_SCAF_REPORT 0x8u
 typedef struct mxg_scaffold_node {
     uint32_t record, start, end;       /* [start, end) of the record */
     uint32_t gap_size;                 /* Ns behind the node (PathNode.gap_size) */
@@ -535,6 +540,51 @@ int mxg_write_fai(mxg_handle *h, int assembly, const char *fai_path, const char 
    MXG_SCAF_BGZF are: member j holds bytes [j P, j P + P) with P = 65 280 (the environment's MXG_BGZF_PAYLOAD, 1 .. 65 280, if set),
    the end marker follows; n = 0 gives the end marker alone.  MXG_EINVAL: a null argument; MXG_EIO: the file. */
 int mxg_bgzf_write(mxg_handle *h, const void *data, uint64_t n, const char *path);
+
+/* ---- next row (f10): the assembly report -- contiguity, base composition and N gaps -------------------------------------------
+   What the reference's `analysis` target asks QUAST for with --split-scaffolds (ntJoin:158-161, 244-252), as far as it needs no
+   alignment, from the text the handle holds and from the scaffold files on their way out.
+   A FASTA file is a list of records.  A record's BASES are the bytes of its sequence text other than '\n' and '\r'; header lines are
+   no part of it.  Classes of a base: A, C, G in either case; T in either case, U/u counted as T; N for N/n; OTHER for anything
+   else.  lower = the bases in 'a' .. 'z'.
+   An N RUN is a maximal stretch of N/n bases inside one record: line ends do not interrupt it, a record border ends it.  A GAP is
+   an N run of at least min_gap bases (default 10, QUAST's rule for --split-scaffolds).  A record's CONTIGS are what is left of it
+   when its gaps are cut out; shorter N runs stay inside contigs, a contig of 0 bases is none.
+   The CONTIGUITY BLOCK of a multiset of lengths: n = how many; over those of at least min_len (default 500): n_min, sum, min, max
+   and, for x in {50, 75, 90}, with the lengths sorted descending and S_j the sum of the first j: Lx = the smallest j with
+   100 S_j >= x sum, Nx = the j-th length.  Nothing selected: zeros.  Exact 64-bit integers throughout.
+   A REPORT holds n_records and bases, the six class counts and lower, n_gaps / gap_bases / max_gap, the contiguity block of the
+   record lengths (scaffold) and of the contig lengths (contig), and the two lists behind them: every gap's and every contig's
+   length, in no particular order.  The lists are the handle's and hold until its next mxg_assembly_report / mxg_scaffold_report /
+   mxg_write_scaffolds with MXG_SCAF_REPORT. */
+typedef struct mxg_contiguity {
+    uint64_t n, n_min, sum, min, max;
+    uint64_t n50, l50, n75, l75, n90, l90;
+} mxg_contiguity;
+typedef struct mxg_seq_report {
+    uint32_t struct_size; /* sizeof(mxg_seq_report), set by the caller */
+    uint32_t reserved;
+    uint64_t min_gap, min_len; /* the parameters the report was made with */
+    uint64_t n_records, bases;
+    uint64_t a, c, g, t, n, other, lower;
+    uint64_t n_gaps, gap_bases, max_gap;
+    mxg_contiguity scaffold, contig;
+    const uint64_t *gap_len;    /* [n_gaps] */
+    const uint64_t *contig_len; /* [contig.n] */
+} mxg_seq_report;
+/* min_gap (0: MXG_EINVAL) and min_len (0 is allowed) of every later report of the handle. */
+int mxg_set_report_params(mxg_handle *h, uint64_t min_gap, uint64_t min_len);
+/* The report of a loaded assembly, computed on the device from its text: of a file the device ingest read (with its line ends) or
+   of host-ingested text (MXG_HOST_INGEST=1, plain gzip).  MXG_EINVAL: an assembly whose text the handle does not hold (a minimizer
+   table from a TSV, side-car or arrays, packed bases, text dropped by MXG_FLAG_DROP_SEQ or released by a one-shot handle, a shard
+   or pieces of a file); out->struct_size too small.  MXG_REPORT_SCAN_W (tests): work items per block of the scan, 2 .. 256. */
+int mxg_assembly_report(mxg_handle *h, int assembly, mxg_seq_report *out);
+/* The reports of the files the last mxg_write_scaffolds with MXG_SCAF_REPORT wrote.  which: */
+#define MXG_REPORT_ASSIGNED 0
+#define MXG_REPORT_UNASSIGNED 1
+#define MXG_REPORT_ALL 2 /* the file that holds both: counts added, contiguity over the merged lists */
+/* MXG_EINVAL: no such write came before (or it failed, or it wrote no unassigned file and that one is asked for). */
+int mxg_scaffold_report(mxg_handle *h, int which, mxg_seq_report *out);
 
 /* ---- next row (f7): the paths adjusted for relocations, --no_cut and overlapping regions ------------------------------------
    What the reference's main_scaffolder (bin/ntjoin_assemble.py:751-786) does to the PathNodes between format_path and the

@@ -12,6 +12,9 @@ reference's names: <p>.mx.dot, <p>.path, <p>.agp (--agp), <fasta>.k<k>.w<w>.n<n>
 --fai: also <fasta>.fai of the target and of every reference sketched from FASTA in this run (what the reference's `%.fai: %` rule
 makes with `samtools faidx`, ntJoin:152-153, 207-208), <fasta>.gzi of a BGZF input, and the .fai (with --gz: and .gzi) of the two
 scaffold files; a reference loaded from its TSV gets a line on stderr instead.
+--report (--report_min_gap, --report_min_len): also <p>.report.tsv -- records, bases, base composition, N gaps, N50 and the like at
+scaffold and at contig level, one row per input read from FASTA in this run and per scaffold file (assigned, unassigned, all),
+computed on the GPU from the text the handle holds and from the scaffold files on their way out (ntjoin_amd/report.py).
 """
 import os
 import re

@@ -13,6 +13,8 @@ MX_UNIQUE, MX_SHARED, MX_INALL = 0x1, 0x2, 0x4
 SCAF_FOLD_CASE = 0x1
 SCAF_BGZF = 0x2
 SCAF_FAI = 0x4
+SCAF_REPORT = 0x8
+REPORT_ASSIGNED, REPORT_UNASSIGNED, REPORT_ALL = 0, 1, 2
 PATHS_AGP_UNASSIGNED = 0x1
 ABI_VERSION = 3
 
@@ -27,6 +29,7 @@ SYMBOLS = [
     "mxg_build_graph", "mxg_get_mx_flags", "mxg_get_graph", "mxg_find_paths", "mxg_path_segments", "mxg_path_segments_mk", "mxg_mk_stats", "mxg_format_paths", "mxg_mk_orientation", "mxg_vertex_hashes", "mxg_overlap_cuts", "mxg_adjust_paths", "mxg_write_scaffolds", "mxg_scaffold_strips", "mxg_bgzf_write", "mxg_write_fai", "mxg_write_paths", "mxg_mx_extremes", "mxg_dg_owner_counts", "mxg_dg_pack_items", "mxg_dg_set_items", "mxg_dg_vertices", "mxg_dg_item_results", "mxg_dg_msg_counts", "mxg_dg_pack_msgs", "mxg_dg_edges", "mxg_dg_pack_slots", "mxg_dg_owner_slots", "mxg_dg_slot_results", "mxg_dg_pack_msg_slots", "mxg_dg_edges_slots", "mxg_write_dot", "mxg_write_outputs", "mxg_dot_part_format", "mxg_dot_part_write",
     "mxg_py_repr_double", "mxg_py_repr_str", "mxg_get_stats", "mxg_reset_timers", "mxg_knobs",
     "mxg_synth_fill_packed_device", "mxg_synth_fill_packed_host", "mxg_synth_write_fasta",
+    "mxg_set_report_params", "mxg_assembly_report", "mxg_scaffold_report",
     "mxg_plan_split", "mxg_add_assembly_packed_device_pieces", "mxg_dg_last_shared", "mxg_dg_set_ghosts",
 ]
 
@@ -90,6 +93,18 @@ class AdjustParams(C.Structure):  # mxg_adjust_params: 16 bytes (api.cpp asserts
 class AdjustedView(C.Structure):  # mxg_adjusted_view: 40 bytes (api.cpp asserts the same); nodes = engine.MxEngine.ADJUST_NODE entries
     _fields_ = [("n_paths", C.c_uint64), ("n_nodes", C.c_uint64), ("node_first", C.POINTER(C.c_uint64)), ("nodes", C.c_void_p),
                 ("source", C.POINTER(C.c_uint64))]
+
+
+class Contiguity(C.Structure):  # mxg_contiguity: 88 bytes (api.cpp asserts the same)
+    _fields_ = [(name, C.c_uint64) for name in ("n", "n_min", "sum", "min", "max", "n50", "l50", "n75", "l75", "n90", "l90")]
+
+
+class SeqReport(C.Structure):  # mxg_seq_report: 312 bytes (api.cpp asserts the same)
+    _fields_ = ([("struct_size", C.c_uint32), ("reserved", C.c_uint32)] +
+                [(name, C.c_uint64) for name in ("min_gap", "min_len", "n_records", "bases", "a", "c", "g", "t", "n", "other", "lower",
+                                                 "n_gaps", "gap_bases", "max_gap")] +
+                [("scaffold", Contiguity), ("contig", Contiguity),
+                 ("gap_len", C.POINTER(C.c_uint64)), ("contig_len", C.POINTER(C.c_uint64))])
 
 
 class SynthSeg(C.Structure):
@@ -215,6 +230,9 @@ def load():
     L.mxg_write_paths.argtypes = [vp, i32, vp, vp, u64, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32]
     L.mxg_bgzf_write.argtypes = [vp, vp, u64, C.c_char_p]
     L.mxg_write_fai.argtypes = [vp, i32, C.c_char_p, C.c_char_p]
+    L.mxg_set_report_params.argtypes = [vp, u64, u64]
+    L.mxg_assembly_report.argtypes = [vp, i32, C.POINTER(SeqReport)]
+    L.mxg_scaffold_report.argtypes = [vp, i32, C.POINTER(SeqReport)]
     L.mxg_scaffold_strips.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64)]
     L.mxg_mx_extremes.argtypes = [vp, i32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)),
                                   C.POINTER(C.c_uint64)]

@@ -1093,6 +1093,68 @@ int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32
     return MXG_OK;
 }
 
+// ---- the assembly report (report.hip) ----
+static_assert(sizeof(mxg_contiguity) == 88, "mxg_contiguity: ntjoin_amd/capi.py Contiguity mirrors this layout");
+static_assert(sizeof(mxg_seq_report) == 312, "mxg_seq_report: ntjoin_amd/capi.py SeqReport mirrors this layout");
+
+int mxg_set_report_params(mxg_handle *h, uint64_t min_gap, uint64_t min_len)
+{
+    if (!h) return MXG_EINVAL;
+    if (!min_gap) return set_err(h, MXG_EINVAL, "mxg_set_report_params: min_gap is 0 (a gap is an N run of at least min_gap bases, 1 or more)");
+    h->rep_min_gap = min_gap, h->rep_min_len = min_len;
+    return MXG_OK;
+}
+
+static int report_out_check(mxg_handle *h, const char *who, const mxg_seq_report *out)
+{
+    if (!out) return set_err(h, MXG_EINVAL, "%s: null argument", who);
+    if (out->struct_size < sizeof(mxg_seq_report)) return set_err(h, MXG_EINVAL, "%s: struct_size %u is too small", who, out->struct_size);
+    return MXG_OK;
+}
+
+int mxg_assembly_report(mxg_handle *h, int assembly, mxg_seq_report *out)
+{
+    if (!h) return MXG_EINVAL;
+    if (assembly < 0 || (size_t)assembly >= h->asms.size()) return set_err(h, MXG_EINVAL, "mxg_assembly_report: no assembly %d", assembly);
+    int rc = report_out_check(h, "mxg_assembly_report", out);
+    if (rc != MXG_OK) return rc;
+    try {
+        if ((rc = assembly_report(h, h->asms[assembly], assembly)) != MXG_OK) return rc;
+        report_fill(h->rep_asm, h->rep_sorted, out);
+        return MXG_OK;
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_assembly_report");
+    }
+}
+
+int mxg_scaffold_report(mxg_handle *h, int which, mxg_seq_report *out)
+{
+    if (!h) return MXG_EINVAL;
+    if (which < MXG_REPORT_ASSIGNED || which > MXG_REPORT_ALL) return set_err(h, MXG_EINVAL, "mxg_scaffold_report: no file %d (0 assigned, 1 unassigned, 2 all)", which);
+    int rc = report_out_check(h, "mxg_scaffold_report", out);
+    if (rc != MXG_OK) return rc;
+    const SeqReportHost &as = h->rep_scaf[MXG_REPORT_ASSIGNED], &un = h->rep_scaf[MXG_REPORT_UNASSIGNED];
+    if (!as.valid)
+        return set_err(h, MXG_EINVAL, "mxg_scaffold_report: no mxg_write_scaffolds with MXG_SCAF_REPORT has succeeded on this handle: there is nothing to report");
+    if (which != MXG_REPORT_ASSIGNED && !un.valid)
+        return set_err(h, MXG_EINVAL, "mxg_scaffold_report: the last mxg_write_scaffolds with MXG_SCAF_REPORT wrote no unassigned file");
+    try {
+        if (which == MXG_REPORT_ALL) {  // the file that holds both: the counts added, the lists merged
+            SeqReportHost &all = h->rep_scaf[MXG_REPORT_ALL];
+            all = as;
+            all.n_records += un.n_records, all.bases += un.bases;
+            for (int c = 0; c < 7; ++c) all.cnt[c] += un.cnt[c];
+            all.rec_len.insert(all.rec_len.end(), un.rec_len.begin(), un.rec_len.end());
+            all.gap_len.insert(all.gap_len.end(), un.gap_len.begin(), un.gap_len.end());
+            all.ctg_len.insert(all.ctg_len.end(), un.ctg_len.begin(), un.ctg_len.end());
+        }
+        report_fill(h->rep_scaf[which], h->rep_sorted, out);
+        return MXG_OK;
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_scaffold_report");
+    }
+}
+
 // ---- distributed graph stage (dgraph.hip; the collectives are the caller's) -----------------------------------------
 #define DG_TRY(expr)                                                                     \
     try {                                                                                \

@@ -477,6 +477,10 @@ int write_fai(mxg_handle *h, Assembly *a, int assembly, const char *fai_path, co
         MXG_HIP(h, hipMemsetAsync(B[FB_VERDICT].p, 0xFF, 8, st));
         FaiRow *rows = B[FB_ROWS].as<FaiRow>();
         hipLaunchKernelGGL(k_fai_rows_init, dim3((uint32_t)((n_rec + 255) / 256)), dim3(256), 0, st, B[FB_ORG].as<uint64_t>(), (uint64_t)n_rec, rows);
+        // MXG_DEBUG_IO: the device time of the pass over the text and its scan (what DESIGN.md 4l sets the report's passes against)
+        hipEvent_t ev_rows[2] = {};
+        const bool dbg_rows = getenv("MXG_DEBUG_IO") != nullptr && hipEventCreate(&ev_rows[0]) == hipSuccess && hipEventCreate(&ev_rows[1]) == hipSuccess;
+        if (dbg_rows) (void)hipEventRecord(ev_rows[0], st);
         if (n_items) {
             FaiSum *sums = B[FB_SUMS].as<FaiSum>(), *agg = B[FB_AGG].as<FaiSum>(), *excl = B[FB_EXCL].as<FaiSum>();
             const IngItem *items = a->d_ing_items.as<IngItem>();
@@ -488,9 +492,17 @@ int write_fai(mxg_handle *h, Assembly *a, int assembly, const char *fai_path, co
                                B[FB_RLEN].as<uint64_t>(), (uint64_t)n_rec, rows, B[FB_VERDICT].as<unsigned long long>());
         }
         MXG_HIP(h, hipGetLastError());
+        if (dbg_rows) (void)hipEventRecord(ev_rows[1], st);
         unsigned long long bad = 0;
         MXG_HIP(h, hipMemcpyAsync(&bad, B[FB_VERDICT].p, 8, hipMemcpyDeviceToHost, st));
         MXG_HIP(h, hipStreamSynchronize(st));
+        if (dbg_rows) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev_rows[0], ev_rows[1]);
+            fprintf(stderr, "[mxg] fai items=%llu rows_ms=%.3f\n", (unsigned long long)n_items, ms);
+        }
+        for (hipEvent_t e : ev_rows)
+            if (e) (void)hipEventDestroy(e);
         if (bad != ~0ull) {  // (nothing has been opened)
             if (bad >= n_rec) return set_err(h, MXG_EDEVICE, "internal error: mxg_write_fai: no record %llu", bad);
             FaiRow row;

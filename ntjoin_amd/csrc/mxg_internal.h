@@ -240,6 +240,15 @@ enum class AsmState : int {
 
 struct JoinPlan;  // graph.hip: the layout of the graph stage's join (plan_join)
 
+// report.hip: one file's report as the handle keeps it (mxg_seq_report points into the vectors)
+struct SeqReportHost {
+    bool valid = false;
+    uint64_t min_gap = 0, min_len = 0;
+    uint64_t n_records = 0, bases = 0;
+    uint64_t cnt[7] = {0, 0, 0, 0, 0, 0, 0};  // A C G T N other lower (seqstat.h)
+    std::vector<uint64_t> rec_len, gap_len, ctg_len;
+};
+
 }  // namespace mxg
 
 struct mxg_handle {
@@ -285,6 +294,16 @@ struct mxg_handle {
     int scaf_iv_asm = -1;
     mxg::DevBuf ptbuf[16];  // scratch of pathtext.hip
     mxg::DevBuf faibuf[16];  // scratch of fai.hip
+    mxg::DevBuf repbuf[16];  // scratch of report.hip
+    uint64_t rep_min_gap = 10, rep_min_len = 500;  // mxg_set_report_params
+    mxg::SeqReportHost rep_asm;                    // the last mxg_assembly_report
+    mxg::SeqReportHost rep_scaf[3];                // the last mxg_write_scaffolds with MXG_SCAF_REPORT: assigned, unassigned; [2]: their union, made on demand
+    std::vector<uint64_t> rep_sorted;              // scratch of the contiguity blocks
+    struct RepRun {  // a report that is being made on the device (report.hip)
+        uint64_t starts_seen = 0, gap_cap = 0, ctg_cap = 0, n_records = 0;
+        const void *d_segs = nullptr;
+        uint32_t n_segs = 0;
+    } rep_run;
     mxg::Segments segs;
     mxg::PathNodes nodes;
     mxg::Timers tm;
@@ -583,6 +602,19 @@ struct FaiOutRec {
 int write_fai_records(mxg_handle *h, const Assembly *a, OutFile &of, const std::vector<FaiOutRec> &recs, bool ntjoin_names);
 // ... and a .gzi: the members that hold text, in file order, each with its place in the file and in the text
 int write_gzi(mxg_handle *h, OutFile &of, const std::vector<uint64_t> &comp_off, const std::vector<uint64_t> &text_off);
+// report.hip: contiguity, composition and gaps (mxg_assembly_report; MXG_SCAF_REPORT)
+int assembly_report(mxg_handle *h, Assembly *a, int assembly);  // fills h->rep_asm
+struct RepSeg {  // a stretch of a scaffold file: it ends where the next one begins
+    uint64_t out;   // offset of its first byte in the file
+    uint32_t kind;  // 0 sequence, 1 passed over (a line end), 2 passed over and a record begins at its first byte (a header line)
+    uint32_t pad;
+};
+// a file written window by window: begin (segs ends with {the file's size, 1}), every window once it is formed at d_win (enqueued on
+// the handle's stream, waits for the first pass), end (cross-checks the bases; fills h->rep_scaf[which])
+int report_file_begin(mxg_handle *h, const std::vector<RepSeg> &segs, uint64_t n_records);
+int report_file_window(mxg_handle *h, const unsigned char *d_win, uint64_t lo, uint64_t hi);
+int report_file_end(mxg_handle *h, int which, std::vector<uint64_t> &&rec_len, const char *path);
+void report_fill(const SeqReportHost &r, std::vector<uint64_t> &scratch, mxg_seq_report *out);
 // adjust.hip: relocations, --no_cut and overlapping regions of the given paths (mxg_adjust_paths); fills h->adj_*
 int adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *path_first, uint64_t n_paths, const mxg_adjust_params &p);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm

@@ -212,8 +212,9 @@ struct PieceTable {
 // the table's bytes into `of`, window by window
 // (bgzf_P: 0, or the file is a BGZF file of that many text bytes a member, deflated on the device: bgzf_deflate.hip)
 // (member_off, if given: where every BGZF member that holds text starts in the file)
+// (report: MXG_SCAF_REPORT -- every window goes through report.hip's passes behind k_scaf_emit; n_records: the file's)
 static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint32_t fold, OutFile &of, uint64_t WIN, uint32_t bgzf_P,
-                          std::vector<uint64_t> *member_off = nullptr)
+                          std::vector<uint64_t> *member_off = nullptr, bool report = false, uint64_t n_records = 0)
 {
     hipStream_t st = h->stream;
     DevBuf *B = h->scbuf;
@@ -221,6 +222,15 @@ static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint
     const size_t n_pieces = pt.pieces.size();
     if (n_pieces >= 0xFFFFFFFFull) return set_err(h, MXG_ELIMIT, "mxg_write_scaffolds: too many pieces of output for one call");
     const char *who = "mxg_write_scaffolds";
+    if (report) {  // the piece table as the report reads it: where sequence is, and where a header begins
+        std::vector<RepSeg> segs;
+        segs.reserve(n_pieces + 1);
+        for (const ScafPiece &pc : pt.pieces)
+            segs.push_back(RepSeg{pc.out, pc.kind != SP_LIT ? 0u : pt.lits[pc.src] == '>' ? 2u : 1u, 0u});
+        if (total) segs.push_back(RepSeg{total, 1u, 0u});
+        const int rc = report_file_begin(h, segs, n_records);
+        if (rc != MXG_OK) return rc;
+    }
     if (!total) return bgzf_P ? bgzf_write_windows(h, of, 0, WIN, bgzf_P, WinFill(), who) : MXG_OK;
     pt.pieces.push_back(ScafPiece{total, 0, 0, SP_LIT});  // (the end of the last piece)
     MXG_HIP(h, B[SC_PIECES].ensure((n_pieces + 1) * sizeof(ScafPiece)));
@@ -231,7 +241,7 @@ static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint
         hipLaunchKernelGGL(k_scaf_emit, dim3((uint32_t)((hi - lo + SCAF_TILE - 1) / SCAF_TILE)), dim3(256), 0, st, t, B[SC_PIECES].as<ScafPiece>(),
                            (uint32_t)n_pieces, B[SC_LITS].as<unsigned char>(), fold, d_win, lo, hi);
         MXG_HIP(h, hipGetLastError());
-        return MXG_OK;
+        return report ? report_file_window(h, d_win, lo, hi) : MXG_OK;
     };
     if (bgzf_P) return bgzf_write_windows(h, of, total, bgzf_window_bytes(WIN, SCAF_TILE, bgzf_P), bgzf_P, fill, who, member_off);
     return write_windows(h, of, total, WIN, 0, fill, who);
@@ -381,6 +391,10 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
     const uint32_t bgzf_P = flags & MXG_SCAF_BGZF ? bgzf_payload(h) : 0u;
     // MXG_SCAF_FAI: <file>.fai beside either FASTA and, for BGZF files, <file>.gzi (fai.hip)
     const bool with_fai = (flags & MXG_SCAF_FAI) != 0;
+    // MXG_SCAF_REPORT: the report of either FASTA from its windows (report.hip); the record lengths are the piece table's
+    const bool with_rep = (flags & MXG_SCAF_REPORT) != 0;
+    std::vector<uint64_t> rep_len;
+    if (with_rep) h->rep_scaf[0].valid = h->rep_scaf[1].valid = false;
     struct IndexFiles {
         OutFile fai, gzi;
         std::vector<FaiOutRec> recs;
@@ -432,11 +446,14 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
                 pt.add(SP_FILL, fill);
             }
             if (with_fai) ix_fa.recs.push_back(FaiOutRec{pt.total - seq0, (uint32_t)(seq0 - head0), 0u, 0u, 0u});
+            if (with_rep) rep_len.push_back(pt.total - seq0);
             pt.literal("\n");
             if (lead_strip) lead_strip[p] = lead;
         }
-        if ((rc = scaf_emit_file(h, t, pt, flags & MXG_SCAF_FOLD_CASE ? 1u : 0u, fa, WIN, bgzf_P, with_fai ? &ix_fa.member_off : nullptr)) != MXG_OK)
+        if ((rc = scaf_emit_file(h, t, pt, flags & MXG_SCAF_FOLD_CASE ? 1u : 0u, fa, WIN, bgzf_P, with_fai ? &ix_fa.member_off : nullptr, with_rep,
+                                 n_paths)) != MXG_OK)
             return rc;
+        if (with_rep && (rc = report_file_end(h, MXG_REPORT_ASSIGNED, std::move(rep_len), assigned_fa)) != MXG_OK) return rc;
         if (with_fai && (rc = write_index(ix_fa, true)) != MXG_OK) return rc;
     }
     uint64_t n_un = 0;
@@ -455,10 +472,15 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
             const uint64_t head0 = pt.total;
             pt.literal(">" + a->recs[iv.rec].id + ":" + std::to_string(iv.lo) + "-" + std::to_string(iv.hi) + "\n");
             if (with_fai) ix_ufa.recs.push_back(FaiOutRec{(uint64_t)len - lead - tail, (uint32_t)(pt.total - head0), iv.rec, iv.lo, iv.hi});
+            if (with_rep) rep_len.push_back((uint64_t)len - lead - tail);
             pt.add(SP_FWD, len - lead - tail, (uint64_t)iv.lo + lead, iv.rec);
             pt.literal("\n");
         }
-        if (unassigned_fa && (rc = scaf_emit_file(h, t, pt, 0u, ufa, WIN, bgzf_P, with_fai ? &ix_ufa.member_off : nullptr)) != MXG_OK) return rc;
+        if (with_rep) rep_len.shrink_to_fit();
+        if (unassigned_fa && (rc = scaf_emit_file(h, t, pt, 0u, ufa, WIN, bgzf_P, with_fai ? &ix_ufa.member_off : nullptr, with_rep, rep_len.size())) !=
+                                 MXG_OK)
+            return rc;
+        if (with_rep && unassigned_fa && (rc = report_file_end(h, MXG_REPORT_UNASSIGNED, std::move(rep_len), unassigned_fa)) != MXG_OK) return rc;
         if (with_fai && unassigned_fa && (rc = write_index(ix_ufa, false)) != MXG_OK) return rc;
     }
     if (want_un) {  // the intervals with their strips: what mxg_write_paths makes the AGP's unassigned lines of

@@ -461,13 +461,14 @@ class MxEngine:
                               ("end_adjust", "<u4"), ("reverse", "u1"), ("pad", "u1", (3,))])
 
     def write_scaffolds(self, assembly, rows, path_first, overlap_gap=None, fold_case=False, assigned=None, unassigned=None, bed=None,
-                        bgzf=False, fai=False):
+                        bgzf=False, fai=False, report=False):
         """mxg_write_scaffolds: rows = array of SCAFFOLD_NODE (or rows (record, start, end, gap_size, start_adjust, end_adjust,
         reverse)), path_first = n_paths + 1 offsets; overlap_gap=None: the overlap stage is off (the adjustments are not read).
         Writes the scaffold FASTA `assigned` and, when named, the unassigned FASTA and BED -> dict(lead_strip u32[n_paths],
         tail_strip u32[n_paths]: N/n stripped from the scaffolds' ends, n_unassigned: records in the unassigned FASTA).
         bgzf=True: the two FASTA files are BGZF files of the same bytes, deflated on the device (MXG_SCAF_BGZF); fai=True: beside
-        either FASTA its <name>.fai and, with bgzf, its <name>.gzi (MXG_SCAF_FAI)"""
+        either FASTA its <name>.fai and, with bgzf, its <name>.gzi (MXG_SCAF_FAI); report=True: the windows of either FASTA go through
+        the report's passes on their way out (MXG_SCAF_REPORT; scaffold_report() hands the reports out)"""
         if assigned is None:
             raise ValueError("write_scaffolds: assigned= names the scaffold FASTA to write")
         nodes = self._scaffold_nodes(rows)
@@ -480,7 +481,8 @@ class MxEngine:
         enc = lambda p: None if p is None else os.fsencode(str(p))  # noqa: E731
         self._check(self._lib.mxg_write_scaffolds(self._h, int(assembly), nodes.ctypes.data, pf.ctypes.data, n_paths,
                                                   -1 if overlap_gap is None else int(overlap_gap),
-                                                  (capi.SCAF_FOLD_CASE if fold_case else 0) | (capi.SCAF_BGZF if bgzf else 0) | (capi.SCAF_FAI if fai else 0),
+                                                  (capi.SCAF_FOLD_CASE if fold_case else 0) | (capi.SCAF_BGZF if bgzf else 0) | (capi.SCAF_FAI if fai else 0) |
+                                                  (capi.SCAF_REPORT if report else 0),
                                                   enc(assigned), enc(unassigned), enc(bed),
                                                   lead.ctypes.data, tail.ctypes.data, C.byref(n_un)))
         return {"lead_strip": lead, "tail_strip": tail, "n_unassigned": int(n_un.value)}
@@ -490,6 +492,37 @@ class MxEngine:
         gzi= names the .gzi to write for an assembly that came from a BGZF file"""
         enc = lambda p: None if p is None else os.fsencode(str(p))  # noqa: E731
         self._check(self._lib.mxg_write_fai(self._h, int(assembly), enc(path), enc(gzi)))
+
+    def set_report_params(self, min_gap=10, min_len=500):
+        """mxg_set_report_params: a gap is an N run of at least min_gap bases (0 is refused); the contiguity blocks are taken over the
+        lengths of at least min_len"""
+        self._check(self._lib.mxg_set_report_params(self._h, int(min_gap), int(min_len)))
+
+    @staticmethod
+    def _report_dict(rep):
+        block = lambda b: {name: int(getattr(b, name)) for name, _ in capi.Contiguity._fields_}  # noqa: E731
+        out = {name: int(getattr(rep, name)) for name in ("min_gap", "min_len", "n_records", "bases", "a", "c", "g", "t", "n", "other", "lower",
+                                                          "n_gaps", "gap_bases", "max_gap")}
+        out["scaffold"], out["contig"] = block(rep.scaffold), block(rep.contig)
+        out["gap_len"] = _np(rep.gap_len, out["n_gaps"], np.uint64)
+        out["contig_len"] = _np(rep.contig_len, out["contig"]["n"], np.uint64)
+        return out
+
+    def assembly_report(self, assembly):
+        """mxg_assembly_report: contiguity, base composition and N gaps of a loaded assembly, from the text the handle holds -> a dict:
+        min_gap, min_len, n_records, bases, a, c, g, t, n, other, lower, n_gaps, gap_bases, max_gap, scaffold / contig (dicts: n, n_min,
+        sum, min, max, n50, l50, n75, l75, n90, l90) and gap_len / contig_len (u64 arrays, copies, in no particular order)"""
+        rep = capi.SeqReport(struct_size=C.sizeof(capi.SeqReport))
+        self._check(self._lib.mxg_assembly_report(self._h, int(assembly), C.byref(rep)))
+        return self._report_dict(rep)
+
+    def scaffold_report(self, which="all"):
+        """mxg_scaffold_report: the report of a file the last write_scaffolds(report=True) wrote; which = "assigned", "unassigned" or
+        "all" (the file that holds both) -> a dict as assembly_report returns"""
+        code = {"assigned": capi.REPORT_ASSIGNED, "unassigned": capi.REPORT_UNASSIGNED, "all": capi.REPORT_ALL}.get(which, which)
+        rep = capi.SeqReport(struct_size=C.sizeof(capi.SeqReport))
+        self._check(self._lib.mxg_scaffold_report(self._h, int(code), C.byref(rep)))
+        return self._report_dict(rep)
 
     def bgzf_write(self, data, path):
         """mxg_bgzf_write: the bytes of `data` (bytes, bytearray, or a contiguous uint8 array) written to `path` as a BGZF file,

@@ -20,6 +20,7 @@ import numpy as np
 from . import capi
 from .engine import MxEngine, MxError
 from .ntjoin_utils import MxGraph, sketch_views
+from .report import COLUMNS as REPORT_COLUMNS, row as report_row
 
 COLOURS = ["red", "green", "blue", "purple", "orange", "turquoise", "pink", "yellow", "orchid", "salmon"]
 
@@ -367,20 +368,54 @@ class Ntjoin:
     def scaffold(self, lengths=None):
         """main_scaffolder (:751-786) behind load_minimizers_scaffold in one handle: make_minimizer_graph -> find_paths ->
         format_paths -> adjust_paths -> trim_overlaps (when args.overlap) -> print_scaffolds.  Read from args, with ntJoin's
-        defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz, fai.  Returns what
-        print_scaffolds returns (the written files by kind).  With args.fai the inputs read from FASTA get their <fasta>.fai first
-        (write_input_indexes)."""
+        defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz, fai, report,
+        report_min_gap, report_min_len.  Returns what print_scaffolds returns (the written files by kind).  With args.fai the inputs
+        read from FASTA get their <fasta>.fai first (write_input_indexes); with args.report <prefix>.report.tsv is written ("report":
+        write_report)."""
         opt = lambda name, dflt: dflt if getattr(self.args, name, None) is None else getattr(self.args, name)  # noqa: E731
         if opt("fai", False):
             self.write_input_indexes()
+        report = bool(opt("report", False))
+        if report:
+            self._engine.set_report_params(int(opt("report_min_gap", 10)), int(opt("report_min_len", 500)))
+            report_rows = self.input_reports()
         self.make_minimizer_graph(materialize=False)
         self.find_paths()
         G = int(opt("G", 0))
         paths = self.format_paths(lengths, g=int(opt("g", 20)), G=G, m=opt("m", 90), mkt=bool(opt("mkt", False)))
         paths = self.adjust_paths(paths, no_cut=bool(opt("no_cut", False)), G=G)
         cuts = self.trim_overlaps(paths, opt("overlap_k", 15), opt("overlap_w", 10)) if opt("overlap", False) else None
-        return self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)),
-                                    gz=bool(opt("gz", False)), fai=bool(opt("fai", False)))
+        files = self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)),
+                                     gz=bool(opt("gz", False)), fai=bool(opt("fai", False)), report=report)
+        if report:
+            files["report"] = self.write_report(report_rows, files)
+        return files
+
+    def input_reports(self):
+        """(fasta, report) of every loaded assembly that was read from FASTA, references in command-line order, then the target
+        (MxEngine.assembly_report).  An assembly loaded from its TSV has no text in the handle: one line on stderr and no entry."""
+        rows = []
+        for a, assembly in enumerate(self._order):
+            fasta = self._fasta.get(assembly)
+            if fasta is None:
+                print(f"ntjoin_amd: {assembly} was loaded from its TSV: the report has no row for it", file=sys.stderr)
+                continue
+            rows.append((fasta, self._engine.assembly_report(a)))
+        return rows
+
+    def write_report(self, input_rows, files):
+        """<prefix>.report.tsv: a header line, then one line per file -- the inputs (input_reports), the assigned, the unassigned and
+        the `all` scaffolds file (named as `ntJoin-mx scaffold` names it) of the last print_scaffolds(report=True).  Returns its name."""
+        rows = list(input_rows)
+        for which in ("assigned", "unassigned"):
+            rows.append((files[which], self._engine.scaffold_report(which)))
+        rows.append((files["assigned"].replace(".assigned.scaffolds.", ".all.scaffolds."), self._engine.scaffold_report("all")))
+        out = self.args.p + ".report.tsv"
+        with open(out, "w", encoding="utf-8") as fh:
+            fh.write("\t".join(REPORT_COLUMNS) + "\n")
+            for name, rep in rows:
+                fh.write(report_row(name, rep) + "\n")
+        return out
 
     def write_input_indexes(self):
         """<fasta>.fai of every loaded assembly that was read from FASTA (the reference's `%.fai: %` rule, ntJoin:152-153, 207-208:
@@ -517,7 +552,7 @@ class Ntjoin:
             if agp_fh:
                 agp_fh.close()
 
-    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False):
+    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False, report=False):
         """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
         trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
         than two nodes are dropped (:585-594), the last kept node's gap is zeroed (check_terminal_node_gap_zero :441-448), and the
@@ -525,7 +560,8 @@ class Ntjoin:
         bedtools runs.  Written: <fasta>.k<k>.w<w>.n<n>.assigned.scaffolds.fa, ...unassigned.scaffolds.fa,
         <p>.<target tsv>.unassigned.bed, <p>.path and, with agp=True, <p>.agp.  gz=True: the two FASTA files are BGZF files
         (`bgzip`'s format, deflated on the device) named ...scaffolds.fa.gz.  fai=True: beside either FASTA its .fai ("assigned_fai",
-        "unassigned_fai") and, with gz, its .gzi ("assigned_gzi", "unassigned_gzi").  Returns the file names by kind."""
+        "unassigned_fai") and, with gz, its .gzi ("assigned_gzi", "unassigned_gzi").  report=True: either FASTA goes through the report's
+        passes on its way out (MxEngine.scaffold_report hands the reports out; no file more).  Returns the file names by kind."""
         eng, tgt = self._engine, len(self._order) - 1
         if tgt < 0:
             raise ValueError("print_scaffolds: no target assembly has been loaded")
@@ -562,7 +598,7 @@ class Ntjoin:
         print(datetime.datetime.today(), ": Printing output scaffolds", file=sys.stdout)
         res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
                                   assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz),
-                                  **({"fai": True} if fai else {}))
+                                  **({"fai": True} if fai else {}), **({"report": True} if report else {}))
         if fai:
             for kind in ("assigned", "unassigned"):
                 files[kind + "_fai"] = files[kind] + ".fai"

@@ -41,6 +41,11 @@ def parse_arguments(argv=None):
     # ours: <fasta>.fai of the target, of every reference read from FASTA and of the scaffold files, .gzi for the BGZF ones
     # (what the reference's `%.fai: %` rule makes with samtools faidx, ntJoin:152-153, 207-208; ntjoin_amd.assemble)
     parser.add_argument("--fai", action="store_true", default=False)
+    # ours: <prefix>.report.tsv -- contiguity, base composition and N gaps of the inputs read from FASTA and of the scaffold files,
+    # computed on the GPU (the alignment-free part of the reference's `analysis` target, ntJoin:158-161, 244-252; ntjoin_amd.assemble)
+    parser.add_argument("--report", action="store_true", default=False)
+    parser.add_argument("--report_min_gap", type=int, default=10, help="an N run of at least this many bases is a gap [10]")
+    parser.add_argument("--report_min_len", type=int, default=500, help="N50 and the like are taken over lengths of at least this [500]")
     parser.add_argument("-v", "--version", action="version", version="ntjoin_amd hot path (ntJoin v1.1.5 compatible)")
     return parser.parse_args(argv)
 
