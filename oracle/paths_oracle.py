@@ -180,12 +180,16 @@ def determine_orientation(positions, m=90):
     return "?"
 
 
-def format_path(state, path, target, lengths, k, g=20, G=0, m=90):
+def prepare_format(state, target):
+    "what format_path reads of the whole graph, for callers that format many paths of one state: pass it as prepared="
+    return mx_extremes(state, target), {frozenset((s, t)): sup for s, t, sup, _w in state["edges"]}
+
+
+def format_path(state, path, target, lengths, k, g=20, G=0, m=90, prepared=None):
     """format_path + calc_start/end_coord + calculate_gap_size (reference bin/ntjoin_assemble.py:175-218,52-65,68-112):
     -> [[contig, ori, start, end, contig_size, first_mx, terminal_mx, gap_size, raw_gap_size], ...]"""
     info = state["list_mx_info"]
-    extremes = mx_extremes(state, target)
-    support = {frozenset((s, t)): sup for s, t, sup, _w in state["edges"]}
+    extremes, support = prepared or prepare_format(state, target)
     index = {mx: i for i, mx in enumerate(path)}
     groups, cur = [], None
     for mx in path:                                         # runs of minimizers on the same target contig

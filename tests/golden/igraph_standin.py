@@ -46,6 +46,11 @@ class _Seq(list):
             list.__setitem__(self, key, values)
 
     def find(self, name):
+        names = getattr(self, "_names", None)   # a graph's vs: its name -> index table (names are unique)
+        if names is not None:
+            if name in names:
+                return self[names[name]]
+            raise ValueError(f"no such vertex: {name}")
         for v in self:
             if v["name"] == name:
                 return v
@@ -56,6 +61,7 @@ class Graph:
     def __init__(self):
         self.vs, self.es = _Seq(), _Seq()
         self._idx = {}
+        self.vs._names = self._idx
         self._adj_cache = None
 
     # -- construction ------------------------------------------------------------------------------------
@@ -136,7 +142,9 @@ class Graph:
         new_id = {old: i for i, old in enumerate(keep)}
         g = Graph()
         g.add_vertices([self.vs[old]["name"] for old in keep])
-        for e in self.es:
+        adj = self._adj()
+        for eid in sorted({eid for old in keep for _n, eid in adj[old]}):   # (edge ids are compact: es[eid] is edge eid)
+            e = self.es[eid]
             if e.source in new_id and e.target in new_id:
                 a, b = new_id[e.source], new_id[e.target]
                 g.es.append(_Edge(len(g.es), min(a, b), max(a, b), dict(e)))

@@ -12,6 +12,7 @@ import types
 import numpy as np
 import pytest
 
+from tests._format_cases import _random_assemblies
 from tests.conftest import GOLDEN, golden_cases, load_case
 
 pytestmark = pytest.mark.gpu
@@ -358,45 +359,7 @@ def test_shape_g_a_reference_as_the_formatted_assembly():
         _check_segments(eng, 0, nodes)
 
 
-# ---- 3. fuzz ------------------------------------------------------------------------------------------------------------
-def _random_assemblies(rng):
-    """two references and a target over one universe of minimizers: collinear stretches with drop-outs, reversed stretches,
-    shuffled stretches and single minimizers as contigs; unique positions per assembly (the reference leaves ties to set order)"""
-    universe = [rng.getrandbits(62) + 1 for _ in range(rng.choice([40, 120, 400]))]
-    asms, lengths = [], {}
-    for a in range(3):
-        recs, at = [], 0
-        keep = rng.choice([0.7, 0.85, 1.0]) if a < 2 else 1.0
-        while at < len(universe):
-            n = rng.choice([1, 1, 2, 3, 5, 8, 20, 70]) if a == 2 else rng.choice([2, 3, 5, 20, 70])
-            picks = [h for h in universe[at:at + n] if rng.random() < keep]
-            at += n
-            mode = rng.random()
-            if a == 2 and mode < 0.25:
-                picks.reverse()
-            elif a == 2 and mode < 0.5 and len(picks) > 2:
-                i, j = rng.randrange(len(picks)), rng.randrange(len(picks))
-                picks[i], picks[j] = picks[j], picks[i]
-            elif a == 2 and mode < 0.6:
-                rng.shuffle(picks)
-            if picks:
-                recs.append(picks)
-        total = sum(len(p) for p in recs)
-        pool = sorted(rng.sample(range(10 ** 6), total))
-        rng.shuffle(recs)
-        out, at = [], 0
-        for r, picks in enumerate(recs):
-            pos = pool[at:at + len(picks)]
-            at += len(picks)
-            if a == 2:  # the target's positions are contig-local: overhangs of tens of bases, as on real contigs
-                shift = pos[0] - rng.randrange(60)
-                pos = [p - shift for p in pos]
-                lengths[f"ctg{r}"] = pos[-1] + K + rng.randrange(60)
-            out.append((f"ctg{r}", list(zip(picks, pos))))
-        asms.append(out)
-    return asms, lengths
-
-
+# ---- 3. fuzz (the generator: tests/_format_cases.py) --------------------------------------------------------------------
 def test_fuzz_against_host_route():
     """random three-assembly inputs; m in {50, 75, 90}, g in {1, 20}, G in {0, 40}, mkt on and off; every field against
     _format_paths_host.  The four kinds of case the kernels treat differently are counted and each must occur.
