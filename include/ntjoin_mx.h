@@ -220,6 +220,24 @@ int mxg_add_assembly_packed_device_pieces(mxg_handle *h, const char *name, doubl
                                           const uint64_t *rec_start, const uint64_t *rec_len, const uint64_t *piece_lo,
                                           const uint64_t *piece_hi, const uint8_t *piece_drop, const char *const *ids,
                                           uint64_t n_records);
+/* FASTA text that lies in HBM already: the n_bytes at d_text, on the handle's device, with no work pending on them.
+   ntJoin is run in rounds, the scaffolds of one run being the target of the next, usually with a smaller w; a handle has one w, so
+   a round is a new handle, and the texts of the old one need not go through a file to reach it.  Any FASTA is accepted:
+   multi-line, CRLF, comments behind the id, no final line end.  The call copies the text device to device into the assembly's own
+   padded text buffer (for a moment two copies exist: one byte per base more); the source may be freed, or its handle destroyed, as
+   soon as the call returns.  From there on the assembly is in every respect what mxg_add_assembly_fasta of a file with those bytes
+   gives by the device route: record ids and lengths, packed bases, run table and tile index, and so the sketch, the TSV, .fai,
+   report, overlap cuts and scaffolds.  n_bytes == 0 gives an assembly without records.
+   Where the file route hands a file to the host parser there is none to go to: more changes between valid and invalid bases than
+   the route records (MXG_INGEST_EV_CAP) is MXG_ELIMIT, a device allocation that finds no room MXG_ENOMEM, each with a message; the
+   handle is left as it was.  MXG_EINVAL: d_text == NULL with n_bytes > 0, a name in use. */
+int mxg_add_assembly_text_device(mxg_handle *h, const char *name, double weight, const void *d_text, uint64_t n_bytes);
+/* The FASTA text of an assembly that the device ingest route loaded (a regular plain or BGZF file, or the entry above): the
+   file's own bytes (of a BGZF file: inflated), line ends included, in device memory of the handle; *n_bytes of them.  The pointer
+   holds until mxg_destroy.  MXG_EINVAL for every assembly without such text, the message naming the reason: a minimizer table from
+   a TSV, side-car or arrays, packed bases, MXG_HOST_INGEST=1, plain gzip, a pipe, text dropped by MXG_FLAG_DROP_SEQ or released by
+   a one-shot handle, a shard or pieces of a file. */
+int mxg_assembly_text(mxg_handle *h, int assembly, const void **d_text, uint64_t *n_bytes);
 /* A sketch computed elsewhere: an indexlr TSV (`id \t hash:pos[:seq] ...`), parsed as read_minimizers does. */
 int mxg_add_assembly_tsv(mxg_handle *h, const char *name, double weight, const char *tsv_path);
 /* ... or the binary side-car mxg_write_sketch_bin left next to the TSV (the reference re-parses ~65
@@ -498,6 +516,14 @@ int mxg_overlap_cuts(mxg_handle *h, int assembly, uint32_t k, uint32_t w, const 
    table knows are checked against the bases the device counts (MXG_EDEVICE on a mismatch).  Every file is byte for byte what the
    call writes without the flag; without it nothing more is launched. */
 #define MXG_SCAF_REPORT 0x8u
+/* MXG_SCAF_KEEP: the bytes of assigned_fa followed by the bytes of unassigned_fa -- the all.scaffolds.fa that `cat`
+   makes of them, the target of the next round -- are also left in a device buffer of the handle: the uncompressed text, also under
+   MXG_SCAF_BGZF; the assigned part folded under MXG_SCAF_FOLD_CASE as its file is.  The unassigned side is always computed with this
+   flag.  The buffer holds until the handle's next mxg_write_scaffolds or mxg_destroy.  With the flag, assigned_fa, unassigned_fa and
+   unassigned_bed may all be NULL; what is not named is not written.  MXG_SCAF_BGZF, MXG_SCAF_FAI or MXG_SCAF_REPORT without
+   assigned_fa is MXG_EINVAL.  Files that are named are byte for byte what they are without the flag; without it nothing more is
+   launched. */
+#define MXG_SCAF_KEEP 0x10u
 typedef struct mxg_scaffold_node {
     uint32_t record, start, end;       /* [start, end) of the record */
     uint32_t gap_size;                 /* Ns behind the node (PathNode.gap_size) */
@@ -515,6 +541,9 @@ int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *no
    (bin/ntjoin_assemble.py:379-404) recomputes from the text of every record (len_diff_start, len_diff_end).  The arrays are the
    handle's and hold until its next mxg_write_scaffolds. */
 int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals);
+/* What the last mxg_write_scaffolds kept under MXG_SCAF_KEEP: the text in device memory, its bytes and (n_records may be NULL) its
+   records.  MXG_EINVAL when that call kept none (no flag, or it failed).  What the records are made of: mxg_scaffold_pieces. */
+int mxg_scaffold_text(mxg_handle *h, const void **d_text, uint64_t *n_bytes, uint64_t *n_records);
 
 /* ---- next row (f9): FASTA indexes -----------------------------------------------------------------------------------------------
    <fasta>.fai as `samtools faidx` writes it (the reference's `%.fai: %` rule, ntJoin:152-153, 207-208: `$(target).fai` and one per
@@ -656,6 +685,46 @@ int mxg_write_paths(mxg_handle *h, int assembly, const mxg_scaffold_node *nodes,
                     const uint32_t *lead_strip, const uint32_t *tail_strip /* [n_paths]; NULL = all 0 */,
                     const char *first_line /* the FASTA's name, written as line 1 of path_file */,
                     const char *path_file, const char *agp_file /* may be NULL */, uint32_t flags);
+
+/* ---- next row (f11): piece tables of scaffolding rounds, composed ----------------------------------------------
+   ntJoin is run in rounds: the scaffold file of one run is the target of the next.  After round 2 the .path and the AGP name
+   records of round 1 (`ntJoin7`, `ctgA:0-5000`), not the contigs the user began with; the reference leaves composing the AGPs of
+   all rounds to the user.  A PIECE TABLE says what every record of a scaffold file is made of, in terms of the records of the file
+   it was cut from: record r is the concatenation of pieces[first[r] .. first[r + 1]), a piece being
+     MXG_PIECE_FWD  bases [start, end) of `record`
+     MXG_PIECE_REV  the same, reversed and mapped through the table of bin/ntjoin_utils.py:145-150
+     MXG_PIECE_GAP  end - start Ns; record and start are 0.
+   A table is VALID when first starts at 0, every record has at least one piece, every piece has start < end and a known kind, and
+   no record is longer than 2^32 - 1 bases.
+   The composition of two tables: outer's `record` fields index inner's records; the result spells outer's records in terms of
+   whatever inner refers to, so that a record spells the same sequence before and after.  Per outer piece, in order:
+     FWD / REV over [a, b) of inner record r: the inner pieces of r that meet [a, b), the first and the last clipped to it; under
+         REV in reverse order, FWD and REV swapped, gaps kept;
+     GAP: itself.
+   Then neighbouring GAP pieces of one record become one piece whose length is their sum (a round may cut inside a gap of the round
+   before, and an AGP has no two gap lines in a row); sequence pieces are never joined.  The result is a valid table again.
+   Computed on the device (count per outer piece, scan, emit, flag what survives the join, scan, compact).  *pieces and *first
+   (n_outer + 1 entries) are host copies owned by the handle, valid until its next call of this entry.
+   MXG_EINVAL: a null argument, a table that is not valid, an outer piece that names no inner record or is not inside it (end beyond
+   the record's length); the message names the table, the record and the piece.  MXG_ELIMIT: 2^31 pieces or records or more in
+   either table or in the result, a record longer than 2^32 - 1 bases.  n_outer == 0 is valid.  Sketches, graph and paths of the
+   handle are left as they are. */
+#define MXG_PIECE_FWD 0u
+#define MXG_PIECE_REV 1u
+#define MXG_PIECE_GAP 2u
+typedef struct mxg_seq_piece {
+    uint32_t record, start, end, kind;
+} mxg_seq_piece;
+int mxg_compose_pieces(mxg_handle *h, const mxg_seq_piece *outer, const uint64_t *outer_first /* n_outer + 1 */, uint64_t n_outer,
+                       const mxg_seq_piece *inner, const uint64_t *inner_first /* n_inner + 1 */, uint64_t n_inner,
+                       const mxg_seq_piece **pieces, const uint64_t **first /* n_outer + 1 */);
+/* The records of the text mxg_write_scaffolds kept under MXG_SCAF_KEEP, in its order, in terms of the records of the assembly they were cut from, as a piece table
+   (above): pieces rec_first[r] .. rec_first[r + 1] spell record r.  This is the table the text was written from,
+   without its header literals and after the N strips were applied; a gap of 0 Ns has no piece.  A path gives FWD / REV pieces with
+   GAP pieces between them, an unassigned interval one FWD piece.  The arrays are the handle's and hold as long as the text.
+   mxg_scaffold_record_id: a kept record's name, ntJoin<p> or id:lo-hi (NULL: no such record, or nothing kept). */
+int mxg_scaffold_pieces(mxg_handle *h, const mxg_seq_piece **pieces, const uint64_t **rec_first, uint64_t *n_records);
+const char *mxg_scaffold_record_id(const mxg_handle *h, uint64_t record);
 
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------
    No counterpart in the reference (it is one process).  Uniqueness and intersection need every occurrence of a hash in

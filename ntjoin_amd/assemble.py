@@ -15,6 +15,8 @@ scaffold files; a reference loaded from its TSV gets a line on stderr instead.
 --report (--report_min_gap, --report_min_len): also <p>.report.tsv -- records, bases, base composition, N gaps, N50 and the like at
 scaffold and at contig level, one row per input read from FASTA in this run and per scaffold file (assigned, unassigned, all),
 computed on the GPU from the text the handle holds and from the scaffold files on their way out (ntjoin_amd/report.py).
+--rounds_w "500 250" (--rounds_keep): further rounds with these window sizes in the same process, the scaffolds of a round being the
+target of the next without a file between them, and <p>.rounds.agp over the contigs of the first target (ntjoin_amd/rounds.py).
 """
 import os
 import re
@@ -67,6 +69,14 @@ def main(argv=None):
     fasta, w = derive_names(args)
     sketch = sources(args, fasta)
     weights = set_weights(args)
+    from . import rounds
+    try:
+        rounds_w = rounds.parse_rounds_w(args.rounds_w)
+    except ValueError:
+        fail(f"--rounds_w {args.rounds_w!r}: window sizes are positive integers, blank-separated")
+    if rounds_w:
+        rounds.run_rounds(args, fasta, w, weights, rounds_w, keep_files=args.rounds_keep)
+        return 0
     from .ntjoin import Ntjoin  # (behind the checks: importing it loads the library)
     nj = Ntjoin(args, fasta=sketch, w=w)
     nj.weights_list = weights

@@ -14,8 +14,10 @@ SCAF_FOLD_CASE = 0x1
 SCAF_BGZF = 0x2
 SCAF_FAI = 0x4
 SCAF_REPORT = 0x8
+SCAF_KEEP = 0x10
 REPORT_ASSIGNED, REPORT_UNASSIGNED, REPORT_ALL = 0, 1, 2
 PATHS_AGP_UNASSIGNED = 0x1
+PIECE_FWD, PIECE_REV, PIECE_GAP = 0, 1, 2
 ABI_VERSION = 3
 
 SYMBOLS = [
@@ -31,6 +33,8 @@ SYMBOLS = [
     "mxg_synth_fill_packed_device", "mxg_synth_fill_packed_host", "mxg_synth_write_fasta",
     "mxg_set_report_params", "mxg_assembly_report", "mxg_scaffold_report",
     "mxg_plan_split", "mxg_add_assembly_packed_device_pieces", "mxg_dg_last_shared", "mxg_dg_set_ghosts",
+    "mxg_compose_pieces", "mxg_add_assembly_text_device", "mxg_assembly_text",
+    "mxg_scaffold_text", "mxg_scaffold_pieces", "mxg_scaffold_record_id",
 ]
 
 
@@ -188,6 +192,8 @@ def load():
                                                  C.POINTER(cp), u64]
     L.mxg_plan_split.argtypes = [vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.mxg_add_assembly_packed_device_pieces.argtypes = [vp, cp, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(cp), u64]
+    L.mxg_add_assembly_text_device.argtypes = [vp, cp, C.c_double, vp, u64]
+    L.mxg_assembly_text.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u64)]
     L.mxg_add_assembly_tsv.argtypes = [vp, cp, C.c_double, cp]
     L.mxg_add_assembly_minimizers.argtypes = [vp, cp, C.c_double, vp, vp, vp, u64, C.POINTER(cp), u64]
     L.mxg_num_assemblies.argtypes = [vp]
@@ -227,7 +233,12 @@ def load():
     L.mxg_overlap_cuts.argtypes = [vp, i32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp]
     L.mxg_adjust_paths.argtypes = [vp, vp, vp, u64, C.POINTER(AdjustParams), C.POINTER(AdjustedView)]
     L.mxg_write_scaffolds.argtypes = [vp, i32, vp, vp, u64, i32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp]
+    L.mxg_scaffold_text.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.mxg_scaffold_pieces.argtypes = [vp, C.POINTER(vp), C.POINTER(C.POINTER(u64)), C.POINTER(u64)]
+    L.mxg_scaffold_record_id.argtypes = [vp, u64]
+    L.mxg_scaffold_record_id.restype = cp
     L.mxg_write_paths.argtypes = [vp, i32, vp, vp, u64, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32]
+    L.mxg_compose_pieces.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(vp), C.POINTER(C.POINTER(u64))]
     L.mxg_bgzf_write.argtypes = [vp, vp, u64, C.c_char_p]
     L.mxg_write_fai.argtypes = [vp, i32, C.c_char_p, C.c_char_p]
     L.mxg_set_report_params.argtypes = [vp, u64, u64]

@@ -180,6 +180,37 @@ int mxg_add_assembly_fasta(mxg_handle *h, const char *name, double weight, const
     return commit(h, a, rc);
 }
 
+int mxg_add_assembly_text_device(mxg_handle *h, const char *name, double weight, const void *d_text, uint64_t n_bytes)
+{
+    Assembly *a;
+    int rc = new_assembly(h, name, weight, &a);
+    if (rc != MXG_OK) return rc;
+    if (!d_text && n_bytes) return commit(h, a, set_err(h, MXG_EINVAL, "mxg_add_assembly_text_device: d_text is NULL"));
+    try {
+        rc = load_text_device(h, a, d_text, n_bytes);
+    } catch (const std::bad_alloc &) {
+        rc = set_err(h, MXG_ENOMEM, "out of host memory in mxg_add_assembly_text_device");
+    }
+    return commit(h, a, rc);
+}
+
+int mxg_assembly_text(mxg_handle *h, int assembly, const void **d_text, uint64_t *n_bytes)
+{
+    if (!h) return MXG_EINVAL;
+    if (assembly < 0 || (size_t)assembly >= h->asms.size()) return set_err(h, MXG_EINVAL, "mxg_assembly_text: no assembly %d", assembly);
+    if (!d_text || !n_bytes) return set_err(h, MXG_EINVAL, "mxg_assembly_text: null argument");
+    const Assembly *a = h->asms[assembly];
+    if (a->holds_pieces || a->shard_lo != 0 || a->shard_hi < a->recs.size())
+        return set_err(h, MXG_EINVAL, "mxg_assembly_text: assembly %d holds a shard or pieces of its file, not the whole text", assembly);
+    if (!(a->text_on_device && a->d_text.p))
+        return set_err(h, MXG_EINVAL, "mxg_assembly_text: assembly %d: the handle does not hold the file's text on the device (a minimizer table from a "
+                       "TSV, side-car or arrays, packed bases, MXG_HOST_INGEST=1, plain gzip, a pipe, text dropped by MXG_FLAG_DROP_SEQ or "
+                       "released by a one-shot handle)", assembly);
+    *d_text = a->d_text.p;
+    *n_bytes = a->text_bytes;
+    return MXG_OK;
+}
+
 int mxg_add_assembly_fasta_shard(mxg_handle *h, const char *name, double weight, const char *fasta_path,
                                  uint32_t shard, uint32_t n_shards)
 {
@@ -1008,7 +1039,7 @@ int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *no
 {
     if (!h) return MXG_EINVAL;
     if (assembly < 0 || (size_t)assembly >= h->asms.size()) return set_err(h, MXG_EINVAL, "mxg_write_scaffolds: no assembly %d", assembly);
-    if (!path_first || !assigned_fa || (n_paths && path_first[n_paths] && !nodes))
+    if (!path_first || (!assigned_fa && !(flags & MXG_SCAF_KEEP)) || (n_paths && path_first[n_paths] && !nodes))
         return set_err(h, MXG_EINVAL, "mxg_write_scaffolds: null argument");
     try {
         return write_scaffolds(h, h->asms[assembly], assembly, nodes, path_first, n_paths, overlap_gap, flags, assigned_fa, unassigned_fa,
@@ -1016,6 +1047,34 @@ int mxg_write_scaffolds(mxg_handle *h, int assembly, const mxg_scaffold_node *no
     } catch (const std::bad_alloc &) {
         return set_err(h, MXG_ENOMEM, "out of host memory in mxg_write_scaffolds");
     }
+}
+
+int mxg_scaffold_text(mxg_handle *h, const void **d_text, uint64_t *n_bytes, uint64_t *n_records)
+{
+    if (!h) return MXG_EINVAL;
+    if (!d_text || !n_bytes) return set_err(h, MXG_EINVAL, "mxg_scaffold_text: null argument");
+    if (!h->scaf_keep_valid) return set_err(h, MXG_EINVAL, "mxg_scaffold_text: the handle's last mxg_write_scaffolds kept no text (MXG_SCAF_KEEP)");
+    *d_text = h->scaf_keep.p;
+    *n_bytes = h->scaf_keep_bytes;
+    if (n_records) *n_records = h->scaf_keep_first.size() - 1;
+    return MXG_OK;
+}
+
+int mxg_scaffold_pieces(mxg_handle *h, const mxg_seq_piece **pieces, const uint64_t **rec_first, uint64_t *n_records)
+{
+    if (!h) return MXG_EINVAL;
+    if (!pieces || !rec_first || !n_records) return set_err(h, MXG_EINVAL, "mxg_scaffold_pieces: null argument");
+    if (!h->scaf_keep_valid) return set_err(h, MXG_EINVAL, "mxg_scaffold_pieces: the handle's last mxg_write_scaffolds kept no text (MXG_SCAF_KEEP)");
+    *pieces = h->scaf_keep_pieces.data();
+    *rec_first = h->scaf_keep_first.data();
+    *n_records = h->scaf_keep_first.size() - 1;
+    return MXG_OK;
+}
+
+const char *mxg_scaffold_record_id(const mxg_handle *h, uint64_t record)
+{
+    if (!h || !h->scaf_keep_valid || record >= h->scaf_keep_id.size()) return nullptr;
+    return h->scaf_keep_id[record].c_str();
 }
 
 int mxg_write_fai(mxg_handle *h, int assembly, const char *fai_path, const char *gzi_path)
@@ -1081,6 +1140,27 @@ int mxg_write_paths(mxg_handle *h, int assembly, const mxg_scaffold_node *nodes,
     } catch (const std::bad_alloc &) {
         return set_err(h, MXG_ENOMEM, "out of host memory in mxg_write_paths");
     }
+}
+
+static_assert(sizeof(mxg_seq_piece) == 16, "mxg_seq_piece: ntjoin_amd/engine.py SEQ_PIECE mirrors this layout");
+
+int mxg_compose_pieces(mxg_handle *h, const mxg_seq_piece *outer, const uint64_t *outer_first, uint64_t n_outer, const mxg_seq_piece *inner,
+                       const uint64_t *inner_first, uint64_t n_inner, const mxg_seq_piece **pieces, const uint64_t **first)
+{
+    if (!h) return MXG_EINVAL;
+    if (!pieces || !first || !outer_first || !inner_first || (n_outer && outer_first[n_outer] && !outer) ||
+        (n_inner && inner_first[n_inner] && !inner))
+        return set_err(h, MXG_EINVAL, "mxg_compose_pieces: null argument");
+    int rc;
+    try {
+        rc = compose_pieces(h, outer, outer_first, n_outer, inner, inner_first, n_inner);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_compose_pieces");
+    }
+    if (rc != MXG_OK) return rc;
+    *pieces = h->cmp_pieces.data();
+    *first = h->cmp_first.data();
+    return MXG_OK;
 }
 
 int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals)

@@ -219,9 +219,40 @@ struct Hdr {
     uint64_t at, end;  // '>' and its line's '\n' (or the text's end)
 };
 
+// a device allocation that failed for want of room: "not for this route" where another route exists
+static bool soft_alloc_failure(hipError_t e)
+{
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation;
+}
+
+// The header lines of a text that lies in HBM (padded to whole tiles), in three steps so that a caller can put work of its own in
+// front of the first sync: hdr_scan_alloc; hdr_scan_count enqueues the count and its scan (n_hdr is there once `st` is synchronised,
+// which is the caller's to do); hdr_scan_lines brings the lines back (hdr; line r's bytes behind its '>' are lines[line_off[r] ...]).
+struct HdrScan {
+    DevBuf d_bsum, d_total, d_at, d_end, d_off, d_lines;  // (scratch of one call: freed with the struct)
+    uint64_t n_tiles = 0, n_hdr = 0;
+};
+static hipError_t hdr_scan_alloc(HdrScan &s, uint64_t usz)  // usz below 2^31 tiles
+{
+    s.n_tiles = (usz + ING_TILE - 1) / ING_TILE;
+    hipError_t e = s.d_bsum.ensure(s.n_tiles * 4);
+    return e != hipSuccess ? e : s.d_total.ensure(16);
+}
+static int hdr_scan_count(mxg_handle *h, HdrScan &s, const unsigned char *d_text, uint64_t usz, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_hdr_count, dim3((uint32_t)s.n_tiles), dim3(256), 0, st, d_text, usz, s.d_bsum.as<uint32_t>());
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, s.d_bsum.as<uint32_t>(), (uint32_t)s.n_tiles, s.d_total.as<uint64_t>());
+    MXG_HIP(h, hipGetLastError());
+    MXG_HIP(h, hipMemcpyAsync(&s.n_hdr, s.d_total.p, 8, hipMemcpyDeviceToHost, st));
+    return MXG_OK;
+}
+static int hdr_scan_lines(mxg_handle *h, const char *path, HdrScan &s, const unsigned char *d_text, uint64_t usz, hipStream_t st,
+                          std::vector<Hdr> &hdr, std::vector<unsigned char> &lines, std::vector<uint64_t> &line_off);
+
 // The BGZF route between the upload and the work items: the members inflated into d_text, the header lines found there and brought
-// back (hdr; line r's bytes behind its '>' are lines[line_off[r] ...]).  MXG_OK, a negative error, or 1: a member's data or CRC is
-// not in order (the host parser and zlib then say what is wrong with the file).
+// back.  MXG_OK, a negative error, or 1: a member's data or CRC is not in order (the host parser and zlib then say what is wrong
+// with the file), or no room on the device (the host parser takes the file).
 static int bgzf_text_and_headers(mxg_handle *h, const char *path, const BgzfPlan &plan, const unsigned char *d_comp, uint64_t comp_bytes,
                                  unsigned char *d_text, hipStream_t st, bool dbg_io, std::vector<Hdr> &hdr, std::vector<unsigned char> &lines,
                                  std::vector<uint64_t> &line_off)
@@ -231,34 +262,36 @@ static int bgzf_text_and_headers(mxg_handle *h, const char *path, const BgzfPlan
     const uint64_t usz = plan.usz;
     const size_t n_mem = plan.members.size();
     if (n_mem >= (1ull << 31)) return 1;
-    auto soft = [&](hipError_t e) {  // (no room on the device: the host parser takes the file)
-        (void)hipGetLastError();
-        return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation;
-    };
-    DevBuf d_mem, d_status, d_bsum, d_total, d_at, d_end, d_off, d_lines;  // (scratch of this call: freed when it returns)
+    DevBuf d_mem, d_status;  // (scratch of this call: freed when it returns)
+    HdrScan scan;
     hipError_t e;
-    const uint64_t n_tiles = (usz + ING_TILE - 1) / ING_TILE;
-    if (n_tiles >= (1ull << 31)) return 1;
+    if ((usz + ING_TILE - 1) / ING_TILE >= (1ull << 31)) return 1;
     if ((e = d_mem.ensure(n_mem * sizeof(BgzfMember))) != hipSuccess || (e = d_status.ensure((n_mem + 1) * 4)) != hipSuccess ||
-        (e = d_bsum.ensure(n_tiles * 4)) != hipSuccess || (e = d_total.ensure(16)) != hipSuccess)
-        return soft(e) ? 1 : set_err(h, MXG_EDEVICE, "device allocation failed: %s", hipGetErrorString(e));
+        (e = hdr_scan_alloc(scan, usz)) != hipSuccess)
+        return soft_alloc_failure(e) ? 1 : set_err(h, MXG_EDEVICE, "device allocation failed: %s", hipGetErrorString(e));
     MXG_HIP(h, hipMemcpyAsync(d_mem.p, plan.members.data(), n_mem * sizeof(BgzfMember), hipMemcpyHostToDevice, st));
     int rc = bgzf_inflate_device(h, d_comp, comp_bytes, d_mem.as<BgzfMember>(), (uint32_t)n_mem, d_text, usz, d_status.as<uint32_t>(), st);
     if (rc != MXG_OK) return rc;
     uint32_t fail = 0;
     MXG_HIP(h, hipMemcpyAsync(&fail, d_status.p, 4, hipMemcpyDeviceToHost, st));
     // (the header count does not wait for the verdict: a member that failed left bytes inside its own range of the text, no more)
-    hipLaunchKernelGGL(k_hdr_count, dim3((uint32_t)n_tiles), dim3(256), 0, st, d_text, usz, d_bsum.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, d_bsum.as<uint32_t>(), (uint32_t)n_tiles, d_total.as<uint64_t>());
-    MXG_HIP(h, hipGetLastError());
-    uint64_t n_hdr = 0;
-    MXG_HIP(h, hipMemcpyAsync(&n_hdr, d_total.p, 8, hipMemcpyDeviceToHost, st));
+    if ((rc = hdr_scan_count(h, scan, d_text, usz, st)) != MXG_OK) return rc;
     MXG_HIP(h, hipStreamSynchronize(st));
     const double t_inf = now_s() - t0;  // (the kernel and, beside it, one pass over the text)
     if (fail != 0) return 1;
     if (dbg_io)
         fprintf(stderr, "[mxg] bgzf_inflate members=%llu bytes_in=%llu bytes_out=%llu ms=%.3f\n", (unsigned long long)n_mem,
                 (unsigned long long)comp_bytes, (unsigned long long)usz, t_inf * 1e3);
+    return hdr_scan_lines(h, path, scan, d_text, usz, st, hdr, lines, line_off);
+}
+
+static int hdr_scan_lines(mxg_handle *h, const char *path, HdrScan &s, const unsigned char *d_text, uint64_t usz, hipStream_t st,
+                          std::vector<Hdr> &hdr, std::vector<unsigned char> &lines, std::vector<uint64_t> &line_off)
+{
+    DevBuf &d_bsum = s.d_bsum, &d_at = s.d_at, &d_end = s.d_end, &d_off = s.d_off, &d_lines = s.d_lines;
+    const uint64_t n_hdr = s.n_hdr, n_tiles = s.n_tiles;
+    auto soft = soft_alloc_failure;
+    hipError_t e;
     if (n_hdr >= (1ull << 32)) return set_err(h, MXG_ELIMIT, "too many records in '%s'", path);
     hdr.resize(n_hdr);
     line_off.assign(n_hdr + 1, 0);
@@ -293,15 +326,23 @@ static int bgzf_text_and_headers(mxg_handle *h, const char *path, const BgzfPlan
     return MXG_OK;
 }
 
+struct IngestTimes {  // MXG_DEBUG_IO: seconds since t0 at which ingest_text's phases ended
+    double t0 = 0, hdr = 0, up = 0, count = 0, pack = 0;
+};
+enum class IngestRefusal { None, NoRoom, Events };  // why ingest_text answered "not for this route"
+static int ingest_text(mxg_handle *h, Assembly *a, const char *path, const std::vector<Hdr> &hdr, const unsigned char *txt,
+                       const std::vector<unsigned char> &hdr_lines, const std::vector<uint64_t> &hdr_line_off, uint64_t tsz, unsigned char *d_text,
+                       const std::function<int()> &text_ready, IngestTimes &tp, IngestRefusal &why);
+static void drop_device_text_if_asked(mxg_handle *h, Assembly *a);
+
 // returns MXG_OK, a negative error, or 1: "not for this route" (the caller falls back to the host parser)
 int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_threads)
 {
-    const uint32_t k = h->cfg.k, w = h->cfg.w;
     n_threads = std::max(1u, std::min(n_threads, 64u));
     const bool dbg_io = getenv("MXG_DEBUG_IO") != nullptr;  // phase timings on stderr
     auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double tp0 = now_s();
-    double tp_alloc = 0, tp_pool = 0, tp_hdr = 0, tp_up = 0, tp_count = 0, tp_pack = 0;
+    double tp_alloc = 0, tp_pool = 0;
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return set_err(h, MXG_EIO, "cannot open FASTA '%s'", path);
     struct stat sb;
@@ -352,10 +393,7 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
     // ---- (2) raw text -> HBM through pinned staging buffers, started first so that it overlaps the header scan ----
     // A device allocation that fails here (the route keeps ~1 byte per base of text in HBM) is no error: the host parser
     // takes the file instead (return 1; nothing has been committed to `a` that the caller's delete / new does not undo).
-    auto dev_fallback = [&](hipError_t e) {
-        (void)hipGetLastError();
-        return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation;
-    };
+    auto dev_fallback = soft_alloc_failure;
     const uint64_t text_alloc = ((tsz + ING_TILE - 1) / ING_TILE + 1) * ING_TILE;
     DevBuf d_comp;  // BGZF: the file's bytes, released as soon as the text is inflated (whole words: the decoder fetches aligned words)
     {
@@ -473,6 +511,44 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
     for (auto &v : found)
         for (auto &x : v)
             if (hdr.empty() || x.at > hdr.back().end) hdr.push_back(x);  // (a chunk border inside a header line)
+    IngestTimes tp;
+    tp.t0 = tp0;
+    IngestRefusal why = IngestRefusal::None;
+    const int rc = ingest_text(h, a, path, hdr, bgzf ? nullptr : txt, hdr_lines, hdr_line_off, tsz, d_text, [&]() {
+        sg.finish();  // the text is in HBM
+        tp.up = now_s() - tp0;
+        return uerr == hipSuccess ? MXG_OK : set_err(h, MXG_EDEVICE, "text upload failed: %s", hipGetErrorString(uerr));
+    }, tp, why);
+    if (rc != MXG_OK) return rc;
+    a->from_bgzf = bgzf;
+    for (const BgzfMember &m : plan.members) {
+        a->bgzf_comp_off.push_back(m.in_off - m.head);
+        a->bgzf_text_off.push_back(m.out_off);
+    }
+    if (dbg_io)
+        fprintf(stderr, "[mxg] load_fasta_device %s: %.3f s = open + map + text buffer %.3f, first pinned buffer at %.3f, headers + items (beside the "
+                        "upload) until %.3f, upload done at %.3f, base counts at %.3f, packed at %.3f, run table at %.3f (%.2f GB)\n", path, now_s() - tp0,
+                tp_alloc, tp_pool, tp.hdr, bgzf ? tp_bgzf : tp.up, tp.count, tp.pack, now_s() - tp0, tsz / 1e9);
+    drop_device_text_if_asked(h, a);
+    return rc;
+}
+
+// Everything behind the header lines, for a text that is (or is about to be) in HBM at d_text, padded with '\n' to whole tiles plus
+// one: the work items, the base counts, record lengths and the packed layout, the packed bases, the run table.  Header line r is
+// txt[hdr[r].at + 1 .. hdr[r].end) where the host has the text, else hdr_lines[hdr_line_off[r] ...].  text_ready is called once,
+// after the items are on their way and before the first kernel reads the text.  MXG_OK, a negative error, or 1: "not for this
+// route" (why says which limit it was).
+static int ingest_text(mxg_handle *h, Assembly *a, const char *path, const std::vector<Hdr> &hdr, const unsigned char *txt,
+                       const std::vector<unsigned char> &hdr_lines, const std::vector<uint64_t> &hdr_line_off, uint64_t tsz, unsigned char *d_text,
+                       const std::function<int()> &text_ready, IngestTimes &tp, IngestRefusal &why)
+{
+    const uint32_t k = h->cfg.k, w = h->cfg.w;
+    auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double tp0 = tp.t0;
+    auto dev_fallback = [&](hipError_t e) {
+        why = IngestRefusal::NoRoom;
+        return soft_alloc_failure(e);
+    };
     const size_t n_rec = hdr.size();
     if (n_rec >= (1ull << 32)) return set_err(h, MXG_ELIMIT, "too many records in '%s'", path);
     // ---- work items: the tiles every record's sequence text overlaps ----
@@ -481,7 +557,7 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
     a->recs.resize(n_rec);
     for (size_t r = 0; r < n_rec; ++r) {
         const uint64_t sb0 = std::min(hdr[r].end + 1, tsz), se = r + 1 < n_rec ? hdr[r + 1].at : tsz;
-        a->recs[r].id = header_token(bgzf ? hdr_lines.data() + hdr_line_off[r] : txt + hdr[r].at + 1, hdr[r].end - hdr[r].at - 1);
+        a->recs[r].id = header_token(txt ? txt + hdr[r].at + 1 : hdr_lines.data() + hdr_line_off[r], hdr[r].end - hdr[r].at - 1);
         a->recs[r].text_off = sb0;
         rec_item0[r] = items.size();
         for (uint64_t p = sb0; p < se;) {
@@ -504,10 +580,8 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
         if ((e = hipMemcpyAsync(d_items.p, items.data(), n_items * sizeof(IngItem), hipMemcpyHostToDevice, st)) != hipSuccess)
             return set_err(h, MXG_EDEVICE, "upload failed: %s", hipGetErrorString(e));
     }
-    tp_hdr = now_s() - tp0;
-    sg.finish();  // the text is in HBM
-    tp_up = now_s() - tp0;
-    if (uerr != hipSuccess) return set_err(h, MXG_EDEVICE, "text upload failed: %s", hipGetErrorString(uerr));
+    tp.hdr = now_s() - tp0;
+    if ((rc = text_ready()) != MXG_OK) return rc;
     std::vector<uint32_t> cnt(n_items);
     if (n_items) {
         hipLaunchKernelGGL(k_ing_count, dim3((uint32_t)n_items), dim3(256), 0, st, d_text, d_items.as<IngItem>(), d_cnt.as<uint32_t>(),
@@ -516,7 +590,7 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
         MXG_HIP(h, hipMemcpyAsync(cnt.data(), d_cnt.p, n_items * 4, hipMemcpyDeviceToHost, st));
         MXG_HIP(h, hipStreamSynchronize(st));
     }
-    tp_count = now_s() - tp0;
+    tp.count = now_s() - tp0;
     // ---- (3) record lengths, packed layout (every record starts at a multiple of 16 bases) ----
     std::vector<uint64_t> pbase(n_items);
     uint64_t cur = 0;
@@ -564,7 +638,10 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
         MXG_HIP(h, hipMemcpyAsync(&n_ev, d_evn.p, 4, hipMemcpyDeviceToHost, st));
         MXG_HIP(h, hipStreamSynchronize(st));
         // more changes than the buffer holds (drafts with scattered N / IUPAC codes): the host parser has no such limit
-        if (n_ev > EV_CAP) return 1;
+        if (n_ev > EV_CAP) {
+            why = IngestRefusal::Events;
+            return 1;
+        }
         events.resize(n_ev);
         if (n_ev) {
             MXG_HIP(h, hipMemcpy(events.data(), d_ev.p, (size_t)n_ev * sizeof(IngEvent), hipMemcpyDeviceToHost));
@@ -572,7 +649,7 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
         }
     }
     a->d_packed = a->d_packed_own.as<uint32_t>();
-    tp_pack = now_s() - tp0;
+    tp.pack = now_s() - tp0;
     // ---- the run table: maximal stretches of valid bases holding at least one k-mer ----
     size_t ev_i = 0;
     for (size_t r = 0; r < n_rec; ++r) {
@@ -627,16 +704,63 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
     a->has_text = false;
     a->text_on_device = true;
     a->text_bytes = tsz;
-    a->from_bgzf = bgzf;
-    for (const BgzfMember &m : plan.members) {
-        a->bgzf_comp_off.push_back(m.in_off - m.head);
-        a->bgzf_text_off.push_back(m.out_off);
-    }
     a->ing_item0.assign(rec_item0.begin(), rec_item0.end());
+    return rc;
+}
+
+// mxg_add_assembly_text_device: FASTA text that lies in HBM already (another handle's, or a scaffold stage's) becomes this assembly's
+// text by one device-to-device copy; header lines by the kernels of the BGZF route, the rest by ingest_text.  There is no host parser
+// to hand the text to: what the file route answers with "not for this route" is MXG_ELIMIT / MXG_ENOMEM here.
+int load_text_device(mxg_handle *h, Assembly *a, const void *d_src, uint64_t n_bytes)
+{
+    const char *what = a->name.c_str();
+    const bool dbg_io = getenv("MXG_DEBUG_IO") != nullptr;
+    auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    IngestTimes tp;
+    tp.t0 = now_s();
+    const uint64_t n_tiles = (n_bytes + ING_TILE - 1) / ING_TILE;
+    if (n_tiles >= (1ull << 31)) return set_err(h, MXG_ELIMIT, "mxg_add_assembly_text_device: %llu bytes are too many for one handle", (unsigned long long)n_bytes);
+    MXG_HIP(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const uint64_t text_alloc = (n_tiles + 1) * ING_TILE;  // (as load_fasta_device allocates and pads it)
+    HdrScan scan;
+    hipError_t e = a->d_text.ensure(text_alloc);
+    if (e == hipSuccess && n_bytes) e = hdr_scan_alloc(scan, n_bytes);
+    if (e != hipSuccess)
+        return soft_alloc_failure(e) ? set_err(h, MXG_ENOMEM, "mxg_add_assembly_text_device: no room on the device for a copy of the text (%llu bytes)",
+                                               (unsigned long long)n_bytes)
+                                     : set_err(h, MXG_EDEVICE, "device allocation failed: %s", hipGetErrorString(e));
+    unsigned char *d_text = a->d_text.as<unsigned char>();
+    if (n_bytes) MXG_HIP(h, hipMemcpyAsync(d_text, d_src, n_bytes, hipMemcpyDeviceToDevice, st));
+    MXG_HIP(h, hipMemsetAsync(d_text + n_bytes, '\n', text_alloc - n_bytes, st));
+    std::vector<Hdr> hdr;
+    std::vector<unsigned char> hdr_lines;
+    std::vector<uint64_t> hdr_line_off(1, 0);
+    int rc = MXG_OK;
+    if (n_bytes) {
+        if ((rc = hdr_scan_count(h, scan, d_text, n_bytes, st)) != MXG_OK) return rc;
+        MXG_HIP(h, hipStreamSynchronize(st));  // (the source is free from here on)
+        rc = hdr_scan_lines(h, what, scan, d_text, n_bytes, st, hdr, hdr_lines, hdr_line_off);
+    } else {
+        MXG_HIP(h, hipStreamSynchronize(st));
+    }
+    IngestRefusal why = IngestRefusal::NoRoom;
+    if (rc == MXG_OK) rc = ingest_text(h, a, what, hdr, nullptr, hdr_lines, hdr_line_off, n_bytes, d_text, []() { return MXG_OK; }, tp, why);
+    if (rc == 1)
+        return why == IngestRefusal::Events
+                   ? set_err(h, MXG_ELIMIT, "mxg_add_assembly_text_device: '%s' has more changes between valid and invalid bases than the device "
+                                            "route records (MXG_INGEST_EV_CAP), and text on the device has no host parser to go to", what)
+                   : set_err(h, MXG_ENOMEM, "mxg_add_assembly_text_device: no room on the device for the tables of '%s'", what);
+    if (rc != MXG_OK) return rc;
     if (dbg_io)
-        fprintf(stderr, "[mxg] load_fasta_device %s: %.3f s = open + map + text buffer %.3f, first pinned buffer at %.3f, headers + items (beside the "
-                        "upload) until %.3f, upload done at %.3f, base counts at %.3f, packed at %.3f, run table at %.3f (%.2f GB)\n", path, now_s() - tp0,
-                tp_alloc, tp_pool, tp_hdr, bgzf ? tp_bgzf : tp_up, tp_count, tp_pack, now_s() - tp0, tsz / 1e9);
+        fprintf(stderr, "[mxg] load_text_device %s: %.3f s = copy + headers + items until %.3f, base counts at %.3f, packed at %.3f, run table at "
+                        "%.3f (%.2f GB)\n", what, now_s() - tp.t0, tp.hdr, tp.count, tp.pack, now_s() - tp.t0, n_bytes / 1e9);
+    drop_device_text_if_asked(h, a);
+    return rc;
+}
+
+static void drop_device_text_if_asked(mxg_handle *h, Assembly *a)
+{
     if (h->cfg.flags & MXG_FLAG_DROP_SEQ) {  // the caller does not want the text kept: k-mers are then printed from the packed bases
         a->d_text.release();
         a->d_ing_items.release();
@@ -645,7 +769,6 @@ int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_t
         a->d_ing_cnt.release();
         a->text_on_device = false;
     }
-    return rc;
 }
 
 // ======================================================================================================

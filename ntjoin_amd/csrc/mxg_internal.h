@@ -284,6 +284,18 @@ struct mxg_handle {
     mxg::DevBuf adjbuf[32];  // scratch of adjust.hip
     std::vector<mxg_adjust_node> adj_nodes;      // the last mxg_adjust_paths' result (what its view points into)
     std::vector<uint64_t> adj_first, adj_source;
+    // MXG_SCAF_KEEP: the text of both scaffold files of the last mxg_write_scaffolds, resident (mxg_scaffold_text), what its records
+    // are made of (mxg_scaffold_pieces) and their names (mxg_scaffold_record_id); valid until the next mxg_write_scaffolds
+    mxg::DevBuf scaf_keep;
+    bool scaf_keep_valid = false;
+    uint64_t scaf_keep_bytes = 0;
+    int scaf_keep_asm = -1;
+    std::vector<mxg_seq_piece> scaf_keep_pieces;
+    std::vector<uint64_t> scaf_keep_first;
+    std::vector<std::string> scaf_keep_id;
+    mxg::DevBuf cmpbuf[16];  // scratch of compose.hip
+    std::vector<mxg_seq_piece> cmp_pieces;       // the last mxg_compose_pieces' result (what its pointers point into)
+    std::vector<uint64_t> cmp_first;
     std::vector<uint32_t> scaf_lead, scaf_tail;  // N/n stripped from either end of every unassigned interval by the last mxg_write_scaffolds
     struct ScafInterval {
         uint32_t rec, lo, hi, lead, tail;
@@ -421,6 +433,8 @@ void build_runs_from_lengths(mxg_handle *h, Assembly *a);  // N-free packed-devi
 int write_tsv(mxg_handle *h, Assembly *a, const char *path, int with_pos, int with_strand, int with_seq);
 // ingest.hip: FASTA -> packed bases + run table on the device (1: not for this route, use load_fasta); TSV text on the device
 int load_fasta_device(mxg_handle *h, Assembly *a, const char *path, uint32_t n_threads);
+// ... and of FASTA text that lies in HBM already (mxg_add_assembly_text_device): MXG_OK or a negative error
+int load_text_device(mxg_handle *h, Assembly *a, const void *d_src, uint64_t n_bytes);
 int write_tsv_device(mxg_handle *h, Assembly *a, const char *path, int with_pos, int with_strand, int with_seq);
 int fetch_device_text(mxg_handle *h, Assembly *a, std::string &seq, std::vector<uint64_t> &rec_off);  // (for the host TSV writer)
 uint32_t host_threads(const mxg_handle *h);
@@ -617,6 +631,9 @@ int report_file_end(mxg_handle *h, int which, std::vector<uint64_t> &&rec_len, c
 void report_fill(const SeqReportHost &r, std::vector<uint64_t> &scratch, mxg_seq_report *out);
 // adjust.hip: relocations, --no_cut and overlapping regions of the given paths (mxg_adjust_paths); fills h->adj_*
 int adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *path_first, uint64_t n_paths, const mxg_adjust_params &p);
+// compose.hip: two piece tables composed (mxg_compose_pieces); fills h->cmp_*
+int compose_pieces(mxg_handle *h, const mxg_seq_piece *outer, const uint64_t *outer_first, uint64_t n_outer, const mxg_seq_piece *inner,
+                   const uint64_t *inner_first, uint64_t n_inner);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm
 int flags_to_host(mxg_handle *h, Assembly *a);
 

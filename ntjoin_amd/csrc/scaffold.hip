@@ -205,6 +205,13 @@ struct PieceTable {
         add(SP_LIT, s.size(), lits.size());
         lits += s;
     }
+    // o's pieces behind this table's, their offsets moved (before o gets its end piece: scaf_emit_file)
+    void append(const PieceTable &o)
+    {
+        for (const ScafPiece &pc : o.pieces) pieces.push_back(ScafPiece{pc.out + total, pc.kind == SP_LIT ? pc.src + lits.size() : pc.src, pc.rec, pc.kind});
+        lits += o.lits;
+        total += o.total;
+    }
 };
 
 }  // namespace
@@ -247,11 +254,50 @@ static int scaf_emit_file(mxg_handle *h, const ScafText &t, PieceTable &pt, uint
     return write_windows(h, of, total, WIN, 0, fill, who);
 }
 
+// MXG_SCAF_KEEP: the combined table (the assigned file's pieces, then the unassigned file's) emitted straight into the handle's
+// resident buffer: SCAF_TILE alignment holds for the whole buffer, the unassigned part needs no unaligned copy.  fold applies to the
+// first fold_end bytes only (the assigned file's): the tiles from the one that holds byte fold_end on are emitted unfolded first, then
+// the tiles up to fold_end folded -- the tile both reach into is written twice, its first fold_end % SCAF_TILE bytes last.
+static int scaf_emit_keep(mxg_handle *h, const ScafText &t, PieceTable &pt, uint32_t fold, uint64_t fold_end)
+{
+    hipStream_t st = h->stream;
+    DevBuf *B = h->scbuf;
+    const uint64_t total = pt.total;
+    const size_t n_pieces = pt.pieces.size();
+    if (n_pieces >= 0xFFFFFFFFull) return set_err(h, MXG_ELIMIT, "mxg_write_scaffolds: too many pieces of output for one call");
+    MXG_HIP(h, h->scaf_keep.ensure((total + SCAF_TILE - 1) / SCAF_TILE * SCAF_TILE + SCAF_TILE));
+    if (!total) return MXG_OK;
+    pt.pieces.push_back(ScafPiece{total, 0, 0, SP_LIT});  // (the end of the last piece)
+    MXG_HIP(h, B[SC_PIECES].ensure((n_pieces + 1) * sizeof(ScafPiece)));
+    MXG_HIP(h, B[SC_LITS].ensure(pt.lits.size() + 16));
+    MXG_HIP(h, hipMemcpyAsync(B[SC_PIECES].p, pt.pieces.data(), (n_pieces + 1) * sizeof(ScafPiece), hipMemcpyHostToDevice, st));
+    if (!pt.lits.empty()) MXG_HIP(h, hipMemcpyAsync(B[SC_LITS].p, pt.lits.data(), pt.lits.size(), hipMemcpyHostToDevice, st));
+    unsigned char *d_keep = h->scaf_keep.as<unsigned char>();
+    auto emit = [&](uint64_t lo, uint64_t hi, uint32_t f) {  // lo: a multiple of SCAF_TILE
+        if (lo >= hi) return;
+        hipLaunchKernelGGL(k_scaf_emit, dim3((uint32_t)((hi - lo + SCAF_TILE - 1) / SCAF_TILE)), dim3(256), 0, st, t, B[SC_PIECES].as<ScafPiece>(),
+                           (uint32_t)n_pieces, B[SC_LITS].as<unsigned char>(), f, d_keep + lo, lo, hi);
+    };
+    if (fold && fold_end) {
+        emit(fold_end / SCAF_TILE * SCAF_TILE, total, 0u);
+        emit(0, std::min(fold_end, total), 1u);
+    } else {
+        emit(0, total, 0u);
+    }
+    MXG_HIP(h, hipGetLastError());
+    MXG_HIP(h, hipStreamSynchronize(st));  // (the piece table is the caller's)
+    return MXG_OK;
+}
+
 int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold_node *nodes, const uint64_t *path_first, uint64_t n_paths,
                     int32_t overlap_gap, uint32_t flags, const char *assigned_fa, const char *unassigned_fa, const char *unassigned_bed,
                     uint32_t *lead_strip, uint32_t *tail_strip, uint64_t *n_unassigned)
 {
     const uint64_t n_nodes = n_paths ? path_first[n_paths] : 0;
+    const bool keep = (flags & MXG_SCAF_KEEP) != 0;
+    h->scaf_keep_valid = false;  // (the kept text of the call before holds until this one)
+    if (!assigned_fa && (flags & (MXG_SCAF_BGZF | MXG_SCAF_FAI | MXG_SCAF_REPORT)))
+        return set_err(h, MXG_EINVAL, "mxg_write_scaffolds: MXG_SCAF_BGZF, MXG_SCAF_FAI and MXG_SCAF_REPORT need assigned_fa, the file they are about");
     if (n_nodes >= (1ull << 31)) return set_err(h, MXG_ELIMIT, "mxg_write_scaffolds: %llu nodes (fewer than 2^31)", (unsigned long long)n_nodes);
     const bool indexed = a->text_on_device && a->d_text.p;
     if (a->holds_pieces || a->shard_lo != 0 || a->shard_hi < a->recs.size())
@@ -304,7 +350,7 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
         uint32_t rec, lo, hi;
     };
     std::vector<Iv> gaps;
-    const bool want_un = unassigned_fa || unassigned_bed || n_unassigned;
+    const bool want_un = unassigned_fa || unassigned_bed || n_unassigned || keep;
     if (want_un) {
         std::vector<Iv> used(n_nodes);
         for (uint64_t i = 0; i < n_nodes; ++i) used[i] = Iv{nodes[i].record, nodes[i].start, nodes[i].end};
@@ -415,12 +461,17 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
         return write_gzi(h, ix.gzi, ix.member_off, text_off);
     };
     OutFile fa, ufa, bed;
-    if (!fa.open(assigned_fa)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", assigned_fa);
+    if (assigned_fa && !fa.open(assigned_fa)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", assigned_fa);
     if (unassigned_fa && !ufa.open(unassigned_fa)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", unassigned_fa);
     if (unassigned_bed && !bed.open(unassigned_bed)) return set_err(h, MXG_EIO, "cannot open '%s' for writing", unassigned_bed);
     int rc;
     if (with_fai && (rc = open_index(ix_fa, assigned_fa)) != MXG_OK) return rc;
     if (with_fai && unassigned_fa && (rc = open_index(ix_ufa, unassigned_fa)) != MXG_OK) return rc;
+    PieceTable kept;  // MXG_SCAF_KEEP: both files' pieces in one table
+    std::vector<mxg_seq_piece> kp;  // ... and what their records are made of (mxg_scaffold_pieces)
+    std::vector<uint64_t> kp_first(1, 0);
+    std::vector<std::string> kp_id;
+    uint64_t kept_fold_end = 0;
     {
         PieceTable pt;
         pt.pieces.reserve(2 * n_nodes + 2 * n_paths + 1);
@@ -442,16 +493,27 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
                 if (y > x) {
                     if (in.reverse) pt.add(SP_REV, y - x, (uint64_t)in.end - 1 - x, in.record);
                     else pt.add(SP_FWD, y - x, (uint64_t)in.start + x, in.record);
+                    if (keep && in.reverse) kp.push_back(mxg_seq_piece{in.record, in.end - y, in.end - x, MXG_PIECE_REV});
+                    if (keep && !in.reverse) kp.push_back(mxg_seq_piece{in.record, in.start + x, in.start + y, MXG_PIECE_FWD});
                 }
                 pt.add(SP_FILL, fill);
+                if (keep && fill) kp.push_back(mxg_seq_piece{0, 0, fill, MXG_PIECE_GAP});
+            }
+            if (keep) {
+                kp_first.push_back(kp.size());
+                kp_id.push_back("ntJoin" + std::to_string(p));
             }
             if (with_fai) ix_fa.recs.push_back(FaiOutRec{pt.total - seq0, (uint32_t)(seq0 - head0), 0u, 0u, 0u});
             if (with_rep) rep_len.push_back(pt.total - seq0);
             pt.literal("\n");
             if (lead_strip) lead_strip[p] = lead;
         }
-        if ((rc = scaf_emit_file(h, t, pt, flags & MXG_SCAF_FOLD_CASE ? 1u : 0u, fa, WIN, bgzf_P, with_fai ? &ix_fa.member_off : nullptr, with_rep,
-                                 n_paths)) != MXG_OK)
+        if (keep) {
+            kept.append(pt);
+            kept_fold_end = pt.total;
+        }
+        if (assigned_fa && (rc = scaf_emit_file(h, t, pt, flags & MXG_SCAF_FOLD_CASE ? 1u : 0u, fa, WIN, bgzf_P, with_fai ? &ix_fa.member_off : nullptr,
+                                                with_rep, n_paths)) != MXG_OK)
             return rc;
         if (with_rep && (rc = report_file_end(h, MXG_REPORT_ASSIGNED, std::move(rep_len), assigned_fa)) != MXG_OK) return rc;
         if (with_fai && (rc = write_index(ix_fa, true)) != MXG_OK) return rc;
@@ -468,14 +530,20 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
             h->scaf_tail[g] = lead >= len ? 0 : tail;  // (N throughout: all of it counts as the lead)
             if (lead >= len) continue;  // N throughout: in the BED only
             ++n_un;
-            if (!unassigned_fa) continue;
+            if (!unassigned_fa && !keep) continue;
             const uint64_t head0 = pt.total;
             pt.literal(">" + a->recs[iv.rec].id + ":" + std::to_string(iv.lo) + "-" + std::to_string(iv.hi) + "\n");
             if (with_fai) ix_ufa.recs.push_back(FaiOutRec{(uint64_t)len - lead - tail, (uint32_t)(pt.total - head0), iv.rec, iv.lo, iv.hi});
             if (with_rep) rep_len.push_back((uint64_t)len - lead - tail);
             pt.add(SP_FWD, len - lead - tail, (uint64_t)iv.lo + lead, iv.rec);
             pt.literal("\n");
+            if (keep) {
+                kp.push_back(mxg_seq_piece{iv.rec, iv.lo + lead, iv.hi - tail, MXG_PIECE_FWD});
+                kp_first.push_back(kp.size());
+                kp_id.push_back(a->recs[iv.rec].id + ":" + std::to_string(iv.lo) + "-" + std::to_string(iv.hi));
+            }
         }
+        if (keep) kept.append(pt);
         if (with_rep) rep_len.shrink_to_fit();
         if (unassigned_fa && (rc = scaf_emit_file(h, t, pt, 0u, ufa, WIN, bgzf_P, with_fai ? &ix_ufa.member_off : nullptr, with_rep, rep_len.size())) !=
                                  MXG_OK)
@@ -492,6 +560,7 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
         for (const Iv &iv : gaps) fprintf(bed.f, "%s\t%u\t%u\n", a->recs[iv.rec].id.c_str(), iv.lo, iv.hi);
         if (ferror(bed.f)) return set_err(h, MXG_EIO, "write error on '%s'", unassigned_bed);
     }
+    if (keep && (rc = scaf_emit_keep(h, t, kept, flags & MXG_SCAF_FOLD_CASE ? 1u : 0u, kept_fold_end)) != MXG_OK) return rc;
     MXG_HIP(h, hipStreamSynchronize(st));
     const bool c_fa = fa.close(), c_ufa = ufa.close(), c_bed = bed.close();
     const bool c_fai = ix_fa.fai.close(), c_gzi = ix_fa.gzi.close(), c_ufai = ix_ufa.fai.close(), c_ugzi = ix_ufa.gzi.close();
@@ -500,6 +569,14 @@ int write_scaffolds(mxg_handle *h, Assembly *a, int assembly, const mxg_scaffold
     fa.complete = ufa.complete = bed.complete = true;
     ix_fa.fai.complete = ix_fa.gzi.complete = ix_ufa.fai.complete = ix_ufa.gzi.complete = true;
     if (n_unassigned) *n_unassigned = n_un;
+    if (keep) {
+        h->scaf_keep_bytes = kept.total;
+        h->scaf_keep_asm = assembly;
+        h->scaf_keep_pieces.swap(kp);
+        h->scaf_keep_first.swap(kp_first);
+        h->scaf_keep_id.swap(kp_id);
+        h->scaf_keep_valid = true;
+    }
     return MXG_OK;
 }
 

@@ -81,6 +81,20 @@ class MxEngine:
         return self._check(self._lib.mxg_add_assembly_fasta(self._h, str(name).encode(), float(weight),
                                                             str(fasta_path).encode()))
 
+    def add_text_device(self, name, weight, d_text, n_bytes):
+        """mxg_add_assembly_text_device: FASTA text that lies in device memory already (d_text: an address, e.g. assembly_text()'s
+        or a torch tensor's data_ptr()) is copied device to device and loaded as add_fasta loads a file with those bytes; the
+        source may go as soon as the call returns"""
+        return self._check(self._lib.mxg_add_assembly_text_device(self._h, str(name).encode(), float(weight), C.c_void_p(int(d_text) or None),
+                                                                  int(n_bytes)))
+
+    def assembly_text(self, a):
+        """mxg_assembly_text: (device address, bytes) of the FASTA text of an assembly that the device ingest route loaded; the
+        memory is the handle's"""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._check(self._lib.mxg_assembly_text(self._h, int(a), C.byref(p), C.byref(n)))
+        return int(p.value or 0), int(n.value)
+
     def add_fasta_shard(self, name, weight, fasta_path, shard, n_shards):
         """every record is registered (global indices) but only shard `shard` of `n_shards` is packed and sketched"""
         return self._check(self._lib.mxg_add_assembly_fasta_shard(self._h, str(name).encode(), float(weight),
@@ -457,19 +471,49 @@ class MxEngine:
             C.memmove(out.ctypes.data, v.nodes, n * self.ADJUST_NODE.itemsize)
         return {"nodes": out, "node_first": _np(v.node_first, int(v.n_paths) + 1, np.uint64), "source": _np(v.source, n, np.uint64)}
 
+    SEQ_PIECE = np.dtype([("record", "<u4"), ("start", "<u4"), ("end", "<u4"), ("kind", "<u4")])
+
+    def compose_pieces(self, outer, outer_first, inner, inner_first):
+        """mxg_compose_pieces: two piece tables (arrays of SEQ_PIECE or rows (record, start, end, kind), kind = capi.PIECE_FWD /
+        PIECE_REV / PIECE_GAP, and n_records + 1 offsets each); outer's records index inner's -> (pieces, first): outer's records
+        spelled over whatever inner refers to, neighbouring gaps joined (include/ntjoin_mx.h)."""
+        def table(pieces, first):
+            a = np.asarray(pieces)
+            if a.dtype != self.SEQ_PIECE:
+                rows = np.asarray(pieces, dtype=np.uint32).reshape(-1, 4)
+                a = np.zeros(len(rows), dtype=self.SEQ_PIECE)
+                for c, name in enumerate(self.SEQ_PIECE.names):
+                    a[name] = rows[:, c]
+            f = np.ascontiguousarray(first, dtype=np.uint64)
+            if f.ndim != 1 or len(f) < 1 or int(f[-1]) != len(a):
+                raise ValueError("compose_pieces: a table needs n_records + 1 offsets, the last one the number of its pieces")
+            return np.ascontiguousarray(a), f
+        op, of = table(outer, outer_first)
+        ip, jf = table(inner, inner_first)
+        pp, pf = C.c_void_p(), C.POINTER(C.c_uint64)()
+        self._check(self._lib.mxg_compose_pieces(self._h, op.ctypes.data, of.ctypes.data, len(of) - 1, ip.ctypes.data, jf.ctypes.data,
+                                                 len(jf) - 1, C.byref(pp), C.byref(pf)))
+        first = _np(pf, len(of), np.uint64)
+        out = np.zeros(int(first[-1]), dtype=self.SEQ_PIECE)
+        if len(out):
+            C.memmove(out.ctypes.data, pp, len(out) * self.SEQ_PIECE.itemsize)
+        return out, first
+
     SCAFFOLD_NODE = np.dtype([("record", "<u4"), ("start", "<u4"), ("end", "<u4"), ("gap_size", "<u4"), ("start_adjust", "<u4"),
                               ("end_adjust", "<u4"), ("reverse", "u1"), ("pad", "u1", (3,))])
 
     def write_scaffolds(self, assembly, rows, path_first, overlap_gap=None, fold_case=False, assigned=None, unassigned=None, bed=None,
-                        bgzf=False, fai=False, report=False):
+                        bgzf=False, fai=False, report=False, keep=False):
         """mxg_write_scaffolds: rows = array of SCAFFOLD_NODE (or rows (record, start, end, gap_size, start_adjust, end_adjust,
         reverse)), path_first = n_paths + 1 offsets; overlap_gap=None: the overlap stage is off (the adjustments are not read).
         Writes the scaffold FASTA `assigned` and, when named, the unassigned FASTA and BED -> dict(lead_strip u32[n_paths],
         tail_strip u32[n_paths]: N/n stripped from the scaffolds' ends, n_unassigned: records in the unassigned FASTA).
         bgzf=True: the two FASTA files are BGZF files of the same bytes, deflated on the device (MXG_SCAF_BGZF); fai=True: beside
         either FASTA its <name>.fai and, with bgzf, its <name>.gzi (MXG_SCAF_FAI); report=True: the windows of either FASTA go through
-        the report's passes on their way out (MXG_SCAF_REPORT; scaffold_report() hands the reports out)"""
-        if assigned is None:
+        the report's passes on their way out (MXG_SCAF_REPORT; scaffold_report() hands the reports out); keep=True: the bytes of both
+        FASTA files, one behind the other, stay in device memory (MXG_SCAF_KEEP; scaffold_text(), scaffold_pieces()), and no file
+        need be named"""
+        if assigned is None and not keep:
             raise ValueError("write_scaffolds: assigned= names the scaffold FASTA to write")
         nodes = self._scaffold_nodes(rows)
         pf = np.ascontiguousarray(path_first, dtype=np.uint64)
@@ -482,10 +526,27 @@ class MxEngine:
         self._check(self._lib.mxg_write_scaffolds(self._h, int(assembly), nodes.ctypes.data, pf.ctypes.data, n_paths,
                                                   -1 if overlap_gap is None else int(overlap_gap),
                                                   (capi.SCAF_FOLD_CASE if fold_case else 0) | (capi.SCAF_BGZF if bgzf else 0) | (capi.SCAF_FAI if fai else 0) |
-                                                  (capi.SCAF_REPORT if report else 0),
+                                                  (capi.SCAF_REPORT if report else 0) | (capi.SCAF_KEEP if keep else 0),
                                                   enc(assigned), enc(unassigned), enc(bed),
                                                   lead.ctypes.data, tail.ctypes.data, C.byref(n_un)))
         return {"lead_strip": lead, "tail_strip": tail, "n_unassigned": int(n_un.value)}
+
+    def scaffold_text(self):
+        """mxg_scaffold_text: (device address, bytes, records) of the text the last write_scaffolds(keep=True) left in device memory"""
+        p, n, r = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.mxg_scaffold_text(self._h, C.byref(p), C.byref(n), C.byref(r)))
+        return int(p.value or 0), int(n.value), int(r.value)
+
+    def scaffold_pieces(self):
+        """mxg_scaffold_pieces: what the records of the kept text are made of -> (pieces: array of SEQ_PIECE over the records of the
+        assembly the scaffolds were cut from, first: u64[n_records + 1], ids: the records' names)"""
+        pp, pf, n = C.c_void_p(), C.POINTER(C.c_uint64)(), C.c_uint64()
+        self._check(self._lib.mxg_scaffold_pieces(self._h, C.byref(pp), C.byref(pf), C.byref(n)))
+        first = _np(pf, int(n.value) + 1, np.uint64)
+        out = np.zeros(int(first[-1]), dtype=self.SEQ_PIECE)
+        if len(out):
+            C.memmove(out.ctypes.data, pp, len(out) * self.SEQ_PIECE.itemsize)
+        return out, first, [self._lib.mxg_scaffold_record_id(self._h, r).decode() for r in range(int(n.value))]
 
     def write_fai(self, assembly, path, gzi=None):
         """mxg_write_fai: the index `samtools faidx` makes of the assembly's FASTA, from the text the handle holds, written to `path`;

@@ -12,6 +12,7 @@ WRITTEN (checkpoint files, ntJoin:202 `.SECONDARY`) rather than read.
 """
 import datetime
 import math
+import os
 import re
 import sys
 
@@ -60,7 +61,7 @@ def mk_orientation(n, s, tie_term):
 class Ntjoin:
     "ntJoin hot path: minimizer sketches -> minimizer graph, on the GPU"
 
-    def __init__(self, args, fasta=None, w=None, variant="v2"):
+    def __init__(self, args, fasta=None, w=None, variant="v2", device_text=None, no_tsv=()):
         self.list_mx_info = {}  # assembly -> {mx: (contig, position)}
         self.list_mxs = {}      # assembly -> [lists of mx]
         self._graph = None
@@ -74,6 +75,11 @@ class Ntjoin:
             raise ValueError("Ntjoin(fasta=...): the window size w must be given when assemblies are sketched from FASTA")
         self._engine = MxEngine(k=int(getattr(args, "k", 32)), w=int(w if w is not None else 1), variant=variant)
         self._order = []
+        # rounds (ntjoin_amd/rounds.py): {tsv name: (device address, bytes)} of FASTA texts that lie in device memory already -- the
+        # assembly named in `fasta` is then loaded from that text, not from its file -- and the names whose TSV is not to be written
+        self._device_text = dict(device_text or {})
+        self._no_tsv = set(no_tsv)
+        self._last_print = None
 
     def close(self):
         self._engine.close()
@@ -95,9 +101,13 @@ class Ntjoin:
     # -- loading (reference order: refs in FILES order, then target) --------------------------------------
     def _add(self, assembly, weight):
         if assembly in self._fasta:
-            a = self._engine.add_fasta(assembly, weight, self._fasta[assembly])
+            if assembly in self._device_text:
+                a = self._engine.add_text_device(assembly, weight, *self._device_text[assembly])
+            else:
+                a = self._engine.add_fasta(assembly, weight, self._fasta[assembly])
             self._engine.sketch(a)
-            self._engine.write_tsv(a, assembly, with_pos=True, with_strand=False, with_seq=True)
+            if assembly not in self._no_tsv:
+                self._engine.write_tsv(a, assembly, with_pos=True, with_strand=False, with_seq=True)
         else:
             print(datetime.datetime.today(), ": Reading minimizers", assembly, file=sys.stdout)
             a = self._engine.add_tsv(assembly, weight, assembly)
@@ -365,14 +375,18 @@ class Ntjoin:
         at = res["node_first"].tolist()
         return [rows[lo:hi] for lo, hi in zip(at, at[1:])]
 
-    def scaffold(self, lengths=None):
+    def scaffold(self, lengths=None, keep=False, quiet=False):
         """main_scaffolder (:751-786) behind load_minimizers_scaffold in one handle: make_minimizer_graph -> find_paths ->
         format_paths -> adjust_paths -> trim_overlaps (when args.overlap) -> print_scaffolds.  Read from args, with ntJoin's
         defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz, fai, report,
         report_min_gap, report_min_len.  Returns what print_scaffolds returns (the written files by kind).  With args.fai the inputs
         read from FASTA get their <fasta>.fai first (write_input_indexes); with args.report <prefix>.report.tsv is written ("report":
-        write_report)."""
+        write_report).  keep / quiet: print_scaffolds' (a round of ntjoin_amd/rounds.py); a quiet round writes no .mx.dot, no index and
+        no report either."""
         opt = lambda name, dflt: dflt if getattr(self.args, name, None) is None else getattr(self.args, name)  # noqa: E731
+        if quiet:
+            opt = lambda name, dflt, _opt=opt: False if name in ("fai", "report") else _opt(name, dflt)  # noqa: E731
+        self._quiet = bool(quiet)
         if opt("fai", False):
             self.write_input_indexes()
         report = bool(opt("report", False))
@@ -386,7 +400,7 @@ class Ntjoin:
         paths = self.adjust_paths(paths, no_cut=bool(opt("no_cut", False)), G=G)
         cuts = self.trim_overlaps(paths, opt("overlap_k", 15), opt("overlap_w", 10)) if opt("overlap", False) else None
         files = self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)),
-                                     gz=bool(opt("gz", False)), fai=bool(opt("fai", False)), report=report)
+                                     gz=bool(opt("gz", False)), fai=bool(opt("fai", False)), report=report, keep=keep, quiet=quiet)
         if report:
             files["report"] = self.write_report(report_rows, files)
         return files
@@ -427,8 +441,10 @@ class Ntjoin:
             if fasta is None:
                 print(f"ntjoin_amd: {assembly} was loaded from its TSV: no FASTA index is written for it", file=sys.stderr)
                 continue
-            with open(fasta, "rb") as fh:
-                gzip_magic = fh.read(2) == b"\x1f\x8b"
+            gzip_magic = False   # (text that came from device memory never was compressed: ntjoin_amd/rounds.py)
+            if assembly not in self._device_text:
+                with open(fasta, "rb") as fh:
+                    gzip_magic = fh.read(2) == b"\x1f\x8b"
             try:
                 self._engine.write_fai(a, fasta + ".fai", gzi=fasta + ".gzi" if gzip_magic else None)
             except MxError as err:
@@ -552,7 +568,7 @@ class Ntjoin:
             if agp_fh:
                 agp_fh.close()
 
-    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False, report=False):
+    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False, report=False, keep=False, quiet=False):
         """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
         trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
         than two nodes are dropped (:585-594), the last kept node's gap is zeroed (check_terminal_node_gap_zero :441-448), and the
@@ -561,7 +577,10 @@ class Ntjoin:
         <p>.<target tsv>.unassigned.bed, <p>.path and, with agp=True, <p>.agp.  gz=True: the two FASTA files are BGZF files
         (`bgzip`'s format, deflated on the device) named ...scaffolds.fa.gz.  fai=True: beside either FASTA its .fai ("assigned_fai",
         "unassigned_fai") and, with gz, its .gzi ("assigned_gzi", "unassigned_gzi").  report=True: either FASTA goes through the report's
-        passes on its way out (MxEngine.scaffold_report hands the reports out; no file more).  Returns the file names by kind."""
+        passes on its way out (MxEngine.scaffold_report hands the reports out; no file more).  keep=True: the text of both FASTA files
+        also stays in device memory (MXG_SCAF_KEEP: MxEngine.scaffold_text, scaffold_pieces).  quiet=True (with keep): only <p>.path
+        and, with agp, <p>.agp are written -- an earlier round of ntjoin_amd/rounds.py.  Returns the file names by kind."""
+        self._last_print = dict(paths=paths, adjust=adjust, n=n, agp=agp, overlap_gap=overlap_gap, gz=gz, fai=fai, report=report)
         eng, tgt = self._engine, len(self._order) - 1
         if tgt < 0:
             raise ValueError("print_scaffolds: no target assembly has been loaded")
@@ -596,9 +615,17 @@ class Ntjoin:
         files = {"assigned": prefix + ".assigned.scaffolds" + ext, "unassigned": prefix + ".unassigned.scaffolds" + ext,
                  "bed": self.args.p + "." + target + ".unassigned.bed", "path": self.args.p + ".path"}
         print(datetime.datetime.today(), ": Printing output scaffolds", file=sys.stdout)
-        res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
-                                  assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz),
-                                  **({"fai": True} if fai else {}), **({"report": True} if report else {}))
+        if quiet:
+            # (the BED is what the host loop below reads the AGP's unassigned lines from, should the library refuse the paths: kept
+            # under a name of its own until the .path is written)
+            bed_tmp = files["bed"] + ".tmp"
+            res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None, bed=bed_tmp, keep=True)
+            files = {"path": files["path"], "bed": bed_tmp}
+            fai = False
+        else:
+            res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
+                                      assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz),
+                                      **({"fai": True} if fai else {}), **({"report": True} if report else {}), **({"keep": True} if keep else {}))
         if fai:
             for kind in ("assigned", "unassigned"):
                 files[kind + "_fai"] = files[kind] + ".fai"
@@ -611,18 +638,25 @@ class Ntjoin:
             try:
                 eng.write_paths(tgt, rows, first, lead_strip=lead, tail_strip=tail, first_line=assembly_fa, path=files["path"],
                                 agp=files.get("agp"), agp_unassigned=agp)
-                return files
+                return self._quiet_files(files) if quiet else files
             except MxError as err:
                 # a cut that leaves a node's interval empty or inverted: the library refuses it and has written nothing; such paths
                 # keep the text the host loop gives them
                 if err.code != capi.MXG_EINVAL or "empty or inverted" not in str(err):
                     raise
         self._write_path_host(files, assembly_fa, kept, lead.tolist(), tail.tolist())
+        return self._quiet_files(files) if quiet else files
+
+    @staticmethod
+    def _quiet_files(files):
+        os.remove(files.pop("bed"))
         return files
 
     def print_graph(self, graph, out_prefix=None):
         "Prints the minimizer graph in dot format"
         out_graph = (self.args.p + ".mx.dot") if out_prefix is None else (out_prefix + "mx.dot")
+        if getattr(self, "_quiet", False):
+            return
         print(datetime.datetime.today(), ": Printing graph", out_graph, sep=" ", file=sys.stdout)
         self._engine.write_dot(out_graph)
         list_files = list(self._order)

@@ -46,6 +46,10 @@ def parse_arguments(argv=None):
     parser.add_argument("--report", action="store_true", default=False)
     parser.add_argument("--report_min_gap", type=int, default=10, help="an N run of at least this many bases is a gap [10]")
     parser.add_argument("--report_min_len", type=int, default=500, help="N50 and the like are taken over lengths of at least this [500]")
+    # ours: scaffolding rounds in one process (ntjoin_amd/rounds.py): one more round per window size listed, the scaffolds of a round
+    # being the target of the next without a file between them; --rounds_keep: every round leaves every file the chain of runs would
+    parser.add_argument("--rounds_w", type=str, default=None, help="window sizes of further rounds, blank-separated inside one quoted argument")
+    parser.add_argument("--rounds_keep", action="store_true", default=False)
     parser.add_argument("-v", "--version", action="version", version="ntjoin_amd hot path (ntJoin v1.1.5 compatible)")
     return parser.parse_args(argv)
 
