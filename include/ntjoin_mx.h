@@ -726,6 +726,63 @@ int mxg_compose_pieces(mxg_handle *h, const mxg_seq_piece *outer, const uint64_t
 int mxg_scaffold_pieces(mxg_handle *h, const mxg_seq_piece **pieces, const uint64_t **rec_first, uint64_t *n_records);
 const char *mxg_scaffold_record_id(const mxg_handle *h, uint64_t record);
 
+/* ---- next row (f12): synteny blocks of one assembly against another, and their PAF ------------------------------
+   What the alignment half of the reference's `analysis` target is asked for (`minimap2 -x asm5 ... | samtools sort` on the target,
+   the references and the scaffolds, ntJoin:158-161, 238-242): where a record lies on another assembly, in which orientation, and
+   whether it is collinear with it -- alignment-free, from the graph: every vertex is a minimizer that occurs exactly once in every
+   assembly, which is what a chaining aligner starts from.
+   Inputs: a handle with a graph built on its own sketches; a query assembly q and a subject assembly s, q != s; the parameters;
+   optionally a piece table over the records of q (mxg_seq_piece rows and first[n_records + 1], valid by the rule of
+   mxg_compose_pieces: the table of mxg_scaffold_pieces makes the scaffolds the query); optionally query_length / subject_length,
+   one entry per record of q / s, which replace the lengths the handle holds as record_length does in mxg_format_paths.
+   ANCHORS.  Every graph vertex v is an anchor (qrec, qpos, srec, spos): its place in q and in s, from the graph.  Without a piece
+   table the anchor list is the vertices ordered by (qrec, qpos): the order of q's sketch.  With one, the list is rebuilt record by
+   record and piece by piece, in table order; off = the sum of the lengths of the earlier pieces of the piece's record, k = the
+   handle's k:
+     MXG_PIECE_FWD over [a, b) of record r takes the anchors with qrec == r, a <= qpos and qpos + k <= b, by rising qpos; the new
+                   record is the table's record, the new qpos' = off + (qpos - a);
+     MXG_PIECE_REV takes the same anchors by falling qpos, qpos' = off + (b - (qpos + k));
+     MXG_PIECE_GAP takes none.
+   An anchor in no piece vanishes, an anchor in two pieces appears twice; the length of a query record is the sum of its pieces.
+   LINKS.  Anchors i and i + 1 of the list, d = sign(spos[i + 1] - spos[i]), are linked with direction d iff they lie on the same
+   query record and the same subject record, d != 0 and, when max_gap > 0, qpos'[i + 1] - qpos'[i] <= max_gap and
+   |spos[i + 1] - spos[i]| <= max_gap.
+   BLOCKS.  A block is a maximal run of consecutive links of equal direction: links j .. j + r - 1 over anchors j .. j + r.  An
+   anchor at which the direction turns belongs to both neighbouring blocks; an anchor without a link makes no block.  Per block:
+     n_anchors = r + 1;  q_record;  q_start = qpos'[j], q_end = qpos'[j + r] + k;  s_record;
+     s_start = min(spos[j], spos[j + r]), s_end = max(...) + k;  reverse = (d < 0).
+   Kept are the blocks with n_anchors >= min_anchors and q_end - q_start >= min_span, in the order of their first anchor.
+   The arrays of the view are host copies owned by the handle, valid until its next mxg_synteny_blocks; n_anchors_total = the length
+   of the anchor list, n_links = its links (of either direction, before the filter).
+   MXG_EINVAL: a null argument, no graph (or the graph of a distributed stage, whose vertex order is not the sketches'), q == s, an
+   assembly out of range, struct_size too small, min_anchors < 2, a length array missing where the handle holds no lengths (an
+   assembly loaded from a TSV, a side-car or minimizers), a table that is not valid or a piece outside its record (the message as
+   mxg_compose_pieces words it, the table named "query").  MXG_ELIMIT: a query record longer than 2^32 - 1 bases, 2^31 anchors or
+   blocks or more.  Zero vertices is valid and gives zero blocks.  Sketches, graph, paths and kept text stay as they are.
+   mxg_write_synteny_paf: the blocks of the last mxg_synteny_blocks as PAF, formatted on the device, one line per block:
+       qname qlen qstart qend strand tname tlen tstart tend matches blocklen 255 cm:i:<n_anchors>       (tab-separated)
+   strand = '-' for a reverse block; matches = min(n_anchors * k, qend - qstart, tend - tstart), blocklen = max(qend - qstart,
+   tend - tstart); cm:i is the tag minimap2 gives the number of minimizers on a chain.  tname = the handle's record ids of s;
+   query_names = one name per query record (NULL: the handle's record ids of q; MXG_EINVAL when the query went through a piece
+   table, whose records the handle has no names for -- those of mxg_scaffold_pieces' table are mxg_scaffold_record_id).  append != 0:
+   the lines are added behind what `path` holds already (a file that a failed call was adding to is left as it is found).
+   MXG_EINVAL: no such blocks.  MXG_SYN_WIN (test knob): bytes of PAF text per device window (at least 1, default and at most 64 Mi). */
+typedef struct mxg_synteny_params {
+    uint32_t struct_size; /* = sizeof(mxg_synteny_params) */
+    uint32_t max_gap;     /* largest distance between linked anchors on either assembly; 0 = none */
+    uint32_t min_anchors; /* >= 2 */
+    uint32_t min_span;    /* smallest q_end - q_start */
+} mxg_synteny_params;
+typedef struct mxg_synteny_view {
+    uint64_t n_blocks, n_anchors_total, n_links;
+    const uint32_t *n_anchors, *q_record, *q_start, *q_end, *s_record, *s_start, *s_end; /* [n_blocks] */
+    const uint8_t *reverse;                                                              /* [n_blocks] 0 = '+', 1 = '-' */
+} mxg_synteny_view;
+int mxg_synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params *params, const mxg_seq_piece *pieces /* may be NULL */,
+                       const uint64_t *first /* n_records + 1 */, uint64_t n_records, const uint32_t *query_length /* NULL: the handle's own */,
+                       const uint32_t *subject_length /* NULL: the handle's own */, mxg_synteny_view *out);
+int mxg_write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append);
+
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------
    No counterpart in the reference (it is one process).  Uniqueness and intersection need every occurrence of a hash in
    one place: every minimizer travels to the rank that owns its hash, the owner runs the ordinary graph kernels on what it

@@ -15,6 +15,9 @@ scaffold files; a reference loaded from its TSV gets a line on stderr instead.
 --report (--report_min_gap, --report_min_len): also <p>.report.tsv -- records, bases, base composition, N gaps, N50 and the like at
 scaffold and at contig level, one row per input read from FASTA in this run and per scaffold file (assigned, unassigned, all),
 computed on the GPU from the text the handle holds and from the scaffold files on their way out (ntjoin_amd/report.py).
+--synteny (--synteny_max_gap, --synteny_min_anchors, --synteny_min_span): also <p>.synteny.paf -- the maximal collinear runs of shared
+unique minimizers between the scaffolds (the records of the assigned, then of the unassigned file) and every reference, one PAF line
+per run, computed on the GPU from the graph; a reference loaded from its TSV needs <fasta>.fai for its lengths, or is left out.
 --rounds_w "500 250" (--rounds_keep): further rounds with these window sizes in the same process, the scaffolds of a round being the
 target of the next without a file between them, and <p>.rounds.agp over the contigs of the first target (ntjoin_amd/rounds.py).
 """

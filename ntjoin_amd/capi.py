@@ -35,6 +35,7 @@ SYMBOLS = [
     "mxg_plan_split", "mxg_add_assembly_packed_device_pieces", "mxg_dg_last_shared", "mxg_dg_set_ghosts",
     "mxg_compose_pieces", "mxg_add_assembly_text_device", "mxg_assembly_text",
     "mxg_scaffold_text", "mxg_scaffold_pieces", "mxg_scaffold_record_id",
+    "mxg_synteny_blocks", "mxg_write_synteny_paf",
 ]
 
 
@@ -97,6 +98,16 @@ class AdjustParams(C.Structure):  # mxg_adjust_params: 16 bytes (api.cpp asserts
 class AdjustedView(C.Structure):  # mxg_adjusted_view: 40 bytes (api.cpp asserts the same); nodes = engine.MxEngine.ADJUST_NODE entries
     _fields_ = [("n_paths", C.c_uint64), ("n_nodes", C.c_uint64), ("node_first", C.POINTER(C.c_uint64)), ("nodes", C.c_void_p),
                 ("source", C.POINTER(C.c_uint64))]
+
+
+class SyntenyParams(C.Structure):  # mxg_synteny_params: 16 bytes (api.cpp asserts the same)
+    _fields_ = [("struct_size", C.c_uint32), ("max_gap", C.c_uint32), ("min_anchors", C.c_uint32), ("min_span", C.c_uint32)]
+
+
+class SyntenyView(C.Structure):  # mxg_synteny_view: 88 bytes (api.cpp asserts the same)
+    _fields_ = ([("n_blocks", C.c_uint64), ("n_anchors_total", C.c_uint64), ("n_links", C.c_uint64)] +
+                [(name, C.POINTER(C.c_uint32)) for name in ("n_anchors", "q_record", "q_start", "q_end", "s_record", "s_start", "s_end")] +
+                [("reverse", C.POINTER(C.c_uint8))])
 
 
 class Contiguity(C.Structure):  # mxg_contiguity: 88 bytes (api.cpp asserts the same)
@@ -239,6 +250,8 @@ def load():
     L.mxg_scaffold_record_id.restype = cp
     L.mxg_write_paths.argtypes = [vp, i32, vp, vp, u64, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32]
     L.mxg_compose_pieces.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(vp), C.POINTER(C.POINTER(u64))]
+    L.mxg_synteny_blocks.argtypes = [vp, i32, i32, C.POINTER(SyntenyParams), vp, vp, u64, vp, vp, C.POINTER(SyntenyView)]
+    L.mxg_write_synteny_paf.argtypes = [vp, C.POINTER(cp), C.c_char_p, i32]
     L.mxg_bgzf_write.argtypes = [vp, vp, u64, C.c_char_p]
     L.mxg_write_fai.argtypes = [vp, i32, C.c_char_p, C.c_char_p]
     L.mxg_set_report_params.argtypes = [vp, u64, u64]

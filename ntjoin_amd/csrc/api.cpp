@@ -936,7 +936,20 @@ int mxg_format_paths(mxg_handle *h, int assembly, const mxg_format_params *p, co
             record_length = own.data();
         }
         bool overhang = false;  // a negative overhang: MXG_EINVAL, but the view is filled all the same
+        // MXG_DEBUG_IO: the call's device time, as the synteny entries print theirs (they read the same vertex arrays)
+        const bool dbg = getenv("MXG_DEBUG_IO") != nullptr;
+        hipEvent_t ev[2] = {};
+        if (dbg && hipSetDevice(h->device) == hipSuccess && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess)
+            (void)hipEventRecord(ev[0], h->stream);
         rc = format_paths(h, (uint32_t)assembly, *p, record_length, &overhang);
+        if (dbg) {
+            float ms = 0;
+            if (ev[1] && hipEventRecord(ev[1], h->stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess)
+                (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+            fprintf(stderr, "[mxg] format_paths assembly=%d vertices=%llu nodes=%zu ms=%.3f\n", assembly, (unsigned long long)h->graph.nv, h->nodes.n_nodes, ms);
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
         if (rc != MXG_OK && !overhang) return rc;
     } catch (const std::bad_alloc &) {
         return set_err(h, MXG_ENOMEM, "out of host memory in mxg_format_paths");
@@ -1161,6 +1174,64 @@ int mxg_compose_pieces(mxg_handle *h, const mxg_seq_piece *outer, const uint64_t
     *pieces = h->cmp_pieces.data();
     *first = h->cmp_first.data();
     return MXG_OK;
+}
+
+static_assert(sizeof(mxg_synteny_params) == 16, "mxg_synteny_params: ntjoin_amd/capi.py SyntenyParams mirrors this layout");
+static_assert(sizeof(mxg_synteny_view) == 88, "mxg_synteny_view: ntjoin_amd/capi.py SyntenyView mirrors this layout");
+
+int mxg_synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params *params, const mxg_seq_piece *pieces, const uint64_t *first,
+                       uint64_t n_records, const uint32_t *query_length, const uint32_t *subject_length, mxg_synteny_view *out)
+{
+    if (!h) return MXG_EINVAL;
+    if (!params || !out || (pieces && !first)) return set_err(h, MXG_EINVAL, "mxg_synteny_blocks: null argument");
+    if (params->struct_size < sizeof(mxg_synteny_params))
+        return set_err(h, MXG_EINVAL, "mxg_synteny_blocks: struct_size %u is too small", params->struct_size);
+    if (params->min_anchors < 2)
+        return set_err(h, MXG_EINVAL, "mxg_synteny_blocks: min_anchors is %u; a block has at least two anchors", params->min_anchors);
+    if (!h->graph.valid) return set_err(h, MXG_EINVAL, "mxg_synteny_blocks: call mxg_build_graph first");
+    if (!h->graph.own_order)
+        return set_err(h, MXG_EINVAL, "mxg_synteny_blocks: the graph of a distributed stage does not hold the sketches' vertex order");
+    for (int a : {q, s})
+        if (a < 0 || (uint32_t)a >= h->graph.n_asm || (size_t)a >= h->asms.size())
+            return set_err(h, MXG_EINVAL, "mxg_synteny_blocks: assembly index %d out of range", a);
+    if (q == s) return set_err(h, MXG_EINVAL, "mxg_synteny_blocks: query and subject are both assembly %d", q);
+    int rc;
+    try {
+        rc = synteny_blocks(h, q, s, *params, pieces, first, pieces ? n_records : 0, query_length, subject_length);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_synteny_blocks");
+    }
+    if (rc != MXG_OK) return rc;
+    const mxg_handle::Synteny &S = h->syn;
+    const size_t n = S.reverse.size();
+    const uint32_t *b = S.block.data();
+    out->n_blocks = n;
+    out->n_anchors_total = S.n_anchors;
+    out->n_links = S.n_links;
+    out->n_anchors = b, out->q_record = b + n, out->q_start = b + 2 * n, out->q_end = b + 3 * n;
+    out->s_record = b + 4 * n, out->s_start = b + 5 * n, out->s_end = b + 6 * n;
+    out->reverse = S.reverse.data();
+    return MXG_OK;
+}
+
+int mxg_write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append)
+{
+    if (!h) return MXG_EINVAL;
+    if (!path) return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf: null argument");
+    if (!h->syn.valid) return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf: the handle's last mxg_synteny_blocks left no blocks (none was called, or it failed)");
+    if (!query_names && h->syn.q_table)
+        return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf: the query went through a piece table of %zu records; pass their names", h->syn.q_len.size());
+    if (query_names)
+        for (size_t r = 0; r < h->syn.q_len.size(); ++r)
+            if (!query_names[r]) return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf: query_names[%zu] is null", r);
+    if ((size_t)h->syn.q >= h->asms.size() || (size_t)h->syn.s >= h->asms.size() || h->asms[h->syn.s]->recs.size() != h->syn.s_len.size() ||
+        (!h->syn.q_table && h->asms[h->syn.q]->recs.size() != h->syn.q_len.size()))
+        return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf: the assemblies have changed since the blocks were made");
+    try {
+        return write_synteny_paf(h, query_names, path, append);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_write_synteny_paf");
+    }
 }
 
 int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals)

@@ -1871,6 +1871,7 @@ struct GraphStage {
             }
         }
         g.valid = true;
+        g.own_order = c.mode == GRAPH_FULL;
         g.host_valid = false;
         return MXG_OK;
     }

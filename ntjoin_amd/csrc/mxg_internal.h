@@ -176,6 +176,7 @@ struct Assembly {
 
 struct Graph {
     bool valid = false;       // device results computed
+    bool own_order = false;   // ... by the whole stage on this handle's own sketches: row a of g_fv / g_frec is assembly a's sketch order
     bool host_valid = false;  // host mirrors below filled (lazily, by graph_to_host)
     uint32_t n_asm = 0;
     uint64_t nv = 0, ne = 0, nv_stride = 0;
@@ -296,6 +297,15 @@ struct mxg_handle {
     mxg::DevBuf cmpbuf[16];  // scratch of compose.hip
     std::vector<mxg_seq_piece> cmp_pieces;       // the last mxg_compose_pieces' result (what its pointers point into)
     std::vector<uint64_t> cmp_first;
+    mxg::DevBuf synbuf[32];  // scratch of synteny.hip
+    struct Synteny {         // the last mxg_synteny_blocks (what its view points into, and what mxg_write_synteny_paf writes)
+        bool valid = false, q_table = false;  // q_table: the query's records are those of a piece table, not the handle's
+        int q = -1, s = -1;
+        uint64_t n_anchors = 0, n_links = 0;
+        std::vector<uint32_t> block;     // eight arrays of n_blocks words: n_anchors, q_record, q_start, q_end, s_record, s_start, s_end, reverse
+        std::vector<uint8_t> reverse;    // [n_blocks]
+        std::vector<uint32_t> q_len, s_len;  // the lengths of the query's records (a piece table's: the sums of their pieces) and the subject's
+    } syn;
     std::vector<uint32_t> scaf_lead, scaf_tail;  // N/n stripped from either end of every unassigned interval by the last mxg_write_scaffolds
     struct ScafInterval {
         uint32_t rec, lo, hi, lead, tail;
@@ -634,6 +644,10 @@ int adjust_paths(mxg_handle *h, const mxg_adjust_node *nodes, const uint64_t *pa
 // compose.hip: two piece tables composed (mxg_compose_pieces); fills h->cmp_*
 int compose_pieces(mxg_handle *h, const mxg_seq_piece *outer, const uint64_t *outer_first, uint64_t n_outer, const mxg_seq_piece *inner,
                    const uint64_t *inner_first, uint64_t n_inner);
+// synteny.hip: the synteny blocks of two assemblies (mxg_synteny_blocks; fills h->syn) and their PAF text (mxg_write_synteny_paf)
+int synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params &p, const mxg_seq_piece *pieces, const uint64_t *first, uint64_t n_records,
+                   const uint32_t *query_length, const uint32_t *subject_length);
+int write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm
 int flags_to_host(mxg_handle *h, Assembly *a);
 

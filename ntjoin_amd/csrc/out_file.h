@@ -74,6 +74,22 @@ struct OutFile {
         removable = regular && lstat(p, &sb) == 0 && S_ISREG(sb.st_mode);
         return true;
     }
+    // The same for a call that adds to a file another call has written: what is there stays, *size is where the new bytes begin, and
+    // the file is never removed (a failed call leaves what it found, and perhaps a part of its own behind it).  A file that does not
+    // exist is created.
+    bool open_append(const char *p, uint64_t *size)
+    {
+        path = p;
+        *size = 0;
+        f = fopen(p, "r+b");
+        if (!f) f = fopen(p, "w+b");
+        if (!f) return false;
+        struct stat sb;
+        if (fstat(fileno(f), &sb) != 0) return false;
+        regular = S_ISREG(sb.st_mode);
+        if (regular) *size = (uint64_t)sb.st_size;
+        return true;
+    }
     // A regular file takes the bytes at offset `off`, in put_parts(bytes, threads) parts side by side; anything else has no
     // offsets: it is written in order at the descriptor's own position, and `off` is not looked at.
     bool put(const char *src, uint64_t bytes, uint64_t off, uint32_t threads)

@@ -25,11 +25,11 @@
 #include <string>
 
 #include "mxg_internal.h"
+#include "scan64_kernels.h"
 #include "text_dev.h"
 
 namespace mxg {
 
-constexpr uint32_t PT_TILE = 1024;  // elements per work-group of the scans (4 per thread)
 enum { PT_NODES, PT_FIRST, PT_LEAD, PT_TAIL, PT_IDOFF, PT_IDS, PT_SUM, PT_POFF, PT_AOFF, PT_TSUM, PT_ERR, PT_BOUNDS, PT_BUF_COUNT };
 static_assert(PT_BUF_COUNT <= 16, "mxg_handle::ptbuf too small");
 enum : uint32_t { PT_BAD_SEGMENT = 1, PT_BAD_END_ADJUST = 2, PT_BAD_RECORD = 3, PT_BAD_INTERVAL = 4 };
@@ -177,67 +177,6 @@ __global__ __launch_bounds__(256) void k_pt_len(const PtParams q)
     q.aoff[i] = ac.n;
 }
 
-// exclusive prefix of per-thread sums `c` inside a block of 256; *total = the block's sum (all threads call)
-__device__ __forceinline__ uint64_t pt_block_exclusive(uint64_t c, uint64_t *sh, uint64_t *total)
-{
-    const uint32_t t = threadIdx.x;
-    sh[t] = c;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {
-        const uint64_t v = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        sh[t] += v;
-        __syncthreads();
-    }
-    const uint64_t incl = sh[t];
-    *total = sh[255];
-    __syncthreads();  // (sh is free for the next call)
-    return incl - c;
-}
-
-__global__ __launch_bounds__(256) void k_pt_tile_sum(const uint64_t *__restrict__ in, uint32_t n, uint64_t *__restrict__ tsum)
-{
-    __shared__ uint64_t sh[256];
-    const uint64_t base = (uint64_t)blockIdx.x * PT_TILE + threadIdx.x * 4u;
-    uint64_t c = 0, total;
-    for (uint32_t u = 0; u < 4; ++u)
-        if (base + u < n) c += in[base + u];
-    (void)pt_block_exclusive(c, sh, &total);
-    if (threadIdx.x == 0) tsum[blockIdx.x] = total;
-}
-
-// tsum[0 .. n_tiles) -> its exclusive sums, in place, by ONE block
-__global__ __launch_bounds__(256) void k_pt_scan_tiles(uint64_t *__restrict__ tsum, uint32_t n_tiles)
-{
-    __shared__ uint64_t sh[256];
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < n_tiles; base += 256) {
-        const uint64_t i = base + threadIdx.x;
-        const uint64_t v = i < n_tiles ? tsum[i] : 0;
-        uint64_t total;
-        const uint64_t ex = pt_block_exclusive(v, sh, &total);
-        if (i < n_tiles) tsum[i] = carry + ex;
-        carry += total;
-    }
-}
-
-// a[i] -> the sum of a[0 .. i), in place (tsum: the tiles' exclusive sums)
-__global__ __launch_bounds__(256) void k_pt_tile_excl(uint64_t *__restrict__ a, uint32_t n, const uint64_t *__restrict__ tsum)
-{
-    __shared__ uint64_t sh[256];
-    const uint64_t base = (uint64_t)blockIdx.x * PT_TILE + threadIdx.x * 4u;
-    uint64_t v[4], c = 0, total;
-    for (uint32_t u = 0; u < 4; ++u) {
-        v[u] = base + u < n ? a[base + u] : 0;
-        c += v[u];
-    }
-    uint64_t run = tsum[blockIdx.x] + pt_block_exclusive(c, sh, &total);
-    for (uint32_t u = 0; u < 4; ++u) {
-        if (base + u < n) a[base + u] = run;
-        run += v[u];
-    }
-}
-
 // bounds[c] = the node whose fragment holds byte c * win of the file (off: [n + 1] offsets, off[n] = the file's size > c * win)
 __global__ __launch_bounds__(256) void k_pt_bounds(const uint64_t *__restrict__ off, uint32_t n, uint64_t win, uint32_t n_win,
                                                    uint32_t *__restrict__ bounds)
@@ -270,11 +209,7 @@ __global__ __launch_bounds__(256) void k_pt_emit(const PtParams q, uint32_t agp,
 
 static int pt_scan(mxg_handle *h, uint64_t *d_a, uint32_t n)  // d_a[0 .. n) -> exclusive sums, in place
 {
-    const uint32_t n_tiles = (n + PT_TILE - 1) / PT_TILE;
-    uint64_t *tsum = h->ptbuf[PT_TSUM].as<uint64_t>();
-    hipLaunchKernelGGL(k_pt_tile_sum, dim3(n_tiles), dim3(256), 0, h->stream, d_a, n, tsum);
-    hipLaunchKernelGGL(k_pt_scan_tiles, dim3(1), dim3(256), 0, h->stream, tsum, n_tiles);
-    hipLaunchKernelGGL(k_pt_tile_excl, dim3(n_tiles), dim3(256), 0, h->stream, d_a, n, tsum);
+    launch_scan_u64(h->stream, d_a, n, h->ptbuf[PT_TSUM].as<uint64_t>());
     MXG_HIP(h, hipGetLastError());
     return MXG_OK;
 }

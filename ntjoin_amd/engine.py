@@ -548,6 +548,59 @@ class MxEngine:
             C.memmove(out.ctypes.data, pp, len(out) * self.SEQ_PIECE.itemsize)
         return out, first, [self._lib.mxg_scaffold_record_id(self._h, r).decode() for r in range(int(n.value))]
 
+    SYNTENY_FIELDS = ("n_anchors", "q_record", "q_start", "q_end", "s_record", "s_start", "s_end")
+
+    def synteny_blocks(self, q, s, max_gap=100000, min_anchors=3, min_span=0, pieces=None, first=None, query_length=None,
+                       subject_length=None):
+        """mxg_synteny_blocks: the maximal collinear runs of graph vertices between query assembly q and subject assembly s
+        (include/ntjoin_mx.h) -> dict(n_blocks, n_anchors_total, n_links, and per kept block n_anchors, q_record, q_start, q_end,
+        s_record, s_start, s_end (u32), reverse (u8)).  pieces / first: a piece table over the records of q (SEQ_PIECE or rows, and
+        n_records + 1 offsets; scaffold_pieces() gives the scaffolds'); query_length / subject_length: one length per record of q / s
+        where the handle holds none (minimizer input)."""
+        p = capi.SyntenyParams()
+        p.struct_size, p.max_gap, p.min_anchors, p.min_span = C.sizeof(capi.SyntenyParams), int(max_gap), int(min_anchors), int(min_span)
+        pc = pf = None
+        if pieces is not None:
+            pc = np.asarray(pieces)
+            if pc.dtype != self.SEQ_PIECE:
+                rows = np.asarray(pieces, dtype=np.uint32).reshape(-1, 4)
+                pc = np.zeros(len(rows), dtype=self.SEQ_PIECE)
+                for c, name in enumerate(self.SEQ_PIECE.names):
+                    pc[name] = rows[:, c]
+            pc = np.ascontiguousarray(pc)
+            pf = np.ascontiguousarray(first, dtype=np.uint64)
+            if pf.ndim != 1 or len(pf) < 1 or int(pf[-1]) != len(pc):
+                raise ValueError("synteny_blocks: a table needs n_records + 1 offsets, the last one the number of its pieces")
+
+        def lengths(ln, a, what):
+            if ln is None:
+                return None
+            ln = np.ascontiguousarray(ln, dtype=np.uint32)
+            if ln.ndim != 1 or (0 <= int(a) < self.n_assemblies and len(ln) != self.n_records(a)):
+                raise ValueError(f"synteny_blocks: {what}_length needs one entry per record of the assembly")
+            return ln
+        ql, sl = lengths(query_length, q, "query"), lengths(subject_length, s, "subject")
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        v = capi.SyntenyView()
+        self._check(self._lib.mxg_synteny_blocks(self._h, int(q), int(s), C.byref(p), ptr(pc), ptr(pf), 0 if pf is None else len(pf) - 1, ptr(ql), ptr(sl), C.byref(v)))
+        self._syn_records = self.n_records(q) if pf is None else len(pf) - 1
+        n = int(v.n_blocks)
+        out = {"n_blocks": n, "n_anchors_total": int(v.n_anchors_total), "n_links": int(v.n_links), "reverse": _np(v.reverse, n, np.uint8)}
+        for name in self.SYNTENY_FIELDS:
+            out[name] = _np(getattr(v, name), n, np.uint32)
+        return out
+
+    def write_synteny_paf(self, path, query_names=None, append=False):
+        """mxg_write_synteny_paf: the blocks of the last synteny_blocks() as PAF lines, formatted on the device; query_names = one name
+        per query record (None: the handle's record ids of q -- not for a query that went through a piece table); append=True adds
+        the lines to what `path` holds already"""
+        names = None
+        if query_names is not None:
+            if len(query_names) != getattr(self, "_syn_records", len(query_names)):
+                raise ValueError(f"write_synteny_paf: {len(query_names)} names for {self._syn_records} query records")
+            names = (C.c_char_p * max(len(query_names), 1))(*[str(i).encode() for i in query_names])
+        self._check(self._lib.mxg_write_synteny_paf(self._h, names, os.fsencode(str(path)), int(bool(append))))
+
     def write_fai(self, assembly, path, gzi=None):
         """mxg_write_fai: the index `samtools faidx` makes of the assembly's FASTA, from the text the handle holds, written to `path`;
         gzi= names the .gzi to write for an assembly that came from a BGZF file"""

@@ -375,14 +375,16 @@ class Ntjoin:
         at = res["node_first"].tolist()
         return [rows[lo:hi] for lo, hi in zip(at, at[1:])]
 
-    def scaffold(self, lengths=None, keep=False, quiet=False):
+    def scaffold(self, lengths=None, keep=False, quiet=False, synteny=None):
         """main_scaffolder (:751-786) behind load_minimizers_scaffold in one handle: make_minimizer_graph -> find_paths ->
         format_paths -> adjust_paths -> trim_overlaps (when args.overlap) -> print_scaffolds.  Read from args, with ntJoin's
         defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz, fai, report,
-        report_min_gap, report_min_len.  Returns what print_scaffolds returns (the written files by kind).  With args.fai the inputs
-        read from FASTA get their <fasta>.fai first (write_input_indexes); with args.report <prefix>.report.tsv is written ("report":
-        write_report).  keep / quiet: print_scaffolds' (a round of ntjoin_amd/rounds.py); a quiet round writes no .mx.dot, no index and
-        no report either."""
+        report_min_gap, report_min_len, synteny, synteny_max_gap, synteny_min_anchors, synteny_min_span.  Returns what print_scaffolds
+        returns (the written files by kind).  With args.fai the inputs read from FASTA get their <fasta>.fai first
+        (write_input_indexes); with args.report <prefix>.report.tsv is written ("report": write_report); with args.synteny
+        <prefix>.synteny.paf ("synteny": write_synteny; synteny=False leaves it out whatever args says: an earlier round of
+        ntjoin_amd/rounds.py).  keep / quiet: print_scaffolds' (a round of ntjoin_amd/rounds.py); a quiet round writes no .mx.dot, no
+        index, no report and no PAF either."""
         opt = lambda name, dflt: dflt if getattr(self.args, name, None) is None else getattr(self.args, name)  # noqa: E731
         if quiet:
             opt = lambda name, dflt, _opt=opt: False if name in ("fai", "report") else _opt(name, dflt)  # noqa: E731
@@ -399,8 +401,13 @@ class Ntjoin:
         paths = self.format_paths(lengths, g=int(opt("g", 20)), G=G, m=opt("m", 90), mkt=bool(opt("mkt", False)))
         paths = self.adjust_paths(paths, no_cut=bool(opt("no_cut", False)), G=G)
         cuts = self.trim_overlaps(paths, opt("overlap_k", 15), opt("overlap_w", 10)) if opt("overlap", False) else None
+        syn = None
+        if (bool(opt("synteny", False)) if synteny is None else synteny) and not quiet:
+            syn = dict(max_gap=int(opt("synteny_max_gap", 100000)), min_anchors=int(opt("synteny_min_anchors", 3)),
+                       min_span=int(opt("synteny_min_span", 0)))
         files = self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)),
-                                     gz=bool(opt("gz", False)), fai=bool(opt("fai", False)), report=report, keep=keep, quiet=quiet)
+                                     gz=bool(opt("gz", False)), fai=bool(opt("fai", False)), report=report, keep=keep, quiet=quiet,
+                                     **({"synteny": syn} if syn else {}))
         if report:
             files["report"] = self.write_report(report_rows, files)
         return files
@@ -568,7 +575,8 @@ class Ntjoin:
             if agp_fh:
                 agp_fh.close()
 
-    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False, report=False, keep=False, quiet=False):
+    def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False, report=False, keep=False, quiet=False,
+                        synteny=None):
         """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
         trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
         than two nodes are dropped (:585-594), the last kept node's gap is zeroed (check_terminal_node_gap_zero :441-448), and the
@@ -579,8 +587,12 @@ class Ntjoin:
         "unassigned_fai") and, with gz, its .gzi ("assigned_gzi", "unassigned_gzi").  report=True: either FASTA goes through the report's
         passes on its way out (MxEngine.scaffold_report hands the reports out; no file more).  keep=True: the text of both FASTA files
         also stays in device memory (MXG_SCAF_KEEP: MxEngine.scaffold_text, scaffold_pieces).  quiet=True (with keep): only <p>.path
-        and, with agp, <p>.agp are written -- an earlier round of ntjoin_amd/rounds.py.  Returns the file names by kind."""
+        and, with agp, <p>.agp are written -- an earlier round of ntjoin_amd/rounds.py.  synteny=dict(max_gap, min_anchors, min_span)
+        (or True for the defaults): also <p>.synteny.paf ("synteny": write_synteny), which needs the scaffolds' piece table and so
+        turns keep on.  Returns the file names by kind."""
         self._last_print = dict(paths=paths, adjust=adjust, n=n, agp=agp, overlap_gap=overlap_gap, gz=gz, fai=fai, report=report)
+        if synteny and not quiet:
+            keep = True
         eng, tgt = self._engine, len(self._order) - 1
         if tgt < 0:
             raise ValueError("print_scaffolds: no target assembly has been loaded")
@@ -626,6 +638,8 @@ class Ntjoin:
             res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
                                       assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz),
                                       **({"fai": True} if fai else {}), **({"report": True} if report else {}), **({"keep": True} if keep else {}))
+        if synteny and not quiet:
+            files["synteny"] = self.write_synteny(**(synteny if isinstance(synteny, dict) else {}))
         if fai:
             for kind in ("assigned", "unassigned"):
                 files[kind + "_fai"] = files[kind] + ".fai"
@@ -646,6 +660,44 @@ class Ntjoin:
                     raise
         self._write_path_host(files, assembly_fa, kept, lead.tolist(), tail.tolist())
         return self._quiet_files(files) if quiet else files
+
+    def write_synteny(self, max_gap=100000, min_anchors=3, min_span=0):
+        """<prefix>.synteny.paf: the synteny blocks (MxEngine.synteny_blocks) of the scaffolds the last print_scaffolds(keep=True) left
+        -- the records of the assigned file, then those of the unassigned file, under their names there -- against every reference,
+        in command-line order, one PAF line per block (MxEngine.write_synteny_paf).  A reference loaded from its TSV has no record
+        lengths in the handle: they are read from <fasta>.fai when that file exists, else the reference is left out with one line on
+        stderr.  Returns the file's name."""
+        eng, tgt = self._engine, len(self._order) - 1
+        pieces, first, ids = eng.scaffold_pieces()
+        out = self.args.p + ".synteny.paf"
+        with open(out, "wb"):
+            pass   # (every reference's lines are appended)
+        for a, assembly in enumerate(self._order[:tgt]):
+            lengths = None
+            if assembly not in self._fasta:
+                lengths = self._fai_lengths(a, assembly)
+                if lengths is None:
+                    print(f"ntjoin_amd: {assembly} was loaded from its TSV and its FASTA has no .fai: the synteny PAF has no lines for it",
+                          file=sys.stderr)
+                    continue
+            eng.synteny_blocks(tgt, a, max_gap=max_gap, min_anchors=min_anchors, min_span=min_span, pieces=pieces, first=first,
+                               subject_length=lengths)
+            eng.write_synteny_paf(out, query_names=ids, append=True)
+        return out
+
+    def _fai_lengths(self, a, assembly):
+        "the lengths of assembly a's records from <fasta>.fai (the TSV being named <fasta>.k<k>.w<w>.tsv), or None"
+        match = re.search(r"^(.+)\.k\d+\.w\d+\.tsv$", assembly)
+        if not match or not os.path.exists(match.group(1) + ".fai"):
+            return None
+        known = {}
+        with open(match.group(1) + ".fai", encoding="utf-8") as fh:
+            for line in fh:
+                cols = line.rstrip("\n").split("\t")
+                if len(cols) >= 2 and cols[1].isdigit():
+                    known.setdefault(cols[0], int(cols[1]))
+        ids = self._engine.record_ids(a, self._engine.n_records(a))
+        return [known[rid] for rid in ids] if all(rid in known for rid in ids) else None
 
     @staticmethod
     def _quiet_files(files):

@@ -13,6 +13,7 @@ device route refuses a text (MXG_ELIMIT, MXG_ENOMEM) the files of the round befo
 The last round writes everything a single run writes; an earlier round its .path and, with --agp, its .agp -- with --rounds_keep
 every file the chain would leave.  <p>.rounds.agp spells every record of the last round's scaffolds over the records of the
 original target: the rounds' piece tables (mxg_scaffold_pieces) composed on the device (mxg_compose_pieces), formatted here.
+--synteny: the last round's scaffolds against the references, <p>.round<i>.synteny.paf beside that round's other files.
 
     python -m ntjoin_amd.rounds last_out TARGET K W N GZ W2 [W3 ...]   prints T_last.k<k>.w<w_last>.n<n> (for the make front-end)
 """
@@ -136,7 +137,7 @@ def run_rounds(args, fasta, w, weights, rounds_w, keep_files=False):
                 if i == 1:
                     tgt = len(nj._order) - 1
                     contig_ids = nj._engine.record_ids(tgt, nj._engine.n_records(tgt))
-                files = nj.scaffold(keep=True, quiet=not full)
+                files = nj.scaffold(keep=True, quiet=not full, **({} if last else {"synteny": False}))
                 if full and not last:
                     files["all"] = write_all(files, gz)
                 pieces, first, ids = nj._engine.scaffold_pieces()

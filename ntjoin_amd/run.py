@@ -50,6 +50,14 @@ def parse_arguments(argv=None):
     # being the target of the next without a file between them; --rounds_keep: every round leaves every file the chain of runs would
     parser.add_argument("--rounds_w", type=str, default=None, help="window sizes of further rounds, blank-separated inside one quoted argument")
     parser.add_argument("--rounds_keep", action="store_true", default=False)
+    # ours: <prefix>.synteny.paf -- the maximal collinear runs of shared unique minimizers between the scaffolds and every reference, as
+    # PAF for a dot-plot viewer, computed on the GPU from the graph (the alignment-free answer to what the reference's `analysis` target
+    # runs minimap2 for, ntJoin:158-161, 238-242; ntjoin_amd.assemble)
+    parser.add_argument("--synteny", action="store_true", default=False)
+    parser.add_argument("--synteny_max_gap", type=int, default=100000,
+                        help="largest distance between neighbouring anchors of a block, 0 = none [100000: QUAST's --scaffold-gap-max-size in ntJoin:247]")
+    parser.add_argument("--synteny_min_anchors", type=int, default=3, help="smallest number of minimizers of a block, at least 2 [3]")
+    parser.add_argument("--synteny_min_span", type=int, default=0, help="smallest extent of a block on the scaffold [0]")
     parser.add_argument("-v", "--version", action="version", version="ntjoin_amd hot path (ntJoin v1.1.5 compatible)")
     return parser.parse_args(argv)
 
