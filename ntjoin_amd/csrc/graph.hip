@@ -18,6 +18,7 @@
 #include <system_error>
 #include <thread>
 
+#include "join_verdict.h"
 #include "mxg_internal.h"
 #include "scan_kernels.h"
 
@@ -136,8 +137,11 @@ __global__ __launch_bounds__(256) void k_flags(const AsmSet p, const Slot *__res
 // concatenated 256-blocks), sorts them by a hash of their key into P partitions INSIDE ITS OWN 4096-record region
 // (LDS histogram, LDS prefix, LDS cursors: no global atomics at all) and writes its row of partition offsets to M.
 // One block of k_pj_join per partition then collects the partition's short segments from every region (column of M),
-// builds the partition's table in LDS and leaves {seen mask, dup mask, slot} in each record, which k_flags_pj picks up
-// through the record position k_pj_bucket stored in slot[a][i].  Slot numbers are partition * (PJ_T + 1) + local slot.
+// builds the partition's table in LDS and sends every record's verdict word to the minimizer the record names
+// (slot[a][i]), where k_flags_pj reads it in order.  The commonest verdict, "once in its assembly, not in every assembly"
+// (a quarter of the records at 3 Gbp + 3 Gbp), is not sent: k_pj_bucket has written it for every minimizer, in order, beside
+// its read of the hashes, and the join's scattered store -- 32 bytes of traffic per 4-byte word -- is kept for the words that
+// differ (join_verdict.h).
 // A partition with more distinct keys than its table holds reports failure through pinned host memory and build_graph
 // redoes the stage with the global table.
 // (PJ_IPB items per bucketing block, PJ_T slots per table, at most PJ_MAX_P partitions: join_plan.h)
@@ -191,15 +195,20 @@ __global__ __launch_bounds__(PJ_BT) void k_pj_bucket(const AsmSet p, uint32_t nb
         key[u] = 0;
         if (blk >= nb) continue;
         const uint64_t *hp = hp0;
+        uint32_t *sp = sp0;
         uint32_t i = ib0 + (u * BPU + sub) * 256u + t256, n = n0;
         if (!one) {
             const uint32_t a = asm_of_block(p, blk);
             hp = p.hash[a];
+            sp = p.slot[a];
             i = (blk - p.bstart[a]) * 256u + t256;
             n = asm_n(p, a);
         }
         const bool lv = i < n;
-        if (lv) key[u] = hp[i];
+        if (lv) {
+            key[u] = hp[i];
+            sp[i] = PJ_VERDICT_PREFILL;  // (followers too; k_pj_join sends only the verdicts that differ)
+        }
         const uint32_t role = pj_run_role(i, n, key[u], lv);
         const uint64_t fb = __ballot(role & 1u);
         if ((threadIdx.x & 63u) == 0) p.fol[(size_t)blk * 4u + ((threadIdx.x >> 6) & 3u)] = fb;
@@ -234,16 +243,14 @@ __global__ __launch_bounds__(PJ_BT) void k_pj_bucket(const AsmSet p, uint32_t nb
         if (!((live >> u) & 1u)) continue;
         const uint32_t blk = blk0 + u * BPU + sub;
         uint32_t a = a0, i = ib0 + (u * BPU + sub) * 256u + t256;
-        uint32_t *sp = sp0;
         if (!one) {
             a = asm_of_block(p, blk);
             i = (blk - p.bstart[a]) * 256u + t256;
-            sp = p.slot[a];
         }
         const uint32_t b = pj_part(key[u], pmask);
         const uint32_t pos = j * PJ_IPB + start[b] + atomicAdd(&hist[b], 1u);
         recs[pos] = make_uint4((uint32_t)key[u], (uint32_t)(key[u] >> 32), i, a | (((dupm >> u) & 1u) ? PJ_REC_DUP : 0u));  // (the record knows whose it is: k_pj_join
-        (void)sp;                                                                   //  sends the verdict straight to slot[a][i])
+                                                                                    //  sends the verdict straight to slot[a][i])
     }
 }
 
@@ -265,7 +272,8 @@ __device__ __forceinline__ uint32_t pj_slot(unsigned long long *keys, uint64_t k
 }
 
 // Two levels (more than PJ_MAX_P x 1280 minimizers): `cursor` != nullptr.  k_pj1_scatter has dealt the minimizers into P1 coarse
-// partitions of capacity cap1 (coarse partition c holds cursor[c * PJ1_CS] records from c * cap1 on), k_pj2_bucket has sorted
+// partitions of capacity cap1 (coarse partition c holds cursor[c * PJ1_CS] records from c * cap1 on) and prefilled every
+// minimizer's verdict word (PJ_VERDICT_PREFILL: the join sends only the verdicts that differ), k_pj2_bucket has sorted
 // every 4096-record region of a coarse partition into P sub-partitions (rows of M: rows2 per coarse partition); block
 // blockIdx.x = c * P + b joins sub-partition b of coarse partition c.
 // (PJ1_CS words between the coarse partitions' cursors: join_plan.h)
@@ -383,7 +391,8 @@ __global__ __launch_bounds__(256) void k_pj_join(uint4 *recs, const uint32_t *__
                     const bool inall = sn == full;
                     fl = (!(d & (1u << a)) ? MXG_MX_UNIQUE : 0u) | ((inall && d == 0) ? MXG_MX_SHARED : 0u) | (inall ? MXG_MX_INALL : 0u);
                 }
-                p.slot[a][i] = ((fl & MXG_MX_SHARED) ? item0[s] << 3 : 0u) | fl;
+                const uint32_t word = ((fl & MXG_MX_SHARED) ? item0[s] << 3 : 0u) | fl;
+                if (!pj_verdict_is_prefill(word)) p.slot[a][i] = word;
             };
 #pragma unroll
             for (uint32_t it = 0; it < QC; ++it) {
@@ -431,6 +440,9 @@ __global__ __launch_bounds__(256) void k_pj_join(uint4 *recs, const uint32_t *__
 // so are the segment bounds of partition k + 2 -- a block of k_pj_join spends most of its ~16 us waiting for exactly these two
 // round trips, one behind the other, and the tables' 32 KB keep more blocks from hiding them.  For partitions of at most 256
 // regions (rows2; always, unless a skewed coarse partition was re-sized); same tables, same verdicts as k_pj_join.
+// Where a record lies: the thread that owns a region writes the region's number over the records of its segment (seg_of, the
+// first QC * 256 records of the partition), so a record finds its segment with one LDS read; only the records beyond
+// those (a key of huge multiplicity) are still located by a search in seg_off, as in k_pj_join.
 template <bool NARROW>
 __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_t *__restrict__ M, uint32_t P, uint32_t n_parts,
                                                       uint64_t *host_fail, uint32_t force_fail, const uint32_t *__restrict__ cursor,
@@ -443,6 +455,7 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
     __shared__ uint32_t seg_off[2][257], seg_rec[2][256], sh[256];
     __shared__ uint32_t failed;
     constexpr uint32_t QC = 4;
+    __shared__ uint8_t seg_of[QC * 256];  // the region whose segment holds record q of the partition laid out last, q < QC * 256
     uint4 rn[QC];                    // the first QC records per thread of the partition whose segments were laid out last
     uint32_t tot_n = 0;              // ... and how many records it has
     uint32_t lo_nn = 0, len_nn = 0;  // segment of this thread's region in the partition after that one
@@ -461,6 +474,9 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
         const uint32_t off = block_exclusive_256(len, sh);
         seg_off[buf][threadIdx.x] = off;
         seg_rec[buf][threadIdx.x] = c * cap1 + threadIdx.x * PJ_IPB + lo;
+        // the thread that owns a region names it to the records of its segment (about a dozen consecutive ones): each of the
+        // first QC records per thread then finds its segment with one LDS read where a search in seg_off took eight in a row
+        for (uint32_t q = off, e = min(off + len, QC * 256u); q < e; ++q) seg_of[q] = (uint8_t)threadIdx.x;
         const uint32_t total = sh[255];
         __syncthreads();
 #pragma unroll
@@ -468,11 +484,7 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
             const uint32_t q = threadIdx.x + it * 256u;
             rn[it] = make_uint4(0u, 0u, 0u, 0u);
             if (q < total) {
-                uint32_t l = 0, h = 256;
-                while (h - l > 1) {
-                    const uint32_t m = (l + h) >> 1;
-                    if (seg_off[buf][m] <= q) l = m; else h = m;
-                }
+                const uint32_t l = seg_of[q];
                 rn[it] = recs[seg_rec[buf][l] + (q - seg_off[buf][l])];
             }
         }
@@ -569,7 +581,8 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
                 const bool inall = sn == full;
                 fl = (!(d & (1u << a)) ? MXG_MX_UNIQUE : 0u) | ((inall && d == 0) ? MXG_MX_SHARED : 0u) | (inall ? MXG_MX_INALL : 0u);
             }
-            p.slot[a][rec.z] = ((fl & MXG_MX_SHARED) ? item0[s] << 3 : 0u) | fl;
+            const uint32_t word = ((fl & MXG_MX_SHARED) ? item0[s] << 3 : 0u) | fl;
+            if (!pj_verdict_is_prefill(word)) p.slot[a][rec.z] = word;
         };
 #pragma unroll
         for (uint32_t it = 0; it < QC; ++it)
@@ -617,7 +630,10 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
         const uint32_t a = subr.n_sub > 1 ? subr.s : asm_of_block(p, blk);
         const uint32_t i = (blk - p.bstart[a]) * 256u + t256, n = asm_n(p, a);
         const bool lv = i < n;
-        if (lv) key[u] = p.hash[a][i];
+        if (lv) {
+            key[u] = p.hash[a][i];
+            p.slot[a][i] = PJ_VERDICT_PREFILL;  // (followers too; in front of this thread's own store of 0 below)
+        }
         const uint32_t role = pj_run_role(i, n, key[u], lv);  // (followers travel with their run's leader)
         const uint64_t fb = __ballot(role & 1u);
         if ((threadIdx.x & 63u) == 0) p.fol[(size_t)blk * 4u + ((threadIdx.x >> 6) & 3u)] = fb;
@@ -659,8 +675,7 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
 // such a partition first collapse what is equal among their 4096 records: records of one (key, assembly) elect one of them,
 // which goes on marked PJ_REC_DUP; the others leave a reference to it as their verdict (PJ_VERDICT_REF, followed by k_flags_pj)
 // and drop out.
-constexpr uint32_t PJ_VERDICT_REF = 2u;  // low bits of a verdict word that is no verdict (SHARED without UNIQUE cannot be):
-                                         // the upper bits name a minimizer of the same assembly whose verdict holds for this one
+// (PJ_VERDICT_REF, the low bits of a verdict word that is no verdict: join_verdict.h)
 __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint4 *__restrict__ recs1, const uint32_t *__restrict__ cursor,
                                                     uint32_t cap1, uint32_t rows2, uint32_t pmask, uint32_t *M, uint4 *recs2,
                                                     uint32_t skew_lim, const PjSub subr)
@@ -847,11 +862,12 @@ __global__ __launch_bounds__(256) void k_flags_pj(const AsmSet p, uint32_t nb, u
     const uint32_t blk0 = blockIdx.x * U, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     TailAsm t[U];
     tail_asms<U>(p, blk0, nb, t);
-    // the verdict k_pj_join left here (k_vertices_pj reads the word's upper part) -- or a reference to the minimizer that
-    // went on for this one (k_pj2_bucket); a follower (pj_run_role) has neither: its leader, the last lane in front of it
-    // that is no follower, says whether the key is in every assembly
-    // (the verdict word is requested beside the follower bits, not behind them: a follower's word -- never written, whatever
-    // the buffer held -- is read and dropped)
+    // the verdict k_pj_join left here (k_vertices_pj reads the word's upper part), the prefill of the partitioning kernel where
+    // the join had nothing else to say (PJ_VERDICT_PREFILL) -- or a reference to the minimizer that went on for this one
+    // (k_pj2_bucket); a follower (pj_run_role) has no verdict of its own: its leader, the last lane in front of it that is no
+    // follower, says whether the key is in every assembly
+    // (the verdict word is requested beside the follower bits, not behind them: a follower's word -- the prefill, nothing
+    // else was written there -- is read and dropped)
     uint64_t fb[U];
     uint32_t v[U], ia[U], ii[U];
     bool in[U];
