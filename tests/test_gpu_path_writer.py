@@ -2,7 +2,8 @@
 write_agp_unassigned :379-404): the goldens, paths that span lanes, waves and blocks, every digit border, orientations, cuts and
 strips, small output windows, either file into a FIFO, the unassigned lines, every refusal, one larger call, and the routing inside Ntjoin.print_scaffolds.
 The writer never reads the bases, so the assemblies are a handful of short records.  Every comparison is byte for byte against
-the restatement (tests/_path_text_restatement.py)."""
+the restatement (tests/_path_text_restatement.py) or, for the generated families of tests/golden/scaffolds/families, against the text
+the reference itself wrote."""
 import argparse
 import glob
 import os
@@ -14,7 +15,7 @@ import pytest
 
 from ntjoin_amd.engine import MxEngine, MxError
 from ntjoin_amd.ntjoin import Ntjoin
-from tests import _fifo, _oracle, _path_text_restatement as pt, _scaffold_cases as cases, _scaffold_restatement as rs
+from tests import _fifo, _oracle, _path_text_restatement as pt, _scaffold_cases as cases, _scaffold_pin as pin, _scaffold_restatement as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -331,3 +332,36 @@ def test_print_scaffolds_takes_the_host_route_only_for_refused_intervals(tmp_pat
         assert read(files["path"]).decode("ascii").splitlines()[1] == "ntJoin0\t1_f+:0-1981 20N 2_f+:50-20 20N 2_f+:100-2329"
     finally:
         nj.close()
+
+
+# ---- the families of tests/golden/scaffolds/families: the reference's own .path, write_agp and write_agp_unassigned -----------------
+
+assert NAMES == pin.AGP_NAME_IDS
+PIN_CASES = pin.all_cases()
+
+
+@pytest.mark.parametrize("family,name", PIN_CASES, ids=[f"{family}-{name}" for family, name in PIN_CASES])
+def test_families_pinned_to_reference(family, name, tmp_path):
+    """write_paths with the strips write_scaffolds returned: the reference's .path and AGP bytes over the paths the writer accepts (with
+    the unassigned lines where it accepts all), and for every path whose recorded interval is inverted a refusal that names it"""
+    entry = pin.load_family(family)[name]
+    case, paths = entry["case"], entry["paths"]
+    index = {rid: r for r, (rid, _) in enumerate(case["records"])}
+    rows, first = cases.rows_of(paths, index)
+    refused = pin.refused_nodes(entry)
+    keep = [q for q in range(len(paths)) if q not in refused]
+    with MxEngine(k=15, w=10) as e:
+        a = e.add_records("t", 1.0, case["records"])
+        res = e.write_scaffolds(a, rows, first, overlap_gap=case["overlap_gap"], assigned=str(tmp_path / "s.fa"), unassigned=str(tmp_path / "s.un.fa"),
+                                bed=str(tmp_path / "s.bed"))
+        leads, tails = res["lead_strip"].tolist(), res["tail_strip"].tolist()
+        got = write(e, a, [paths[q] for q in keep], [leads[q] for q in keep], [tails[q] for q in keep], tmp_path / "kept", index)
+        assert got == tuple(text.encode("ascii") for text in pin.renumbered(entry, keep))
+        if not refused:
+            got = write(e, a, paths, leads, tails, tmp_path / "all", index, unassigned=True)
+            assert got == (entry["path"].encode("ascii"), (entry["agp"] + entry["agp_unassigned"]).encode("ascii"))
+        for q, i in refused.items():
+            sub = [x for x in keep if x < q] + [q]
+            with pytest.raises(MxError, match=f"path {len(sub) - 1} node {i}: the adjusted interval is empty or inverted") as ei:
+                write(e, a, [paths[x] for x in sub], [leads[x] for x in sub], [tails[x] for x in sub], tmp_path / f"refused{q}", index)
+            assert ei.value.code == EINVAL and not os.path.exists(tmp_path / f"refused{q}.path") and not os.path.exists(tmp_path / f"refused{q}.agp")

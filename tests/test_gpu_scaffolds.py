@@ -1,6 +1,6 @@
 """GPU tests of the scaffold stage (mxg_write_scaffolds, csrc/scaffold.hip; reference print_scaffolds and print_unassigned,
-bin/ntjoin_assemble.py:580-658): the goldens (the reference's own output) end to end through Ntjoin, seeded fuzz and one large call
-against the restatement (tests/_scaffold_restatement.py), both text layouts, small output windows, the assigned file into a FIFO, and every refusal.  Text only:
+bin/ntjoin_assemble.py:580-658): the goldens (the reference's own output) end to end through Ntjoin, the generated families of
+tests/golden/scaffolds/families against the reference's recorded answers, seeded fuzz and one large call against the restatement (tests/_scaffold_restatement.py), both text layouts, small output windows, the assigned file into a FIFO, and every refusal.  Text only:
 every comparison is byte for byte."""
 import argparse
 import glob
@@ -14,7 +14,7 @@ import pytest
 from ntjoin_amd import synth
 from ntjoin_amd.engine import MxEngine, MxError
 from ntjoin_amd.ntjoin import Ntjoin
-from tests import _fifo, _oracle, _scaffold_cases as cases, _scaffold_restatement as rs
+from tests import _fifo, _oracle, _scaffold_cases as cases, _scaffold_pin as pin, _scaffold_restatement as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -357,3 +357,67 @@ def test_one_large_call(tmp_path):
         assert sha.hexdigest() == hashlib.sha256(want.encode("ascii")).hexdigest(), name
     assert res["lead_strip"].tolist() == leads and res["tail_strip"].tolist() == tails and res["n_unassigned"] == n_un
     assert sum(1 for x in leads + tails if x) > 10
+
+
+# ---- the families of tests/golden/scaffolds/families: generated inputs, the reference's own print_scaffolds ------------------------
+
+def check_pinned_to_reference(family, name, tmp_path):
+    """write_scaffolds over the paths the reference answered, the last gap zeroed, on both ingest routes: the assigned FASTA record by
+    record against the recorded name, length and sha256, and the strips against those the reference's .path coordinates show"""
+    entry = pin.load_family(family)[name]
+    case, paths = entry["case"], entry["paths"]
+    fasta = str(tmp_path / "t.fa")
+    cases.write_fasta(fasta, case["records"], case["width"], case["final_newline"])
+    rows, first = cases.rows_of(paths, {rid: r for r, (rid, _) in enumerate(case["records"])})
+    strips = [pin.reference_strips(path, line) for path, line in zip(paths, entry["path_lines"])]
+    with MxEngine(k=15, w=10) as eng:
+        for route, a in (("fasta", eng.add_fasta("t", 1.0, fasta)), ("records", eng.add_records("h", 1.0, case["records"]))):
+            names = [str(tmp_path / (route + s)) for s in (".assigned.fa", ".unassigned.fa", ".bed")]
+            res = eng.write_scaffolds(a, rows, first, overlap_gap=case["overlap_gap"], assigned=names[0], unassigned=names[1], bed=names[2])
+            assert pin.scaffold_digests(read(names[0]).decode("ascii")) == entry["scaffolds"], route
+            assert list(zip(res["lead_strip"].tolist(), res["tail_strip"].tolist())) == strips, route
+
+
+@pytest.mark.parametrize("seed", cases.FUZZ_SEEDS)
+def test_fuzz_pinned_to_reference(seed, tmp_path):
+    check_pinned_to_reference("fuzz", f"seed{seed:02d}", tmp_path)
+
+
+@pytest.mark.parametrize("name", [name for name, _g, _a in pin.family_specs()["strip_beside_cuts"]])
+def test_strip_beside_cuts_pinned_to_reference(name, tmp_path):
+    "a strip that moves a coordinate in a path whose other nodes carry cuts and replaced gaps: the only such answers ntJoin gives"
+    check_pinned_to_reference("strip_beside_cuts", name, tmp_path)
+
+
+@pytest.mark.parametrize("name", [name for name, _g, _a in pin.family_specs()["agp_names"]])
+def test_agp_names_pinned_to_reference(name, tmp_path):
+    check_pinned_to_reference("agp_names", name, tmp_path)
+
+
+PIN_CASES = pin.all_cases()
+
+
+@pytest.mark.parametrize("family,name", PIN_CASES, ids=[f"{family}-{name}" for family, name in PIN_CASES])
+def test_families_end_to_end_through_print_scaffolds(family, name, tmp_path, monkeypatch):
+    """Ntjoin.print_scaffolds over a target loaded from the case's FASTA: the assigned FASTA, the .path and the AGP (assigned and
+    unassigned lines) are the reference's bytes for all pinned paths, also where the writer refuses an inverted interval and
+    _write_path_host writes both files.  The nodes go in as format_paths() gives them: print_scaffolds zeroes the last gap itself."""
+    entry = pin.load_family(family)[name]
+    case = entry["case"]
+    monkeypatch.chdir(tmp_path)
+    cases.write_fasta("t.fa", case["records"], case["width"], case["final_newline"])
+    on = case["overlap_gap"] is not None
+    paths9 = [pin.rows9(case["paths"][p]) for p in entry["pinned"]]
+    adjust = [[(nd[5], nd[6]) for nd in path] for path in entry["paths"]] if on else None
+    with MxEngine(k=15, w=10) as eng:
+        eng.add_fasta(pin.TARGET, 1.0, "t.fa")
+        nj = Ntjoin.__new__(Ntjoin)
+        nj._engine, nj._order, nj._fasta, nj.args = eng, [pin.TARGET], {pin.TARGET: "t.fa"}, argparse.Namespace(p="out")
+        host = []
+        monkeypatch.setattr(nj, "_write_path_host", lambda *a, _host=nj._write_path_host: (host.append(1), _host(*a))[1])
+        files = nj.print_scaffolds(paths9, adjust, n=1, agp=True, overlap_gap=case["overlap_gap"] if on else 20)
+    assert files["assigned"] == "t.fa.k15.w10.n1.assigned.scaffolds.fa" and files["path"] == "out.path" and files["agp"] == "out.agp"
+    assert pin.scaffold_digests(read(files["assigned"]).decode("ascii")) == entry["scaffolds"]
+    assert read(files["path"]) == entry["path"].encode("ascii")
+    assert read(files["agp"]) == (entry["agp"] + entry["agp_unassigned"]).encode("ascii")
+    assert bool(host) == bool(pin.refused_nodes(entry))   # the host loop wrote the files exactly where an interval is inverted

@@ -8,10 +8,11 @@ import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from ntjoin_amd import assemble, capi, run
-from tests import _oracle, _path_text_restatement as pt, _scaffold_cases as cases, _scaffold_restatement as rs
+from tests import _oracle, _path_text_restatement as pt, _scaffold_cases as cases, _scaffold_pin as pin, _scaffold_restatement as rs
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = sorted(glob.glob(os.path.join(cases.GOLDEN, "scaffolds", "*.json")))
@@ -176,3 +177,65 @@ def test_make_scaffold_has_the_reference_s_defaults_and_needs_no_checkout():
     on = make_n("scaffold", "target=t.fa", "references=a.fa", "reference_weights=2", "g=33")
     assert "--overlap_gap 33" in on  # overlap_g follows g, as in the reference
     assert "scaffold" in make_n("help")
+
+
+# ---- the families of tests/golden/scaffolds/families: the reference's own .path, write_agp and write_agp_unassigned -----------------
+
+PIN_CASES = pin.all_cases()
+PIN_IDS = [f"{family}-{name}" for family, name in PIN_CASES]
+
+
+@pytest.mark.parametrize("family,name", PIN_CASES, ids=PIN_IDS)
+def test_both_formulations_give_the_reference_s_path_and_agp(family, name):
+    """by_regex: every pinned path, the inverted intervals and their negative lengths included, and the unassigned lines; direct: the
+    same text over the paths it does not refuse, and a refusal that names the path and node for each of the others"""
+    entry = pin.load_family(family)[name]
+    case, paths = entry["case"], entry["paths"]
+    _text, leads, tails = rs.scaffolds(paths, dict(case["records"]), case["overlap_gap"])
+    unassigned = pin.unassigned_intervals(case, paths)
+    assert pt.by_regex(paths, leads, tails, pin.TARGET[:4], unassigned) == (entry["path"], entry["agp"] + entry["agp_unassigned"])
+    refused = pin.refused_nodes(entry)
+    keep = [q for q in range(len(paths)) if q not in refused]
+    want = pin.renumbered(entry, keep)
+    assert pt.direct([paths[q] for q in keep], [leads[q] for q in keep], [tails[q] for q in keep], pin.TARGET[:4]) == want
+    if not refused:
+        assert pt.direct(paths, leads, tails, pin.TARGET[:4], unassigned) == (entry["path"], entry["agp"] + entry["agp_unassigned"])
+    for q, i in refused.items():
+        with pytest.raises(pt.Refused, match=f"path 0 node {i}: the adjusted interval is empty or inverted"):
+            pt.direct([paths[q]], [leads[q]], [tails[q]], pin.TARGET[:4])
+        assert any(int(line.split("\t")[2]) < int(line.split("\t")[1]) for line in entry["agp_lines"][q])  # the reference prints them
+
+
+def test_the_reference_s_round_trip_keeps_every_id_of_agp_names():
+    "finding of the agp_names family: write_agp's two expressions recover all six ids, '+:1-' and '-:7-9' inside them included"
+    for entry in pin.load_family("agp_names").values():
+        for path, lines in zip(entry["paths"], entry["agp_lines"]):
+            assert [line.split("\t")[5] for line in lines[::2]] == [nd[0] for nd in path]
+            assert [line.split("\t")[8] for line in lines[::2]] == [nd[1] for nd in path]
+
+
+@pytest.mark.parametrize("family,name", PIN_CASES, ids=PIN_IDS)
+def test_the_host_loop_gives_the_reference_s_path_and_agp(family, name, tmp_path):
+    "Ntjoin._write_path_host, the route print_scaffolds takes when the writer refuses a path: every pinned path, inverted intervals included"
+    from ntjoin_amd.ntjoin import Ntjoin
+    entry = pin.load_family(family)[name]
+    case, paths = entry["case"], entry["paths"]
+    _text, leads, tails = rs.scaffolds(paths, dict(case["records"]), case["overlap_gap"])
+    unassigned = pin.unassigned_intervals(case, paths)
+
+    class Strips:
+        "the one call the host loop makes on the engine"
+        @staticmethod
+        def scaffold_strips():
+            return np.array([u[3] for u in unassigned], dtype=np.uint32), np.array([u[4] for u in unassigned], dtype=np.uint32)
+
+    nj = Ntjoin.__new__(Ntjoin)
+    nj._engine = Strips()
+    files = {kind: str(tmp_path / ("out." + kind)) for kind in ("path", "agp", "bed")}
+    with open(files["bed"], "w", encoding="ascii") as fh:
+        fh.write(rs.unassigned(case["records"], paths)[0])
+    nj._write_path_host(files, pin.TARGET[:4], [(pin.rows9(path), [(nd[5], nd[6]) for nd in path]) for path in paths], leads, tails)
+    with open(files["path"], encoding="ascii") as fh:
+        assert fh.read() == entry["path"]
+    with open(files["agp"], encoding="ascii") as fh:
+        assert fh.read() == entry["agp"] + entry["agp_unassigned"]

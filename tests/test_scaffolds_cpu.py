@@ -1,6 +1,7 @@
 """Scaffold stage, CPU side: the restatement of the contract (tests/_scaffold_restatement.py) is held to every
 golden under tests/golden/scaffolds (the reference's own print_scaffolds output, tests/golden/make_golden_scaffolds.py) and to the
-four result files the reference's tests hold for the f-f run; the fuzz cases of the GPU test cover what they must and leave out no
+four result files the reference's tests hold for the f-f run, and to the reference's answers on the generated families
+(tests/golden/scaffolds/families, tests/golden/make_golden_scaffold_fuzz.py), whose conditions are recomputed here; the fuzz cases of the GPU test cover what they must and leave out no
 more than their cap; the symbol is in the header and in the built library; a TSV-loaded target is refused by name."""
 import argparse
 import glob
@@ -10,7 +11,7 @@ import re
 import pytest
 
 from ntjoin_amd import capi
-from tests import _scaffold_cases as cases, _scaffold_restatement as rs
+from tests import _scaffold_cases as cases, _scaffold_pin as pin, _scaffold_restatement as rs
 from tests import _oracle
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -111,3 +112,36 @@ def test_print_scaffolds_refuses_a_tsv_target_before_anything_runs():
     nj.args = argparse.Namespace(p="out")
     with pytest.raises(ValueError, match="TSV.*FASTA"):
         nj.print_scaffolds([])
+
+
+# ---- the families of tests/golden/scaffolds/families: generated inputs, the reference's own print_scaffolds ------------------------
+
+PIN_CASES = pin.all_cases()
+PIN_IDS = [f"{family}-{name}" for family, name in PIN_CASES]
+
+
+@pytest.mark.parametrize("family,name", PIN_CASES, ids=PIN_IDS)
+def test_restatement_equals_the_reference_on_the_families(family, name):
+    "every pinned path: the scaffold's name, length and digest, the .path line, and the strips the reference's coordinates show"
+    entry = pin.load_family(family)[name]
+    case = entry["case"]
+    text, leads, tails = rs.scaffolds(entry["paths"], dict(case["records"]), case["overlap_gap"])
+    assert pin.scaffold_digests(text) == entry["scaffolds"]
+    assert rs.path_text(pin.TARGET[:4], entry["paths"], leads, tails) == entry["path"]
+    assert list(zip(leads, tails)) == [pin.reference_strips(path, line) for path, line in zip(entry["paths"], entry["path_lines"])]
+
+
+@pytest.mark.parametrize("family", pin.FAMILIES)
+def test_the_families_hold_what_their_readme_promises(family):
+    "the conditions of tests/golden/scaffolds/families/README.md, recomputed from the committed files; no file beyond the size limit"
+    found = pin.check_conditions(family, pin.load_family(family))
+    assert found["pinned"] + found["raised"] == found["generated"]
+    for f in os.listdir(pin.FAMILY_DIR):
+        assert os.path.getsize(os.path.join(pin.FAMILY_DIR, f)) <= 720_100, f
+
+
+def test_the_family_fuzz_is_the_gpu_fuzz_with_the_fold_off():
+    for seed in (1, 2, 47):
+        ours, theirs = pin.fuzz_case(seed), cases.fuzz_case(seed)
+        assert all(ours[key] == theirs[key] for key in ours)
+    assert [args["seed"] for _n, _g, args in pin.family_specs()["fuzz"]] == cases.FUZZ_SEEDS
