@@ -10,66 +10,10 @@
 // collide at random like any gather.  The text leaves through a word accumulator: whole aligned words of the member are stored as
 // words, the bytes of a word the member shares with its neighbour (first and last) as bytes, so no lane writes a neighbour's byte.
 // The CRC-32 of the text is taken as the bytes are put (table in LDS) and compared with the trailer's in the same kernel.
-#include "bgzf_inflate.h"
+#include "bgzf_dev_io.h"
 #include "mxg_internal.h"
 
 namespace mxg {
-
-constexpr uint32_t BGZF_BLOCK = 64;  // lanes = members per block
-static_assert(BGZF_TAB_ELEMS % 2 == 0, "two entries per LDS word");
-static_assert((BGZF_TAB_ELEMS / 2) * BGZF_BLOCK * 4 + 1024 <= 64 * 1024, "tables + CRC table fit a block's LDS");
-
-struct BgzfLdsTab {
-    uint16_t *lane;  // the lane's first entry: entries e and e + 1 (e even) share a word, the next pair is 64 words on
-    __device__ __forceinline__ uint32_t get(uint32_t e) const { return lane[(e >> 1) * (2u * BGZF_BLOCK) + (e & 1u)]; }
-    __device__ __forceinline__ void set(uint32_t e, uint32_t v) { lane[(e >> 1) * (2u * BGZF_BLOCK) + (e & 1u)] = (uint16_t)v; }
-};
-
-struct BgzfDevSrc {
-    const unsigned char *p;  // the member's deflate data
-    uint32_t n;
-    uint32_t have = 0xFFFFFFFFu, word = 0;  // the aligned word fetched last (members start at any byte; the buffer ends on a whole word)
-    __device__ __forceinline__ uint32_t len() const { return n; }
-    __device__ __forceinline__ uint32_t byte(uint32_t i)  // i < n
-    {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(p) + i;
-        const uint32_t w = (uint32_t)(a >> 2);
-        if (w != have) {
-            word = *reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
-            have = w;
-        }
-        return (word >> (8u * ((uint32_t)a & 3u))) & 255u;
-    }
-};
-
-struct BgzfDevSink {
-    unsigned char *out;  // the member's text
-    const uint32_t *crc_tab;
-    uint32_t n = 0, acc = 0, pend = 0, crc = 0xFFFFFFFFu;  // bytes put, the word being filled, its bytes so far
-    __device__ __forceinline__ uint32_t lane_of(uint32_t i) const { return 8u * ((uint32_t)(reinterpret_cast<uintptr_t>(out) + i) & 3u); }
-    __device__ __forceinline__ void flush()
-    {
-        if (pend == 4u) *reinterpret_cast<uint32_t *>(out + n - 4u) = acc;  // (n - 4 is the word's first byte: it ends at n)
-        else
-            for (uint32_t i = n - pend; i < n; ++i) out[i] = (unsigned char)(acc >> lane_of(i));
-        pend = 0;
-        acc = 0;
-    }
-    __device__ __forceinline__ void put(uint8_t b)  // the decoder has counted the byte against ISIZE
-    {
-        crc = crc_tab[(crc ^ b) & 255u] ^ (crc >> 8);
-        const uint32_t sh = lane_of(n);
-        acc |= (uint32_t)b << sh;
-        ++n;
-        ++pend;
-        if (sh == 24u) flush();
-    }
-    __device__ __forceinline__ uint8_t back(uint32_t d) const  // 1 <= d <= n
-    {
-        const uint32_t i = n - d;
-        return d <= pend ? (uint8_t)(acc >> lane_of(i)) : out[i];
-    }
-};
 
 __global__ __launch_bounds__(BGZF_BLOCK) void k_bgzf_inflate(const unsigned char *__restrict__ comp, uint64_t comp_bytes,
                                                             const BgzfMember *__restrict__ members, uint32_t n_members, unsigned char *text,

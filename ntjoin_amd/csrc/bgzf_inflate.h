@@ -1,14 +1,15 @@
 // BGZF (what `bgzip` writes: a chain of independent gzip members of at most 64 KiB of text each) taken apart: the walk over a file's
 // members and a raw DEFLATE decoder for ONE member.  Plain C++ over an abstract byte source, byte sink and table storage: the kernel
-// (bgzf.hip, one member per lane, tables in LDS) and a CPU test (tests/test_bgzf_cpu.py, also under the sanitizers) compile the
-// same text.
+// (bgzf.hip, one member per lane, tables in LDS) and the CPU tests (tests/test_bgzf_cpu.py, tests/test_bgzf_craft_cpu.py, also
+// under the sanitizers) compile the same text; the kernel's source, sink and table types are in bgzf_dev_io.h for the same reason.
 //
 // The decoder is safe on any input by construction, not by trust in the file:
 //   - every input byte is fetched through BgzfBits::need, which stops at the member's deflate length;
 //   - every output byte is counted against the member's ISIZE before it is put;
 //   - a match distance never reaches in front of what THIS member has produced (no dictionary from another member);
-//   - code-length sets are accepted by zlib's rules: an over-subscribed set is refused, an incomplete one too, except the distance
-//     set of exactly one code of one bit (and the one without any code: a block of literals only);
+//   - code-length sets are accepted by zlib's rules: an over-subscribed set is refused, an incomplete one too, except a literal/length
+//     or distance set of exactly one code of one bit -- the other bit is then no code of the set -- and the distance set without any
+//     code (a block of literals only); the code-length code itself must be complete, and the end-of-block code must have a length;
 //   - the symbol tables are indexed only below the number of symbols that were counted into them;
 //   - the decode must end on the end-of-block code of a final block, with exactly ISIZE bytes put and every input byte used.
 // Every loop consumes input bits, produces output bytes or runs over a constant: `steps` counts the decoded symbols and block
@@ -262,8 +263,11 @@ template <class Src, class Tab> MXG_BGZF_FN uint32_t bgzf_dynamic_tables(BgzfBit
         for (; rep; --rep) bgzf_len_set(tab, index++, len);
     }
     if (bgzf_len_get(tab, 256) == 0) return BGZF_CODE_LENGTHS;  // no end-of-block code
-    if (bgzf_construct(tab, BGZF_E_CNT_L, BGZF_E_SYM_L, 0, nlen) != 0) return BGZF_CODE_LENGTHS;
-    const int left = bgzf_construct(tab, BGZF_E_CNT_D, BGZF_E_SYM_D, nlen, ndist);
+    // (an incomplete set of ONE code of one bit is zlib's exception for both sets: the other bit is no code, BGZF_SYMBOL)
+    int left = bgzf_construct(tab, BGZF_E_CNT_L, BGZF_E_SYM_L, 0, nlen);
+    if (left < 0) return BGZF_CODE_LENGTHS;
+    if (left > 0 && !(tab.get(BGZF_E_CNT_L + 1) == 1u && tab.get(BGZF_E_CNT_L) + 1u == nlen)) return BGZF_CODE_LENGTHS;
+    left = bgzf_construct(tab, BGZF_E_CNT_D, BGZF_E_SYM_D, nlen, ndist);
     if (left < 0) return BGZF_CODE_LENGTHS;
     if (left > 0 && !(tab.get(BGZF_E_CNT_D + 1) == 1u && tab.get(BGZF_E_CNT_D) + 1u == ndist)) return BGZF_CODE_LENGTHS;
     return BGZF_OK;
