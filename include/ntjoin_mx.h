@@ -783,6 +783,67 @@ int mxg_synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params *pa
                        const uint32_t *subject_length /* NULL: the handle's own */, mxg_synteny_view *out);
 int mxg_write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append);
 
+/* ---- next row (f13): reference-based assessment of the kept blocks: chains, breakpoints, NGA50 --------------------
+   What the reference's `analysis` target runs QUAST for (`quast -r ref --split-scaffolds --scaffold-gap-max-size 100000`,
+   ntJoin:243-252): how much of the reference the query covers in how long collinear stretches, and where it breaks collinearity --
+   from the kept blocks of the handle's last successful mxg_synteny_blocks: the blocks in their order, with the piece table, the
+   query lengths and the subject lengths that call used (the handle keeps what it needs of these).  k = the handle's k.
+   PIECE OF A BASE.  piece_of(r, x) = the index of the piece of query record r that holds base x: the piece with
+   off <= x < off + len (off = the sum of the lengths of the record's earlier pieces).  GAP pieces count.  Without a piece table
+   every record is one piece.
+   JOINED.  Consecutive kept blocks i and i + 1 are joined iff all of these hold:
+     they have the same q_record, the same s_record and the same reverse;
+     gq = q_start[i+1] - q_end[i];  gs = s_start[i+1] - s_end[i] when forward, s_start[i] - s_end[i+1] when reverse (signed 64-bit):
+         gq >= 1 - k and gs >= 1 - k (the next block's first anchor lies beyond this block's last anchor on both assemblies, in
+         the block's direction);
+     when merge_gap > 0: max(gq, gs) <= merge_gap;
+     with at_join(i) = (piece_of(q_record, q_end[i] - 1) != piece_of(q_record, q_start[i+1])) and
+         bound = at_join(i) ? join_indel : max_indel: when bound > 0, |gq - gs| <= bound.
+   CHAINS.  A chain is a maximal run of joined consecutive kept blocks; chains are kept in order.  Per chain: n_blocks; first_block;
+   n_anchors = the sum of its blocks' counts (joined blocks share no anchor); q_record; q_start of its first block, q_end of its
+   last; s_record; s_start = min and s_end = max over its first and last block; reverse.  There is no chain filter (min_anchors /
+   min_span of the blocks call filter what should not count).
+   BREAKPOINTS.  Every pair of consecutive chains c, c + 1 with equal q_record is a breakpoint, of the first kind that applies:
+   MXG_BP_TRANSLOCATION the subject records differ; MXG_BP_INVERSION reverse differs; MXG_BP_RELOCATION anything else.  Per
+   breakpoint: chain = c; kind; at_join, taken from the last block of c and the first block of c + 1; q_lo = q_end[c];
+   q_hi = q_start[c+1] (q_lo > q_hi where the two chains share a turning anchor).
+   SUMMARY (exact 64-bit integers).  n_blocks, n_chains, n_breakpoints; breakpoints[kind][at_join]; query_bases and subject_bases =
+   the sums of the record lengths; aligned_query = the sum of q_end - q_start over chains; chained_subject = the sum of
+   s_end - s_start over chains; covered_subject = the sum over subject records of the size of the union of that record's chains'
+   [s_start, s_end); three Nx blocks {n50, l50, n75, l75, n90, l90}:
+       na   the chains' query spans,     D = query_bases
+       nga  the chains' query spans,     D = subject_bases
+       ng   the query record lengths,    D = subject_bases
+   With the multiset sorted descending and S_j the sum of its first j: Lx = the smallest j with 100 S_j >= x D, Nx = the j-th
+   length; both 0 when no j reaches it or D == 0.
+   Computed on the device (assess.hip): the blocks are uploaded from the host copy the blocks view holds, so the result spells that
+   view.  The view's arrays are host copies owned by the handle until its next mxg_synteny_assess.
+   MXG_EINVAL: a null argument, struct_size too small, no successful mxg_synteny_blocks before.  MXG_ELIMIT: as in the blocks call
+   (2^31 blocks or more; the blocks call refuses them first).  Zero blocks is valid: zero chains, zero breakpoints, zero sums, and
+   ng still computed.  Sketches, graph, paths, kept text and the blocks stay as they are: mxg_write_synteny_paf still works. */
+#define MXG_BP_TRANSLOCATION 0u
+#define MXG_BP_INVERSION 1u
+#define MXG_BP_RELOCATION 2u
+typedef struct mxg_assess_params {
+    uint32_t struct_size; /* = sizeof(mxg_assess_params) */
+    uint32_t merge_gap;   /* largest gap between joined blocks, on either assembly; 0 = no bound.  Default 100000 */
+    uint32_t max_indel;   /* largest |gq - gs| between joined blocks inside one piece; 0 = no bound.  Default 1000 */
+    uint32_t join_indel;  /* the same where the two blocks lie in different pieces; 0 = no bound.  Default 100000 */
+} mxg_assess_params;
+typedef struct mxg_nx {
+    uint64_t n50, l50, n75, l75, n90, l90;
+} mxg_nx;
+typedef struct mxg_assess_view {
+    uint64_t n_blocks, n_chains, n_breakpoints;
+    uint64_t breakpoints[3][2]; /* [kind][at_join] */
+    uint64_t query_bases, subject_bases, aligned_query, chained_subject, covered_subject;
+    mxg_nx na, nga, ng;
+    const uint32_t *chain_n_blocks, *chain_first_block, *chain_n_anchors, *chain_q_record, *chain_q_start, *chain_q_end, *chain_s_record,
+        *chain_s_start, *chain_s_end, *chain_reverse;                      /* [n_chains] */
+    const uint32_t *bp_chain, *bp_kind, *bp_at_join, *bp_q_lo, *bp_q_hi; /* [n_breakpoints] */
+} mxg_assess_view;
+int mxg_synteny_assess(mxg_handle *h, const mxg_assess_params *params, mxg_assess_view *out);
+
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------
    No counterpart in the reference (it is one process).  Uniqueness and intersection need every occurrence of a hash in
    one place: every minimizer travels to the rank that owns its hash, the owner runs the ordinary graph kernels on what it

@@ -18,6 +18,9 @@ computed on the GPU from the text the handle holds and from the scaffold files o
 --synteny (--synteny_max_gap, --synteny_min_anchors, --synteny_min_span): also <p>.synteny.paf -- the maximal collinear runs of shared
 unique minimizers between the scaffolds (the records of the assigned, then of the unassigned file) and every reference, one PAF line
 per run, computed on the GPU from the graph; a reference loaded from its TSV needs <fasta>.fai for its lengths, or is left out.
+--assess (--assess_merge_gap, --assess_max_indel, --assess_join_indel): also <p>.assess.tsv and <p>.breakpoints.bed -- the target and
+the scaffolds against every reference: the blocks of --synteny_* merged into chains, aligned and covered bases, NA50 / NGA50 / NG50,
+and the breakpoints by kind, each blamed on a join the scaffolder made or on a contig; computed on the GPU (ntjoin_amd/report.py).
 --rounds_w "500 250" (--rounds_keep): further rounds with these window sizes in the same process, the scaffolds of a round being the
 target of the next without a file between them, and <p>.rounds.agp over the contigs of the first target (ntjoin_amd/rounds.py).
 """

@@ -18,6 +18,7 @@ SCAF_KEEP = 0x10
 REPORT_ASSIGNED, REPORT_UNASSIGNED, REPORT_ALL = 0, 1, 2
 PATHS_AGP_UNASSIGNED = 0x1
 PIECE_FWD, PIECE_REV, PIECE_GAP = 0, 1, 2
+BP_TRANSLOCATION, BP_INVERSION, BP_RELOCATION = 0, 1, 2
 ABI_VERSION = 3
 
 SYMBOLS = [
@@ -35,7 +36,7 @@ SYMBOLS = [
     "mxg_plan_split", "mxg_add_assembly_packed_device_pieces", "mxg_dg_last_shared", "mxg_dg_set_ghosts",
     "mxg_compose_pieces", "mxg_add_assembly_text_device", "mxg_assembly_text",
     "mxg_scaffold_text", "mxg_scaffold_pieces", "mxg_scaffold_record_id",
-    "mxg_synteny_blocks", "mxg_write_synteny_paf",
+    "mxg_synteny_blocks", "mxg_write_synteny_paf", "mxg_synteny_assess",
 ]
 
 
@@ -108,6 +109,26 @@ class SyntenyView(C.Structure):  # mxg_synteny_view: 88 bytes (api.cpp asserts t
     _fields_ = ([("n_blocks", C.c_uint64), ("n_anchors_total", C.c_uint64), ("n_links", C.c_uint64)] +
                 [(name, C.POINTER(C.c_uint32)) for name in ("n_anchors", "q_record", "q_start", "q_end", "s_record", "s_start", "s_end")] +
                 [("reverse", C.POINTER(C.c_uint8))])
+
+
+class AssessParams(C.Structure):  # mxg_assess_params: 16 bytes (api.cpp asserts the same)
+    _fields_ = [("struct_size", C.c_uint32), ("merge_gap", C.c_uint32), ("max_indel", C.c_uint32), ("join_indel", C.c_uint32)]
+
+
+class Nx(C.Structure):  # mxg_nx
+    _fields_ = [(name, C.c_uint64) for name in ("n50", "l50", "n75", "l75", "n90", "l90")]
+
+
+ASSESS_CHAIN_FIELDS = ("n_blocks", "first_block", "n_anchors", "q_record", "q_start", "q_end", "s_record", "s_start", "s_end", "reverse")
+ASSESS_BP_FIELDS = ("chain", "kind", "at_join", "q_lo", "q_hi")
+
+
+class AssessView(C.Structure):  # mxg_assess_view: 376 bytes (api.cpp asserts the same)
+    _fields_ = ([(name, C.c_uint64) for name in ("n_blocks", "n_chains", "n_breakpoints")] + [("breakpoints", (C.c_uint64 * 2) * 3)] +
+                [(name, C.c_uint64) for name in ("query_bases", "subject_bases", "aligned_query", "chained_subject", "covered_subject")] +
+                [("na", Nx), ("nga", Nx), ("ng", Nx)] +
+                [("chain_" + name, C.POINTER(C.c_uint32)) for name in ASSESS_CHAIN_FIELDS] +
+                [("bp_" + name, C.POINTER(C.c_uint32)) for name in ASSESS_BP_FIELDS])
 
 
 class Contiguity(C.Structure):  # mxg_contiguity: 88 bytes (api.cpp asserts the same)
@@ -252,6 +273,7 @@ def load():
     L.mxg_compose_pieces.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(vp), C.POINTER(C.POINTER(u64))]
     L.mxg_synteny_blocks.argtypes = [vp, i32, i32, C.POINTER(SyntenyParams), vp, vp, u64, vp, vp, C.POINTER(SyntenyView)]
     L.mxg_write_synteny_paf.argtypes = [vp, C.POINTER(cp), C.c_char_p, i32]
+    L.mxg_synteny_assess.argtypes = [vp, C.POINTER(AssessParams), C.POINTER(AssessView)]
     L.mxg_bgzf_write.argtypes = [vp, vp, u64, C.c_char_p]
     L.mxg_write_fai.argtypes = [vp, i32, C.c_char_p, C.c_char_p]
     L.mxg_set_report_params.argtypes = [vp, u64, u64]

@@ -1234,6 +1234,49 @@ int mxg_write_synteny_paf(mxg_handle *h, const char *const *query_names, const c
     }
 }
 
+static_assert(sizeof(mxg_assess_params) == 16, "mxg_assess_params: ntjoin_amd/capi.py AssessParams mirrors this layout");
+static_assert(sizeof(mxg_assess_view) == 376, "mxg_assess_view: ntjoin_amd/capi.py AssessView mirrors this layout");
+
+int mxg_synteny_assess(mxg_handle *h, const mxg_assess_params *params, mxg_assess_view *out)
+{
+    if (!h) return MXG_EINVAL;
+    if (!params || !out) return set_err(h, MXG_EINVAL, "mxg_synteny_assess: null argument");
+    if (params->struct_size < sizeof(mxg_assess_params))
+        return set_err(h, MXG_EINVAL, "mxg_synteny_assess: struct_size %u is too small", params->struct_size);
+    if (!h->syn.valid) return set_err(h, MXG_EINVAL, "mxg_synteny_assess: the handle's last mxg_synteny_blocks left no blocks (none was called, or it failed)");
+    int rc;
+    try {
+        rc = synteny_assess(h, *params);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_synteny_assess");
+    }
+    if (rc != MXG_OK) return rc;
+    const mxg_handle::Assess &A = h->assess;
+    out->n_blocks = h->syn.reverse.size();
+    out->n_chains = A.n_chains;
+    out->n_breakpoints = A.n_bp;
+    for (int kind = 0; kind < 3; ++kind)
+        for (int j = 0; j < 2; ++j) out->breakpoints[kind][j] = A.sum[AS_BP0 + kind * 2 + j];
+    out->query_bases = A.query_bases;
+    out->subject_bases = A.subject_bases;
+    out->aligned_query = A.sum[AS_ALIGNED];
+    out->chained_subject = A.sum[AS_CHAINED];
+    out->covered_subject = A.sum[AS_COVERED];
+    const int at[3] = {AS_NA, AS_NGA, AS_NG};
+    mxg_nx *nx[3] = {&out->na, &out->nga, &out->ng};
+    for (int u = 0; u < 3; ++u) {
+        const uint64_t *w = A.sum + at[u];
+        nx[u]->n50 = w[0], nx[u]->l50 = w[1], nx[u]->n75 = w[2], nx[u]->l75 = w[3], nx[u]->n90 = w[4], nx[u]->l90 = w[5];
+    }
+    const uint32_t *c = A.chain.data(), *b = A.bp.data();
+    const size_t n = A.n_chains, m = A.n_bp;
+    out->chain_n_blocks = c, out->chain_first_block = c + n, out->chain_n_anchors = c + 2 * n, out->chain_q_record = c + 3 * n;
+    out->chain_q_start = c + 4 * n, out->chain_q_end = c + 5 * n, out->chain_s_record = c + 6 * n, out->chain_s_start = c + 7 * n;
+    out->chain_s_end = c + 8 * n, out->chain_reverse = c + 9 * n;
+    out->bp_chain = b, out->bp_kind = b + m, out->bp_at_join = b + 2 * m, out->bp_q_lo = b + 3 * m, out->bp_q_hi = b + 4 * m;
+    return MXG_OK;
+}
+
 int mxg_scaffold_strips(mxg_handle *h, const uint32_t **lead_strip, const uint32_t **tail_strip, uint64_t *n_intervals)
 {
     if (!h) return MXG_EINVAL;

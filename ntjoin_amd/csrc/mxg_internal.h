@@ -305,7 +305,16 @@ struct mxg_handle {
         std::vector<uint32_t> block;     // eight arrays of n_blocks words: n_anchors, q_record, q_start, q_end, s_record, s_start, s_end, reverse
         std::vector<uint8_t> reverse;    // [n_blocks]
         std::vector<uint32_t> q_len, s_len;  // the lengths of the query's records (a piece table's: the sums of their pieces) and the subject's
+        std::vector<uint32_t> q_pre, q_first;  // q_table: every piece's offset in its record, and the records' first pieces (n_records + 1)
     } syn;
+    mxg::DevBuf asbuf[32];   // scratch of assess.hip
+    struct Assess {          // the last mxg_synteny_assess (what its view points into)
+        uint64_t n_chains = 0, n_bp = 0, query_bases = 0, subject_bases = 0;
+        uint64_t sum[32] = {};          // assess.hip's summary words
+        std::vector<uint32_t> chain;    // ten arrays of n_chains words, in the order of AsChain's fields
+        std::vector<uint32_t> bp;       // five arrays of n_bp words: chain, kind, at_join, q_lo, q_hi
+        std::vector<uint32_t> bp_all;   // scratch: the same as they come home, five arrays of n_chains words
+    } assess;
     std::vector<uint32_t> scaf_lead, scaf_tail;  // N/n stripped from either end of every unassigned interval by the last mxg_write_scaffolds
     struct ScafInterval {
         uint32_t rec, lo, hi, lead, tail;
@@ -648,6 +657,10 @@ int compose_pieces(mxg_handle *h, const mxg_seq_piece *outer, const uint64_t *ou
 int synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params &p, const mxg_seq_piece *pieces, const uint64_t *first, uint64_t n_records,
                    const uint32_t *query_length, const uint32_t *subject_length);
 int write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append);
+// assess.hip: chains, breakpoints and the summary of h->syn's kept blocks (mxg_synteny_assess; fills h->assess)
+int synteny_assess(mxg_handle *h, const mxg_assess_params &p);
+enum { AS_BP0, AS_ALIGNED = 6, AS_CHAINED, AS_COVERED, AS_NA, AS_NGA = AS_NA + 6, AS_NG = AS_NGA + 6, AS_HEADS = AS_NG + 6, AS_NBP, AS_SCRATCH, AS_WORDS };
+static_assert(AS_WORDS <= 32, "mxg_handle::Assess::sum too small");
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm
 int flags_to_host(mxg_handle *h, Assembly *a);
 

@@ -198,8 +198,10 @@ int synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params &p, con
         rc = cmp_table("query", pieces, first, n_records, qlen_in.size(), qlen_in.data(), tab, msg);
         if (rc != MXG_OK) return set_err(h, rc, "mxg_synteny_blocks: %s", msg.c_str());
         S.q_len = tab.len;
+        S.q_pre = tab.pre, S.q_first = tab.first;  // (what mxg_synteny_assess asks of the table: the piece of a base)
     } else {
         S.q_len = qlen_in;
+        S.q_pre.clear(), S.q_first.clear();
     }
     S.q = q, S.s = s, S.q_table = pieces != nullptr;
     S.n_anchors = S.n_links = 0;

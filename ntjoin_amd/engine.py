@@ -601,6 +601,24 @@ class MxEngine:
             names = (C.c_char_p * max(len(query_names), 1))(*[str(i).encode() for i in query_names])
         self._check(self._lib.mxg_write_synteny_paf(self._h, names, os.fsencode(str(path)), int(bool(append))))
 
+    def synteny_assess(self, merge_gap=100000, max_indel=1000, join_indel=100000):
+        """mxg_synteny_assess: the kept blocks of the last synteny_blocks() merged into chains, the breakpoints between the chains and
+        the summary (include/ntjoin_mx.h) -> dict(n_blocks, n_chains, n_breakpoints, breakpoints: {(kind, at_join): count} with kind in
+        capi.BP_*, query_bases, subject_bases, aligned_query, chained_subject, covered_subject, na / nga / ng: dict(n50, l50, n75, l75,
+        n90, l90), chains: dict of u32 arrays by capi.ASSESS_CHAIN_FIELDS, bps: dict of u32 arrays by capi.ASSESS_BP_FIELDS)."""
+        p = capi.AssessParams()
+        p.struct_size, p.merge_gap, p.max_indel, p.join_indel = C.sizeof(capi.AssessParams), int(merge_gap), int(max_indel), int(join_indel)
+        v = capi.AssessView()
+        self._check(self._lib.mxg_synteny_assess(self._h, C.byref(p), C.byref(v)))
+        out = {name: int(getattr(v, name)) for name in ("n_blocks", "n_chains", "n_breakpoints", "query_bases", "subject_bases", "aligned_query",
+                                                        "chained_subject", "covered_subject")}
+        out["breakpoints"] = {(kind, j): int(v.breakpoints[kind][j]) for kind in range(3) for j in range(2)}
+        for which in ("na", "nga", "ng"):
+            out[which] = {name: int(getattr(getattr(v, which), name)) for name, _ in capi.Nx._fields_}
+        out["chains"] = {name: _np(getattr(v, "chain_" + name), out["n_chains"], np.uint32) for name in capi.ASSESS_CHAIN_FIELDS}
+        out["bps"] = {name: _np(getattr(v, "bp_" + name), out["n_breakpoints"], np.uint32) for name in capi.ASSESS_BP_FIELDS}
+        return out
+
     def write_fai(self, assembly, path, gzi=None):
         """mxg_write_fai: the index `samtools faidx` makes of the assembly's FASTA, from the text the handle holds, written to `path`;
         gzi= names the .gzi to write for an assembly that came from a BGZF file"""

@@ -21,12 +21,13 @@ import numpy as np
 from . import capi
 from .engine import MxEngine, MxError
 from .ntjoin_utils import MxGraph, sketch_views
-from .report import COLUMNS as REPORT_COLUMNS, row as report_row
+from .report import ASSESS_COLUMNS, COLUMNS as REPORT_COLUMNS, assess_row, breakpoint_lines, row as report_row
 
 COLOURS = ["red", "green", "blue", "purple", "orange", "turquoise", "pink", "yellow", "orchid", "salmon"]
 
 MK_Z975 = 1.959963984540054  # scipy.stats.norm.ppf(0.975): original_test's threshold on |z| at alpha = 0.05
 _SQRT1_2 = 0.7071067811865476
+SYNTENY_DEFAULTS = dict(max_gap=100000, min_anchors=3, min_span=0)  # write_synteny's and write_assess's, of the blocks call
 
 
 def _norm_cdf(a):
@@ -375,16 +376,18 @@ class Ntjoin:
         at = res["node_first"].tolist()
         return [rows[lo:hi] for lo, hi in zip(at, at[1:])]
 
-    def scaffold(self, lengths=None, keep=False, quiet=False, synteny=None):
+    def scaffold(self, lengths=None, keep=False, quiet=False, synteny=None, assess=None):
         """main_scaffolder (:751-786) behind load_minimizers_scaffold in one handle: make_minimizer_graph -> find_paths ->
         format_paths -> adjust_paths -> trim_overlaps (when args.overlap) -> print_scaffolds.  Read from args, with ntJoin's
         defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz, fai, report,
-        report_min_gap, report_min_len, synteny, synteny_max_gap, synteny_min_anchors, synteny_min_span.  Returns what print_scaffolds
-        returns (the written files by kind).  With args.fai the inputs read from FASTA get their <fasta>.fai first
+        report_min_gap, report_min_len, synteny, synteny_max_gap, synteny_min_anchors, synteny_min_span, assess, assess_merge_gap,
+        assess_max_indel, assess_join_indel.  Returns what print_scaffolds returns (the written files by kind).  With args.fai the inputs read from FASTA get their <fasta>.fai first
         (write_input_indexes); with args.report <prefix>.report.tsv is written ("report": write_report); with args.synteny
         <prefix>.synteny.paf ("synteny": write_synteny; synteny=False leaves it out whatever args says: an earlier round of
-        ntjoin_amd/rounds.py).  keep / quiet: print_scaffolds' (a round of ntjoin_amd/rounds.py); a quiet round writes no .mx.dot, no
-        index, no report and no PAF either."""
+        ntjoin_amd/rounds.py); with args.assess <prefix>.assess.tsv and <prefix>.breakpoints.bed ("assess", "breakpoints":
+        write_assess, with the blocks parameters of --synteny_*; assess=False leaves them out likewise).  keep / quiet:
+        print_scaffolds' (a round of ntjoin_amd/rounds.py); a quiet round writes no .mx.dot, no index, no report, no PAF and no
+        assessment either."""
         opt = lambda name, dflt: dflt if getattr(self.args, name, None) is None else getattr(self.args, name)  # noqa: E731
         if quiet:
             opt = lambda name, dflt, _opt=opt: False if name in ("fai", "report") else _opt(name, dflt)  # noqa: E731
@@ -401,13 +404,17 @@ class Ntjoin:
         paths = self.format_paths(lengths, g=int(opt("g", 20)), G=G, m=opt("m", 90), mkt=bool(opt("mkt", False)))
         paths = self.adjust_paths(paths, no_cut=bool(opt("no_cut", False)), G=G)
         cuts = self.trim_overlaps(paths, opt("overlap_k", 15), opt("overlap_w", 10)) if opt("overlap", False) else None
-        syn = None
+        syn = asz = None
+        blocks_kw = dict(max_gap=int(opt("synteny_max_gap", 100000)), min_anchors=int(opt("synteny_min_anchors", 3)),
+                         min_span=int(opt("synteny_min_span", 0)))
         if (bool(opt("synteny", False)) if synteny is None else synteny) and not quiet:
-            syn = dict(max_gap=int(opt("synteny_max_gap", 100000)), min_anchors=int(opt("synteny_min_anchors", 3)),
-                       min_span=int(opt("synteny_min_span", 0)))
+            syn = blocks_kw
+        if (bool(opt("assess", False)) if assess is None else assess) and not quiet:
+            asz = dict(blocks_kw, merge_gap=int(opt("assess_merge_gap", 100000)), max_indel=int(opt("assess_max_indel", 1000)),
+                       join_indel=int(opt("assess_join_indel", 100000)))
         files = self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)),
                                      gz=bool(opt("gz", False)), fai=bool(opt("fai", False)), report=report, keep=keep, quiet=quiet,
-                                     **({"synteny": syn} if syn else {}))
+                                     **({"synteny": syn} if syn else {}), **({"assess": asz} if asz else {}))
         if report:
             files["report"] = self.write_report(report_rows, files)
         return files
@@ -576,7 +583,7 @@ class Ntjoin:
                 agp_fh.close()
 
     def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False, report=False, keep=False, quiet=False,
-                        synteny=None):
+                        synteny=None, assess=None):
         """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
         trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
         than two nodes are dropped (:585-594), the last kept node's gap is zeroed (check_terminal_node_gap_zero :441-448), and the
@@ -589,9 +596,18 @@ class Ntjoin:
         also stays in device memory (MXG_SCAF_KEEP: MxEngine.scaffold_text, scaffold_pieces).  quiet=True (with keep): only <p>.path
         and, with agp, <p>.agp are written -- an earlier round of ntjoin_amd/rounds.py.  synteny=dict(max_gap, min_anchors, min_span)
         (or True for the defaults): also <p>.synteny.paf ("synteny": write_synteny), which needs the scaffolds' piece table and so
-        turns keep on.  Returns the file names by kind."""
+        turns keep on.  assess=dict(merge_gap, max_indel, join_indel, max_gap, min_anchors, min_span) (or True for the defaults): also
+        <p>.assess.tsv and <p>.breakpoints.bed ("assess", "breakpoints": write_assess); it turns keep on as well, and with synteny the
+        scaffolds' blocks are computed once for both, so the two must then name the same max_gap, min_anchors and min_span (ValueError
+        otherwise, before anything is written).  Returns the file names by kind."""
+        if synteny and assess:
+            given = [{key: (arg if isinstance(arg, dict) else {}).get(key, default) for key, default in SYNTENY_DEFAULTS.items()}
+                     for arg in (synteny, assess)]
+            if given[0] != given[1]:
+                raise ValueError(f"print_scaffolds: synteny= and assess= share one blocks call and must agree on its parameters: {given[0]} "
+                                 f"against {given[1]}")
         self._last_print = dict(paths=paths, adjust=adjust, n=n, agp=agp, overlap_gap=overlap_gap, gz=gz, fai=fai, report=report)
-        if synteny and not quiet:
+        if (synteny or assess) and not quiet:
             keep = True
         eng, tgt = self._engine, len(self._order) - 1
         if tgt < 0:
@@ -638,7 +654,10 @@ class Ntjoin:
             res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
                                       assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz),
                                       **({"fai": True} if fai else {}), **({"report": True} if report else {}), **({"keep": True} if keep else {}))
-        if synteny and not quiet:
+        if assess and not quiet:
+            files.update(self.write_assess(**(assess if isinstance(assess, dict) else {}), paf=bool(synteny),
+                                           scaffolds_name=files["assigned"].replace(".assigned.scaffolds.", ".all.scaffolds.")))
+        elif synteny and not quiet:
             files["synteny"] = self.write_synteny(**(synteny if isinstance(synteny, dict) else {}))
         if fai:
             for kind in ("assigned", "unassigned"):
@@ -667,23 +686,62 @@ class Ntjoin:
         in command-line order, one PAF line per block (MxEngine.write_synteny_paf).  A reference loaded from its TSV has no record
         lengths in the handle: they are read from <fasta>.fai when that file exists, else the reference is left out with one line on
         stderr.  Returns the file's name."""
+        return self._synteny_files(dict(max_gap=max_gap, min_anchors=min_anchors, min_span=min_span), paf=True)["synteny"]
+
+    def write_assess(self, merge_gap=100000, max_indel=1000, join_indel=100000, max_gap=100000, min_anchors=3, min_span=0, paf=False,
+                     scaffolds_name="scaffolds"):
+        """<prefix>.assess.tsv and <prefix>.breakpoints.bed: for every reference, in command-line order, the target as loaded and then
+        the scaffolds the last print_scaffolds(keep=True) left (write_synteny's records) are assessed against it -- one
+        MxEngine.synteny_blocks (max_gap, min_anchors, min_span) and one MxEngine.synteny_assess (merge_gap, max_indel, join_indel)
+        each.  The TSV has a header line and one row per (query, reference) (ntjoin_amd/report.py: assess_row); the BED holds the
+        scaffolds' breakpoints (breakpoint_lines).  paf=True: the scaffolds' blocks are also written to <prefix>.synteny.paf, as
+        write_synteny does.  A reference loaded from its TSV is treated as write_synteny treats it.  Returns the files by kind."""
+        return self._synteny_files(dict(max_gap=max_gap, min_anchors=min_anchors, min_span=min_span), paf=paf,
+                                   assess=dict(merge_gap=merge_gap, max_indel=max_indel, join_indel=join_indel), scaffolds_name=scaffolds_name)
+
+    def _synteny_files(self, blocks_kw, paf, assess=None, scaffolds_name="scaffolds"):
+        "write_synteny and write_assess: one pass over the references, the scaffolds' blocks computed once for the PAF and the assessment"
         eng, tgt = self._engine, len(self._order) - 1
         pieces, first, ids = eng.scaffold_pieces()
-        out = self.args.p + ".synteny.paf"
-        with open(out, "wb"):
-            pass   # (every reference's lines are appended)
+        files = {}
+        if paf:
+            files["synteny"] = self.args.p + ".synteny.paf"
+            with open(files["synteny"], "wb"):
+                pass   # (every reference's lines are appended)
+        rows, bed = [], []
+        if assess is not None:
+            target_ids = eng.record_ids(tgt, eng.n_records(tgt))
+            target_name = self._fasta.get(self._order[tgt], self._order[tgt])
         for a, assembly in enumerate(self._order[:tgt]):
             lengths = None
             if assembly not in self._fasta:
                 lengths = self._fai_lengths(a, assembly)
                 if lengths is None:
-                    print(f"ntjoin_amd: {assembly} was loaded from its TSV and its FASTA has no .fai: the synteny PAF has no lines for it",
-                          file=sys.stderr)
+                    what = ("the synteny PAF has no lines" if paf else "") + (" and " if paf and assess is not None else "") + \
+                        ("the assessment has no rows" if assess is not None else "")
+                    print(f"ntjoin_amd: {assembly} was loaded from its TSV and its FASTA has no .fai: {what} for it", file=sys.stderr)
                     continue
-            eng.synteny_blocks(tgt, a, max_gap=max_gap, min_anchors=min_anchors, min_span=min_span, pieces=pieces, first=first,
-                               subject_length=lengths)
-            eng.write_synteny_paf(out, query_names=ids, append=True)
-        return out
+            if assess is not None:
+                match = re.search(r"^(.+)\.k\d+\.w\d+\.tsv$", assembly)
+                ref_name = self._fasta.get(assembly) or (match.group(1) if match else assembly)
+                blk = eng.synteny_blocks(tgt, a, subject_length=lengths, **blocks_kw)
+                rows.append(assess_row(target_name, ref_name, len(target_ids), blk["n_anchors_total"], eng.synteny_assess(**assess)))
+            blk = eng.synteny_blocks(tgt, a, pieces=pieces, first=first, subject_length=lengths, **blocks_kw)
+            if paf:
+                eng.write_synteny_paf(files["synteny"], query_names=ids, append=True)
+            if assess is not None:
+                res = eng.synteny_assess(**assess)
+                rows.append(assess_row(scaffolds_name, ref_name, len(ids), blk["n_anchors_total"], res))
+                bed += breakpoint_lines(res, ids, ref_name, eng.record_ids(a, eng.n_records(a)))
+        if assess is not None:
+            files["assess"], files["breakpoints"] = self.args.p + ".assess.tsv", self.args.p + ".breakpoints.bed"
+            with open(files["assess"], "w", encoding="utf-8") as fh:
+                fh.write("\t".join(ASSESS_COLUMNS) + "\n")
+                for row in rows:
+                    fh.write(row + "\n")
+            with open(files["breakpoints"], "w", encoding="utf-8") as fh:
+                fh.writelines(bed)
+        return files
 
     def _fai_lengths(self, a, assembly):
         "the lengths of assembly a's records from <fasta>.fai (the TSV being named <fasta>.k<k>.w<w>.tsv), or None"

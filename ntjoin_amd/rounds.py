@@ -14,6 +14,7 @@ The last round writes everything a single run writes; an earlier round its .path
 every file the chain would leave.  <p>.rounds.agp spells every record of the last round's scaffolds over the records of the
 original target: the rounds' piece tables (mxg_scaffold_pieces) composed on the device (mxg_compose_pieces), formatted here.
 --synteny: the last round's scaffolds against the references, <p>.round<i>.synteny.paf beside that round's other files.
+--assess: likewise, the last round's target and scaffolds: <p>.round<i>.assess.tsv and <p>.round<i>.breakpoints.bed.
 
     python -m ntjoin_amd.rounds last_out TARGET K W N GZ W2 [W3 ...]   prints T_last.k<k>.w<w_last>.n<n> (for the make front-end)
 """
@@ -137,7 +138,7 @@ def run_rounds(args, fasta, w, weights, rounds_w, keep_files=False):
                 if i == 1:
                     tgt = len(nj._order) - 1
                     contig_ids = nj._engine.record_ids(tgt, nj._engine.n_records(tgt))
-                files = nj.scaffold(keep=True, quiet=not full, **({} if last else {"synteny": False}))
+                files = nj.scaffold(keep=True, quiet=not full, **({} if last else {"synteny": False, "assess": False}))
                 if full and not last:
                     files["all"] = write_all(files, gz)
                 pieces, first, ids = nj._engine.scaffold_pieces()

@@ -58,6 +58,16 @@ def parse_arguments(argv=None):
                         help="largest distance between neighbouring anchors of a block, 0 = none [100000: QUAST's --scaffold-gap-max-size in ntJoin:247]")
     parser.add_argument("--synteny_min_anchors", type=int, default=3, help="smallest number of minimizers of a block, at least 2 [3]")
     parser.add_argument("--synteny_min_span", type=int, default=0, help="smallest extent of a block on the scaffold [0]")
+    # ours: <prefix>.assess.tsv and <prefix>.breakpoints.bed -- the target and the scaffolds against every reference: the blocks above
+    # merged into chains, aligned and covered bases, NA50 / NGA50 / NG50 and the breakpoints by kind, each blamed on a join or on a
+    # contig; computed on the GPU (what the reference's `analysis` target runs QUAST for, ntJoin:243-252; ntjoin_amd.assemble).  The
+    # blocks are made with the --synteny_* parameters
+    parser.add_argument("--assess", action="store_true", default=False)
+    parser.add_argument("--assess_merge_gap", type=int, default=100000,
+                        help="largest gap between blocks of a chain, 0 = none [100000: QUAST's --scaffold-gap-max-size in ntJoin:247]")
+    parser.add_argument("--assess_max_indel", type=int, default=1000,
+                        help="largest difference of the two gaps between blocks of a chain inside a contig, 0 = none [1000: QUAST's --extensive-mis-size]")
+    parser.add_argument("--assess_join_indel", type=int, default=100000, help="the same across a join of the scaffolder, 0 = none [100000]")
     parser.add_argument("-v", "--version", action="version", version="ntjoin_amd hot path (ntJoin v1.1.5 compatible)")
     return parser.parse_args(argv)
 
