@@ -844,6 +844,93 @@ typedef struct mxg_assess_view {
 } mxg_assess_view;
 int mxg_synteny_assess(mxg_handle *h, const mxg_assess_params *params, mxg_assess_view *out);
 
+/* ---- next row (f14): base-level identity of stretches whose ends are pinned -------------------------------------
+   How far apart two stretches of bases are, where the caller -- the graph's anchors, say -- already knows where both begin and end:
+   a narrow-band edit distance per SEGMENT, nothing is searched for, no alignment is kept.
+   BASES.  The bases of a record are the bytes of its sequence text that are no line breaks ('\n', '\r').  A base's class is 0..3 for
+   A C G T/U in either case and 4 for anything else; the complement of class c < 4 is 3 - c.
+   A SEGMENT is lq >= 1 bases of record q_record of the query text from base q_start, and ls >= 1 bases of record s_record of the
+   subject text from base s_start.  Q = the classes of the query interval; S = the classes of the subject interval, read backwards
+   and complemented when reverse != 0.  d = ls - lq.
+   STATUS, the first rule that applies:
+     MXG_IDY_SKIP_LEN    lq > max_seg or ls > max_seg
+     MXG_IDY_SKIP_SHIFT  |d| > MXG_IDY_MAX_SHIFT
+     MXG_IDY_SKIP_N      a base of Q or S has class 4 (a base outside the interval does not count)
+     MXG_IDY_ALIGNED     edits = D[lq][ls] of the unit-cost DP over the cells (i, j), 0 <= i <= lq, 0 <= j <= ls, whose diagonal
+                         j - i lies in [min(0, d) - MXG_IDY_E, max(0, d) + MXG_IDY_E] (at most 64 diagonals):  D[0][0] = 0,
+                         D[i][j] = min(D[i-1][j-1] + (Q[i] != S[j]), D[i-1][j] + 1, D[i][j-1] + 1) over the neighbours inside the
+                         band.  The status word also carries MXG_IDY_SATURATED iff edits > |d| + 2 MXG_IDY_E; without that flag
+                         edits is the unbanded edit distance (a path that cheap cannot leave the band), with it an upper bound.
+   out_status[i] = the status, with the flag; out_edits[i] = edits, 0 for a skipped segment.
+   TEXTS.  q_text and s_text name texts the handle holds on the device: an assembly index, whose records are the file's (folded
+   lines, "\r\n" and records across many tiles are all walked), or MXG_TEXT_SCAFFOLDS, the text the last mxg_write_scaffolds kept
+   under MXG_SCAF_KEEP, whose records are those of mxg_scaffold_pieces.  q_text == s_text is allowed.
+   Computed on the device (identity.hip): one lane per segment, the band in one 64-bit word per lane (identity.h), the bases read
+   from the resident text in aligned words.  segs, out_edits and out_status are host arrays of n entries.
+   MXG_EINVAL: a null argument with n > 0, max_seg == 0, no such assembly, an assembly whose text the handle does not hold on the
+   device (the conditions of mxg_write_fai), MXG_TEXT_SCAFFOLDS with nothing kept, a record out of range, lq == 0 or ls == 0, an
+   interval that ends beyond its record; the message names the segment.  MXG_ELIMIT: 2^31 segments or more.  n == 0 is valid.
+   Nothing of the handle changes; it stays usable after every refusal. */
+#define MXG_IDY_E 16u
+#define MXG_IDY_MAX_SHIFT 31u
+#define MXG_IDY_ALIGNED 0u
+#define MXG_IDY_SKIP_LEN 1u
+#define MXG_IDY_SKIP_SHIFT 2u
+#define MXG_IDY_SKIP_N 3u
+#define MXG_IDY_STATUS_MASK 0xFFu
+#define MXG_IDY_SATURATED 0x100u
+#define MXG_IDY_DEFAULT_MAX_SEG 10000u
+#define MXG_TEXT_SCAFFOLDS (-1)
+typedef struct mxg_identity_seg {
+    uint32_t q_record, q_start, lq;
+    uint32_t s_record, s_start, ls;
+    uint32_t reverse, pad; /* pad: 0 */
+} mxg_identity_seg;
+int mxg_identity_segments(mxg_handle *h, int q_text, int s_text, const mxg_identity_seg *segs, uint64_t n, uint32_t max_seg,
+                          uint32_t *out_edits, uint32_t *out_status);
+/* mxg_synteny_identity: the segments between the anchors of the kept blocks of the handle's last successful mxg_synteny_blocks.
+   SEGMENTS OF A BLOCK over anchors j .. j + r of the anchor list (qpos' = the query positions of that list, through the piece table
+   when there was one; k = the handle's k):
+     link i -> i + 1:  query bases [qpos'[i], qpos'[i+1]); subject bases [spos[i], spos[i+1]) in a forward block,
+                       [spos[i+1] + k, spos[i] + k) with reverse = 1 in a reverse block;
+     the last anchor:  query bases [qpos'[j+r], + k), subject bases [spos[j+r], + k), reverse as the block's.
+   A block has n_anchors segments, and its aligned segments cover q_end - q_start query bases when none is skipped.
+   PER BLOCK (the view's arrays, in the order of the kept blocks): n_aligned, n_skip_len, n_skip_shift, n_skip_n = its segments by
+   status; n_saturated = its aligned segments that carry the flag; aligned_q, aligned_s = the sums of lq and of ls over its aligned
+   segments; edits = the sum over its aligned segments, the flagged ones included (they are upper bounds).
+   SUMMARY: the same fields summed over all kept blocks, n_segments, and block_q = the sum of q_end - q_start.
+   The query text is assembly q of the blocks call, or, when that call went through a piece table, the text mxg_write_scaffolds
+   kept under MXG_SCAF_KEEP: the table must then be the one of mxg_scaffold_pieces of that text (same assembly, same number of
+   records, same lengths).  The subject text is assembly s.  Either assembly's record lengths must be the ones the blocks call used.
+   Computed on the device (identity.hip): the anchors and the blocks' first anchors are read where the blocks call left them; one
+   thread per anchor of a kept block, placed by a scan over n_anchors, writes its segment; the segment kernel of
+   mxg_identity_segments; six 64-bit prefix scans over the segments, the blocks' sums as differences at their borders.  A run that
+   never calls this allocates and launches nothing for it.  The view's arrays are host copies owned by the handle until its next
+   mxg_synteny_identity or mxg_synteny_blocks.
+   MXG_EINVAL: a null argument, struct_size too small, max_seg == 0, flags != 0, no successful mxg_synteny_blocks before, a text
+   that is not held on the device (as mxg_identity_segments), a piece table that is not the kept text's, record lengths that differ
+   from the text's.  MXG_ELIMIT: 2^31 segments or more.  Zero blocks is valid.  Sketches, graph, paths, kept text, blocks and the
+   assessment stay as they are: mxg_synteny_blocks' view, mxg_write_synteny_paf and mxg_synteny_assess work as before. */
+typedef struct mxg_identity_params {
+    uint32_t struct_size; /* = sizeof(mxg_identity_params) */
+    uint32_t max_seg;     /* segments longer than this on either side are counted, not aligned; default MXG_IDY_DEFAULT_MAX_SEG */
+    uint32_t flags;       /* 0 */
+    uint32_t reserved;    /* 0 */
+} mxg_identity_params;
+typedef struct mxg_identity_view {
+    uint64_t n_blocks, n_segments, n_aligned, n_skip_len, n_skip_shift, n_skip_n, n_saturated, block_q, aligned_q, aligned_s, edits;
+    const uint64_t *blk_n_aligned, *blk_n_skip_len, *blk_n_skip_shift, *blk_n_skip_n, *blk_n_saturated, *blk_aligned_q, *blk_aligned_s,
+        *blk_edits; /* [n_blocks] */
+} mxg_identity_view;
+int mxg_synteny_identity(mxg_handle *h, const mxg_identity_params *params, mxg_identity_view *out);
+/* mxg_write_synteny_paf_ex: mxg_write_synteny_paf with flags.  flags == 0: byte for byte that call.  MXG_PAF_IDENTITY: every line
+   gets "\tal:i:<aligned_q>" appended and, when aligned_q > 0, "\tNM:i:<edits>\tdv:f:0.dddd" with
+   dddd = floor(10000 edits / max(aligned_q, aligned_s)) in four digits ("1.0000" when the ratio reaches 1), the block's values of
+   the last mxg_synteny_identity, computed in integers on the device; columns 1 to 13 do not change.  MXG_EINVAL also: an unknown
+   flag; MXG_PAF_IDENTITY without a successful mxg_synteny_identity since the last mxg_synteny_blocks. */
+#define MXG_PAF_IDENTITY 0x1u
+int mxg_write_synteny_paf_ex(mxg_handle *h, const char *const *query_names, const char *path, int append, uint32_t flags);
+
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------
    No counterpart in the reference (it is one process).  Uniqueness and intersection need every occurrence of a hash in
    one place: every minimizer travels to the rank that owns its hash, the owner runs the ordinary graph kernels on what it

@@ -21,6 +21,9 @@ per run, computed on the GPU from the graph; a reference loaded from its TSV nee
 --assess (--assess_merge_gap, --assess_max_indel, --assess_join_indel): also <p>.assess.tsv and <p>.breakpoints.bed -- the target and
 the scaffolds against every reference: the blocks of --synteny_* merged into chains, aligned and covered bases, NA50 / NGA50 / NG50,
 and the breakpoints by kind, each blamed on a join the scaffolder made or on a contig; computed on the GPU (ntjoin_amd/report.py).
+--identity (--identity_max_seg): also <p>.identity.tsv -- the target and the scaffolds against every reference: the edit distances of
+the stretches between neighbouring minimizers of the blocks of --synteny_*, summed, and edits per 100 kbp; with --synteny the PAF lines
+carry al:i, NM:i and dv:f; computed on the GPU.  A reference loaded from its TSV has no text in the handle and is left out.
 --rounds_w "500 250" (--rounds_keep): further rounds with these window sizes in the same process, the scaffolds of a round being the
 target of the next without a file between them, and <p>.rounds.agp over the contigs of the first target (ntjoin_amd/rounds.py).
 """

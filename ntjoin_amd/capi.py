@@ -19,6 +19,11 @@ REPORT_ASSIGNED, REPORT_UNASSIGNED, REPORT_ALL = 0, 1, 2
 PATHS_AGP_UNASSIGNED = 0x1
 PIECE_FWD, PIECE_REV, PIECE_GAP = 0, 1, 2
 BP_TRANSLOCATION, BP_INVERSION, BP_RELOCATION = 0, 1, 2
+IDY_E, IDY_MAX_SHIFT, IDY_DEFAULT_MAX_SEG = 16, 31, 10000
+IDY_ALIGNED, IDY_SKIP_LEN, IDY_SKIP_SHIFT, IDY_SKIP_N = 0, 1, 2, 3
+IDY_STATUS_MASK, IDY_SATURATED = 0xFF, 0x100
+TEXT_SCAFFOLDS = -1
+PAF_IDENTITY = 0x1
 ABI_VERSION = 3
 
 SYMBOLS = [
@@ -37,6 +42,7 @@ SYMBOLS = [
     "mxg_compose_pieces", "mxg_add_assembly_text_device", "mxg_assembly_text",
     "mxg_scaffold_text", "mxg_scaffold_pieces", "mxg_scaffold_record_id",
     "mxg_synteny_blocks", "mxg_write_synteny_paf", "mxg_synteny_assess",
+    "mxg_identity_segments", "mxg_synteny_identity", "mxg_write_synteny_paf_ex",
 ]
 
 
@@ -109,6 +115,23 @@ class SyntenyView(C.Structure):  # mxg_synteny_view: 88 bytes (api.cpp asserts t
     _fields_ = ([("n_blocks", C.c_uint64), ("n_anchors_total", C.c_uint64), ("n_links", C.c_uint64)] +
                 [(name, C.POINTER(C.c_uint32)) for name in ("n_anchors", "q_record", "q_start", "q_end", "s_record", "s_start", "s_end")] +
                 [("reverse", C.POINTER(C.c_uint8))])
+
+
+class IdentitySeg(C.Structure):  # mxg_identity_seg: 32 bytes (api.cpp asserts the same); engine.MxEngine.IDENTITY_SEG is its numpy twin
+    _fields_ = [(name, C.c_uint32) for name in ("q_record", "q_start", "lq", "s_record", "s_start", "ls", "reverse", "pad")]
+
+
+class IdentityParams(C.Structure):  # mxg_identity_params: 16 bytes (api.cpp asserts the same)
+    _fields_ = [("struct_size", C.c_uint32), ("max_seg", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+IDENTITY_SUM_FIELDS = ("n_blocks", "n_segments", "n_aligned", "n_skip_len", "n_skip_shift", "n_skip_n", "n_saturated", "block_q", "aligned_q",
+                       "aligned_s", "edits")
+IDENTITY_BLOCK_FIELDS = ("n_aligned", "n_skip_len", "n_skip_shift", "n_skip_n", "n_saturated", "aligned_q", "aligned_s", "edits")
+
+
+class IdentityView(C.Structure):  # mxg_identity_view: 152 bytes (api.cpp asserts the same)
+    _fields_ = ([(name, C.c_uint64) for name in IDENTITY_SUM_FIELDS] + [("blk_" + name, C.POINTER(C.c_uint64)) for name in IDENTITY_BLOCK_FIELDS])
 
 
 class AssessParams(C.Structure):  # mxg_assess_params: 16 bytes (api.cpp asserts the same)
@@ -274,6 +297,9 @@ def load():
     L.mxg_synteny_blocks.argtypes = [vp, i32, i32, C.POINTER(SyntenyParams), vp, vp, u64, vp, vp, C.POINTER(SyntenyView)]
     L.mxg_write_synteny_paf.argtypes = [vp, C.POINTER(cp), C.c_char_p, i32]
     L.mxg_synteny_assess.argtypes = [vp, C.POINTER(AssessParams), C.POINTER(AssessView)]
+    L.mxg_identity_segments.argtypes = [vp, i32, i32, vp, u64, C.c_uint32, vp, vp]
+    L.mxg_synteny_identity.argtypes = [vp, C.POINTER(IdentityParams), C.POINTER(IdentityView)]
+    L.mxg_write_synteny_paf_ex.argtypes = [vp, C.POINTER(cp), C.c_char_p, i32, C.c_uint32]
     L.mxg_bgzf_write.argtypes = [vp, vp, u64, C.c_char_p]
     L.mxg_write_fai.argtypes = [vp, i32, C.c_char_p, C.c_char_p]
     L.mxg_set_report_params.argtypes = [vp, u64, u64]

@@ -1214,11 +1214,14 @@ int mxg_synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params *pa
     return MXG_OK;
 }
 
-int mxg_write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append)
+int mxg_write_synteny_paf_ex(mxg_handle *h, const char *const *query_names, const char *path, int append, uint32_t flags)
 {
     if (!h) return MXG_EINVAL;
     if (!path) return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf: null argument");
     if (!h->syn.valid) return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf: the handle's last mxg_synteny_blocks left no blocks (none was called, or it failed)");
+    if (flags & ~MXG_PAF_IDENTITY) return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf_ex: unknown flags 0x%x", flags);
+    if ((flags & MXG_PAF_IDENTITY) && (!h->idy.valid || h->idy.blk.size() != h->syn.reverse.size() * 8))
+        return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf_ex: MXG_PAF_IDENTITY needs a successful mxg_synteny_identity since the last mxg_synteny_blocks");
     if (!query_names && h->syn.q_table)
         return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf: the query went through a piece table of %zu records; pass their names", h->syn.q_len.size());
     if (query_names)
@@ -1228,10 +1231,15 @@ int mxg_write_synteny_paf(mxg_handle *h, const char *const *query_names, const c
         (!h->syn.q_table && h->asms[h->syn.q]->recs.size() != h->syn.q_len.size()))
         return set_err(h, MXG_EINVAL, "mxg_write_synteny_paf: the assemblies have changed since the blocks were made");
     try {
-        return write_synteny_paf(h, query_names, path, append);
+        return write_synteny_paf(h, query_names, path, append, flags);
     } catch (const std::bad_alloc &) {
         return set_err(h, MXG_ENOMEM, "out of host memory in mxg_write_synteny_paf");
     }
+}
+
+int mxg_write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append)
+{
+    return mxg_write_synteny_paf_ex(h, query_names, path, append, 0u);
 }
 
 static_assert(sizeof(mxg_assess_params) == 16, "mxg_assess_params: ntjoin_amd/capi.py AssessParams mirrors this layout");
@@ -1274,6 +1282,57 @@ int mxg_synteny_assess(mxg_handle *h, const mxg_assess_params *params, mxg_asses
     out->chain_q_start = c + 4 * n, out->chain_q_end = c + 5 * n, out->chain_s_record = c + 6 * n, out->chain_s_start = c + 7 * n;
     out->chain_s_end = c + 8 * n, out->chain_reverse = c + 9 * n;
     out->bp_chain = b, out->bp_kind = b + m, out->bp_at_join = b + 2 * m, out->bp_q_lo = b + 3 * m, out->bp_q_hi = b + 4 * m;
+    return MXG_OK;
+}
+
+static_assert(sizeof(mxg_identity_seg) == 32, "mxg_identity_seg: ntjoin_amd/capi.py IdentitySeg mirrors this layout");
+
+int mxg_identity_segments(mxg_handle *h, int q_text, int s_text, const mxg_identity_seg *segs, uint64_t n, uint32_t max_seg, uint32_t *out_edits,
+                          uint32_t *out_status)
+{
+    if (!h) return MXG_EINVAL;
+    if (n && (!segs || !out_edits || !out_status)) return set_err(h, MXG_EINVAL, "mxg_identity_segments: null argument");
+    if (!max_seg) return set_err(h, MXG_EINVAL, "mxg_identity_segments: max_seg is 0 (at least 1)");
+    try {
+        return identity_segments(h, q_text, s_text, segs, n, max_seg, out_edits, out_status);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_identity_segments");
+    }
+}
+
+static_assert(sizeof(mxg_identity_params) == 16, "mxg_identity_params: ntjoin_amd/capi.py IdentityParams mirrors this layout");
+static_assert(sizeof(mxg_identity_view) == 152, "mxg_identity_view: ntjoin_amd/capi.py IdentityView mirrors this layout");
+
+int mxg_synteny_identity(mxg_handle *h, const mxg_identity_params *params, mxg_identity_view *out)
+{
+    if (!h) return MXG_EINVAL;
+    if (!params || !out) return set_err(h, MXG_EINVAL, "mxg_synteny_identity: null argument");
+    if (params->struct_size < sizeof(mxg_identity_params))
+        return set_err(h, MXG_EINVAL, "mxg_synteny_identity: struct_size %u is too small", params->struct_size);
+    if (!params->max_seg) return set_err(h, MXG_EINVAL, "mxg_synteny_identity: max_seg is 0 (at least 1)");
+    if (params->flags) return set_err(h, MXG_EINVAL, "mxg_synteny_identity: unknown flags 0x%x", params->flags);
+    if (!h->syn.valid) return set_err(h, MXG_EINVAL, "mxg_synteny_identity: the handle's last mxg_synteny_blocks left no blocks (none was called, or it failed)");
+    if ((size_t)h->syn.q >= h->asms.size() || (size_t)h->syn.s >= h->asms.size())
+        return set_err(h, MXG_EINVAL, "mxg_synteny_identity: the assemblies have changed since the blocks were made");
+    int rc;
+    try {
+        rc = synteny_identity(h, *params);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_synteny_identity");
+    }
+    if (rc != MXG_OK) return rc;
+    const mxg_handle::Synteny &S = h->syn;
+    const size_t n = S.reverse.size();
+    const uint64_t *b = h->idy.blk.data();
+    uint64_t sum[8] = {}, block_q = 0;
+    for (size_t u = 0; u < 8; ++u)
+        for (size_t i = 0; i < n; ++i) sum[u] += b[u * n + i];
+    for (size_t i = 0; i < n; ++i) block_q += S.block[3 * n + i] - S.block[2 * n + i];
+    out->n_blocks = n, out->n_segments = h->idy.n_segments;
+    out->n_aligned = sum[0], out->n_skip_len = sum[1], out->n_skip_shift = sum[2], out->n_skip_n = sum[3], out->n_saturated = sum[4];
+    out->block_q = block_q, out->aligned_q = sum[5], out->aligned_s = sum[6], out->edits = sum[7];
+    out->blk_n_aligned = b, out->blk_n_skip_len = b + n, out->blk_n_skip_shift = b + 2 * n, out->blk_n_skip_n = b + 3 * n;
+    out->blk_n_saturated = b + 4 * n, out->blk_aligned_q = b + 5 * n, out->blk_aligned_s = b + 6 * n, out->blk_edits = b + 7 * n;
     return MXG_OK;
 }
 

@@ -306,7 +306,17 @@ struct mxg_handle {
         std::vector<uint8_t> reverse;    // [n_blocks]
         std::vector<uint32_t> q_len, s_len;  // the lengths of the query's records (a piece table's: the sums of their pieces) and the subject's
         std::vector<uint32_t> q_pre, q_first;  // q_table: every piece's offset in its record, and the records' first pieces (n_records + 1)
+        // what the call left in synbuf, for mxg_synteny_identity: the anchor list, and per block (kept or not) its first and last
+        // anchor, the keep flag and the kept blocks before it.  Nothing but the next mxg_synteny_blocks writes these arrays
+        const void *d_anchor = nullptr;
+        const uint32_t *d_first = nullptr, *d_last = nullptr, *d_keep = nullptr, *d_kscan = nullptr;
+        uint32_t n_dev_blocks = 0;
     } syn;
+    struct Identity {        // the last mxg_synteny_identity (what its view points into); void after the next mxg_synteny_blocks
+        bool valid = false;
+        uint64_t n_segments = 0;
+        std::vector<uint64_t> blk;  // eight arrays of n_blocks words: n_aligned, n_skip_len, n_skip_shift, n_skip_n, n_saturated, aligned_q, aligned_s, edits
+    } idy;
     mxg::DevBuf asbuf[32];   // scratch of assess.hip
     struct Assess {          // the last mxg_synteny_assess (what its view points into)
         uint64_t n_chains = 0, n_bp = 0, query_bases = 0, subject_bases = 0;
@@ -315,6 +325,7 @@ struct mxg_handle {
         std::vector<uint32_t> bp;       // five arrays of n_bp words: chain, kind, at_join, q_lo, q_hi
         std::vector<uint32_t> bp_all;   // scratch: the same as they come home, five arrays of n_chains words
     } assess;
+    mxg::DevBuf idybuf[24];   // scratch of identity.hip
     std::vector<uint32_t> scaf_lead, scaf_tail;  // N/n stripped from either end of every unassigned interval by the last mxg_write_scaffolds
     struct ScafInterval {
         uint32_t rec, lo, hi, lead, tail;
@@ -656,11 +667,16 @@ int compose_pieces(mxg_handle *h, const mxg_seq_piece *outer, const uint64_t *ou
 // synteny.hip: the synteny blocks of two assemblies (mxg_synteny_blocks; fills h->syn) and their PAF text (mxg_write_synteny_paf)
 int synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params &p, const mxg_seq_piece *pieces, const uint64_t *first, uint64_t n_records,
                    const uint32_t *query_length, const uint32_t *subject_length);
-int write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append);
+int write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append, uint32_t flags = 0);
 // assess.hip: chains, breakpoints and the summary of h->syn's kept blocks (mxg_synteny_assess; fills h->assess)
 int synteny_assess(mxg_handle *h, const mxg_assess_params &p);
 enum { AS_BP0, AS_ALIGNED = 6, AS_CHAINED, AS_COVERED, AS_NA, AS_NGA = AS_NA + 6, AS_NG = AS_NGA + 6, AS_HEADS = AS_NG + 6, AS_NBP, AS_SCRATCH, AS_WORDS };
 static_assert(AS_WORDS <= 32, "mxg_handle::Assess::sum too small");
+// identity.hip: the banded edit distance of explicit segments over texts the handle holds on the device (mxg_identity_segments)
+int identity_segments(mxg_handle *h, int q_text, int s_text, const mxg_identity_seg *segs, uint64_t n, uint32_t max_seg, uint32_t *out_edits,
+                      uint32_t *out_status);
+// ... and of the segments between the anchors of h->syn's kept blocks (mxg_synteny_identity; fills h->idy)
+int synteny_identity(mxg_handle *h, const mxg_identity_params &p);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm
 int flags_to_host(mxg_handle *h, Assembly *a);
 

@@ -29,7 +29,7 @@
 namespace mxg {
 
 enum { SY_A0, SY_A1, SY_PIECES, SY_PREC, SY_POFF, SY_PLO, SY_CNT, SY_ESCAN, SY_BSUM, SY_BSUM64, SY_HEAD, SY_HSCAN, SY_FIRST, SY_LAST, SY_BLK,
-       SY_KEEP, SY_KSCAN, SY_OUT, SY_TOT, SY_QLEN, SY_SLEN, SY_IDOFF, SY_IDS, SY_LOFF, SY_TSUM, SY_BOUNDS, SY_BUF_COUNT };
+       SY_KEEP, SY_KSCAN, SY_OUT, SY_TOT, SY_QLEN, SY_SLEN, SY_IDOFF, SY_IDS, SY_LOFF, SY_TSUM, SY_BOUNDS, SY_IDY, SY_BUF_COUNT };
 static_assert(SY_BUF_COUNT <= 32, "mxg_handle::synbuf too small");
 enum { ST_EXP, ST_HEADS, ST_KEPT, ST_LINKS, ST_BAD, ST_WORDS };  // the words of SY_TOT
 constexpr uint64_t SYN_MAX = 0x7FFFFFFFull;                         // 2^31 anchors or blocks or more: MXG_ELIMIT
@@ -186,6 +186,8 @@ int synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params &p, con
 {
     mxg_handle::Synteny &S = h->syn;
     S.valid = false;
+    h->idy.valid = false;  // (mxg_synteny_identity is about the blocks of the call before it)
+    S.d_anchor = nullptr, S.n_dev_blocks = 0;
     const Graph &g = h->graph;
     const Assembly *aq = h->asms[q], *as = h->asms[s];
     int rc;
@@ -313,6 +315,11 @@ int synteny_blocks(mxg_handle *h, int q, int s, const mxg_synteny_params &p, con
     }
     if (dbg && ev[1]) (void)hipEventRecord(ev[1], st);
     MXG_HIP(h, hipStreamSynchronize(st));
+    if (n_keep) {  // (what mxg_synteny_identity reads, where it lies already)
+        S.d_anchor = d_a, S.n_dev_blocks = n_blk;
+        S.d_first = B[SY_FIRST].as<uint32_t>(), S.d_last = B[SY_LAST].as<uint32_t>();
+        S.d_keep = B[SY_KEEP].as<uint32_t>(), S.d_kscan = B[SY_KSCAN].as<uint32_t>();
+    }
     S.reverse.resize(n_keep);
     for (uint32_t i = 0; i < n_keep; ++i) S.reverse[i] = (uint8_t)S.block[(size_t)7 * n_keep + i];
     if (dbg) {
@@ -335,6 +342,7 @@ struct SynPaf {
     const char *ids;
     uint64_t *loff;  // [n + 1] bytes of the lines, then their offsets
     uint32_t n, k;
+    const uint64_t *idy;  // MXG_PAF_IDENTITY: the eight arrays of n words of mxg_synteny_identity; else null
 };
 
 template <class Sink> __device__ __forceinline__ void syn_paf_line(const SynPaf &q, uint32_t i, Sink &o)
@@ -366,6 +374,27 @@ template <class Sink> __device__ __forceinline__ void syn_paf_line(const SynPaf 
     o.num(syn_blocklen(b));
     o.lit("\t255\tcm:i:", 10u);
     o.num(b.n_anchors);
+    if (q.idy) {  // al:i:<aligned_q>, and where anything was aligned NM:i:<edits> and dv:f:<edits / the longer aligned side>, four digits, floored
+        const uint64_t aq = q.idy[(size_t)5 * q.n + i], as = q.idy[(size_t)6 * q.n + i], ed = q.idy[(size_t)7 * q.n + i];
+        o.lit("\tal:i:", 6u);
+        o.num(aq);
+        if (aq) {
+            o.lit("\tNM:i:", 6u);
+            o.num(ed);
+            o.lit("\tdv:f:", 6u);
+            const uint64_t den = aq > as ? aq : as;
+            if (ed >= den) {
+                o.lit("1.0000", 6u);
+            } else {
+                const uint32_t d = (uint32_t)(ed * 10000ull / den);  // (ed < den < 2^50: no overflow)
+                o.lit("0.", 2u);
+                o.ch((char)('0' + d / 1000u));
+                o.ch((char)('0' + d / 100u % 10u));
+                o.ch((char)('0' + d / 10u % 10u));
+                o.ch((char)('0' + d % 10u));
+            }
+        }
+    }
     o.ch('\n');
 }
 
@@ -403,9 +432,10 @@ __global__ __launch_bounds__(256) void k_syn_paf_emit(const SynPaf q, uint32_t i
     syn_paf_line(q, i, w);
 }
 
-int write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append)
+int write_synteny_paf(mxg_handle *h, const char *const *query_names, const char *path, int append, uint32_t flags)
 {
     const mxg_handle::Synteny &S = h->syn;
+    const bool with_idy = (flags & MXG_PAF_IDENTITY) != 0;
     const uint32_t n = (uint32_t)S.reverse.size();
     const Assembly *aq = h->asms[S.q], *as = h->asms[S.s];
     const size_t n_q = S.q_len.size(), n_s = S.s_len.size();
@@ -450,6 +480,11 @@ int write_synteny_paf(mxg_handle *h, const char *const *query_names, const char 
         q.ids = B[SY_IDS].as<char>();
         q.loff = B[SY_LOFF].as<uint64_t>();
         q.n = n, q.k = h->cfg.k;
+        if (with_idy) {  // (from the host copy, as the blocks: what the identity view spells)
+            MXG_HIP(h, B[SY_IDY].ensure((size_t)n * 64));
+            MXG_HIP(h, hipMemcpyAsync(B[SY_IDY].p, h->idy.blk.data(), (size_t)n * 64, hipMemcpyHostToDevice, st));
+            q.idy = B[SY_IDY].as<uint64_t>();
+        }
         hipLaunchKernelGGL(k_syn_paf_len, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, q);
         launch_scan_u64(st, q.loff, n + 1, B[SY_TSUM].as<uint64_t>());
         MXG_HIP(h, hipGetLastError());

@@ -590,16 +590,29 @@ class MxEngine:
             out[name] = _np(getattr(v, name), n, np.uint32)
         return out
 
-    def write_synteny_paf(self, path, query_names=None, append=False):
-        """mxg_write_synteny_paf: the blocks of the last synteny_blocks() as PAF lines, formatted on the device; query_names = one name
+    def write_synteny_paf(self, path, query_names=None, append=False, identity=False):
+        """mxg_write_synteny_paf_ex: the blocks of the last synteny_blocks() as PAF lines, formatted on the device; query_names = one name
         per query record (None: the handle's record ids of q -- not for a query that went through a piece table); append=True adds
-        the lines to what `path` holds already"""
+        the lines to what `path` holds already; identity=True: every line also carries al:i, NM:i and dv:f of the last
+        synteny_identity() (MXG_PAF_IDENTITY)"""
         names = None
         if query_names is not None:
             if len(query_names) != getattr(self, "_syn_records", len(query_names)):
                 raise ValueError(f"write_synteny_paf: {len(query_names)} names for {self._syn_records} query records")
             names = (C.c_char_p * max(len(query_names), 1))(*[str(i).encode() for i in query_names])
-        self._check(self._lib.mxg_write_synteny_paf(self._h, names, os.fsencode(str(path)), int(bool(append))))
+        self._check(self._lib.mxg_write_synteny_paf_ex(self._h, names, os.fsencode(str(path)), int(bool(append)), capi.PAF_IDENTITY if identity else 0))
+
+    def synteny_identity(self, max_seg=capi.IDY_DEFAULT_MAX_SEG):
+        """mxg_synteny_identity: the banded edit distances of the segments between the anchors of the kept blocks of the last
+        synteny_blocks() (include/ntjoin_mx.h) -> dict(the summary: n_blocks, n_segments, n_aligned, n_skip_len, n_skip_shift, n_skip_n,
+        n_saturated, block_q, aligned_q, aligned_s, edits; blocks: dict of u64 arrays by capi.IDENTITY_BLOCK_FIELDS)"""
+        p = capi.IdentityParams()
+        p.struct_size, p.max_seg = C.sizeof(capi.IdentityParams), int(max_seg)
+        v = capi.IdentityView()
+        self._check(self._lib.mxg_synteny_identity(self._h, C.byref(p), C.byref(v)))
+        out = {name: int(getattr(v, name)) for name in capi.IDENTITY_SUM_FIELDS}
+        out["blocks"] = {name: _np(getattr(v, "blk_" + name), out["n_blocks"], np.uint64) for name in capi.IDENTITY_BLOCK_FIELDS}
+        return out
 
     def synteny_assess(self, merge_gap=100000, max_indel=1000, join_indel=100000):
         """mxg_synteny_assess: the kept blocks of the last synteny_blocks() merged into chains, the breakpoints between the chains and
@@ -618,6 +631,26 @@ class MxEngine:
         out["chains"] = {name: _np(getattr(v, "chain_" + name), out["n_chains"], np.uint32) for name in capi.ASSESS_CHAIN_FIELDS}
         out["bps"] = {name: _np(getattr(v, "bp_" + name), out["n_breakpoints"], np.uint32) for name in capi.ASSESS_BP_FIELDS}
         return out
+
+    IDENTITY_SEG = np.dtype([(name, "<u4") for name in ("q_record", "q_start", "lq", "s_record", "s_start", "ls", "reverse", "pad")])
+
+    def identity_segments(self, q_text, s_text, segs, max_seg=capi.IDY_DEFAULT_MAX_SEG):
+        """mxg_identity_segments: the banded edit distance of explicit segments over two texts the handle holds on the device
+        (include/ntjoin_mx.h).  q_text / s_text: an assembly index or capi.TEXT_SCAFFOLDS (the text write_scaffolds(keep=True) left);
+        segs: array of IDENTITY_SEG, or rows (q_record, q_start, lq, s_record, s_start, ls, reverse) -> dict(edits u32[n], status
+        u32[n]: capi.IDY_ALIGNED .. IDY_SKIP_N, saturated bool[n])"""
+        sg = np.asarray(segs)
+        if sg.dtype != self.IDENTITY_SEG:
+            rows = np.asarray(segs, dtype=np.uint32).reshape(-1, 7)
+            sg = np.zeros(len(rows), dtype=self.IDENTITY_SEG)
+            for c, name in enumerate(self.IDENTITY_SEG.names[:7]):
+                sg[name] = rows[:, c]
+        sg = np.ascontiguousarray(sg)
+        n = len(sg)
+        edits, status = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.mxg_identity_segments(self._h, int(q_text), int(s_text), sg.ctypes.data if n else None, n, int(max_seg),
+                                                    edits.ctypes.data if n else None, status.ctypes.data if n else None))
+        return {"edits": edits, "status": status & capi.IDY_STATUS_MASK, "saturated": (status & capi.IDY_SATURATED) != 0}
 
     def write_fai(self, assembly, path, gzi=None):
         """mxg_write_fai: the index `samtools faidx` makes of the assembly's FASTA, from the text the handle holds, written to `path`;

@@ -21,7 +21,7 @@ import numpy as np
 from . import capi
 from .engine import MxEngine, MxError
 from .ntjoin_utils import MxGraph, sketch_views
-from .report import ASSESS_COLUMNS, COLUMNS as REPORT_COLUMNS, assess_row, breakpoint_lines, row as report_row
+from .report import ASSESS_COLUMNS, COLUMNS as REPORT_COLUMNS, IDENTITY_COLUMNS, assess_row, breakpoint_lines, identity_row, row as report_row
 
 COLOURS = ["red", "green", "blue", "purple", "orange", "turquoise", "pink", "yellow", "orchid", "salmon"]
 
@@ -376,7 +376,7 @@ class Ntjoin:
         at = res["node_first"].tolist()
         return [rows[lo:hi] for lo, hi in zip(at, at[1:])]
 
-    def scaffold(self, lengths=None, keep=False, quiet=False, synteny=None, assess=None):
+    def scaffold(self, lengths=None, keep=False, quiet=False, synteny=None, assess=None, identity=None):
         """main_scaffolder (:751-786) behind load_minimizers_scaffold in one handle: make_minimizer_graph -> find_paths ->
         format_paths -> adjust_paths -> trim_overlaps (when args.overlap) -> print_scaffolds.  Read from args, with ntJoin's
         defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz, fai, report,
@@ -385,7 +385,8 @@ class Ntjoin:
         (write_input_indexes); with args.report <prefix>.report.tsv is written ("report": write_report); with args.synteny
         <prefix>.synteny.paf ("synteny": write_synteny; synteny=False leaves it out whatever args says: an earlier round of
         ntjoin_amd/rounds.py); with args.assess <prefix>.assess.tsv and <prefix>.breakpoints.bed ("assess", "breakpoints":
-        write_assess, with the blocks parameters of --synteny_*; assess=False leaves them out likewise).  keep / quiet:
+        write_assess, with the blocks parameters of --synteny_*; assess=False leaves them out likewise); with args.identity
+        <prefix>.identity.tsv ("identity": write_identity, args.identity_max_seg; identity=False leaves it out likewise).  keep / quiet:
         print_scaffolds' (a round of ntjoin_amd/rounds.py); a quiet round writes no .mx.dot, no index, no report, no PAF and no
         assessment either."""
         opt = lambda name, dflt: dflt if getattr(self.args, name, None) is None else getattr(self.args, name)  # noqa: E731
@@ -412,9 +413,12 @@ class Ntjoin:
         if (bool(opt("assess", False)) if assess is None else assess) and not quiet:
             asz = dict(blocks_kw, merge_gap=int(opt("assess_merge_gap", 100000)), max_indel=int(opt("assess_max_indel", 1000)),
                        join_indel=int(opt("assess_join_indel", 100000)))
+        idy = None
+        if (bool(opt("identity", False)) if identity is None else identity) and not quiet:
+            idy = dict(blocks_kw, max_seg=int(opt("identity_max_seg", 10000)))
         files = self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)),
                                      gz=bool(opt("gz", False)), fai=bool(opt("fai", False)), report=report, keep=keep, quiet=quiet,
-                                     **({"synteny": syn} if syn else {}), **({"assess": asz} if asz else {}))
+                                     **({"synteny": syn} if syn else {}), **({"assess": asz} if asz else {}), **({"identity": idy} if idy else {}))
         if report:
             files["report"] = self.write_report(report_rows, files)
         return files
@@ -583,7 +587,7 @@ class Ntjoin:
                 agp_fh.close()
 
     def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False, report=False, keep=False, quiet=False,
-                        synteny=None, assess=None):
+                        synteny=None, assess=None, identity=None):
         """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
         trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
         than two nodes are dropped (:585-594), the last kept node's gap is zeroed (check_terminal_node_gap_zero :441-448), and the
@@ -606,8 +610,14 @@ class Ntjoin:
             if given[0] != given[1]:
                 raise ValueError(f"print_scaffolds: synteny= and assess= share one blocks call and must agree on its parameters: {given[0]} "
                                  f"against {given[1]}")
+        if identity and (synteny or assess):
+            given = [{key: (arg if isinstance(arg, dict) else {}).get(key, default) for key, default in SYNTENY_DEFAULTS.items()}
+                     for arg in (identity, synteny or assess)]
+            if given[0] != given[1]:
+                raise ValueError(f"print_scaffolds: identity= shares one blocks call with synteny= and assess= and must agree on its parameters: "
+                                 f"{given[0]} against {given[1]}")
         self._last_print = dict(paths=paths, adjust=adjust, n=n, agp=agp, overlap_gap=overlap_gap, gz=gz, fai=fai, report=report)
-        if (synteny or assess) and not quiet:
+        if (synteny or assess or identity) and not quiet:
             keep = True
         eng, tgt = self._engine, len(self._order) - 1
         if tgt < 0:
@@ -654,7 +664,15 @@ class Ntjoin:
             res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
                                       assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz),
                                       **({"fai": True} if fai else {}), **({"report": True} if report else {}), **({"keep": True} if keep else {}))
-        if assess and not quiet:
+        if identity and not quiet:   # (one pass over the references for the table, the PAF and the assessment)
+            idy = identity if isinstance(identity, dict) else {}
+            files.update(self._synteny_files({key: idy.get(key, default) for key, default in SYNTENY_DEFAULTS.items()}, paf=bool(synteny),
+                                             assess=None if not assess else {key: (assess if isinstance(assess, dict) else {}).get(key, default)
+                                                                              for key, default in (("merge_gap", 100000), ("max_indel", 1000),
+                                                                                                   ("join_indel", 100000))},
+                                             scaffolds_name=files["assigned"].replace(".assigned.scaffolds.", ".all.scaffolds."),
+                                             identity=dict(max_seg=idy.get("max_seg", 10000))))
+        elif assess and not quiet:
             files.update(self.write_assess(**(assess if isinstance(assess, dict) else {}), paf=bool(synteny),
                                            scaffolds_name=files["assigned"].replace(".assigned.scaffolds.", ".all.scaffolds.")))
         elif synteny and not quiet:
@@ -699,8 +717,18 @@ class Ntjoin:
         return self._synteny_files(dict(max_gap=max_gap, min_anchors=min_anchors, min_span=min_span), paf=paf,
                                    assess=dict(merge_gap=merge_gap, max_indel=max_indel, join_indel=join_indel), scaffolds_name=scaffolds_name)
 
-    def _synteny_files(self, blocks_kw, paf, assess=None, scaffolds_name="scaffolds"):
-        "write_synteny and write_assess: one pass over the references, the scaffolds' blocks computed once for the PAF and the assessment"
+    def write_identity(self, max_seg=10000, max_gap=100000, min_anchors=3, min_span=0, paf=False, scaffolds_name="scaffolds"):
+        """<prefix>.identity.tsv: for every reference, in command-line order, the target as loaded and then the scaffolds the last
+        print_scaffolds(keep=True) left get one row each: one MxEngine.synteny_blocks (max_gap, min_anchors, min_span) and one
+        MxEngine.synteny_identity (max_seg), a header line first (ntjoin_amd/report.py: identity_row).  paf=True: the scaffolds' blocks
+        are also written to <prefix>.synteny.paf with the identity tags.  A reference loaded from its TSV has no text in the handle:
+        one line on stderr and no rows.  Returns the files by kind."""
+        return self._synteny_files(dict(max_gap=max_gap, min_anchors=min_anchors, min_span=min_span), paf=paf, scaffolds_name=scaffolds_name,
+                                   identity=dict(max_seg=max_seg))
+
+    def _synteny_files(self, blocks_kw, paf, assess=None, scaffolds_name="scaffolds", identity=None):
+        """write_synteny, write_assess and write_identity: one pass over the references, the scaffolds' blocks computed once for the PAF,
+        the assessment and the identity table"""
         eng, tgt = self._engine, len(self._order) - 1
         pieces, first, ids = eng.scaffold_pieces()
         files = {}
@@ -708,12 +736,18 @@ class Ntjoin:
             files["synteny"] = self.args.p + ".synteny.paf"
             with open(files["synteny"], "wb"):
                 pass   # (every reference's lines are appended)
-        rows, bed = [], []
-        if assess is not None:
+        rows, bed, idy_rows = [], [], []
+        if assess is not None or identity is not None:
             target_ids = eng.record_ids(tgt, eng.n_records(tgt))
             target_name = self._fasta.get(self._order[tgt], self._order[tgt])
         for a, assembly in enumerate(self._order[:tgt]):
             lengths = None
+            idy = identity if assembly in self._fasta else None   # (the reference's text is what its bases are read from)
+            if identity is not None and idy is None:
+                print(f"ntjoin_amd: {assembly} was loaded from its TSV and the handle holds no text of it: the identity table has no rows for it",
+                      file=sys.stderr)
+                if not paf and assess is None:
+                    continue
             if assembly not in self._fasta:
                 lengths = self._fai_lengths(a, assembly)
                 if lengths is None:
@@ -721,14 +755,19 @@ class Ntjoin:
                         ("the assessment has no rows" if assess is not None else "")
                     print(f"ntjoin_amd: {assembly} was loaded from its TSV and its FASTA has no .fai: {what} for it", file=sys.stderr)
                     continue
-            if assess is not None:
+            if assess is not None or idy is not None:
                 match = re.search(r"^(.+)\.k\d+\.w\d+\.tsv$", assembly)
                 ref_name = self._fasta.get(assembly) or (match.group(1) if match else assembly)
                 blk = eng.synteny_blocks(tgt, a, subject_length=lengths, **blocks_kw)
-                rows.append(assess_row(target_name, ref_name, len(target_ids), blk["n_anchors_total"], eng.synteny_assess(**assess)))
+                if assess is not None:
+                    rows.append(assess_row(target_name, ref_name, len(target_ids), blk["n_anchors_total"], eng.synteny_assess(**assess)))
+                if idy is not None:
+                    idy_rows.append(identity_row(target_name, ref_name, eng.synteny_identity(**idy)))
             blk = eng.synteny_blocks(tgt, a, pieces=pieces, first=first, subject_length=lengths, **blocks_kw)
+            if idy is not None:
+                idy_rows.append(identity_row(scaffolds_name, ref_name, eng.synteny_identity(**idy)))
             if paf:
-                eng.write_synteny_paf(files["synteny"], query_names=ids, append=True)
+                eng.write_synteny_paf(files["synteny"], query_names=ids, append=True, identity=idy is not None)
             if assess is not None:
                 res = eng.synteny_assess(**assess)
                 rows.append(assess_row(scaffolds_name, ref_name, len(ids), blk["n_anchors_total"], res))
@@ -741,6 +780,12 @@ class Ntjoin:
                     fh.write(row + "\n")
             with open(files["breakpoints"], "w", encoding="utf-8") as fh:
                 fh.writelines(bed)
+        if identity is not None:
+            files["identity"] = self.args.p + ".identity.tsv"
+            with open(files["identity"], "w", encoding="utf-8") as fh:
+                fh.write("\t".join(IDENTITY_COLUMNS) + "\n")
+                for row in idy_rows:
+                    fh.write(row + "\n")
         return files
 
     def _fai_lengths(self, a, assembly):

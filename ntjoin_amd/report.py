@@ -1,6 +1,7 @@
 """The lines of <prefix>.report.tsv (Ntjoin.write_report): one row per file from a report as MxEngine.assembly_report and
 MxEngine.scaffold_report return it, and those of <prefix>.assess.tsv and <prefix>.breakpoints.bed (Ntjoin.write_assess) from what
-MxEngine.synteny_assess returns.  The numbers are the library's (report.hip, assess.hip); only the text is formed here."""
+MxEngine.synteny_assess returns, and those of <prefix>.identity.tsv (Ntjoin.write_identity) from what MxEngine.synteny_identity returns.
+The numbers are the library's (report.hip, assess.hip, identity.hip); only the text is formed here."""
 
 COLUMNS = ("file records bases A C G T N other lower gaps gap_bases max_gap n n_min sum min max N50 L50 N75 L75 N90 L90 "
            "ctg_n ctg_n_min ctg_sum ctg_min ctg_max ctg_N50 ctg_L50 ctg_N75 ctg_L75 ctg_N90 ctg_L90").split()
@@ -45,3 +46,19 @@ def breakpoint_lines(res, query_names, reference, subject_names):
                 side(c), side(c + 1))
         out.append("\t".join(str(x) for x in cols) + "\n")
     return out
+
+
+# ---- <prefix>.identity.tsv (Ntjoin.write_identity): the numbers are the library's (identity.hip) ------------------------------------
+IDENTITY_COLUMNS = ("query reference blocks segments aligned skipped_len skipped_shift skipped_n saturated block_query_bases aligned_query "
+                    "aligned_subject edits edits_per_100kbp").split()
+
+
+def identity_row(query, reference, res):
+    """one row of <prefix>.identity.tsv from what MxEngine.synteny_identity returns; edits_per_100kbp = edits * 10^5 / max(aligned_query,
+    aligned_subject) in integers, two decimals, floored (0.00 where nothing was aligned)"""
+    den = max(res["aligned_q"], res["aligned_s"])
+    cents = res["edits"] * 10 ** 7 // den if den else 0
+    cells = [query, reference, res["n_blocks"], res["n_segments"], res["n_aligned"], res["n_skip_len"], res["n_skip_shift"], res["n_skip_n"],
+             res["n_saturated"], res["block_q"], res["aligned_q"], res["aligned_s"], res["edits"], f"{cents // 100}.{cents % 100:02d}"]
+    assert len(cells) == len(IDENTITY_COLUMNS)
+    return "\t".join(str(c) for c in cells)

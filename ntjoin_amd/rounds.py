@@ -15,6 +15,7 @@ every file the chain would leave.  <p>.rounds.agp spells every record of the las
 original target: the rounds' piece tables (mxg_scaffold_pieces) composed on the device (mxg_compose_pieces), formatted here.
 --synteny: the last round's scaffolds against the references, <p>.round<i>.synteny.paf beside that round's other files.
 --assess: likewise, the last round's target and scaffolds: <p>.round<i>.assess.tsv and <p>.round<i>.breakpoints.bed.
+--identity: likewise: <p>.round<i>.identity.tsv.
 
     python -m ntjoin_amd.rounds last_out TARGET K W N GZ W2 [W3 ...]   prints T_last.k<k>.w<w_last>.n<n> (for the make front-end)
 """
@@ -138,7 +139,7 @@ def run_rounds(args, fasta, w, weights, rounds_w, keep_files=False):
                 if i == 1:
                     tgt = len(nj._order) - 1
                     contig_ids = nj._engine.record_ids(tgt, nj._engine.n_records(tgt))
-                files = nj.scaffold(keep=True, quiet=not full, **({} if last else {"synteny": False, "assess": False}))
+                files = nj.scaffold(keep=True, quiet=not full, **({} if last else {"synteny": False, "assess": False, "identity": False}))
                 if full and not last:
                     files["all"] = write_all(files, gz)
                 pieces, first, ids = nj._engine.scaffold_pieces()

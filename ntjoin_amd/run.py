@@ -68,6 +68,13 @@ def parse_arguments(argv=None):
     parser.add_argument("--assess_max_indel", type=int, default=1000,
                         help="largest difference of the two gaps between blocks of a chain inside a contig, 0 = none [1000: QUAST's --extensive-mis-size]")
     parser.add_argument("--assess_join_indel", type=int, default=100000, help="the same across a join of the scaffolder, 0 = none [100000]")
+    # ours: <prefix>.identity.tsv -- how similar the target and the scaffolds are to every reference inside the blocks above: banded
+    # edit distances of the stretches between neighbouring minimizers of a block, summed (QUAST's mismatches and indels per 100 kbp;
+    # with --synteny the PAF lines also carry al:i, NM:i and dv:f); computed on the GPU (ntjoin_amd.assemble).  The blocks are made
+    # with the --synteny_* parameters
+    parser.add_argument("--identity", action="store_true", default=False)
+    parser.add_argument("--identity_max_seg", type=int, default=10000,
+                        help="stretches longer than this on either assembly are counted, not aligned, at least 1 [10000]")
     parser.add_argument("-v", "--version", action="version", version="ntjoin_amd hot path (ntJoin v1.1.5 compatible)")
     return parser.parse_args(argv)
 
