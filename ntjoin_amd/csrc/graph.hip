@@ -255,10 +255,9 @@ __global__ __launch_bounds__(PJ_BT) void k_pj_bucket(const AsmSet p, uint32_t nb
 }
 
 // slot of `key` in the partition's LDS table, inserting it if absent; PJ_T + 1: table full
-__device__ __forceinline__ uint32_t pj_slot(unsigned long long *keys, uint64_t key)
+__device__ __forceinline__ uint32_t pj_slot_from(unsigned long long *keys, uint64_t key, uint32_t s)
 {
     if (key == HT_EMPTY) return PJ_T;
-    uint32_t s = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) & (PJ_T - 1u);
     for (uint32_t step = 0; step < PJ_T; ++step) {
         const unsigned long long cur = keys[s];
         if (cur == key) return s;
@@ -269,6 +268,30 @@ __device__ __forceinline__ uint32_t pj_slot(unsigned long long *keys, uint64_t k
         s = (s + 1u) & (PJ_T - 1u);
     }
     return PJ_T + 1u;
+}
+__device__ __forceinline__ uint32_t pj_slot(unsigned long long *keys, uint64_t key)
+{
+    return pj_slot_from(keys, key, (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) & (PJ_T - 1u));
+}
+
+// The two-level join's records, 16 or 12 bytes (R12: join_plan.h, "the two-level join's 12-byte records"), as the kernels hold
+// them: a uint4 whose fourth word is not there in the 12-byte form.  Record r of an array of 12-byte records: words 3 r .. 3 r + 2
+// (one dwordx3 access, 4-byte aligned).
+struct PjRec3 {
+    uint32_t x, y, z;
+};
+template <bool R12>
+__device__ __forceinline__ uint4 pj_rec_load(const uint4 *recs, size_t r)
+{
+    if (!R12) return recs[r];
+    const PjRec3 v = reinterpret_cast<const PjRec3 *>(recs)[r];
+    return make_uint4(v.x, v.y, v.z, 0u);
+}
+template <bool R12>
+__device__ __forceinline__ void pj_rec_store(uint4 *recs, size_t r, const uint4 v)
+{
+    if (!R12) recs[r] = v;
+    else reinterpret_cast<PjRec3 *>(recs)[r] = PjRec3{v.x, v.y, v.z};
 }
 
 // Two levels (more than PJ_MAX_P x 1280 minimizers): `cursor` != nullptr.  k_pj1_scatter has dealt the minimizers into P1 coarse
@@ -293,7 +316,7 @@ struct PjSubCaps {  // what the join asks the cursors: did a sub-range outgrow i
 template <bool NARROW>
 __global__ __launch_bounds__(256) void k_pj_join(uint4 *recs, const uint32_t *__restrict__ M, uint32_t P, uint32_t n_rows,
                                                  uint64_t *host_fail, uint32_t force_fail, const uint32_t *__restrict__ cursor,
-                                                 uint32_t cap1, uint32_t rows2, const AsmSet p, const PjSubCaps caps)
+                                                 uint32_t cap1, uint32_t rows2, const AsmSet p, const PjSubCaps caps, uint32_t prefill0)
 {
     const uint32_t full = p.full;
     __shared__ unsigned long long keys[PJ_T + 1];
@@ -392,7 +415,7 @@ __global__ __launch_bounds__(256) void k_pj_join(uint4 *recs, const uint32_t *__
                     fl = (!(d & (1u << a)) ? MXG_MX_UNIQUE : 0u) | ((inall && d == 0) ? MXG_MX_SHARED : 0u) | (inall ? MXG_MX_INALL : 0u);
                 }
                 const uint32_t word = ((fl & MXG_MX_SHARED) ? item0[s] << 3 : 0u) | fl;
-                if (!pj_verdict_is_prefill(word)) p.slot[a][i] = word;
+                if (word != pj_verdict_prefill(prefill0, a, i)) p.slot[a][i] = word;
             };
 #pragma unroll
             for (uint32_t it = 0; it < QC; ++it) {
@@ -443,12 +466,20 @@ __global__ __launch_bounds__(256) void k_pj_join(uint4 *recs, const uint32_t *__
 // Where a record lies: the thread that owns a region writes the region's number over the records of its segment (seg_of, the
 // first QC * 256 records of the partition), so a record finds its segment with one LDS read; only the records beyond
 // those (a key of huge multiplicity) are still located by a search in seg_off, as in k_pj_join.
-template <bool NARROW>
+// R12: 12-byte records {product lo, product hi with the tag, item}; the table keeps the product without its tag.
+template <bool NARROW, bool R12>
 __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_t *__restrict__ M, uint32_t P, uint32_t n_parts,
                                                       uint64_t *host_fail, uint32_t force_fail, const uint32_t *__restrict__ cursor,
-                                                      uint32_t cap1, uint32_t rows2, const AsmSet p, const PjSubCaps caps)
+                                                      uint32_t cap1, uint32_t rows2, const AsmSet p, const PjSubCaps caps, uint32_t prefill0)
 {
     const uint32_t full = p.full;
+    const uint32_t lgP = R12 ? 31u - (uint32_t)__clz(P) : 0u, tag_mask = R12 ? pj12_tag_mask(lgP) : 0u;
+    auto rec_a = [&](const uint4 rec) { return R12 ? pj12_unpack_tag(rec.y, lgP) & (PJ12_TAG_DUP - 1u) : rec.w & ~PJ_REC_DUP; };
+    auto rec_dup = [&](const uint4 rec) { return R12 ? (pj12_unpack_tag(rec.y, lgP) & PJ12_TAG_DUP) != 0 : (rec.w & PJ_REC_DUP) != 0; };
+    auto rec_slot = [&](unsigned long long *tab, const uint4 rec) {
+        if (R12) return pj_slot_from(tab, ((uint64_t)(rec.y & ~tag_mask) << 32) | rec.x, rec.y & (PJ_T - 1u));
+        return pj_slot(tab, ((uint64_t)rec.y << 32) | rec.x);
+    };
     __shared__ unsigned long long keys[PJ_T + 1];
     __shared__ uint32_t seen[PJ_T + 1], dup[NARROW ? 1 : PJ_T + 1];
     __shared__ uint32_t item0[PJ_T + 1];
@@ -485,7 +516,7 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
             rn[it] = make_uint4(0u, 0u, 0u, 0u);
             if (q < total) {
                 const uint32_t l = seg_of[q];
-                rn[it] = recs[seg_rec[buf][l] + (q - seg_off[buf][l])];
+                rn[it] = pj_rec_load<R12>(recs, seg_rec[buf][l] + (q - seg_off[buf][l]));
             }
         }
         return total;
@@ -531,15 +562,15 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
             return seg_rec[buf][l] + (q - seg_off[buf][l]);
         };
         auto insert_rec = [&](const uint4 rec, bool record) {
-            const uint32_t a = rec.w & ~PJ_REC_DUP;
-            const uint32_t s = pj_slot(keys, ((uint64_t)rec.y << 32) | rec.x);
+            const uint32_t a = rec_a(rec);
+            const uint32_t s = rec_slot(keys, rec);
             if (record) {
                 const uint32_t bit = 1u << a;
                 if (s > PJ_T) failed = 1;
                 else {
                     const uint32_t cur = seen[s], dcur = NARROW ? cur >> 16 : dup[s];
                     if (!((cur & bit) && (dcur & bit))) {
-                        if (rec.w & PJ_REC_DUP) {
+                        if (rec_dup(rec)) {
                             if (NARROW) atomicOr(&seen[s], bit | (bit << 16));
                             else {
                                 atomicOr(&seen[s], bit);
@@ -564,7 +595,7 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
 #pragma unroll
             for (uint32_t u = 0; u < TU; ++u) {
                 const uint32_t q = q0 + u * 256u;
-                rv[u] = q < total ? recs[locate(q)] : make_uint4(0u, 0u, 0u, 0u);
+                rv[u] = q < total ? pj_rec_load<R12>(recs, locate(q)) : make_uint4(0u, 0u, 0u, 0u);
             }
 #pragma unroll
             for (uint32_t u = 0; u < TU; ++u)
@@ -574,7 +605,7 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
         const bool bad = failed != 0;
         if (bad && threadIdx.x == 0) *host_fail = 1;
         auto finish = [&](const uint4 rec, uint32_t s) {
-            const uint32_t a = rec.w & ~PJ_REC_DUP;
+            const uint32_t a = rec_a(rec);
             uint32_t fl = 0;
             if (!bad) {
                 const uint32_t sn = seen[s] & full, d = (NARROW ? seen[s] >> 16 : dup[s]) & full;
@@ -582,7 +613,7 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
                 fl = (!(d & (1u << a)) ? MXG_MX_UNIQUE : 0u) | ((inall && d == 0) ? MXG_MX_SHARED : 0u) | (inall ? MXG_MX_INALL : 0u);
             }
             const uint32_t word = ((fl & MXG_MX_SHARED) ? item0[s] << 3 : 0u) | fl;
-            if (!pj_verdict_is_prefill(word)) p.slot[a][rec.z] = word;
+            if (word != pj_verdict_prefill(prefill0, a, rec.z)) p.slot[a][rec.z] = word;
         };
 #pragma unroll
         for (uint32_t it = 0; it < QC; ++it)
@@ -592,7 +623,7 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
 #pragma unroll
             for (uint32_t u = 0; u < TU; ++u) {
                 const uint32_t q = q0 + u * 256u;
-                rv[u] = q < total ? recs[locate(q)] : make_uint4(0u, 0u, 0u, 0u);
+                rv[u] = q < total ? pj_rec_load<R12>(recs, locate(q)) : make_uint4(0u, 0u, 0u, 0u);
             }
 #pragma unroll
             for (uint32_t u = 0; u < TU; ++u)
@@ -609,9 +640,14 @@ __global__ __launch_bounds__(256) void k_pj_join_pipe(uint4 *recs, const uint32_
 // sub.s, whose records go to its own sub-range of every coarse partition.
 __device__ __forceinline__ uint32_t pj1_part(uint64_t key, uint32_t p1mask) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 52) & p1mask; }
 
+// R12 (sub-ranges per assembly only): 12-byte records {product lo, product hi, item | PJ12_ITEM_DUP}; key[] then holds the products.
+// prefill0: the verdict prefill of assembly 0 (join_verdict.h).
+template <bool R12>
 __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t blk_lo, uint32_t blk_hi, uint32_t p1mask, uint32_t cap1,
-                                                     uint32_t *cursor, uint4 *recs1, uint32_t *sup, uint32_t n_sup, const PjSub subr)
+                                                     uint32_t *cursor, uint4 *recs1, uint32_t *sup, uint32_t n_sup, const PjSub subr,
+                                                     uint32_t prefill0)
 {
+    auto part1 = [&](uint64_t k) { return R12 ? (uint32_t)(k >> 52) & p1mask : pj1_part(k, p1mask); };
     extern __shared__ uint32_t pj_lds[];
     uint32_t *hist = pj_lds, *start = pj_lds + p1mask + 1;
     if (blockIdx.x == 0)  // super-counts of the two counting kernels that follow (scan_kernels.h)
@@ -632,11 +668,12 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
         const bool lv = i < n;
         if (lv) {
             key[u] = p.hash[a][i];
-            p.slot[a][i] = PJ_VERDICT_PREFILL;  // (followers too; in front of this thread's own store of 0 below)
+            p.slot[a][i] = pj_verdict_prefill(prefill0, a, i);  // (followers too; in front of this thread's own store of 0 below)
         }
         const uint32_t role = pj_run_role(i, n, key[u], lv);  // (followers travel with their run's leader)
         const uint64_t fb = __ballot(role & 1u);
         if ((threadIdx.x & 63u) == 0) p.fol[(size_t)blk * 4u + ((threadIdx.x >> 6) & 3u)] = fb;
+        if (R12) key[u] *= PJ_MUL;
         if (lv && !(role & 1u)) {
             ia[u] = a | ((role & 2u) ? PJ_REC_DUP : 0u);
             ii[u] = i;
@@ -647,7 +684,7 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
     __syncthreads();
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u)
-        if ((live >> u) & 1u) atomicAdd(&hist[pj1_part(key[u], p1mask)], 1u);
+        if ((live >> u) & 1u) atomicAdd(&hist[part1(key[u])], 1u);
     __syncthreads();
     for (uint32_t b = threadIdx.x; b <= p1mask; b += PJ_BT) {
         const uint32_t c = hist[b];
@@ -658,9 +695,11 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
         if (!((live >> u) & 1u)) continue;
-        const uint32_t b = pj1_part(key[u], p1mask);
+        const uint32_t b = part1(key[u]);
         const uint32_t pos = start[b] + atomicAdd(&hist[b], 1u);
-        if (pos < subr.cap) recs1[(size_t)b * cap1 + subr.off + pos] = make_uint4((uint32_t)key[u], (uint32_t)(key[u] >> 32), ii[u], ia[u]);
+        if (pos < subr.cap)
+            pj_rec_store<R12>(recs1, (size_t)b * cap1 + subr.off + pos,
+                              make_uint4((uint32_t)key[u], (uint32_t)(key[u] >> 32), R12 && (ia[u] & PJ_REC_DUP) ? ii[u] | PJ12_ITEM_DUP : ii[u], ia[u]));
         else p.slot[ia[u] & ~PJ_REC_DUP][ii[u]] = 0;  // beyond the capacity: no verdict will come (the cursor says so, k_pj_join reports it and
                                         // the host redoes the stage with the global table); leave a harmless one behind
     }
@@ -676,6 +715,9 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
 // which goes on marked PJ_REC_DUP; the others leave a reference to it as their verdict (PJ_VERDICT_REF, followed by k_flags_pj)
 // and drop out.
 // (PJ_VERDICT_REF, the low bits of a verdict word that is no verdict: join_verdict.h)
+// R12: reads level 1's 12-byte records (the assembly is the sub-range's, x and y hold the product), writes {product lo, product
+// hi with the tag in implied bits, item}
+template <bool R12>
 __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint4 *__restrict__ recs1, const uint32_t *__restrict__ cursor,
                                                     uint32_t cap1, uint32_t rows2, uint32_t pmask, uint32_t *M, uint4 *recs2,
                                                     uint32_t skew_lim, const PjSub subr)
@@ -684,6 +726,8 @@ __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint
     uint32_t *hist = pj_lds, *start = pj_lds + pmask + 1;
     __shared__ uint32_t sh[256];
     const uint32_t j = blockIdx.x, c = blockIdx.y;
+    const uint32_t lgP = R12 ? 31u - (uint32_t)__clz(pmask + 1u) : 0u;
+    auto part2 = [&](const uint4 r) { return R12 ? (r.y >> PJ12_FINE_SHIFT) & pmask : pj_part(((uint64_t)r.y << 32) | r.x, pmask); };
     // (the launch sorts the rows of ONE sub-range of every coarse partition: j counts from the sub-range's first row)
     const uint32_t n_all = cursor[(c * subr.n_sub + subr.s) * PJ1_CS], n_c = min(n_all, subr.cap);
     const uint32_t row_j = subr.off / PJ_IPB + j;
@@ -701,7 +745,11 @@ __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint
         const uint32_t q = u * PJ_BT + threadIdx.x;
         rec[u] = make_uint4(0u, 0u, 0u, 0u);
         if (j * PJ_IPB + q < n_c) {
-            rec[u] = recs1[base + q];
+            rec[u] = pj_rec_load<R12>(recs1, base + q);
+            if (R12) {
+                rec[u].w = subr.s | ((rec[u].z & PJ12_ITEM_DUP) ? PJ_REC_DUP : 0u);
+                rec[u].z &= ~PJ12_ITEM_DUP;
+            }
             live |= 1u << u;
         }
     }
@@ -760,7 +808,7 @@ __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint
     __syncthreads();
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u)
-        if ((live >> u) & 1u) atomicAdd(&hist[pj_part(((uint64_t)rec[u].y << 32) | rec[u].x, pmask)], 1u);
+        if ((live >> u) & 1u) atomicAdd(&hist[part2(rec[u])], 1u);
     __syncthreads();
     const uint32_t P = pmask + 1, per = P >= PJ_BT ? P / PJ_BT : 1u, b0 = threadIdx.x * per;
     uint32_t cn = 0;
@@ -781,9 +829,10 @@ __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
         if (!((live >> u) & 1u)) continue;
-        const uint32_t b = pj_part(((uint64_t)rec[u].y << 32) | rec[u].x, pmask);
+        const uint32_t b = part2(rec[u]);
         const uint32_t pos = (uint32_t)base + start[b] + atomicAdd(&hist[b], 1u);
-        recs2[pos] = rec[u];
+        if (R12) rec[u].y = pj12_pack(rec[u].y, lgP, pj12_tag(rec[u].w & ~PJ_REC_DUP, (rec[u].w & PJ_REC_DUP) != 0));
+        pj_rec_store<R12>(recs2, pos, rec[u]);
     }
 }
 
@@ -1410,6 +1459,12 @@ static int plan_join(mxg_handle *h, int mode, const GraphBounds *gb, bool global
     rq.join_global = join_env && !strcmp(join_env, "global");
     rq.force_two_level = knob_u64(h, "MXG_PJ_TWO_LEVEL", 0) != 0;
     rq.graph_u = (uint32_t)std::min<uint64_t>(knob_u64(h, "MXG_GRAPH_U", 0), 8);  // 1 | 2 | 4 forces the tail passes' width
+    // MXG_PJ_REC12=0 / MXG_PJ_PREFILL0=0: the 16-byte records / the one prefill rule where the plan would choose otherwise (A/B knobs);
+    // MXG_PJ_SPLIT=1: sub-ranges per assembly in the stage's own plan too (test knob: the fused call's layout over given minimizers)
+    rq.no_rec12 = knob_u64(h, "MXG_PJ_REC12", 1) == 0;
+    rq.no_pipe = knob_u64(h, "MXG_PJ_PIPE", 1024) == 0;
+    rq.no_prefill0 = knob_u64(h, "MXG_PJ_PREFILL0", 1) == 0;
+    if (knob_u64(h, "MXG_PJ_SPLIT", 0) && mode == GRAPH_FULL) rq.split = true;
     switch (join_shape(rq, h->pj_learnt, pl)) {
     case JS_TOO_MANY_MINIMIZERS: return set_err(h, MXG_ELIMIT, "too many minimizers for one table (%llu)", (unsigned long long)pl.N);
     case JS_TOO_MANY_ITEMS: return set_err(h, MXG_ELIMIT, "graph too large for 32-bit item indices");
@@ -1489,10 +1544,11 @@ static void launch_partition(mxg_handle *h, const JoinPlan &pl, uint32_t a_lo, u
         skew_lim = pl.skew_lim[a_lo];
     }
     if (n_rows1)
-        hipLaunchKernelGGL(k_pj1_scatter, dim3(n_rows1), dim3(PJ_BT), (size_t)pl.P1 * 8, st, pl.as_all, blk_lo, blk_hi, pl.P1 - 1, pl.cap1,
-                           pl.cursor, pl.recs1, pl.fsup, n_sup_clear, sub);
-    hipLaunchKernelGGL(k_pj2_bucket, dim3(sub.cap / PJ_IPB, pl.P1), dim3(PJ_BT), (size_t)pl.P * 8, st, pl.as_all, pl.recs1, pl.cursor, pl.cap1,
-                       pl.rows2, pl.P - 1, pl.M, pl.recs2, knob_u64(h, "MXG_PJ_SKEW", 0) ? 0u : skew_lim, sub);
+        hipLaunchKernelGGL(pl.rec12 ? k_pj1_scatter<true> : k_pj1_scatter<false>, dim3(n_rows1), dim3(PJ_BT), (size_t)pl.P1 * 8, st, pl.as_all,
+                           blk_lo, blk_hi, pl.P1 - 1, pl.cap1, pl.cursor, pl.recs1, pl.fsup, n_sup_clear, sub, pl.prefill0);
+    hipLaunchKernelGGL(pl.rec12 ? k_pj2_bucket<true> : k_pj2_bucket<false>, dim3(sub.cap / PJ_IPB, pl.P1), dim3(PJ_BT), (size_t)pl.P * 8, st,
+                       pl.as_all, pl.recs1, pl.cursor, pl.cap1, pl.rows2, pl.P - 1, pl.M, pl.recs2,
+                       knob_u64(h, "MXG_PJ_SKEW", 0) ? 0u : skew_lim, sub);
 }
 
 // A timed span of kind 5 (flush_timers adds it to ms_join and ms_graph).  What ms_join means on the early path, in one place:
@@ -1632,6 +1688,10 @@ struct GraphStage {
         if (timing) MXG_HIP(h, hipEventRecord(h->ev0, h->stream));
         if (!resume)
             h->stat_graph_join = (pl.pj ? (pl.two_level ? MXG_JOIN_LDS_TWO_LEVEL : MXG_JOIN_LDS) : MXG_JOIN_GLOBAL) | (early ? MXG_JOIN_EARLY : 0);
+        // MXG_DEBUG_JOIN=1: the plan's choices that mxg_stats::graph_join has no bit for, one line per attempt (tests read it)
+        if (!resume && knob_u64(h, "MXG_DEBUG_JOIN", 0))
+            fprintf(stderr, "[mxg] join pj=%d two_level=%d split=%d early=%d record_bytes=%d prefill0=%u P1=%u rows2=%u\n", (int)pl.pj,
+                    (int)pl.two_level, (int)pl.split, (int)early, pl.rec12 ? 12 : 16, pl.prefill0, pl.P1, pl.rows2);
         // (the LDS joins clear nothing: every word of M and of the record regions that is read is written by this call)
         if (!pl.pj && !resume) MXG_HIP(h, hipMemsetAsync(h->g_keys.p, 0xFF, ((size_t)pl.cap + 1) * sizeof(Slot), h->stream));  // one fill: see Slot
         ctl = h->g_ctl.as<uint64_t>();  // every word the host reads of it is written by a kernel of this call
@@ -1649,12 +1709,15 @@ struct GraphStage {
         const bool narrow = pl.A <= 16;  // the seen and dup masks share one word per slot
         const uint32_t cap1 = cursor ? pl.cap1 : 0u, rows2 = cursor ? pl.rows2 : 0u;
         const uint64_t pipe_blocks = cursor ? knob_u64(h, "MXG_PJ_PIPE", 1024) : 0;
-        if (pipe_blocks && rows2 <= 256)
-            hipLaunchKernelGGL(narrow ? k_pj_join_pipe<true> : k_pj_join_pipe<false>, dim3((uint32_t)std::min<uint64_t>(pipe_blocks, n_parts)),
-                               dim3(256), 0, h->stream, recs, M, pl.P, n_parts, pj_fail, pl.pj_force_fail, cursor, cap1, rows2, pl.as_all, pl.sc);
-        else
+        const uint32_t prefill0 = cursor ? pl.prefill0 : 0u;  // (one level: k_pj_bucket knows the one rule)
+        if (pipe_blocks && rows2 <= 256) {
+            auto kernel = pl.rec12 ? (narrow ? k_pj_join_pipe<true, true> : k_pj_join_pipe<false, true>)
+                                   : (narrow ? k_pj_join_pipe<true, false> : k_pj_join_pipe<false, false>);
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)std::min<uint64_t>(pipe_blocks, n_parts)), dim3(256), 0, h->stream, recs, M, pl.P, n_parts,
+                               pj_fail, pl.pj_force_fail, cursor, cap1, rows2, pl.as_all, pl.sc, prefill0);
+        } else  // (join_shape gives 12-byte records to the pipelined kernel only)
             hipLaunchKernelGGL(narrow ? k_pj_join<true> : k_pj_join<false>, dim3(n_parts), dim3(256), 0, h->stream, recs, M, pl.P, n_rows,
-                               pj_fail, pl.pj_force_fail, cursor, cap1, rows2, pl.as_all, pl.sc);
+                               pj_fail, pl.pj_force_fail, cursor, cap1, rows2, pl.as_all, pl.sc, prefill0);
     }
     void flags_pj()
     {
@@ -1662,7 +1725,10 @@ struct GraphStage {
     }
     int join_two_level()
     {
-        if (!early) {  // (else: both levels ran behind every assembly's own k_emit, the cursors were cleared in front of the step)
+        if (!early && pl.split) {  // (MXG_PJ_SPLIT: the fused call's layout, one assembly after the other)
+            MXG_HIP(h, hipMemsetAsync(pl.fsup, 0, pl.clear_words * 4, h->stream));
+            for (uint32_t a = 0; a < pl.A; ++a) launch_partition(h, pl, a, a + 1, h->stream, 0u);
+        } else if (!early) {  // (else: both levels ran behind every assembly's own k_emit, the cursors were cleared in front of the step)
             MXG_HIP(h, hipMemsetAsync(pl.cursor, 0, (size_t)pl.P1 * PJ1_CS * 4, h->stream));
             launch_partition(h, pl, 0, pl.A, h->stream, pl.n_fsup + pl.n_esup);
         }
@@ -1869,6 +1935,8 @@ struct GraphStage {
                 return set_err(h, MXG_EDEVICE, "internal error: shared-minimizer counts differ between assemblies (%llu vs %llu)",
                                (unsigned long long)hctl[CTL_SHARED + a], (unsigned long long)nv);
         g.nv = nv;
+        // (what the next plan for these sizes chooses assembly 0's verdict prefill by)
+        if (c.mode == GRAPH_FULL) h->pj_learnt.shared_counted(pl.pre_sig, nv, pl.n_of[0]);
         g.nv_stride = pl.nvs;
         g.ne = pl.nvs > 0 ? hctl[CTL_EDGES] : 0;
         h->stat_unique = ~0ull;  // counted lazily from the flags (mxg_get_stats)

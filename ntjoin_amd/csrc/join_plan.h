@@ -1,13 +1,20 @@
 // The arithmetic of the graph stage's join, the one place that knows it: from the assemblies' sizes to which join runs and how its
 // partitions are sized (join_shape), what a handle has learnt from overflows (JoinLearnt), and what the cursors of an overflowed
-// two-level join ask for (join_overflow_verdict).  No device, no handle: graph.hip's plan_join reads the knobs, calls join_shape
-// and lays the arrays out; tests/test_join_plan_cpu.py compiles this header on its own.
+// two-level join ask for (join_overflow_verdict), and the bits of the two-level join's 12-byte records (pj12_*).  No device, no
+// handle: graph.hip's plan_join reads the knobs, calls join_shape and lays the arrays out; tests/test_join_plan_cpu.py and
+// tests/test_join_records_cpu.py compile this header on their own.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 
 #include "ntjoin_mx.h"
+
+#if defined(__HIPCC__)
+#define PJP_HD __host__ __device__ inline
+#else
+#define PJP_HD inline
+#endif
 
 namespace mxg {
 
@@ -28,6 +35,10 @@ struct JoinLearnt {
     uint32_t sub_P1 = 0;      // fused call: what the sub-ranges of a coarse partition must hold per assembly (cap1_need's counterpart)
     uint64_t sub_need[MXG_MAX_ASSEMBLIES] = {};
     bool dg_off = false;      // owner of a partitioned graph stage: the LDS join failed once over the slots (global table from then on)
+    // the verdict prefill of assembly 0 (join_verdict.h): how many of its minimizers the last build found shared, of how many, and
+    // for which sizes (prefill_signature: the fused call's bounds have one too)
+    bool pre_known = false;
+    uint64_t pre_sig = 0, pre_shared0 = 0, pre_n0 = 0;
 
     static uint64_t signature(uint32_t n_asm, const uint64_t *n_mx)
     {
@@ -51,12 +62,85 @@ struct JoinLearnt {
     // an assembly was added to the handle.  Leaves sub_P1 / sub_need[], sig and dg_off alone.
     void assembly_added()
     {
+        pre_known = false;
         overflowed = false;
         cap1_P1 = 0;
         cap1_need = 0;
     }
     void gave_up() { overflowed = true; }  // the LDS join fell to the global table
+
+    // The sizes a plan was made for, as one word: the sketches' own sizes or the fused call's bounds (which settle from the second
+    // call on: they follow the counts of the call before).
+    static uint64_t prefill_signature(uint32_t n_asm, const uint64_t *n_of, bool bounds)
+    {
+        return signature(n_asm, n_of) ^ (bounds ? 0xB0B0B0B0B0B0B0B0ull : 0ull);
+    }
+    // a build ended: `shared0` of the n0 minimizers the plan counted for assembly 0 are shared (= the graph's vertices)
+    void shared_counted(uint64_t plan_sig, uint64_t shared0, uint64_t n0)
+    {
+        pre_known = true;
+        pre_sig = plan_sig;
+        pre_shared0 = shared0;
+        pre_n0 = n0;
+    }
+    // Assembly 0's verdicts are prefilled "shared, own index" (PJ_PREFILL_OWN0) only where the previous build, of the same sizes,
+    // found more than half of assembly 0 shared: the join then sends assembly 0's other words instead of its shared ones, which
+    // are fewer.  The first build, a build after other sizes or after an added assembly: PJ_PREFILL_UNIQUE.
+    bool prefill_own0(uint64_t plan_sig) const { return pre_known && pre_sig == plan_sig && 2 * pre_shared0 > pre_n0; }
 };
+
+// ---- the two-level join's 12-byte records -------------------------------------------------------------------------------------
+// A record is {key lo, key hi, item, assembly | PJ_REC_DUP}: 16 bytes, written by k_pj1_scatter, read and rewritten by
+// k_pj2_bucket, read by the join.  The fourth word holds 6 bits (5 of the assembly, MXG_MAX_ASSEMBLIES = 32, and the mark
+// "more than once in its assembly"), and the place of a record says as much already:
+//   level 1 (sub-ranges per assembly): the record lies in ITS assembly's sub-range.  {product lo, product hi, item | mark << 31}
+//       (items are below 2^29, join_shape), product = key * 0x9E3779B97F4A7C15.
+//   level 2: the record lies in fine partition b of coarse partition c, so bits 44 .. 44 + lg P - 1 (b) and 52 .. 52 + lg P1 - 1
+//       (c) of its product are known.  The 6-bit tag (assembly | mark << 5) takes the lowest 6 of those bits: the fine
+//       partition's first, then the coarse one's.  {product lo, product hi with the tag, item}.
+// The multiplier is odd, so the product is a bijection of the key: two records of one fine partition have equal keys exactly when
+// their products agree in every bit that is not implied, i.e. when pj12_key() of both is equal.  The table slot of the join
+// (bits 32..42 of the product) lies below the tag.  pj12_key() is never the table's empty mark (all ones): the tag's bits are 0.
+constexpr uint64_t PJ_MUL = 0x9E3779B97F4A7C15ull;
+constexpr uint32_t PJ12_TAG_BITS = 6, PJ12_TAG_DUP = 32u, PJ12_ITEM_DUP = 0x80000000u;
+constexpr uint32_t PJ12_FINE_SHIFT = 44 - 32, PJ12_COARSE_SHIFT = 52 - 32;  // in the product's high word
+
+PJP_HD uint32_t pj12_lg(uint32_t x)  // x = 2^n
+{
+    uint32_t n = 0;
+    while ((1u << n) < x && n < 31) ++n;
+    return n;
+}
+// do the partitions imply 6 bits?  (P1 = 0: one level)
+PJP_HD bool pj12_fits(uint32_t P1, uint32_t P) { return P1 != 0 && P != 0 && (uint64_t)P1 * P >= (1u << PJ12_TAG_BITS); }
+// tag bits taken from the fine partition's field (the rest come from the coarse one's)
+PJP_HD uint32_t pj12_fine_bits(uint32_t lgP) { return lgP < PJ12_TAG_BITS ? lgP : PJ12_TAG_BITS; }
+// the bits of the product's high word that hold the tag
+PJP_HD uint32_t pj12_tag_mask(uint32_t lgP)
+{
+    const uint32_t f = pj12_fine_bits(lgP);
+    return (((1u << f) - 1u) << PJ12_FINE_SHIFT) | (((1u << (PJ12_TAG_BITS - f)) - 1u) << PJ12_COARSE_SHIFT);
+}
+PJP_HD uint32_t pj12_tag(uint32_t assembly, bool dup) { return assembly | (dup ? PJ12_TAG_DUP : 0u); }
+PJP_HD uint32_t pj12_pack(uint32_t prod_hi, uint32_t lgP, uint32_t tag)
+{
+    const uint32_t f = pj12_fine_bits(lgP);
+    return (prod_hi & ~pj12_tag_mask(lgP)) | ((tag & ((1u << f) - 1u)) << PJ12_FINE_SHIFT) | ((tag >> f) << PJ12_COARSE_SHIFT);
+}
+PJP_HD uint32_t pj12_unpack_tag(uint32_t word, uint32_t lgP)
+{
+    const uint32_t f = pj12_fine_bits(lgP);
+    return ((word >> PJ12_FINE_SHIFT) & ((1u << f) - 1u)) | (((word >> PJ12_COARSE_SHIFT) & ((1u << (PJ12_TAG_BITS - f)) - 1u)) << f);
+}
+// what two records of one fine partition compare (and the join's table keeps)
+PJP_HD uint64_t pj12_key(uint32_t lo, uint32_t word, uint32_t lgP) { return ((uint64_t)(word & ~pj12_tag_mask(lgP)) << 32) | lo; }
+PJP_HD bool pj12_same_key(uint32_t lo_a, uint32_t word_a, uint32_t lo_b, uint32_t word_b, uint32_t lgP)
+{
+    return pj12_key(lo_a, word_a, lgP) == pj12_key(lo_b, word_b, lgP);
+}
+// the partitions of a product (what pj1_part / pj_part of graph.hip take of key * PJ_MUL)
+PJP_HD uint32_t pj12_coarse(uint64_t prod, uint32_t P1) { return (uint32_t)(prod >> 52) & (P1 - 1u); }
+PJP_HD uint32_t pj12_fine(uint64_t prod, uint32_t P) { return (uint32_t)(prod >> 44) & (P - 1u); }
 
 struct JoinRequest {
     uint32_t A = 0;                          // assemblies, 1..MXG_MAX_ASSEMBLIES
@@ -67,6 +151,9 @@ struct JoinRequest {
     bool split = false;            // a sub-range of every coarse partition per assembly (the fused call's early partition)
     bool force_two_level = false;  // MXG_PJ_TWO_LEVEL
     bool join_global = false;      // MXG_GRAPH_JOIN=global
+    bool no_rec12 = false;         // MXG_PJ_REC12=0: 16-byte records everywhere
+    bool no_pipe = false;          // MXG_PJ_PIPE=0: k_pj_join behind two levels too (it reads 16-byte records only)
+    bool no_prefill0 = false;      // MXG_PJ_PREFILL0=0: assembly 0 keeps PJ_PREFILL_UNIQUE whatever was learnt
     uint32_t graph_u = 0;          // MXG_GRAPH_U: 1, 2 or 4 forces the width of the tail's ordered passes (anything else: by size)
 };
 
@@ -87,6 +174,9 @@ struct JoinShape {
     uint32_t nb = 0;                               // ... and their number
     size_t nb0 = 0;                                // assembly 0's
     uint32_t n_items = 0, e_blocks = 0;            // A * nvs items of the edge kernels, in blocks of 256
+    bool rec12 = false;        // 12-byte records (two levels, sub-ranges per assembly, the pipelined join kernel)
+    uint32_t prefill0 = 0;     // assembly 0's verdict prefill (PjPrefillRule of join_verdict.h: 0 unless learnt otherwise)
+    uint64_t pre_sig = 0;      // JoinLearnt::prefill_signature of these sizes
     size_t n_cur = 0;  // split: words of the sub-ranges' cursors that lie between the super-counts and the counts
     // 256-blocks per thread block of the ordered passes (graph_tail_u): k_flags_pj and k_vertices_pj over nb, the adjacency and
     // edge passes over e_blocks
@@ -191,6 +281,11 @@ inline JoinShapeError join_shape(const JoinRequest &rq, const JoinLearnt &learnt
     pl.n_items = (uint32_t)((size_t)A * pl.nvs);
     pl.e_blocks = (pl.n_items + 255) / 256;
     if (pl.split && pl.pj && pl.two_level) pl.n_cur = (size_t)P1 * A * PJ1_CS;
+    // 12-byte records: where the record's place implies its fourth word.  Level 1 needs the sub-ranges per assembly, level 2 six
+    // implied bits; k_pj_join_pipe reads them (partitions of at most 256 rows), k_pj_join and every other route keep 16 bytes.
+    pl.rec12 = pl.split && pl.pj && pl.two_level && pj12_fits(P1, P) && pl.rows2 <= 256 && !rq.no_rec12 && !rq.no_pipe;
+    pl.pre_sig = JoinLearnt::prefill_signature(A, rq.n_of, rq.bounds);
+    pl.prefill0 = pl.pj && pl.two_level && !rq.no_prefill0 && learnt.prefill_own0(pl.pre_sig) ? 1u : 0u;
     pl.u_flags = graph_tail_u(pl.nb, rq.graph_u);
     // (by size the vertex pass stops at GRAPH_TAIL_U_VERTICES; MXG_GRAPH_U=4 still runs it at 4)
     pl.u_vertices = graph_tail_u(0, rq.graph_u) == rq.graph_u ? rq.graph_u : std::min(pl.u_flags, GRAPH_TAIL_U_VERTICES);

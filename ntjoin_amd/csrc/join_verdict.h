@@ -24,4 +24,19 @@ constexpr uint32_t PJ_VERDICT_REF = 2u;
 
 PJV_HD bool pj_verdict_is_prefill(uint32_t word) { return word == PJ_VERDICT_PREFILL; }
 
+// The second prefill rule (two-level join).  Where most of assembly 0's minimizers are shared, the commonest word of assembly 0 is
+// "shared, and the key's minimizer in assembly 0 is this very one": (i << 3) | UNIQUE | SHARED | INALL, which k_pj1_scatter can
+// write in order as well.  The other assemblies keep PJ_VERDICT_PREFILL.  Which rule a build takes is decided on the host from
+// what an earlier build of the same sketches counted (JoinLearnt::prefill_own0, join_plan.h).
+// Neither prefill can be taken for one of the other words a partitioning kernel leaves: 0 (a record beyond its sub-range's
+// capacity) has no flag, a reference has the low bits PJ_VERDICT_REF; the prefills' low bits are 1 and 7.
+enum PjPrefillRule : uint32_t { PJ_PREFILL_UNIQUE = 0, PJ_PREFILL_OWN0 = 1 };
+constexpr uint32_t PJ_VERDICT_SHARED = MXG_MX_UNIQUE | MXG_MX_SHARED | MXG_MX_INALL;
+
+// the word the partitioning kernel writes for minimizer i of assembly a, and the join does not send
+PJV_HD uint32_t pj_verdict_prefill(uint32_t rule, uint32_t a, uint32_t i)
+{
+    return rule == PJ_PREFILL_OWN0 && a == 0 ? (i << 3) | PJ_VERDICT_SHARED : PJ_VERDICT_PREFILL;
+}
+
 }  // namespace mxg
