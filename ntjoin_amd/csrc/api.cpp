@@ -774,6 +774,7 @@ int mxg_set_sketch_device(mxg_handle *h, int assembly, const void *d_out_hash, c
     a->host_valid = false;
     a->flags_valid = false;
     h->graph.valid = false;
+    h->pj_learnt.sketch_replaced();  // (an overflow was the old minimizers'; the prefill's guess stays: join_plan.h)
     return MXG_OK;
 }
 

@@ -68,6 +68,16 @@ struct JoinLearnt {
         cap1_need = 0;
     }
     void gave_up() { overflowed = true; }  // the LDS join fell to the global table
+    // mxg_set_sketch_device put other minimizers in an assembly's place.  What overflowed was the data that left, and the sizes
+    // alone (sketches_are) cannot tell: the next build tries the LDS join again.  The verdict prefill's count stays (pre_known):
+    // a guess that no longer fits costs bytes, never the result (prefill_own0 below), and sub_P1 / sub_need[] only ever widen.
+    // (mxg_set_sketch_gathered does not call this: the exchange installs the same union again every step, and the lesson holds.)
+    void sketch_replaced()
+    {
+        overflowed = false;
+        cap1_P1 = 0;
+        cap1_need = 0;
+    }
 
     // The sizes a plan was made for, as one word: the sketches' own sizes or the fused call's bounds (which settle from the second
     // call on: they follow the counts of the call before).
@@ -86,6 +96,11 @@ struct JoinLearnt {
     // Assembly 0's verdicts are prefilled "shared, own index" (PJ_PREFILL_OWN0) only where the previous build, of the same sizes,
     // found more than half of assembly 0 shared: the join then sends assembly 0's other words instead of its shared ones, which
     // are fewer.  The first build, a build after other sizes or after an added assembly: PJ_PREFILL_UNIQUE.
+    // "The same sizes" is all the guess knows, and a sketch can be replaced on a live handle without changing them:
+    // mxg_set_sketch_device and mxg_set_sketch_gathered with as many minimizers as before, a borrowed packed buffer that is
+    // refilled and sketched again (the fused call's key is its bounds, which follow the record layout alone).  The guess may then
+    // be wrong, by design: the join sends every word that differs from the prefill, word 1 included, so a wrong guess moves more
+    // bytes and gives the same flags, vertices and edges (tests/test_gpu_join_prefill_stale.py).
     bool prefill_own0(uint64_t plan_sig) const { return pre_known && pre_sig == plan_sig && 2 * pre_shared0 > pre_n0; }
 };
 

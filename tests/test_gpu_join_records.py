@@ -32,6 +32,11 @@ def _from_products(prods):
     return np.array([(int(p) * INV) & ONES for p in prods], dtype=np.uint64)
 
 
+def _join_lines(err):
+    """the [mxg] join lines of a build's stderr, one dict of numbers per attempt"""
+    return [dict((k, int(v)) for k, v in re.findall(r"(\w+)=(\d+)", ln)) for ln in err.splitlines() if ln.startswith("[mxg] join")]
+
+
 def _build(monkeypatch, capfd, sets, env, builds=1):
     """-> (state of every build, graph_join of every build, the [mxg] join lines of every build)"""
     from ntjoin_amd.engine import MxEngine
@@ -46,8 +51,7 @@ def _build(monkeypatch, capfd, sets, env, builds=1):
         for _ in range(builds):
             capfd.readouterr()
             eng.build_graph()
-            err = capfd.readouterr().err
-            lines.append([dict((k, int(v)) for k, v in re.findall(r"(\w+)=(\d+)", ln)) for ln in err.splitlines() if ln.startswith("[mxg] join")])
+            lines.append(_join_lines(capfd.readouterr().err))
             states.append(_state(eng, len(sets)))
             joins.append(int(eng.stats()["graph_join"]))
     return states, joins, lines

@@ -74,6 +74,21 @@ int main()
             JoinShape s;
             put(join_shape(rq, l, s));
             put(s.P1); put(s.P); put(s.two_level); put(s.pj); put(s.split); put(s.rows2); put(s.rec12); put(s.prefill0);
+        } else if (cmd == 4) {  // a sketch replaced behind a join that gave up: shared0 n0 A n[A] -> overflowed before, after, prefill0 after
+            JoinLearnt l;
+            const uint64_t shared0 = get(), n0 = get();
+            JoinRequest rq;
+            rq.force_two_level = true;
+            rq.A = (uint32_t)get();
+            for (uint32_t a = 0; a < rq.A; ++a) rq.n_of[a] = get();
+            l.gave_up();
+            l.shared_counted(JoinLearnt::prefill_signature(rq.A, rq.n_of, false), shared0, n0);
+            put(l.overflowed);
+            l.sketch_replaced();
+            rq.global_table = l.overflowed;
+            JoinShape s;
+            join_shape(rq, l, s);
+            put(l.overflowed); put(s.pj); put(s.prefill0);
         } else {  // prefill words: rule a i
             const uint32_t rule = (uint32_t)get(), a = (uint32_t)get(), i = (uint32_t)get();
             put(pj_verdict_prefill(rule, a, i)); put(PJ_VERDICT_PREFILL); put(PJ_VERDICT_REF);
@@ -267,6 +282,12 @@ def test_learnt_prefill_choice(run):
     for (line, want), row in zip(cases, rows):
         got = dict(zip(SHAPE, row))
         assert got["prefill0"] == want, (line, got)
+
+
+def test_replaced_sketch_forgets_the_overflow_and_keeps_the_guess(run):
+    """sketch_replaced() (mxg_set_sketch_device): the next build tries the LDS join again, with the prefill the build before taught
+    -- the guess is keyed by the sizes and stays, right or wrong"""
+    assert run(["4 900 1000 2 1000 800", "4 400 1000 2 1000 800"]) == [[1, 0, 1, 1], [1, 0, 1, 0]]
 
 
 def test_prefill_words_are_distinct(run):
