@@ -642,7 +642,14 @@ __device__ __forceinline__ uint32_t pj1_part(uint64_t key, uint32_t p1mask) { re
 
 // R12 (sub-ranges per assembly only): 12-byte records {product lo, product hi, item | PJ12_ITEM_DUP}; key[] then holds the products.
 // prefill0: the verdict prefill of assembly 0 (join_verdict.h).
-template <bool R12>
+// G: thread block j takes tiles j G .. j G + G - 1 of the launch (the same 256-blocks in the same order as <1>: tile g of the
+// block is 256-blocks blk0 + 16 g ..) and a thread keeps 4 G records.  All G tiles' hashes are requested before the first is used;
+// the ordered work (prefill, fol ballots) follows per tile as before; there is ONE histogram over the G tiles and ONE add per
+// coarse bin and thread block -- G times fewer adds to every cursor -- and a bin's records of all G tiles share its place.
+// On the 12-byte route a record's assembly is the sub-range's and its index follows from where it was read, so a thread carries
+// the product and two mask bits per record.  G by the launch's tile count: pj1_tiles (join_plan.h, with what was measured:
+// one tile at every size; MXG_PJ_TILES=2 forces two on the 12-byte route, the A/B of that finding).
+template <bool R12, uint32_t G>
 __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t blk_lo, uint32_t blk_hi, uint32_t p1mask, uint32_t cap1,
                                                      uint32_t *cursor, uint4 *recs1, uint32_t *sup, uint32_t n_sup, const PjSub subr,
                                                      uint32_t prefill0)
@@ -652,38 +659,63 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
     uint32_t *hist = pj_lds, *start = pj_lds + p1mask + 1;
     if (blockIdx.x == 0)  // super-counts of the two counting kernels that follow (scan_kernels.h)
         for (uint32_t i = threadIdx.x; i < n_sup; i += PJ_BT) sup[i] = 0;
-    constexpr uint32_t U = PJ_IPB / PJ_BT, BPU = PJ_BT / 256;
-    const uint32_t j = blockIdx.x, sub = threadIdx.x >> 8, t256 = threadIdx.x & 255u;
-    const uint32_t blk0 = blk_lo + j * (PJ_IPB / 256);
-    uint64_t key[U];
-    uint32_t ia[U], ii[U], live = 0;
+    constexpr uint32_t U = PJ_IPB / PJ_BT, BPU = PJ_BT / 256, NU = U * G;
+    const uint32_t j = blockIdx.x;
+    const uint32_t blk0 = blk_lo + j * (G * (PJ_IPB / 256));
+    // record u of thread t: item u % U of tile u / U, element t % 256 of its 256-block
+    auto blk_of = [&](uint32_t u, uint32_t t) { return blk0 + (u / U) * (PJ_IPB / 256) + (u % U) * BPU + (t >> 8); };
+    // Each pass over the records works their 256-blocks and indices out anew from a copy of the thread's number that the compiler
+    // cannot see through: it would otherwise keep every record's block, index and predicates from the first pass to the last,
+    // five registers per record where the record itself is two.
+    auto thread_again = [] {
+        uint32_t t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return t;
+    };
+    const bool own = R12 || subr.n_sub > 1;  // the launch is one assembly's (sub-ranges; the 12-byte route has them)
+    const uint32_t bs_own = p.bstart[subr.s], n_own = own ? asm_n(p, subr.s) : 0u;
+    // (the records' arrays are written by plain assignments and selects, never under a branch: a conditional store into one of
+    // them makes the compiler carry the whole array through the join, 4 G records of copies per record)
+    uint64_t key[NU];
+    uint32_t ia[R12 ? 1 : NU], ii[R12 ? 1 : NU], live = 0, dupm = 0;
+    const uint32_t t_a = thread_again();
 #pragma unroll
-    for (uint32_t u = 0; u < U; ++u) {
-        const uint32_t blk = blk0 + u * BPU + sub;
-        key[u] = 0;
-        ia[u] = ii[u] = 0;
-        if (blk >= blk_hi) continue;
-        const uint32_t a = subr.n_sub > 1 ? subr.s : asm_of_block(p, blk);
-        const uint32_t i = (blk - p.bstart[a]) * 256u + t256, n = asm_n(p, a);
-        const bool lv = i < n;
-        if (lv) {
-            key[u] = p.hash[a][i];
-            p.slot[a][i] = pj_verdict_prefill(prefill0, a, i);  // (followers too; in front of this thread's own store of 0 below)
-        }
+    for (uint32_t u = 0; u < NU; ++u) {  // every tile's loads, before the first is used
+        const uint32_t blk = blk_of(u, t_a), in = blk < blk_hi, t256 = t_a & 255u;
+        const uint32_t a = own ? subr.s : asm_of_block(p, min(blk, blk_hi - 1u));
+        const uint32_t i = (blk - (own ? bs_own : p.bstart[a])) * 256u + t256, n = own ? n_own : asm_n(p, a);
+        const bool lv = in && i < n;
+        key[u] = p.hash[a][lv ? i : 0u];  // (a minimizer that is not there reads the first, which the launch has, and drops it below)
+        if (lv) p.slot[a][i] = pj_verdict_prefill(prefill0, a, i);  // (followers too; in front of this thread's own store of 0 below)
+    }
+    const uint32_t t_b = thread_again();
+#pragma unroll
+    for (uint32_t u = 0; u < NU; ++u) {
+        const uint32_t blk = blk_of(u, t_b), in = blk < blk_hi, t256 = t_b & 255u;
+        const uint32_t a = own ? subr.s : asm_of_block(p, min(blk, blk_hi - 1u));
+        const uint32_t i = (blk - (own ? bs_own : p.bstart[a])) * 256u + t256, n = own ? n_own : asm_n(p, a);
+        const bool lv = in && i < n;
         const uint32_t role = pj_run_role(i, n, key[u], lv);  // (followers travel with their run's leader)
         const uint64_t fb = __ballot(role & 1u);
-        if ((threadIdx.x & 63u) == 0) p.fol[(size_t)blk * 4u + ((threadIdx.x >> 6) & 3u)] = fb;
+        if (in && (threadIdx.x & 63u) == 0) p.fol[(size_t)blk * 4u + ((threadIdx.x >> 6) & 3u)] = fb;
         if (R12) key[u] *= PJ_MUL;
-        if (lv && !(role & 1u)) {
-            ia[u] = a | ((role & 2u) ? PJ_REC_DUP : 0u);
-            ii[u] = i;
-            live |= 1u << u;
+        const bool rec = lv && !(role & 1u);
+        if (!R12) {
+            ia[u] = rec ? a | ((role & 2u) ? PJ_REC_DUP : 0u) : 0u;
+            ii[u] = rec ? i : 0u;
         }
+        dupm |= rec && (role & 2u) ? 1u << u : 0u;
+        live |= rec ? 1u << u : 0u;
     }
+    // (here, not where they are next read: the compiler would otherwise put off the run test and the product of every record to
+    // the last pass and keep the hash, its neighbour's and the index until then)
+    asm volatile("" : "+v"(live), "+v"(dupm));
+#pragma unroll
+    for (uint32_t u = 0; u < NU; ++u) asm volatile("" : "+v"(key[u]));
     for (uint32_t b = threadIdx.x; b <= p1mask; b += PJ_BT) hist[b] = 0;
     __syncthreads();
 #pragma unroll
-    for (uint32_t u = 0; u < U; ++u)
+    for (uint32_t u = 0; u < NU; ++u)
         if ((live >> u) & 1u) atomicAdd(&hist[part1(key[u])], 1u);
     __syncthreads();
     for (uint32_t b = threadIdx.x; b <= p1mask; b += PJ_BT) {
@@ -692,15 +724,18 @@ __global__ __launch_bounds__(PJ_BT) void k_pj1_scatter(const AsmSet p, uint32_t 
         hist[b] = 0;  // from here on: records of this bin already placed
     }
     __syncthreads();
+    const uint32_t t_c = thread_again();
 #pragma unroll
-    for (uint32_t u = 0; u < U; ++u) {
+    for (uint32_t u = 0; u < NU; ++u) {
         if (!((live >> u) & 1u)) continue;
         const uint32_t b = part1(key[u]);
         const uint32_t pos = start[b] + atomicAdd(&hist[b], 1u);
+        // (12 bytes: the item is where its hash was read, the assembly the sub-range's, the mark a bit of dupm)
+        const uint32_t i = R12 ? (blk_of(u, t_c) - bs_own) * 256u + (t_c & 255u) : ii[u], aw = R12 ? subr.s : ia[u];
         if (pos < subr.cap)
             pj_rec_store<R12>(recs1, (size_t)b * cap1 + subr.off + pos,
-                              make_uint4((uint32_t)key[u], (uint32_t)(key[u] >> 32), R12 && (ia[u] & PJ_REC_DUP) ? ii[u] | PJ12_ITEM_DUP : ii[u], ia[u]));
-        else p.slot[ia[u] & ~PJ_REC_DUP][ii[u]] = 0;  // beyond the capacity: no verdict will come (the cursor says so, k_pj_join reports it and
+                              make_uint4((uint32_t)key[u], (uint32_t)(key[u] >> 32), R12 && ((dupm >> u) & 1u) ? i | PJ12_ITEM_DUP : i, aw));
+        else p.slot[aw & ~PJ_REC_DUP][i] = 0;  // beyond the capacity: no verdict will come (the cursor says so, k_pj_join reports it and
                                         // the host redoes the stage with the global table); leave a harmless one behind
     }
 }
@@ -1459,6 +1494,7 @@ static int plan_join(mxg_handle *h, int mode, const GraphBounds *gb, bool global
     rq.join_global = join_env && !strcmp(join_env, "global");
     rq.force_two_level = knob_u64(h, "MXG_PJ_TWO_LEVEL", 0) != 0;
     rq.graph_u = (uint32_t)std::min<uint64_t>(knob_u64(h, "MXG_GRAPH_U", 0), 8);  // 1 | 2 | 4 forces the tail passes' width
+    rq.pj_tiles = (uint32_t)std::min<uint64_t>(knob_u64(h, "MXG_PJ_TILES", 0), 8);  // 1 | 2 forces level 1's tiles per thread block
     // MXG_PJ_REC12=0 / MXG_PJ_PREFILL0=0: the 16-byte records / the one prefill rule where the plan would choose otherwise (A/B knobs);
     // MXG_PJ_SPLIT=1: sub-ranges per assembly in the stage's own plan too (test knob: the fused call's layout over given minimizers)
     rq.no_rec12 = knob_u64(h, "MXG_PJ_REC12", 1) == 0;
@@ -1543,9 +1579,12 @@ static void launch_partition(mxg_handle *h, const JoinPlan &pl, uint32_t a_lo, u
         sub = PjSub{pl.A, a_lo, pl.sub_off[a_lo], pl.sub_cap[a_lo]};
         skew_lim = pl.skew_lim[a_lo];
     }
+    // level 1's tiles per thread block, by THIS launch's tile count (pj1_launch_tiles: one unless forced)
+    const uint32_t g1 = pj1_launch_tiles(pl, a_lo, a_hi);
+    auto level1 = pl.rec12 ? (g1 == 2 ? k_pj1_scatter<true, 2> : k_pj1_scatter<true, 1>) : k_pj1_scatter<false, 1>;
     if (n_rows1)
-        hipLaunchKernelGGL(pl.rec12 ? k_pj1_scatter<true> : k_pj1_scatter<false>, dim3(n_rows1), dim3(PJ_BT), (size_t)pl.P1 * 8, st, pl.as_all,
-                           blk_lo, blk_hi, pl.P1 - 1, pl.cap1, pl.cursor, pl.recs1, pl.fsup, n_sup_clear, sub, pl.prefill0);
+        hipLaunchKernelGGL(level1, dim3(pj_tiles_grid(n_rows1, g1)), dim3(PJ_BT), (size_t)pl.P1 * 8, st, pl.as_all, blk_lo, blk_hi, pl.P1 - 1,
+                           pl.cap1, pl.cursor, pl.recs1, pl.fsup, n_sup_clear, sub, pl.prefill0);
     hipLaunchKernelGGL(pl.rec12 ? k_pj2_bucket<true> : k_pj2_bucket<false>, dim3(sub.cap / PJ_IPB, pl.P1), dim3(PJ_BT), (size_t)pl.P * 8, st,
                        pl.as_all, pl.recs1, pl.cursor, pl.cap1, pl.rows2, pl.P - 1, pl.M, pl.recs2,
                        knob_u64(h, "MXG_PJ_SKEW", 0) ? 0u : skew_lim, sub);
@@ -1689,9 +1728,15 @@ struct GraphStage {
         if (!resume)
             h->stat_graph_join = (pl.pj ? (pl.two_level ? MXG_JOIN_LDS_TWO_LEVEL : MXG_JOIN_LDS) : MXG_JOIN_GLOBAL) | (early ? MXG_JOIN_EARLY : 0);
         // MXG_DEBUG_JOIN=1: the plan's choices that mxg_stats::graph_join has no bit for, one line per attempt (tests read it)
-        if (!resume && knob_u64(h, "MXG_DEBUG_JOIN", 0))
-            fprintf(stderr, "[mxg] join pj=%d two_level=%d split=%d early=%d record_bytes=%d prefill0=%u P1=%u rows2=%u\n", (int)pl.pj,
-                    (int)pl.two_level, (int)pl.split, (int)early, pl.rec12 ? 12 : 16, pl.prefill0, pl.P1, pl.rows2);
+        // (tiles1: level 1's tiles per thread block, the widest of the attempt's launches; 0: one level or no LDS join.  Level 2
+        // always takes one)
+        if (!resume && knob_u64(h, "MXG_DEBUG_JOIN", 0)) {
+            uint32_t t1 = 0;
+            for (uint32_t a = 0; pl.pj && pl.two_level && a < (pl.split ? pl.A : 1u); ++a)
+                t1 = std::max(t1, pj1_launch_tiles(pl, pl.split ? a : 0u, pl.split ? a + 1 : pl.A));
+            fprintf(stderr, "[mxg] join pj=%d two_level=%d split=%d early=%d record_bytes=%d prefill0=%u P1=%u rows2=%u tiles1=%u\n", (int)pl.pj,
+                    (int)pl.two_level, (int)pl.split, (int)early, pl.rec12 ? 12 : 16, pl.prefill0, pl.P1, pl.rows2, t1);
+        }
         // (the LDS joins clear nothing: every word of M and of the record regions that is read is written by this call)
         if (!pl.pj && !resume) MXG_HIP(h, hipMemsetAsync(h->g_keys.p, 0xFF, ((size_t)pl.cap + 1) * sizeof(Slot), h->stream));  // one fill: see Slot
         ctl = h->g_ctl.as<uint64_t>();  // every word the host reads of it is written by a kernel of this call

@@ -170,6 +170,7 @@ struct JoinRequest {
     bool no_pipe = false;          // MXG_PJ_PIPE=0: k_pj_join behind two levels too (it reads 16-byte records only)
     bool no_prefill0 = false;      // MXG_PJ_PREFILL0=0: assembly 0 keeps PJ_PREFILL_UNIQUE whatever was learnt
     uint32_t graph_u = 0;          // MXG_GRAPH_U: 1, 2 or 4 forces the width of the tail's ordered passes (anything else: by size)
+    uint32_t pj_tiles = 0;         // MXG_PJ_TILES: 1 or 2 forces level 1's tiles per thread block on the 12-byte route (anything else: by size)
 };
 
 enum JoinShapeError { JS_OK = 0, JS_TOO_MANY_MINIMIZERS, JS_TOO_MANY_ITEMS };
@@ -196,6 +197,7 @@ struct JoinShape {
     // 256-blocks per thread block of the ordered passes (graph_tail_u): k_flags_pj and k_vertices_pj over nb, the adjacency and
     // edge passes over e_blocks
     uint32_t u_flags = 1, u_vertices = 1, u_edges = 1;
+    uint32_t pj_tiles_forced = 0;  // level 1's tiles per thread block as forced (0: pj1_tiles decides per launch)
 };
 
 // The tail's ordered passes (k_flags_pj, k_vertices_pj over nb 256-blocks; k_adjacency, k_edge_flags, k_edges over e_blocks) give
@@ -219,6 +221,35 @@ inline uint32_t graph_tail_u(uint64_t blocks, uint32_t forced = 0)
 }
 // thread blocks of a pass over `blocks` 256-blocks, U to each
 inline uint32_t graph_tail_grid(uint64_t blocks, uint32_t U) { return (uint32_t)((blocks + U - 1) / U); }
+
+// Level 1 of the two-level join (k_pj1_scatter) can give a thread block G consecutive 4096-minimizer tiles of its launch: one
+// histogram and one add per coarse bin for all of them, G times fewer adds to every cursor.  A 1024-thread block has two places
+// per CU, 512 on the chip, and a launch of the two-level route has about a thousand tiles (1 465 per assembly at 3 Gbp + 3 Gbp):
+// wider blocks are fewer rounds of blocks, and their last round runs on a part of the chip.  Traced minimum of the kernel, the
+// target's launch alone on the GPU, at forced G = 1 / 2 / 4, two runs each (profiles/r13/join_tiles_ab.txt; us; in brackets the
+// kernel before it asked for a tile's four hashes ahead of their first use, which is where the time went):
+//   1.4 + 1.4 Gbp    (684 tiles per launch)      21.4 21.2 / 23.1 24.0 / 25.3 24.2   [28.7]   the wider, the slower
+//   2 + 2 Gbp        (977 tiles)                 34.0 32.8 / 31.2 32.0 / 37.4 37.9   [39.7]
+//   3 + 3 Gbp        (1 465 tiles)               42.1 41.9 / 40.7 40.5 / 47.8 48.1   [53.4 52.5]
+// (below 1.3 + 1.3 Gbp the join has one level).  G = 4 takes 92 VGPRs, one block per CU, and is slower at every size: it is not
+// built.  G = 2 (52 VGPRs, two blocks per CU as G = 1) is 1 to 2 us ahead from about 900 tiles on and buys nothing in the step:
+// at 3 Gbp + 3 Gbp the step's median is 2.2219 ms with it and 2.2208 without, and with four assemblies (2 930 tiles a launch, the
+// reference's launches beside the others' filters) every run with it is slower, 6.68-6.71 against 6.63-6.67 ms.  So NO size takes
+// it: the rule below answers 1 unless MXG_PJ_TILES=2 forces the 12-byte route's launches to two, which is how the figures above
+// can be had again.  The 16-byte route (one launch for all assemblies, the block looks every tile's assembly up) was slower with
+// wider blocks (189 / 247 / 275 us on 4.5 + 4.5 Gbp) and has one width; so has level 2 (39.3 / 46.9 / 56.0 us at 3 Gbp + 3 Gbp).
+// The rule is PER LAUNCH (on the fused route every assembly has its own), so that a threshold, should a later chip want one,
+// leaves a small assembly beside a large one at G = 1.
+constexpr uint32_t PJ1_TILES_G2 = 0xFFFFFFFFu;  // tiles per launch from which G = 2 is taken: never
+
+inline uint32_t pj1_tiles(uint64_t tiles, bool rec12, uint32_t forced = 0)
+{
+    if (!rec12) return 1u;
+    if (forced == 1 || forced == 2) return forced;
+    return tiles >= PJ1_TILES_G2 ? 2u : 1u;
+}
+// thread blocks of a launch over `tiles` tiles, G to each
+inline uint32_t pj_tiles_grid(uint64_t tiles, uint32_t G) { return (uint32_t)((tiles + G - 1) / G); }
 
 inline JoinShapeError join_shape(const JoinRequest &rq, const JoinLearnt &learnt, JoinShape &pl)
 {
@@ -305,7 +336,16 @@ inline JoinShapeError join_shape(const JoinRequest &rq, const JoinLearnt &learnt
     // (by size the vertex pass stops at GRAPH_TAIL_U_VERTICES; MXG_GRAPH_U=4 still runs it at 4)
     pl.u_vertices = graph_tail_u(0, rq.graph_u) == rq.graph_u ? rq.graph_u : std::min(pl.u_flags, GRAPH_TAIL_U_VERTICES);
     pl.u_edges = graph_tail_u(pl.e_blocks, rq.graph_u);
+    pl.pj_tiles_forced = rq.pj_tiles == 1 || rq.pj_tiles == 2 ? rq.pj_tiles : 0u;
     return JS_OK;
+}
+
+// Level 1's tiles per thread block for the launch over assemblies [a_lo, a_hi) of a two-level plan (sub-ranges: one assembly per
+// launch; else one launch for all)
+inline uint32_t pj1_launch_tiles(const JoinShape &pl, uint32_t a_lo, uint32_t a_hi)
+{
+    const uint32_t tiles = (pl.bstart[a_hi] - pl.bstart[a_lo] + PJ_IPB / 256 - 1) / (PJ_IPB / 256);
+    return pj1_tiles(tiles, pl.rec12, pl.pj_tiles_forced);
 }
 
 // build_graph_impl's answer to an LDS join that reported failure
