@@ -19,6 +19,7 @@
 #include <thread>
 
 #include "join_verdict.h"
+#include "graph_rank.h"
 #include "mxg_internal.h"
 #include "scan_kernels.h"
 
@@ -872,7 +873,8 @@ __global__ __launch_bounds__(PJ_BT) void k_pj2_bucket(const AsmSet p, const uint
 }
 
 // ---- the tail's ordered passes: U consecutive 256-blocks per thread block ---------------------------------------------------
-// k_flags_pj, k_vertices_pj, k_adjacency, k_edge_flags and k_edges are plain ordered passes, one item per thread.  With one 256-block
+// k_flags_pj, k_vertices_pj, k_adjacency, k_edge_flags and k_edges (and the rank route's k_edge_flags_rank, k_edges_rank, which run
+// without k_adjacency) are plain ordered passes, one item per thread.  With one 256-block
 // per thread block a CU has 8 KB of loads in flight where an HBM round trip wants tens of KB, and every 256 items pay a block's
 // bookkeeping ("The tail's ordered passes").  Thread block j of <U> takes 256-blocks j U .. j U + U - 1
 // ("sub-blocks"); thread t keeps item t of each, so a wave still holds 64 consecutive items and the ballots, fol and mask0 words
@@ -1086,6 +1088,8 @@ struct VertexPjParams {
     const uint32_t *bpref0;
     uint64_t *vhash;
     uint32_t *vpos, *vrec, *fv, *frec;  // [A][nvs]
+    uint32_t *rank;  // [A][nvs], rows 1 .. A - 1: the place of every vertex in the assembly's filtered order (the rank route of the
+                     // edge kernels, graph_rank.h; nullptr: not wanted).  Row 0 is never written: assembly 0's vertex ids are its places
     uint32_t nvs;
     uint32_t *ivid[MXG_MAX_ASSEMBLIES];  // (owner of a partitioned graph stage: item -> vertex id, NONE32 for an item that is no vertex)
 };
@@ -1177,6 +1181,7 @@ __global__ __launch_bounds__(256) void k_vertices_pj(const VertexPjParams p, uin
         const size_t o = (size_t)a * p.nvs;
         p.vpos[o + v] = pos[u];
         p.vrec[o + v] = rec[u];
+        if (a && p.rank) p.rank[o + v] = r;  // (beside the two scattered stores above, at their index)
         p.fv[o + r] = v;
         p.frec[o + r] = rec[u];
     }
@@ -1226,7 +1231,8 @@ __global__ __launch_bounds__(256) void k_adjacency(const uint32_t *__restrict__ 
 
 struct EdgeParams {
     const uint32_t *fv;   // [A][nv]   (nv = stride = upper bound of the vertex count; the count itself is *nv_ptr)
-    const uint2 *adj;     // [A][nv]: {successor, predecessor} (k_adjacency)
+    const uint2 *adj;     // [A][nv]: {successor, predecessor} (k_adjacency); the rank route has none
+    const uint32_t *frec, *rank;  // the rank route (k_edge_flags_rank, k_edges_rank): [A][nv] records of the filtered order, places of the vertices
     const uint64_t *nv_ptr;
     uint32_t nv, n_asm;
     uint8_t *eflag;       // [A*nv]
@@ -1376,6 +1382,187 @@ __global__ __launch_bounds__(256) void k_edges(const EdgeParams p, uint32_t n_it
     }
 }
 
+// ---- the rank route of the two edge passes (GRAPH_FULL behind an LDS join; MXG_GRAPH_RANK=0: k_adjacency and the passes above) ----
+// No adjacency table (graph_rank.h).  The successor of item (a, r) is fv[a][r + 1] if frec[a][r + 1] == frec[a][r] and r + 1 is
+// below the vertex count: coalesced loads of the item's own row.  v is next to u in another assembly b iff their places there,
+// rank[b][u] and rank[b][v] (k_vertices_pj; assembly 0's are the vertex ids themselves), differ by one and lie in one record: two
+// neighbouring words of frec[b], fetched only where the places differ by one.  An item of assembly 0 has u = r and v = r + 1, so
+// its places in the others are coalesced loads too, requested beside fv and frec.
+__device__ __forceinline__ uint32_t edge_mask_rank(const EdgeParams &p, uint32_t u, uint32_t v)
+{
+    const uint32_t last = p.nv - 1u;  // (a vertex and a place are held against their row: see rank_fetch)
+    return rank_support_mask(
+        p.n_asm, u, v, [&](uint32_t b, uint32_t x) { return b ? p.rank[(size_t)b * p.nv + min(x, last)] : x; },
+        [&](uint32_t b, uint32_t r) { return p.frec[(size_t)b * p.nv + min(r, last)]; });
+}
+
+// k_edge_flags from ranks.  NB: how many OTHER assemblies' places and records are requested up front -- 1 (n_asm <= 2), 3
+// (n_asm <= 4) -- or 0: more than four assemblies, looked up item by item (edge_mask_rank).  The k-th other assembly of an item of
+// assembly a is b = k < a ? k : k + 1.
+template <uint32_t U, uint32_t NB>
+__global__ __launch_bounds__(256) void k_edge_flags_rank(const EdgeParams p, uint32_t n_items)
+{
+    __shared__ TailScan<U> ts;
+    const uint32_t blk0 = blockIdx.x * U, nblk = (n_items + 255u) / 256u, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    constexpr uint32_t K = NB ? NB : 1u;
+    // The rows are strided by an upper bound of the vertex count (the smallest assembly's minimizers; four assemblies at 0.5 to
+    // 2 % divergence share one minimizer in six).  A thread block all of whose items lie beyond the count of their row reads
+    // nothing: its sub-blocks count no edge, its flag bytes stay unwritten, and k_edges_rank, which decides the same way from the
+    // same count, does not read them.  So the count comes first here, not beside the loads.
+    const uint32_t nvc = (uint32_t)*p.nv_ptr;
+    if (rank_items_unused(blk0 * 256u, U * 256u, n_items, p.nv, nvc)) {
+        if (wv < U && lane == 0 && blk0 + wv < nblk) count_publish(p.bsum, p.bsuper, blk0 + wv, 0u);
+        return;
+    }
+    // vertex and record of the item and of the one behind it for all U sub-blocks; and, as if the item
+    // were assembly 0's (item = r = u, v = r + 1), its two places in the other assemblies (any other item: word 0, dropped)
+    uint32_t uu[U], vv[U], rc[U], rn[U], r0[U][K], r1[U][K];
+    bool in[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t item = (blk0 + u) * 256u + threadIdx.x;
+        in[u] = blk0 + u < nblk && item < n_items;
+        const uint32_t i0 = in[u] ? item : 0u, i1 = in[u] && item + 1u < n_items ? item + 1u : 0u;
+        const bool first = item < p.nv;  // assembly 0's row is the identity (k_vertices_pj): its vertices are not fetched
+        uu[u] = p.fv[first ? 0u : i0];
+        vv[u] = p.fv[first ? 0u : i1];
+        if (first) uu[u] = item, vv[u] = item + 1u;
+        rc[u] = p.frec[i0];
+        rn[u] = p.frec[i1];
+        const uint32_t j0 = in[u] && first ? item : 0u, j1 = in[u] && item + 1u < p.nv ? item + 1u : 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < NB; ++k) {
+            const size_t row = k + 1u < p.n_asm ? (size_t)(k + 1u) * p.nv : (size_t)0;
+            r0[u][k] = p.rank[row + j0];
+            r1[u][k] = p.rank[row + j1];
+        }
+    }
+    uint32_t ia[U];
+    bool succ[U];  // the item has a successor: the pair (u, v) exists
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t item = (blk0 + u) * 256u + threadIdx.x;
+        ia[u] = in[u] ? item / p.nv : 0u;
+        succ[u] = in[u] && item - ia[u] * p.nv + 1u < nvc && rn[u] == rc[u];  // (nvc <= nv: the one behind is in the item's row)
+    }
+    uint8_t f[U];
+    if constexpr (NB > 0) {
+        // places of u and v in the other assemblies that are neither assembly 0 nor this item's own: gathers, for all U together
+        uint32_t gu[U][K], gv[U][K];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u)
+#pragma unroll
+            for (uint32_t k = 1; k < NB; ++k) {
+                const uint32_t b = k < ia[u] ? k : k + 1u;
+                const bool need = succ[u] && ia[u] != 0u && b < p.n_asm && uu[u] < p.nv && vv[u] < p.nv;  // (held against the row, as the places are)
+                const size_t row = need ? (size_t)b * p.nv : (size_t)0;
+                gu[u][k] = p.rank[row + (need ? uu[u] : 0u)];
+                gv[u][k] = p.rank[row + (need ? vv[u] : 0u)];
+            }
+        // the two records, where the places differ by one (else word 0 twice, dropped)
+        uint32_t x[U][K], y[U][K];
+        bool w[U][K];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u)
+#pragma unroll
+            for (uint32_t k = 0; k < NB; ++k) {
+                const uint32_t b = k < ia[u] ? k : k + 1u;
+                const uint32_t ru = ia[u] == 0u ? r0[u][k] : k == 0u ? uu[u] : gu[u][k];
+                const uint32_t rv = ia[u] == 0u ? r1[u][k] : k == 0u ? vv[u] : gv[u][k];
+                uint32_t lo, hi;
+                w[u][k] = rank_fetch(succ[u] && b < p.n_asm, ru, rv, p.nv, lo, hi);
+                const size_t row = w[u][k] ? (size_t)b * p.nv : (size_t)0;
+                x[u][k] = p.frec[row + lo];
+                y[u][k] = p.frec[row + hi];
+            }
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            uint32_t m = 1u << ia[u];  // (its own assembly: v is its successor there)
+#pragma unroll
+            for (uint32_t k = 0; k < NB; ++k)
+                if (w[u][k] && x[u][k] == y[u][k]) m |= 1u << (k < ia[u] ? k : k + 1u);
+            f[u] = succ[u] ? rank_edge_flag(m, ia[u], p.n_asm) : (uint8_t)0;
+        }
+    } else {
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            f[u] = 0;
+            if (!succ[u]) continue;
+            f[u] = rank_edge_flag(edge_mask_rank(p, uu[u], vv[u]), ia[u], p.n_asm);
+        }
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t item = (blk0 + u) * 256u + threadIdx.x;
+        if (in[u]) p.eflag[item] = f[u];
+        uint64_t bm;
+        tail_ballot(ts, u, f[u] != 0, bm);
+    }
+    __syncthreads();
+    if (wv < U && lane == 0 && blk0 + wv < nblk) count_publish(p.bsum, p.bsuper, blk0 + wv, tail_total(ts, wv));
+}
+
+// k_edges from ranks: v is the vertex behind u in the item's own row (a flagged item has one), requested beside the flag
+template <uint32_t U>
+__global__ __launch_bounds__(256) void k_edges_rank(const EdgeParams p, uint32_t n_items)
+{
+    __shared__ TailScan<U> ts;
+    const uint32_t blk0 = blockIdx.x * U, nblk = (n_items + 255u) / 256u, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    // the last tile also reports the totals (all 64 lanes of the wave that holds it)
+    auto report_totals = [&]() {
+        const uint32_t all = count_prefix(p.bsum, p.bsuper, nblk);
+        if (lane == 0) {
+            *p.n_edges = all;
+            p.host_ctl[32] = all;  // CTL_EDGES
+        }
+        if (lane < p.n_asm) p.host_ctl[lane] = p.nv_ptr[lane];  // shared minimizers per assembly
+    };
+    // a thread block of unused items (see k_edge_flags_rank, which left their flag bytes unwritten) has no edge
+    if (rank_items_unused(blk0 * 256u, U * 256u, n_items, p.nv, (uint32_t)*p.nv_ptr)) {
+        if (wv < U && blk0 + wv + 1 == nblk) report_totals();
+        return;
+    }
+    uint32_t fb[U], uu[U], v[U], m[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t item = (blk0 + u) * 256u + threadIdx.x;
+        const bool in = blk0 + u < nblk && item < n_items;
+        const bool first = item < p.nv;  // assembly 0's row is the identity (k_vertices_pj): its vertices are not fetched
+        fb[u] = p.eflag[in ? item : 0u];
+        uu[u] = p.fv[in && !first ? item : 0u];
+        v[u] = p.fv[in && !first && item + 1u < n_items ? item + 1u : 0u];
+        if (first) uu[u] = item, v[u] = item + 1u;
+        if (!in) fb[u] = 0;
+    }
+    uint64_t bm[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) tail_ballot(ts, u, fb[u] != 0, bm[u]);
+    if (wv < U && blk0 + wv < nblk) {  // wave u: edges in front of sub-block u
+        const uint32_t bef = count_prefix(p.bsum, p.bsuper, blk0 + wv);
+        if (lane == 0) ts.before[wv] = bef;
+        if (blk0 + wv + 1 == nblk) report_totals();
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        m[u] = fb[u];
+        if (fb[u] && p.n_asm > 8u) m[u] = edge_mask_rank(p, uu[u], v[u]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        if (!fb[u]) continue;
+        // python: sum(weights[f] for f in support) -- int 0 start, then float adds in support (= assembly) order
+        double wsum = 0.0;
+        for (uint32_t b = 0; b < p.n_asm; ++b)
+            if (m[u] & (1u << b)) wsum = wsum + p.weights[b];
+        const uint32_t e = ts.before[u] + tail_rank(ts, u, bm[u]);
+        p.eu[e] = uu[u];
+        p.ev[e] = v[u];
+        p.esup[e] = m[u];
+        p.ew[e] = wsum;
+    }
+}
+
 // distributed graph, owner side (dgraph.hip): adjacency arrives as messages {kind << 8 | assembly, local vertex, other
 // vertex (global id), 0}: kind 0 sets the successor, kind 1 the predecessor of adj[a][local] (the array was filled with NONE32)
 __global__ __launch_bounds__(256) void k_apply_msgs(const uint4 *__restrict__ msgs, uint64_t n, uint32_t stride, uint32_t *adj)
@@ -1494,6 +1681,7 @@ static int plan_join(mxg_handle *h, int mode, const GraphBounds *gb, bool global
     rq.join_global = join_env && !strcmp(join_env, "global");
     rq.force_two_level = knob_u64(h, "MXG_PJ_TWO_LEVEL", 0) != 0;
     rq.graph_u = (uint32_t)std::min<uint64_t>(knob_u64(h, "MXG_GRAPH_U", 0), 8);  // 1 | 2 | 4 forces the tail passes' width
+    rq.no_graph_rank = knob_u64(h, "MXG_GRAPH_RANK", 1) == 0;  // 0: k_adjacency and the table's edge passes where the plan takes the rank route (A/B knob)
     rq.pj_tiles = (uint32_t)std::min<uint64_t>(knob_u64(h, "MXG_PJ_TILES", 0), 8);  // 1 | 2 forces level 1's tiles per thread block
     // MXG_PJ_REC12=0 / MXG_PJ_PREFILL0=0: the 16-byte records / the one prefill rule where the plan would choose otherwise (A/B knobs);
     // MXG_PJ_SPLIT=1: sub-ranges per assembly in the stage's own plan too (test knob: the fused call's layout over given minimizers)
@@ -1689,6 +1877,14 @@ static int take_or_make_plan(mxg_handle *h, const GraphCall &c, bool global_tabl
         else hipLaunchKernelGGL(kernel<1>, grid, dim3(256), 0, stream, __VA_ARGS__);                   \
     } while (0)
 
+// ... of a kernel with a second template argument
+#define TAIL_LAUNCH2(kernel, U, X, grid, stream, ...)                                                  \
+    do {                                                                                               \
+        if ((U) == 4) hipLaunchKernelGGL((kernel<4, X>), grid, dim3(256), 0, stream, __VA_ARGS__);     \
+        else if ((U) == 2) hipLaunchKernelGGL((kernel<2, X>), grid, dim3(256), 0, stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL((kernel<1, X>), grid, dim3(256), 0, stream, __VA_ARGS__);              \
+    } while (0)
+
 // One attempt at the stage: the phases of build_graph_impl, in the order it enqueues them.
 struct GraphStage {
     mxg_handle *const h;
@@ -1734,8 +1930,8 @@ struct GraphStage {
             uint32_t t1 = 0;
             for (uint32_t a = 0; pl.pj && pl.two_level && a < (pl.split ? pl.A : 1u); ++a)
                 t1 = std::max(t1, pj1_launch_tiles(pl, pl.split ? a : 0u, pl.split ? a + 1 : pl.A));
-            fprintf(stderr, "[mxg] join pj=%d two_level=%d split=%d early=%d record_bytes=%d prefill0=%u P1=%u rows2=%u tiles1=%u\n", (int)pl.pj,
-                    (int)pl.two_level, (int)pl.split, (int)early, pl.rec12 ? 12 : 16, pl.prefill0, pl.P1, pl.rows2, t1);
+            fprintf(stderr, "[mxg] join pj=%d two_level=%d split=%d early=%d record_bytes=%d prefill0=%u P1=%u rows2=%u tiles1=%u rank=%d\n",
+                    (int)pl.pj, (int)pl.two_level, (int)pl.split, (int)early, pl.rec12 ? 12 : 16, pl.prefill0, pl.P1, pl.rows2, t1, (int)pl.graph_rank);
         }
         // (the LDS joins clear nothing: every word of M and of the record regions that is read is written by this call)
         if (!pl.pj && !resume) MXG_HIP(h, hipMemsetAsync(h->g_keys.p, 0xFF, ((size_t)pl.cap + 1) * sizeof(Slot), h->stream));  // one fill: see Slot
@@ -1817,7 +2013,9 @@ struct GraphStage {
         MXG_HIP(h, h->g_vrec.ensure(anv() * 4));
         MXG_HIP(h, h->g_fv.ensure(anv() * 4));
         MXG_HIP(h, h->g_frec.ensure(anv() * 4));
-        MXG_HIP(h, h->g_nxt.ensure(2 * anv() * 4));  // adj[A][nvs] = {successor, predecessor}: k_adjacency writes every entry that is read;
+        // adj[A][nvs] = {successor, predecessor}: k_adjacency writes every entry that is read -- or, on the rank route, which builds
+        // no adj, rank[A][nvs] in the same storage: k_vertices_pj writes every entry below the vertex count of rows 1 .. A - 1
+        MXG_HIP(h, h->g_nxt.ensure(2 * anv() * 4));
         if (c.mode == GRAPH_DG_EDGES) MXG_HIP(h, hipMemsetAsync(h->g_nxt.p, 0xFF, 2 * anv() * 4, h->stream));  // messages set single words
         return MXG_OK;
     }
@@ -1850,6 +2048,7 @@ struct GraphStage {
         vp.vrec = h->g_vrec.as<uint32_t>();
         vp.fv = h->g_fv.as<uint32_t>();
         vp.frec = h->g_frec.as<uint32_t>();
+        vp.rank = pl.graph_rank ? h->g_nxt.as<uint32_t>() : nullptr;
         vp.nvs = (uint32_t)pl.nvs;
         return MXG_OK;
     }
@@ -1927,6 +2126,8 @@ struct GraphStage {
     {
         ep.fv = h->g_fv.as<uint32_t>();
         ep.adj = h->g_nxt.as<uint2>();
+        ep.frec = h->g_frec.as<uint32_t>();
+        ep.rank = h->g_nxt.as<uint32_t>();  // (the rank route: no adj, its storage holds the places)
         ep.nv_ptr = ctl + CTL_SHARED;
         ep.nv = (uint32_t)pl.nvs;
         ep.n_asm = pl.A;
@@ -1954,8 +2155,15 @@ struct GraphStage {
         EdgeParams ep;
         fill(ep);
         const dim3 grid(graph_tail_grid(pl.e_blocks, pl.u_edges));
-        TAIL_LAUNCH(k_edge_flags, pl.u_edges, grid, h->stream, ep, n_items);  // + per-256 counts
-        TAIL_LAUNCH(k_edges, pl.u_edges, grid, h->stream, ep, n_items);
+        if (pl.graph_rank) {  // from fv, frec and the places k_vertices_pj stored: no k_adjacency in front
+            if (pl.A <= 2) TAIL_LAUNCH2(k_edge_flags_rank, pl.u_edges, 1, grid, h->stream, ep, n_items);
+            else if (pl.A <= 4) TAIL_LAUNCH2(k_edge_flags_rank, pl.u_edges, 3, grid, h->stream, ep, n_items);
+            else TAIL_LAUNCH2(k_edge_flags_rank, pl.u_edges, 0, grid, h->stream, ep, n_items);
+            TAIL_LAUNCH(k_edges_rank, pl.u_edges, grid, h->stream, ep, n_items);
+        } else {
+            TAIL_LAUNCH(k_edge_flags, pl.u_edges, grid, h->stream, ep, n_items);  // + per-256 counts
+            TAIL_LAUNCH(k_edges, pl.u_edges, grid, h->stream, ep, n_items);
+        }
         MXG_HIP(h, hipGetLastError());
         return MXG_OK;
     }
@@ -2025,8 +2233,8 @@ static int build_graph_impl(mxg_handle *h, const GraphCall &c, bool global_table
     }
     if (c.mode == GRAPH_DG_VERTICES) return s.hand_back_vertices();
     if (pl.nvs > 0) {
-        if (c.mode == GRAPH_FULL) s.adjacency_own();
-        else s.adjacency_of_owner();
+        if (c.mode != GRAPH_FULL) s.adjacency_of_owner();
+        else if (!pl.graph_rank) s.adjacency_own();  // (the rank route needs no table)
         if ((rc = s.mark(h->ev_g[1])) != MXG_OK) return rc;
         if ((rc = s.edges()) != MXG_OK) return rc;
     }

@@ -169,6 +169,7 @@ struct JoinRequest {
     bool no_rec12 = false;         // MXG_PJ_REC12=0: 16-byte records everywhere
     bool no_pipe = false;          // MXG_PJ_PIPE=0: k_pj_join behind two levels too (it reads 16-byte records only)
     bool no_prefill0 = false;      // MXG_PJ_PREFILL0=0: assembly 0 keeps PJ_PREFILL_UNIQUE whatever was learnt
+    bool no_graph_rank = false;    // MXG_GRAPH_RANK=0: the adjacency table and its edge passes where the rank route would run
     uint32_t graph_u = 0;          // MXG_GRAPH_U: 1, 2 or 4 forces the width of the tail's ordered passes (anything else: by size)
     uint32_t pj_tiles = 0;         // MXG_PJ_TILES: 1 or 2 forces level 1's tiles per thread block on the 12-byte route (anything else: by size)
 };
@@ -197,10 +198,14 @@ struct JoinShape {
     // 256-blocks per thread block of the ordered passes (graph_tail_u): k_flags_pj and k_vertices_pj over nb, the adjacency and
     // edge passes over e_blocks
     uint32_t u_flags = 1, u_vertices = 1, u_edges = 1;
+    // the edge passes work from rank arrays, no adjacency table (graph_rank.h): the whole stage behind an LDS join.  The global
+    // table's route and both distributed modes (adjacency arrives as messages) keep k_adjacency / the table.
+    bool graph_rank = false;
     uint32_t pj_tiles_forced = 0;  // level 1's tiles per thread block as forced (0: pj1_tiles decides per launch)
 };
 
-// The tail's ordered passes (k_flags_pj, k_vertices_pj over nb 256-blocks; k_adjacency, k_edge_flags, k_edges over e_blocks) give
+// The tail's ordered passes (k_flags_pj, k_vertices_pj over nb 256-blocks; k_adjacency, k_edge_flags, k_edges or, on the rank route,
+// k_edge_flags_rank, k_edges_rank over e_blocks) give
 // every thread block U consecutive 256-blocks whose loads are all requested before the first is used: a pass of one 256-block per
 // thread block keeps 8 KB of loads in flight per CU, where an HBM round trip wants tens of KB ("The tail's
 // ordered passes").  Wider blocks are fewer blocks: the pass must still fill the chip's 256 CUs x 8 resident thread blocks several
@@ -336,6 +341,7 @@ inline JoinShapeError join_shape(const JoinRequest &rq, const JoinLearnt &learnt
     // (by size the vertex pass stops at GRAPH_TAIL_U_VERTICES; MXG_GRAPH_U=4 still runs it at 4)
     pl.u_vertices = graph_tail_u(0, rq.graph_u) == rq.graph_u ? rq.graph_u : std::min(pl.u_flags, GRAPH_TAIL_U_VERTICES);
     pl.u_edges = graph_tail_u(pl.e_blocks, rq.graph_u);
+    pl.graph_rank = rq.mode == GRAPH_FULL && pl.pj && !rq.no_graph_rank;
     pl.pj_tiles_forced = rq.pj_tiles == 1 || rq.pj_tiles == 2 ? rq.pj_tiles : 0u;
     return JS_OK;
 }
