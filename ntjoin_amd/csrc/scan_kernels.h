@@ -63,7 +63,8 @@ __device__ __forceinline__ uint32_t block_exclusive(uint32_t c, uint32_t *sh)
 }
 __device__ __forceinline__ uint32_t block_exclusive_256(uint32_t c, uint32_t *sh) { return block_exclusive<4>(c, sh); }
 
-// exclusive scan of bsum[0..n) in place by ONE 256-thread block (16 elements per thread per pass); total -> *total
+// exclusive scan of bsum[0..n) in place by ONE 256-thread block (16 elements per thread per pass), mod 2^32; *total = the sum of the
+// passes' sums, each pass's (4096 entries) taken mod 2^32 (see launch_scan_u32)
 static __global__ __launch_bounds__(256) void k_scan_sums(uint32_t *__restrict__ bsum, uint32_t n, uint64_t *__restrict__ total)
 {
     __shared__ uint32_t sh[256];
@@ -126,7 +127,14 @@ static __global__ __launch_bounds__(256) void k_tile_excl_u32(const uint32_t *__
     }
 }
 
-// out[0 .. n) = exclusive prefix sums of in[0 .. n), *total = their sum; bsum: (n + TILE - 1) / TILE words of scratch
+// out[0 .. n) = exclusive prefix sums of in[0 .. n) mod 2^32; bsum: (n + TILE - 1) / TILE words of scratch; n >= 1.
+// *total: the tile sums and a pass's sh[255] in k_scan_sums are 32-bit words, only the carry between its passes is 64-bit.  So *total
+// = the sum, over the aligned runs of 4096 * TILE = 4 194 304 consecutive inputs, of (the run's sum mod 2^32): the inputs' sum as long as
+// every such run sums below 2^32 (so whenever the whole sum does; the total itself may pass 2^32), and something else otherwise.  Every
+// caller stays inside: compose and synteny take a 64-bit sum of their counts first and refuse 2^31; adjust, paths, assess, identity,
+// the sort and the sketch's dense route sum flags or counts of fewer than 2^32 items; the BGZF writer's member sizes sum below
+// its 2^32-byte window; ingest (k_scan_sums alone) counts at most 2^24 header lines per pass.
+// (tests/test_gpu_primitives.py pins both sides.)
 static inline void launch_scan_u32(hipStream_t stream, const uint32_t *in, uint32_t n, uint32_t *bsum, uint32_t *out, uint64_t *total)
 {
     const uint32_t tiles = (n + TILE - 1) / TILE;

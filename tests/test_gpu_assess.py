@@ -89,7 +89,8 @@ def test_equal_subject_keys():
     """the query's one chain seen through 1300 table records that are prefixes of different lengths of it: every chain starts at the
     same subject place and ends elsewhere, so all sort keys are equal and the union is the longest one.  This is no test of the
     sort's stability: the union is the same in whatever order chains of one whole key come out, and nothing reads that order today.
-    What pins the stability of the single passes is every result that takes more than one pass (the other tests here)"""
+    What pins the stability of the single passes here is every result that takes more than one pass (the other tests of this file);
+    the direct test of the sort's stability is tests/test_gpu_primitives.py::test_sort (values = indices against numpy's stable argsort)"""
     case = AC.row_case(40, "chain")
     ln = case["lengths"][1][0]
     ends = [min(ln, 250 + 200 * (r * 7 % 39)) for r in range(1300)]
