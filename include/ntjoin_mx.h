@@ -931,6 +931,75 @@ int mxg_synteny_identity(mxg_handle *h, const mxg_identity_params *params, mxg_i
 #define MXG_PAF_IDENTITY 0x1u
 int mxg_write_synteny_paf_ex(mxg_handle *h, const char *const *query_names, const char *path, int append, uint32_t flags);
 
+/* ---- next row (f15): features of the source records lifted onto the records a piece table spells ---------------
+   A user's gene models, repeat tracks and variant sites lie on the contigs they began with; the scaffold file's records are
+   `ntJoin7` and `ctgA:0-5000`, cut, reverse-complemented, trimmed and, over several rounds, renamed twice.  The reference leaves an
+   AGP and the liftover to the user.  The piece table (row f11; mxg_scaffold_pieces, mxg_compose_pieces) is the answer read the
+   other way round: from the SOURCE records -- those the table's FWD / REV pieces name -- to the records it spells.
+   A FEATURE is (record r, start a, end b), 0-based and half-open, over the source records.  Its PARTS come from the sequence
+   pieces p of the table with p.record == r, p.start < b and p.end > a, ordered by (p.start, index of p in the table).  A GAP piece
+   never matches; a base in two pieces is lifted twice; a base in no piece (a trimmed overlap, stripped Ns, a dropped interval) is
+   lost.  For each such piece, with lo = max(a, p.start), hi = min(b, p.end), R the table record of p and off the bases of R in
+   front of p, the part is (R, s_start, s_end, src_start = lo, reverse):
+     FWD  [off + lo - p.start, off + hi - p.start), reverse = 0        REV  [off + p.end - hi, off + p.end - lo), reverse = 1
+   With lifted = the sum of hi - lo over the parts, the feature's STATUS is the first that holds of
+     MXG_LIFT_INVALID  r >= n_source, a >= b or b > source_length[r]     MXG_LIFT_UNKNOWN  (BED only) the name is no source record
+     MXG_LIFT_LOST     no part                                           MXG_LIFT_WHOLE    one part and lifted == b - a
+     MXG_LIFT_PARTIAL  lifted < b - a                                    MXG_LIFT_SPLIT    anything else
+   INVALID and UNKNOWN give no parts.  Parts are never joined (composition never joins sequence pieces either).
+
+   mxg_lift_prepare checks the table as mxg_compose_pieces does (valid; every sequence piece inside the source record it names,
+   source_length[n_source] giving their lengths; the same messages, the table named "table") and builds the table's index on the
+   device: the sequence pieces compacted, sorted by (record << 32) | start with a stable radix sort over exactly the key bits
+   n_source needs, and the running maximum of (record << 32) | end over that order.  The handle keeps the index until the next
+   mxg_lift_prepare (a failed one leaves none) or mxg_destroy; sketches, graph, paths and kept text stay as they are.
+   n_records == 0 is valid.  MXG_ELIMIT: as mxg_compose_pieces, and 2^31 source records or more.
+
+   mxg_lift_intervals lifts n features, one thread each: two bisections bound the candidate pieces, those that end behind a are
+   counted, the counts' 64-bit sum is taken before anything is scanned in 32 bits (2^31 parts or more: MXG_ELIMIT, nothing is
+   emitted), then the parts are emitted.  The view's arrays are host copies owned by the handle, valid until its next lift call:
+   feature i's parts are part_first[i] .. part_first[i + 1].  MXG_LIFT_WHOLE_ONLY: a feature that is not WHOLE keeps its status
+   and gives no parts.  MXG_EINVAL: no prepared index, a null argument, an unknown flag.  n == 0 is valid.
+
+   mxg_lift_bed lifts the features of a BED file.  Lines end in '\n' (a '\r' in front of it is dropped; the last line may lack
+   its '\n'); empty lines and lines that begin with '#', "track" or "browser" are skipped.  Fields are separated by tabs; fewer
+   than three, or a column 2 or 3 that is not 1 to 10 decimal digits of a value <= 2^32 - 1, make the feature INVALID.  Column 1
+   is matched exactly against source_names[n_source] (the first record of a name wins; no match: UNKNOWN).  lifted_path gets one
+   line per part, in input order, then part order:
+       scaffold_names[R] \t s_start \t s_end [\t the input line from column 4 on, byte for byte] \n
+   but that a column 6 that is exactly "+" or "-" is flipped on a reverse part.  The text is formatted on the device and leaves
+   window by window.  unlifted_path (may be NULL) gets, for every feature that is not WHOLE, in input order, a line "#<reason>" and
+   the original line: "Split in new", "Partially deleted in new", "Deleted in new" (UCSC liftOver's wording), "Invalid", "Unknown
+   record".  The file is worked through in batches of whole lines of at most MXG_LIFT_BATCH bytes (a longer line is a batch of
+   its own); neither file depends on the batch size or on the window size MXG_LIFT_WIN.  A failing call removes the files it
+   created.  MXG_EIO: a file that cannot be read or written. */
+#define MXG_LIFT_WHOLE 0u
+#define MXG_LIFT_SPLIT 1u
+#define MXG_LIFT_PARTIAL 2u
+#define MXG_LIFT_LOST 3u
+#define MXG_LIFT_INVALID 4u
+#define MXG_LIFT_UNKNOWN 5u
+#define MXG_LIFT_WHOLE_ONLY 0x1u
+typedef struct mxg_lift_view {
+    uint64_t n_features, n_parts;
+    const uint64_t *part_first; /* n_features + 1 */
+    const uint8_t *status;      /* n_features */
+    const uint32_t *s_record, *s_start, *s_end, *src_start; /* n_parts */
+    const uint8_t *reverse;                                 /* n_parts */
+} mxg_lift_view;
+typedef struct mxg_lift_stats {
+    uint64_t lines, skipped, features;
+    uint64_t status[6]; /* features per MXG_LIFT_* */
+    uint64_t parts, lifted_bytes, unlifted_bytes;
+} mxg_lift_stats;
+int mxg_lift_prepare(mxg_handle *h, const mxg_seq_piece *pieces, const uint64_t *first /* n_records + 1 */, uint64_t n_records,
+                     const uint32_t *source_length /* n_source */, uint64_t n_source);
+int mxg_lift_intervals(mxg_handle *h, const uint32_t *record, const uint32_t *start, const uint32_t *end, uint64_t n, uint32_t flags,
+                       mxg_lift_view *out);
+int mxg_lift_bed(mxg_handle *h, const char *bed_path, const char *const *source_names /* n_source */,
+                 const char *const *scaffold_names /* n_records */, const char *lifted_path, const char *unlifted_path /* may be NULL */,
+                 uint32_t flags, mxg_lift_stats *stats /* may be NULL */);
+
 /* ---- graph stage distributed over ranks by hash range (one process per GPU) --------------------------
    No counterpart in the reference (it is one process).  Uniqueness and intersection need every occurrence of a hash in
    one place: every minimizer travels to the rank that owns its hash, the owner runs the ordinary graph kernels on what it

@@ -24,6 +24,10 @@ and the breakpoints by kind, each blamed on a join the scaffolder made or on a c
 --identity (--identity_max_seg): also <p>.identity.tsv -- the target and the scaffolds against every reference: the edit distances of
 the stretches between neighbouring minimizers of the blocks of --synteny_*, summed, and edits per 100 kbp; with --synteny the PAF lines
 carry al:i, NM:i and dv:f; computed on the GPU.  A reference loaded from its TSV has no text in the handle and is left out.
+--lift a.bed [b.bed ...] (--lift_whole_only): also <p>.<a>.lifted.bed and <p>.<a>.unlifted.bed per file -- the BED features of the
+target's records in scaffold coordinates, carried through the scaffolds' piece table on the GPU: one line per piece a feature lands
+in, column 4 on unchanged, the strand flipped on a reversed piece; what is not lifted whole also goes to the unlifted file behind its
+reason.  The list of files ends at the next option.  With --rounds_w: once, behind the last round, from the first target's contigs.
 --rounds_w "500 250" (--rounds_keep): further rounds with these window sizes in the same process, the scaffolds of a round being the
 target of the next without a file between them, and <p>.rounds.agp over the contigs of the first target (ntjoin_amd/rounds.py).
 """

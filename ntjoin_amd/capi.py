@@ -24,6 +24,8 @@ IDY_ALIGNED, IDY_SKIP_LEN, IDY_SKIP_SHIFT, IDY_SKIP_N = 0, 1, 2, 3
 IDY_STATUS_MASK, IDY_SATURATED = 0xFF, 0x100
 TEXT_SCAFFOLDS = -1
 PAF_IDENTITY = 0x1
+LIFT_WHOLE, LIFT_SPLIT, LIFT_PARTIAL, LIFT_LOST, LIFT_INVALID, LIFT_UNKNOWN = 0, 1, 2, 3, 4, 5
+LIFT_WHOLE_ONLY = 0x1
 ABI_VERSION = 3
 
 SYMBOLS = [
@@ -43,6 +45,7 @@ SYMBOLS = [
     "mxg_scaffold_text", "mxg_scaffold_pieces", "mxg_scaffold_record_id",
     "mxg_synteny_blocks", "mxg_write_synteny_paf", "mxg_synteny_assess",
     "mxg_identity_segments", "mxg_synteny_identity", "mxg_write_synteny_paf_ex",
+    "mxg_lift_prepare", "mxg_lift_intervals", "mxg_lift_bed",
 ]
 
 
@@ -132,6 +135,19 @@ IDENTITY_BLOCK_FIELDS = ("n_aligned", "n_skip_len", "n_skip_shift", "n_skip_n", 
 
 class IdentityView(C.Structure):  # mxg_identity_view: 152 bytes (api.cpp asserts the same)
     _fields_ = ([(name, C.c_uint64) for name in IDENTITY_SUM_FIELDS] + [("blk_" + name, C.POINTER(C.c_uint64)) for name in IDENTITY_BLOCK_FIELDS])
+
+
+class LiftView(C.Structure):  # mxg_lift_view: 72 bytes (api.cpp asserts the same)
+    _fields_ = ([("n_features", C.c_uint64), ("n_parts", C.c_uint64), ("part_first", C.POINTER(C.c_uint64)), ("status", C.POINTER(C.c_uint8))] +
+                [(name, C.POINTER(C.c_uint32)) for name in ("s_record", "s_start", "s_end", "src_start")] + [("reverse", C.POINTER(C.c_uint8))])
+
+
+LIFT_STATS_FIELDS = ("lines", "skipped", "features", "whole", "split", "partial", "lost", "invalid", "unknown", "parts", "lifted_bytes",
+                     "unlifted_bytes")
+
+
+class LiftStats(C.Structure):  # mxg_lift_stats: 96 bytes (api.cpp asserts the same); status[6] spelled out
+    _fields_ = [(name, C.c_uint64) for name in LIFT_STATS_FIELDS]
 
 
 class AssessParams(C.Structure):  # mxg_assess_params: 16 bytes (api.cpp asserts the same)
@@ -300,6 +316,9 @@ def load():
     L.mxg_identity_segments.argtypes = [vp, i32, i32, vp, u64, C.c_uint32, vp, vp]
     L.mxg_synteny_identity.argtypes = [vp, C.POINTER(IdentityParams), C.POINTER(IdentityView)]
     L.mxg_write_synteny_paf_ex.argtypes = [vp, C.POINTER(cp), C.c_char_p, i32, C.c_uint32]
+    L.mxg_lift_prepare.argtypes = [vp, vp, vp, u64, vp, u64]
+    L.mxg_lift_intervals.argtypes = [vp, vp, vp, vp, u64, C.c_uint32, C.POINTER(LiftView)]
+    L.mxg_lift_bed.argtypes = [vp, C.c_char_p, C.POINTER(cp), C.POINTER(cp), C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(LiftStats)]
     L.mxg_bgzf_write.argtypes = [vp, vp, u64, C.c_char_p]
     L.mxg_write_fai.argtypes = [vp, i32, C.c_char_p, C.c_char_p]
     L.mxg_set_report_params.argtypes = [vp, u64, u64]

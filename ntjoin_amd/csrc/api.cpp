@@ -1243,7 +1243,71 @@ int mxg_write_synteny_paf(mxg_handle *h, const char *const *query_names, const c
     return mxg_write_synteny_paf_ex(h, query_names, path, append, 0u);
 }
 
-static_assert(sizeof(mxg_assess_params) == 16, "mxg_assess_params: ntjoin_amd/capi.py AssessParams mirrors this layout");
+static_assert(sizeof(mxg_lift_view) == 72, "mxg_lift_view: ntjoin_amd/capi.py LiftView mirrors this layout");
+static_assert(sizeof(mxg_lift_stats) == 96, "mxg_lift_stats: ntjoin_amd/capi.py LiftStats mirrors this layout");
+
+int mxg_lift_prepare(mxg_handle *h, const mxg_seq_piece *pieces, const uint64_t *first, uint64_t n_records, const uint32_t *source_length,
+                     uint64_t n_source)
+{
+    if (!h) return MXG_EINVAL;
+    h->lift.valid = false;
+    if (!first || (n_records && first[n_records] && !pieces) || (n_source && !source_length))
+        return set_err(h, MXG_EINVAL, "mxg_lift_prepare: null argument");
+    try {
+        return lift_prepare(h, pieces, first, n_records, source_length, n_source);
+    } catch (const std::bad_alloc &) {
+        h->lift.valid = false;
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_lift_prepare");
+    }
+}
+
+int mxg_lift_intervals(mxg_handle *h, const uint32_t *record, const uint32_t *start, const uint32_t *end, uint64_t n, uint32_t flags,
+                       mxg_lift_view *out)
+{
+    if (!h) return MXG_EINVAL;
+    if (!out || (n && (!record || !start || !end))) return set_err(h, MXG_EINVAL, "mxg_lift_intervals: null argument");
+    if (flags & ~MXG_LIFT_WHOLE_ONLY) return set_err(h, MXG_EINVAL, "mxg_lift_intervals: unknown flags 0x%x", flags);
+    if (!h->lift.valid) return set_err(h, MXG_EINVAL, "mxg_lift_intervals: the handle holds no index (call mxg_lift_prepare first)");
+    int rc;
+    try {
+        rc = lift_intervals(h, record, start, end, n, flags, true);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_lift_intervals");
+    }
+    if (rc != MXG_OK) return rc;
+    const mxg_handle::Lift &L = h->lift;
+    const size_t np = L.n_parts;
+    const uint32_t *p = L.parts.data();
+    out->n_features = n;
+    out->n_parts = np;
+    out->part_first = L.part_first.data();
+    out->status = L.status.data();
+    out->s_record = p, out->s_start = p + np, out->s_end = p + 2 * np, out->src_start = p + 3 * np;
+    out->reverse = L.reverse.data();
+    return MXG_OK;
+}
+
+int mxg_lift_bed(mxg_handle *h, const char *bed_path, const char *const *source_names, const char *const *scaffold_names, const char *lifted_path,
+                 const char *unlifted_path, uint32_t flags, mxg_lift_stats *stats)
+{
+    if (!h) return MXG_EINVAL;
+    if (!bed_path || !lifted_path) return set_err(h, MXG_EINVAL, "mxg_lift_bed: null argument");
+    if (flags & ~MXG_LIFT_WHOLE_ONLY) return set_err(h, MXG_EINVAL, "mxg_lift_bed: unknown flags 0x%x", flags);
+    if (!h->lift.valid) return set_err(h, MXG_EINVAL, "mxg_lift_bed: the handle holds no index (call mxg_lift_prepare first)");
+    if ((!h->lift.src_len.empty() && !source_names) || (h->lift.n_records && !scaffold_names))
+        return set_err(h, MXG_EINVAL, "mxg_lift_bed: null argument");
+    for (size_t r = 0; r < h->lift.src_len.size(); ++r)
+        if (!source_names[r]) return set_err(h, MXG_EINVAL, "mxg_lift_bed: source_names[%zu] is null", r);
+    for (uint64_t r = 0; r < h->lift.n_records; ++r)
+        if (!scaffold_names[r]) return set_err(h, MXG_EINVAL, "mxg_lift_bed: scaffold_names[%llu] is null", (unsigned long long)r);
+    try {
+        return lift_bed(h, bed_path, source_names, scaffold_names, lifted_path, unlifted_path, flags, stats);
+    } catch (const std::bad_alloc &) {
+        return set_err(h, MXG_ENOMEM, "out of host memory in mxg_lift_bed");
+    }
+}
+
+static_assert(sizeof(mxg_assess_params) == 16,"mxg_assess_params: ntjoin_amd/capi.py AssessParams mirrors this layout");
 static_assert(sizeof(mxg_assess_view) == 376, "mxg_assess_view: ntjoin_amd/capi.py AssessView mirrors this layout");
 
 int mxg_synteny_assess(mxg_handle *h, const mxg_assess_params *params, mxg_assess_view *out)

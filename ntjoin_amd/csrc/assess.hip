@@ -11,7 +11,7 @@
 //                  in LDS, then one atomic each
 //   scan, k_as_bp_emit   the breakpoints, in order
 //   sort           chains by (s_record, s_start)
-//   k_as_cover_words, k_as_max_tile, k_as_max_tiles, k_as_cover   the running maximum of (s_record, s_end) in front of every chain
+//   k_as_cover_words, k_pt_max_tile, k_pt_max_tiles, k_as_cover   the running maximum of (s_record, s_end) in front of every chain
 //                  -- a plain 64-bit max scan, see assess.h -- gives what the chain adds to the union; their sum
 //   k_as_span_keys / k_as_len_keys, sort, k_as_lens, 64-bit scan, k_as_nx   lengths descending, their running sums, and per x one
 //                  lower bound: once over the chains' query spans (na, nga), once over the query's record lengths (ng)
@@ -138,50 +138,7 @@ __global__ __launch_bounds__(256) void k_as_cover_words(const uint64_t *__restri
     cw[j] = c < n_ch ? as_cover_word((uint32_t)(key[j] >> 32), s_end[c]) : 0;  // (c < n_ch: the payloads are a permutation)
 }
 
-// inside a block of 256: the maximum of the values of the threads in front of this one (0 for thread 0); *total = the block's
-__device__ __forceinline__ uint64_t as_block_exclusive_max(uint64_t c, uint64_t *sh, uint64_t *total)
-{
-    const uint32_t t = threadIdx.x;
-    sh[t] = c;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {
-        const uint64_t v = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        if (v > sh[t]) sh[t] = v;
-        __syncthreads();
-    }
-    const uint64_t ex = t ? sh[t - 1] : 0;
-    *total = sh[255];
-    __syncthreads();  // (sh is free for the next call)
-    return ex;
-}
-
-__global__ __launch_bounds__(256) void k_as_max_tile(const uint64_t *__restrict__ cw, uint32_t n, uint64_t *__restrict__ tmax)
-{
-    __shared__ uint64_t sh[256];
-    const uint64_t base = (uint64_t)blockIdx.x * PT_TILE + threadIdx.x * 4u;
-    uint64_t c = 0, total;
-    for (uint32_t u = 0; u < 4; ++u)
-        if (base + u < n && cw[base + u] > c) c = cw[base + u];
-    (void)as_block_exclusive_max(c, sh, &total);
-    if (threadIdx.x == 0) tmax[blockIdx.x] = total;
-}
-
-// tmax[0 .. n_tiles) -> the maximum of the tiles in front of each, in place, by ONE block
-__global__ __launch_bounds__(256) void k_as_max_tiles(uint64_t *__restrict__ tmax, uint32_t n_tiles)
-{
-    __shared__ uint64_t sh[256];
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < n_tiles; base += 256) {
-        const uint64_t i = base + threadIdx.x;
-        const uint64_t v = i < n_tiles ? tmax[i] : 0;
-        uint64_t total;
-        const uint64_t ex = as_block_exclusive_max(v, sh, &total);
-        if (i < n_tiles) tmax[i] = ex > carry ? ex : carry;
-        if (total > carry) carry = total;
-    }
-}
-
+// (the running maximum itself: pt_block_exclusive_max, k_pt_max_tile, k_pt_max_tiles of scan64_kernels.h)
 __global__ __launch_bounds__(256) void k_as_cover(const uint64_t *__restrict__ key, const uint64_t *__restrict__ cw, uint32_t n,
                                                   const uint64_t *__restrict__ tmax, unsigned long long *__restrict__ sum)
 {
@@ -192,7 +149,7 @@ __global__ __launch_bounds__(256) void k_as_cover(const uint64_t *__restrict__ k
         v[u] = base + u < n ? cw[base + u] : 0;
         if (v[u] > c) c = v[u];
     }
-    uint64_t run = as_block_exclusive_max(c, sh, &total);
+    uint64_t run = pt_block_exclusive_max(c, sh, &total);
     if (tmax[blockIdx.x] > run) run = tmax[blockIdx.x];
     uint64_t add = 0;
     for (uint32_t u = 0; u < 4; ++u) {
@@ -367,8 +324,8 @@ int synteny_assess(mxg_handle *h, const mxg_assess_params &p)
         const uint32_t max_tiles = (n_ch + PT_TILE - 1) / PT_TILE;
         uint64_t *d_cw = B[AB_CW].as<uint64_t>(), *d_tmax = B[AB_TMAX].as<uint64_t>();
         hipLaunchKernelGGL(k_as_cover_words, grid(n_ch), b, 0, st, ks, vs, d_chain + (size_t)8 * n_ch, n_ch, d_cw);
-        hipLaunchKernelGGL(k_as_max_tile, dim3(max_tiles), b, 0, st, d_cw, n_ch, d_tmax);
-        hipLaunchKernelGGL(k_as_max_tiles, dim3(1), b, 0, st, d_tmax, max_tiles);
+        hipLaunchKernelGGL(k_pt_max_tile, dim3(max_tiles), b, 0, st, d_cw, n_ch, d_tmax);
+        hipLaunchKernelGGL(k_pt_max_tiles, dim3(1), b, 0, st, d_tmax, max_tiles);
         hipLaunchKernelGGL(k_as_cover, dim3(max_tiles), b, 0, st, ks, d_cw, n_ch, d_tmax, d_sum);
         MXG_HIP(h, hipGetLastError());
         // 5: na, nga over the chains' query spans

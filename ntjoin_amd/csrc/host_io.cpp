@@ -15,9 +15,11 @@
 #include <cmath>
 #include <cstdlib>
 #include <functional>
+#include <string_view>
 #include <thread>
 #include <unordered_map>
 
+#include "lift.h"
 #include "mxg_internal.h"
 #include "nthash_tab.h"
 
@@ -1308,6 +1310,94 @@ int load_sketch_bin(mxg_handle *h, Assembly *a, const char *path, std::vector<ui
         at = e + 1;
     }
     return MXG_OK;
+}
+
+// ---- BED input of mxg_lift_bed (the line rules are lift.h's) ---------------------------------------------------------------------
+bool BedFile::open(const char *path)
+{
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return false;
+    struct stat sb;
+    if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        ::close(fd);
+        return false;
+    }
+    size = (uint64_t)sb.st_size;
+    if (size) {
+        map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (map == MAP_FAILED) map = nullptr;
+        text = static_cast<const char *>(map);
+    }
+    ::close(fd);
+    return size == 0 || map != nullptr;
+}
+BedFile::~BedFile()
+{
+    if (map) (void)munmap(map, size);
+}
+
+struct BedNames {
+    std::unordered_map<std::string_view, uint32_t> first;  // (the views look into the caller's strings)
+};
+BedNames *bed_names_make(const char *const *names, uint64_t n)
+{
+    BedNames *b = new BedNames;
+    b->first.reserve(n * 2);
+    for (uint64_t r = 0; r < n; ++r) b->first.emplace(std::string_view(names[r]), (uint32_t)r);  // (emplace keeps the first of a name)
+    return b;
+}
+void bed_names_free(BedNames *b) { delete b; }
+
+// whole lines from `from` on: as many as fit max_bytes, at least one
+bool bed_next_batch(const BedFile &f, uint64_t from, uint64_t max_bytes, const BedNames *names, BedBatch &out)
+{
+    if (from >= f.size) return false;
+    const char *t = f.text;
+    uint64_t hi = std::min(f.size, from + max_bytes);
+    if (hi < f.size) {
+        while (hi > from && t[hi - 1] != '\n') --hi;
+        if (hi == from) {  // (a line longer than a batch is a batch of its own)
+            const void *nl = memchr(t + from, '\n', f.size - from);
+            hi = nl ? (uint64_t)(static_cast<const char *>(nl) - t) + 1 : f.size;
+        }
+    }
+    out.lo = from, out.hi = hi;
+    out.lines = out.skipped = 0;
+    for (auto *v : {&out.line_off, &out.line_len}) v->clear();
+    for (auto *v : {&out.record, &out.a, &out.b, &out.rest_off, &out.rest_len, &out.strand}) v->clear();
+    out.unknown.clear();
+    for (uint64_t at = from; at < hi;) {
+        const void *nl = memchr(t + at, '\n', hi - at);
+        const uint64_t end = nl ? (uint64_t)(static_cast<const char *>(nl) - t) : hi;
+        const char *line = t + at;
+        const uint64_t len = end - at;
+        ++out.lines;
+        if (bed_skipped(line, len)) {
+            ++out.skipped;
+        } else {
+            const BedLine bl = bed_parse(line, len);
+            uint32_t rec = LFT_NONE, a = 0, b = 0;
+            bool unknown = false;
+            if (bl.ok) {
+                a = bl.a, b = bl.b;
+                const auto it = names->first.find(std::string_view(line, bl.name_len));
+                if (it != names->first.end()) rec = it->second;
+                else if (a < b) unknown = true;
+            }
+            out.line_off.push_back(at);
+            out.line_len.push_back(bed_line_end(line, len));
+            out.record.push_back(rec);
+            out.a.push_back(a);
+            out.b.push_back(b);
+            out.unknown.push_back(unknown ? 1 : 0);
+            // (offsets into the batch: the caller refuses a batch of 2^32 - 1 bytes or more before it reads them)
+            out.rest_off.push_back(bl.rest_off ? (uint32_t)(at - from + bl.rest_off) : LFT_NONE);
+            out.rest_len.push_back((uint32_t)bl.rest_len);
+            out.strand.push_back(bl.strand_off ? (uint32_t)(at - from + bl.strand_off) : LFT_NONE);
+        }
+        at = nl ? end + 1 : hi;
+    }
+    return true;
 }
 
 }  // namespace mxg

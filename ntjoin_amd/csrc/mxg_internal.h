@@ -326,6 +326,18 @@ struct mxg_handle {
         std::vector<uint32_t> bp_all;   // scratch: the same as they come home, five arrays of n_chains words
     } assess;
     mxg::DevBuf idybuf[24];   // scratch of identity.hip
+    mxg::DevBuf lftbuf[48];   // scratch of lift.hip, and the index of the last mxg_lift_prepare
+    struct Lift {             // the last mxg_lift_prepare, and the last lift call's result (what mxg_lift_view points into)
+        bool valid = false;
+        uint32_t m = 0;                 // sequence pieces in the index
+        int sorted_in = 0;              // which of the sort's two buffers holds the sorted keys
+        uint64_t n_records = 0;         // records of the table
+        std::vector<uint32_t> src_len;  // [n_source]
+        std::vector<uint64_t> part_first;
+        std::vector<uint8_t> status, reverse;
+        std::vector<uint32_t> parts;    // five arrays of n_parts words: s_record, s_start, s_end, src_start, reverse
+        uint64_t n_parts = 0;
+    } lift;
     std::vector<uint32_t> scaf_lead, scaf_tail;  // N/n stripped from either end of every unassigned interval by the last mxg_write_scaffolds
     struct ScafInterval {
         uint32_t rec, lo, hi, lead, tail;
@@ -677,6 +689,36 @@ int identity_segments(mxg_handle *h, int q_text, int s_text, const mxg_identity_
                       uint32_t *out_status);
 // ... and of the segments between the anchors of h->syn's kept blocks (mxg_synteny_identity; fills h->idy)
 int synteny_identity(mxg_handle *h, const mxg_identity_params &p);
+// lift.hip: the index of a piece table (mxg_lift_prepare; fills h->lift), features through it (mxg_lift_intervals) and a BED file's
+// (mxg_lift_bed).  BedBatch (host_io.cpp: bed_next_batch) is a batch of whole lines as the device takes it.
+int lift_prepare(mxg_handle *h, const mxg_seq_piece *pieces, const uint64_t *first, uint64_t n_records, const uint32_t *source_length,
+                 uint64_t n_source);
+int lift_intervals(mxg_handle *h, const uint32_t *record, const uint32_t *start, const uint32_t *end, uint64_t n, uint32_t flags, bool host_parts);
+int lift_bed(mxg_handle *h, const char *bed_path, const char *const *source_names, const char *const *scaffold_names, const char *lifted_path,
+             const char *unlifted_path, uint32_t flags, mxg_lift_stats *stats);
+struct BedFile {  // a BED file mapped for reading (host_io.cpp)
+    const char *text = nullptr;
+    uint64_t size = 0;
+    void *map = nullptr;
+    BedFile() = default;
+    BedFile(const BedFile &) = delete;
+    BedFile &operator=(const BedFile &) = delete;
+    bool open(const char *path);
+    ~BedFile();
+};
+struct BedBatch {
+    uint64_t lo = 0, hi = 0;  // the batch is text[lo, hi)
+    uint64_t lines = 0, skipped = 0;
+    std::vector<uint64_t> line_off, line_len;          // per feature: its line in the file, without the line end
+    std::vector<uint32_t> record, a, b;                // per feature: LFT_NONE for a name that is no record; a = b = 0 when not parsed
+    std::vector<uint32_t> rest_off, rest_len, strand;  // per feature, relative to lo: column 4 on (LFT_NONE: none), column 6 if a strand
+    std::vector<uint8_t> unknown;
+};
+// the names -> the first record of each; the batch that begins at `from` (false: the file is through)
+struct BedNames;
+BedNames *bed_names_make(const char *const *names, uint64_t n);
+void bed_names_free(BedNames *);
+bool bed_next_batch(const BedFile &f, uint64_t from, uint64_t max_bytes, const BedNames *names, BedBatch &out);
 int flush_timers(mxg_handle *h);                // sketch.hip: fold the recorded event pairs into h->tm
 int flags_to_host(mxg_handle *h, Assembly *a);
 

@@ -499,6 +499,61 @@ class MxEngine:
             C.memmove(out.ctypes.data, pp, len(out) * self.SEQ_PIECE.itemsize)
         return out, first
 
+    LIFT_PART = np.dtype([("s_record", "<u4"), ("s_start", "<u4"), ("s_end", "<u4"), ("src_start", "<u4"), ("reverse", "u1")])
+
+    def lift_prepare(self, pieces, first, source_length):
+        """mxg_lift_prepare: the index of a piece table (SEQ_PIECE or rows, and n_records + 1 offsets) over source records of the
+        lengths source_length, built on the device and kept by the handle until the next lift_prepare (include/ntjoin_mx.h)"""
+        pc = np.asarray(pieces)
+        if pc.dtype != self.SEQ_PIECE:
+            rows = np.asarray(pieces, dtype=np.uint32).reshape(-1, 4)
+            pc = np.zeros(len(rows), dtype=self.SEQ_PIECE)
+            for c, name in enumerate(self.SEQ_PIECE.names):
+                pc[name] = rows[:, c]
+        pc = np.ascontiguousarray(pc)
+        pf = np.ascontiguousarray(first, dtype=np.uint64)
+        if pf.ndim != 1 or len(pf) < 1 or int(pf[-1]) != len(pc):
+            raise ValueError("lift_prepare: a table needs n_records + 1 offsets, the last one the number of its pieces")
+        sl = np.ascontiguousarray(source_length, dtype=np.uint32)
+        if sl.ndim != 1:
+            raise ValueError("lift_prepare: source_length needs one entry per source record")
+        self._lift_shape = None
+        self._check(self._lib.mxg_lift_prepare(self._h, pc.ctypes.data, pf.ctypes.data, len(pf) - 1, sl.ctypes.data, len(sl)))
+        self._lift_shape = (len(sl), len(pf) - 1)
+
+    def lift_intervals(self, record, start, end, whole_only=False):
+        """mxg_lift_intervals: the features (record[i], start[i], end[i]) of the source records through the prepared index ->
+        (status: u8 per feature (capi.LIFT_*), part_first: u64[n + 1], parts: array of LIFT_PART); whole_only: a feature that is not
+        WHOLE keeps its status and gives no parts"""
+        r, a, b = (np.ascontiguousarray(x, dtype=np.uint32) for x in (record, start, end))
+        if r.ndim != 1 or r.shape != a.shape or r.shape != b.shape:
+            raise ValueError("lift_intervals: record, start and end need one entry per feature each")
+        v = capi.LiftView()
+        self._check(self._lib.mxg_lift_intervals(self._h, r.ctypes.data, a.ctypes.data, b.ctypes.data, len(r),
+                                                 capi.LIFT_WHOLE_ONLY if whole_only else 0, C.byref(v)))
+        n, n_parts = int(v.n_features), int(v.n_parts)
+        parts = np.zeros(n_parts, dtype=self.LIFT_PART)
+        for name in ("s_record", "s_start", "s_end", "src_start"):
+            parts[name] = _np(getattr(v, name), n_parts, np.uint32)
+        parts["reverse"] = _np(v.reverse, n_parts, np.uint8)
+        return _np(v.status, n, np.uint8), _np(v.part_first, n + 1, np.uint64), parts
+
+    def lift_bed(self, bed, source_names, scaffold_names, lifted, unlifted=None, whole_only=False):
+        """mxg_lift_bed: the features of the BED file `bed`, named by source_names (one per source record of the prepared index),
+        lifted into `lifted` with the records named by scaffold_names (one per record of the table), formatted on the device;
+        `unlifted`: what was not lifted whole, with the reason -> dict of capi.LIFT_STATS_FIELDS"""
+        shape = getattr(self, "_lift_shape", None)
+        if shape is not None and (len(source_names), len(scaffold_names)) != shape:
+            raise ValueError(f"lift_bed: {len(source_names)} source names and {len(scaffold_names)} scaffold names for an index of "
+                             f"{shape[0]} source records and {shape[1]} records")
+        src = (C.c_char_p * max(len(source_names), 1))(*[str(i).encode() for i in source_names])
+        dst = (C.c_char_p * max(len(scaffold_names), 1))(*[str(i).encode() for i in scaffold_names])
+        st = capi.LiftStats()
+        self._check(self._lib.mxg_lift_bed(self._h, os.fsencode(str(bed)), src, dst, os.fsencode(str(lifted)),
+                                           None if unlifted is None else os.fsencode(str(unlifted)), capi.LIFT_WHOLE_ONLY if whole_only else 0,
+                                           C.byref(st)))
+        return {name: int(getattr(st, name)) for name in capi.LIFT_STATS_FIELDS}
+
     SCAFFOLD_NODE = np.dtype([("record", "<u4"), ("start", "<u4"), ("end", "<u4"), ("gap_size", "<u4"), ("start_adjust", "<u4"),
                               ("end_adjust", "<u4"), ("reverse", "u1"), ("pad", "u1", (3,))])
 

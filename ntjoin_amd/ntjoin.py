@@ -27,6 +27,14 @@ COLOURS = ["red", "green", "blue", "purple", "orange", "turquoise", "pink", "yel
 
 MK_Z975 = 1.959963984540054  # scipy.stats.norm.ppf(0.975): original_test's threshold on |z| at alpha = 0.05
 _SQRT1_2 = 0.7071067811865476
+def lift_outputs(prefix, bed):
+    "the two files --lift makes of the BED file `bed`: <prefix>.<basename without a trailing .bed>.lifted.bed and ...unlifted.bed"
+    stem = os.path.basename(str(bed))
+    if stem.endswith(".bed"):
+        stem = stem[:-4]
+    return f"{prefix}.{stem}.lifted.bed", f"{prefix}.{stem}.unlifted.bed"
+
+
 SYNTENY_DEFAULTS = dict(max_gap=100000, min_anchors=3, min_span=0)  # write_synteny's and write_assess's, of the blocks call
 
 
@@ -376,7 +384,7 @@ class Ntjoin:
         at = res["node_first"].tolist()
         return [rows[lo:hi] for lo, hi in zip(at, at[1:])]
 
-    def scaffold(self, lengths=None, keep=False, quiet=False, synteny=None, assess=None, identity=None):
+    def scaffold(self, lengths=None, keep=False, quiet=False, synteny=None, assess=None, identity=None, lift=None):
         """main_scaffolder (:751-786) behind load_minimizers_scaffold in one handle: make_minimizer_graph -> find_paths ->
         format_paths -> adjust_paths -> trim_overlaps (when args.overlap) -> print_scaffolds.  Read from args, with ntJoin's
         defaults where one is missing: n, g, G, m, mkt, no_cut, overlap, overlap_k, overlap_w, overlap_gap, agp, gz, fai, report,
@@ -388,7 +396,9 @@ class Ntjoin:
         write_assess, with the blocks parameters of --synteny_*; assess=False leaves them out likewise); with args.identity
         <prefix>.identity.tsv ("identity": write_identity, args.identity_max_seg; identity=False leaves it out likewise).  keep / quiet:
         print_scaffolds' (a round of ntjoin_amd/rounds.py); a quiet round writes no .mx.dot, no index, no report, no PAF and no
-        assessment either."""
+        assessment either.  With args.lift (BED files over the target's records) every one of them is lifted onto the scaffolds
+        ("lifted", "unlifted": lists of files, lift_outputs' names; args.lift_whole_only); lift=[...] names the files instead, and
+        lift=[] lifts nothing whatever args says (ntjoin_amd/rounds.py lifts once, behind the last round)."""
         opt = lambda name, dflt: dflt if getattr(self.args, name, None) is None else getattr(self.args, name)  # noqa: E731
         if quiet:
             opt = lambda name, dflt, _opt=opt: False if name in ("fai", "report") else _opt(name, dflt)  # noqa: E731
@@ -416,8 +426,10 @@ class Ntjoin:
         idy = None
         if (bool(opt("identity", False)) if identity is None else identity) and not quiet:
             idy = dict(blocks_kw, max_seg=int(opt("identity_max_seg", 10000)))
+        beds = list(opt("lift", None) or []) if lift is None else list(lift)
         files = self.print_scaffolds(paths, cuts, n=int(opt("n", 1)), agp=bool(opt("agp", False)), overlap_gap=int(opt("overlap_gap", 20)),
                                      gz=bool(opt("gz", False)), fai=bool(opt("fai", False)), report=report, keep=keep, quiet=quiet,
+                                     **({"lift": beds, "lift_whole_only": bool(opt("lift_whole_only", False))} if beds and not quiet else {}),
                                      **({"synteny": syn} if syn else {}), **({"assess": asz} if asz else {}), **({"identity": idy} if idy else {}))
         if report:
             files["report"] = self.write_report(report_rows, files)
@@ -587,7 +599,7 @@ class Ntjoin:
                 agp_fh.close()
 
     def print_scaffolds(self, paths, adjust=None, n=1, agp=False, overlap_gap=20, gz=False, fai=False, report=False, keep=False, quiet=False,
-                        synteny=None, assess=None, identity=None):
+                        synteny=None, assess=None, identity=None, lift=None, lift_whole_only=False):
         """print_scaffolds (:580-613) and print_unassigned (:628-658) for paths as format_paths() returns them; adjust = what
         trim_overlaps(paths) returns, or None when the overlap stage is off.  Nodes of orientation '?' and paths left with fewer
         than two nodes are dropped (:585-594), the last kept node's gap is zeroed (check_terminal_node_gap_zero :441-448), and the
@@ -603,7 +615,9 @@ class Ntjoin:
         turns keep on.  assess=dict(merge_gap, max_indel, join_indel, max_gap, min_anchors, min_span) (or True for the defaults): also
         <p>.assess.tsv and <p>.breakpoints.bed ("assess", "breakpoints": write_assess); it turns keep on as well, and with synteny the
         scaffolds' blocks are computed once for both, so the two must then name the same max_gap, min_anchors and min_span (ValueError
-        otherwise, before anything is written).  Returns the file names by kind."""
+        otherwise, before anything is written).  lift=[BED files over the target's records]: every one of them is lifted onto the
+        scaffolds ("lifted", "unlifted": lists of files, lift_outputs' names; lift_bed); it turns keep on as synteny= does.  Returns
+        the file names by kind."""
         if synteny and assess:
             given = [{key: (arg if isinstance(arg, dict) else {}).get(key, default) for key, default in SYNTENY_DEFAULTS.items()}
                      for arg in (synteny, assess)]
@@ -617,7 +631,7 @@ class Ntjoin:
                 raise ValueError(f"print_scaffolds: identity= shares one blocks call with synteny= and assess= and must agree on its parameters: "
                                  f"{given[0]} against {given[1]}")
         self._last_print = dict(paths=paths, adjust=adjust, n=n, agp=agp, overlap_gap=overlap_gap, gz=gz, fai=fai, report=report)
-        if (synteny or assess or identity) and not quiet:
+        if (synteny or assess or identity or lift) and not quiet:
             keep = True
         eng, tgt = self._engine, len(self._order) - 1
         if tgt < 0:
@@ -664,6 +678,9 @@ class Ntjoin:
             res = eng.write_scaffolds(tgt, rows, first, overlap_gap=overlap_gap if adjust is not None else None,
                                       assigned=files["assigned"], unassigned=files["unassigned"], bed=files["bed"], bgzf=bool(gz),
                                       **({"fai": True} if fai else {}), **({"report": True} if report else {}), **({"keep": True} if keep else {}))
+        self._lift_prepared = False
+        if lift and not quiet:
+            files.update(self.lift_beds(lift, whole_only=lift_whole_only))
         if identity and not quiet:   # (one pass over the references for the table, the PAF and the assessment)
             idy = identity if isinstance(identity, dict) else {}
             files.update(self._synteny_files({key: idy.get(key, default) for key, default in SYNTENY_DEFAULTS.items()}, paf=bool(synteny),
@@ -697,6 +714,43 @@ class Ntjoin:
                     raise
         self._write_path_host(files, assembly_fa, kept, lead.tolist(), tail.tolist())
         return self._quiet_files(files) if quiet else files
+
+    def lift_prepare(self, table=None):
+        """The index the lifts below go through (MxEngine.lift_prepare), kept until the next print_scaffolds: of the table and ids of
+        scaffold_pieces() over the target's record ids and lengths, or of table=(pieces, first, ids, source_ids, source_length) --
+        the rounds' composed one (ntjoin_amd/rounds.py)."""
+        eng, tgt = self._engine, len(self._order) - 1
+        if table is None:
+            pieces, first, ids = eng.scaffold_pieces()
+            table = (pieces, first, ids, eng.record_ids(tgt, eng.n_records(tgt)), eng.record_lengths(tgt))
+        pieces, first, ids, source_ids, source_length = table
+        self._lift_prepared = False
+        eng.lift_prepare(pieces, first, source_length)
+        self._lift_names = (list(source_ids), list(ids))
+        self._lift_prepared = True
+
+    def lift_bed(self, bed, lifted, unlifted=None, whole_only=False):
+        """The features of the BED file `bed`, which lie on the target's records, lifted onto the scaffolds the last
+        print_scaffolds(keep=True) left: `lifted` gets one line per part, `unlifted` what was not lifted whole, with the reason
+        (lift_prepare, once per print_scaffolds; MxEngine.lift_bed).  Returns MxEngine.lift_bed's counts."""
+        if not getattr(self, "_lift_prepared", False):
+            self.lift_prepare()
+        source_ids, ids = self._lift_names
+        return self._engine.lift_bed(bed, source_ids, ids, lifted, unlifted, whole_only=whole_only)
+
+    def lift_beds(self, beds, whole_only=False, table=None):
+        "lift_bed for every file of `beds`, under lift_outputs' names (table: lift_prepare's) -> {'lifted': [files], 'unlifted': [files]}"
+        if table is not None:
+            self.lift_prepare(table)
+        files = {"lifted": [], "unlifted": []}
+        for bed in beds:
+            lifted, unlifted = lift_outputs(self.args.p, bed)
+            st = self.lift_bed(bed, lifted, unlifted, whole_only=whole_only)
+            print(f"ntjoin_amd: {bed}: {st['features']} features, {st['whole']} lifted whole, {st['split']} split, {st['partial']} partially "
+                  f"deleted, {st['lost']} deleted, {st['invalid']} invalid, {st['unknown']} on unknown records", file=sys.stderr)
+            files["lifted"].append(lifted)
+            files["unlifted"].append(unlifted)
+        return files
 
     def write_synteny(self, max_gap=100000, min_anchors=3, min_span=0):
         """<prefix>.synteny.paf: the synteny blocks (MxEngine.synteny_blocks) of the scaffolds the last print_scaffolds(keep=True) left

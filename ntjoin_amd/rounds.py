@@ -16,6 +16,8 @@ original target: the rounds' piece tables (mxg_scaffold_pieces) composed on the 
 --synteny: the last round's scaffolds against the references, <p>.round<i>.synteny.paf beside that round's other files.
 --assess: likewise, the last round's target and scaffolds: <p>.round<i>.assess.tsv and <p>.round<i>.breakpoints.bed.
 --identity: likewise: <p>.round<i>.identity.tsv.
+--lift: the BED files lie on the contigs of the first target and are lifted once, behind the last round, through the composed table
+onto the last round's scaffolds: <p>.round<i>.<name>.lifted.bed and <p>.round<i>.<name>.unlifted.bed.
 
     python -m ntjoin_amd.rounds last_out TARGET K W N GZ W2 [W3 ...]   prints T_last.k<k>.w<w_last>.n<n> (for the make front-end)
 """
@@ -83,7 +85,7 @@ def run_rounds(args, fasta, w, weights, rounds_w, keep_files=False):
     k, n, gz = int(args.k), int(args.n), bool(getattr(args, "gz", False))
     refs = [fasta[tsv] for tsv in args.FILES]
     rounds = chain(fasta[args.s], k, w, n, rounds_w, gz)
-    prev, prov, contig_ids, all_files = None, None, None, []
+    prev, prov, contig_ids, contig_len, all_files = None, None, None, None, []
     try:
         for i, (target_fa, wi) in enumerate(rounds, start=1):
             last = i == len(rounds)
@@ -139,7 +141,9 @@ def run_rounds(args, fasta, w, weights, rounds_w, keep_files=False):
                 if i == 1:
                     tgt = len(nj._order) - 1
                     contig_ids = nj._engine.record_ids(tgt, nj._engine.n_records(tgt))
-                files = nj.scaffold(keep=True, quiet=not full, **({} if last else {"synteny": False, "assess": False, "identity": False}))
+                    contig_len = nj._engine.record_lengths(tgt)
+                # (lift=[]: the BED files are about the contigs of round 1, not about this round's target)
+                files = nj.scaffold(keep=True, quiet=not full, lift=[], **({} if last else {"synteny": False, "assess": False, "identity": False}))
                 if full and not last:
                     files["all"] = write_all(files, gz)
                 pieces, first, ids = nj._engine.scaffold_pieces()
@@ -154,6 +158,9 @@ def run_rounds(args, fasta, w, weights, rounds_w, keep_files=False):
         agp = args.p + ".rounds.agp"
         write_rounds_agp(agp, prov[0], prov[1], ids, contig_ids)
         all_files[-1]["rounds_agp"] = agp
+        if getattr(args, "lift", None):
+            all_files[-1].update(prev.lift_beds(args.lift, whole_only=bool(getattr(args, "lift_whole_only", False)),
+                                                table=(prov[0], prov[1], ids, contig_ids, contig_len)))
     finally:
         if prev is not None:
             prev.close()

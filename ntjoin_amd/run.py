@@ -75,6 +75,12 @@ def parse_arguments(argv=None):
     parser.add_argument("--identity", action="store_true", default=False)
     parser.add_argument("--identity_max_seg", type=int, default=10000,
                         help="stretches longer than this on either assembly are counted, not aligned, at least 1 [10000]")
+    # ours: BED files over the target's records lifted onto the scaffolds, <prefix>.<name>.lifted.bed and <prefix>.<name>.unlifted.bed
+    # for <name>.bed: cuts, reverse complements, trimmed overlaps and the rounds' renaming followed through the scaffolds' piece table
+    # on the GPU (ntjoin_amd.assemble).  Another option, or the end of the command line, ends the list of files
+    parser.add_argument("--lift", nargs="+", default=[], metavar="BED", help="BED files of features on the target's records to lift onto the scaffolds")
+    parser.add_argument("--lift_whole_only", action="store_true", default=False,
+                        help="lift only the features that land whole in one piece; the others go to the unlifted file alone")
     parser.add_argument("-v", "--version", action="version", version="ntjoin_amd hot path (ntJoin v1.1.5 compatible)")
     return parser.parse_args(argv)
 
