@@ -1,6 +1,7 @@
 """Tables, features and BED text for the tests of mxg_lift_prepare / mxg_lift_intervals / mxg_lift_bed (tests/test_lift_cpu.py,
 tests/test_gpu_lift.py): the hand-made cases, the seeded fuzz, the refusals, and the property every lift must keep: a part spells in
 the scaffold what its stretch of the feature spells in the source record, reverse-complemented when `reverse`."""
+import functools
 import random
 
 from tests import _compose_cases as CC, _compose_restatement as C, _lift_restatement as R
@@ -172,6 +173,68 @@ def sized_features(n, n_source, seed=0):
         a = rng.randrange(64)
         out.append((r, a, rng.randint(a, 65)))   # (a == b and b == 65 are INVALID)
     return out
+
+
+CARRY_CASES = [(1023, 4400), (1024, 4400), (262143, 262444), (262144, 262444)]   # (long_at, n_short)
+CARRY_SECOND = 1000   # the second source record's short pieces
+
+
+@functools.lru_cache(maxsize=None)
+def carry_case(long_at, n_short):
+    """-> (table, source_length, features, statuses): a table whose lookups live on the carries of the index's running maximum.
+    Source record 0 is cut into n_short pieces [3 j, 3 j + 2) -- every third base is in no piece -- and ONE long piece from the gap
+    base in front of 3 long_at to the record's end: it starts behind short piece long_at - 1 and in front of short piece long_at, so it
+    takes place long_at of the sorted index, and whatever lies behind it there finds it only through rmax.  Behind it source record 1,
+    cut the same way into CARRY_SECOND short pieces, with its long piece on the last place of a tile of the index: the running maximum
+    starts over at the record's border, and behind that tile's border it is the carry again.  The pieces are dealt in shuffled order to
+    table records of 1 to 40 pieces, so the table's order is not the index's"""
+    rng = random.Random(9000 + long_at)
+    assert 10 < long_at < n_short - 10
+    n1 = CARRY_SECOND
+    at1 = 1023 - (n_short + 1) % 1024   # (record 1's piece i has place n_short + 1 + i)
+    assert 20 < at1 < n1 - 20
+    source_length = [3 * n_short + 10, 3 * n1 + 10]
+    pieces = []
+    for r, n, at in ((0, n_short, long_at), (1, n1, at1)):
+        pieces += [(r, 3 * j, 3 * j + 2, rng.choice((F, V))) for j in range(n)]
+        pieces.append((r, 3 * at - 1, source_length[r], rng.choice((F, V))))
+    rng.shuffle(pieces)
+    table, at = [], 0
+    while at < len(pieces):
+        n = rng.randint(1, 40)
+        table.append(pieces[at:at + n])
+        at += n
+    L0, L1 = source_length
+    named = [
+        ((0, L0 - 5, L0 - 1), R.WHOLE),                                     # in the long piece's far end, behind every short piece
+        ((0, 3 * n_short - 1, 3 * n_short), R.WHOLE),                       # the last gap base: the long piece alone
+        ((0, 3 * long_at + 5, 3 * long_at + 6), R.WHOLE),                   # a gap base just behind the long piece's place
+        ((0, 3 * (long_at + 5), 3 * (long_at + 5) + 3), R.SPLIT),           # a short piece and its gap base there: both pieces
+        ((0, 3 * (long_at - 10), 3 * (long_at - 10) + 2), R.WHOLE),         # in front of it: the short piece alone
+        ((0, 3 * (long_at - 10) + 2, 3 * (long_at - 10) + 3), R.LOST),      # a gap base in front of it
+        ((1, L1 - 5, L1 - 1), R.WHOLE),                                     # the second record: in its long piece's far end,
+        ((1, 3 * (n1 - 1) + 2, 3 * n1), R.WHOLE),                           # on its last gap base,
+        ((1, 15, 17), R.WHOLE),                                             # in front of its long piece
+        ((1, 17, 18), R.LOST),                                              # and on a gap base there
+    ]
+    return table, source_length, [f for f, _ in named], [s for _, s in named]
+
+
+@functools.lru_cache(maxsize=None)
+def carry_expected(long_at, n_short):
+    "the restatement's answer for carry_case's features, worked out once for all tests of a process (nobody changes it)"
+    table, source_length, features, _ = carry_case(long_at, n_short)
+    return R.lift(table, source_length, features)
+
+
+def index_words(table):
+    """the sorted index of a table as lift.h states it, in numpy: -> (key, word, start, end) with key[i] = (record << 32) | start in
+    stable order and word[i] = (record << 32) | end, the words whose running maximum is rmax"""
+    import numpy as np
+    rows = np.array([p for rec in table for p in rec if p[3] != G], dtype=np.uint64).reshape(-1, 4)
+    key = rows[:, 0] << np.uint64(32) | rows[:, 1]
+    order = np.argsort(key, kind="stable")
+    return key[order], (rows[:, 0] << np.uint64(32) | rows[:, 2])[order], rows[order, 1].astype(np.int64), rows[order, 2].astype(np.int64)
 
 
 def table_text(table, source_length):

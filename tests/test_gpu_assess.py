@@ -1,13 +1,16 @@
 """GPU tests of mxg_synteny_assess (include/ntjoin_mx.h, row f13) against the sequential restatement of the contract
 (tests/_assess_restatement.py) applied to the blocks mxg_synteny_blocks returned: the hand-made cases of tests/_assess_cases.py, block
 counts around the wave, the 256-thread block, the 1024-element tile of the scans and of the sort and past 2^16, one chain over all
-blocks and a chain per block, subject keys sorted, reversed, equal, interleaved and under one long interval, piece tables, each
-parameter at 0, three assemblies, every refusal with the handle usable afterwards, and the PAF text after an assess call."""
+blocks and a chain per block, subject keys sorted, reversed, equal, interleaved and under one long interval -- at the head of the
+order, on the last place of a tile and on the last place of the first round of the running maximum --, piece tables, each parameter
+at 0, three assemblies, every refusal with the handle usable afterwards, and the PAF text after an assess call."""
 import ctypes as C
+import time
 
+import numpy as np
 import pytest
 
-from tests import _assess_cases as AC, _assess_restatement as A, _synteny_cases as cases, _synteny_restatement as R
+from tests import _assess_cases as AC, _assess_restatement as A, _cover_scale as CS, _synteny_cases as cases, _synteny_restatement as R
 from tests.test_gpu_synteny import as_tuples, device, load
 
 pytestmark = pytest.mark.gpu
@@ -107,6 +110,36 @@ def test_one_long_interval_covers_every_later_one():
         blocks, want = check(eng, case)
     assert blocks["n_blocks"] == 2960 and want["n_chains"] == 2901
     assert want["covered_subject"] == want["chains"]["s_end"][0] - want["chains"]["s_start"][0] == 60 * 200 - 118
+
+
+@pytest.mark.parametrize("m0,m1", CS.CARRY_CASES)
+def test_chains_under_a_long_chain_behind_a_carry(m0, m1):
+    """tests/_cover_scale.py: two subject records, on each one long chain over m single ones.  Sorted by subject place the second
+    record's long chain stands on place m0 + 1 -- the last of tile 0, and the last of the first round of k_pt_max_tiles (256 tiles) --
+    and its singles behind the border: the largest subject end in front of them is the carry, and it must be their own record's chain.
+    tests/test_maxscan_model_cpu.py shows that covered_subject differs when that carry is dropped or comes a tile early"""
+    from ntjoin_amd.engine import MxEngine
+    t0 = time.time()
+    case = CS.cover_scale_case(m0, m1)
+    with MxEngine(k=case["k"], w=10) as eng:
+        for a, asm in enumerate(case["asms"]):
+            eng.add_minimizers(f"asm{a}", 1.0, asm["hash"], asm["pos"], asm["record"], asm["names"])
+        eng.build_graph()
+        got = eng.synteny_blocks(1, 0, max_gap=case["max_gap"], min_anchors=case["min_anchors"], query_length=case["lengths"][1],
+                                 subject_length=case["lengths"][0])
+        assert (got["n_anchors_total"], got["n_links"]) == (case["n_anchors_total"], case["n_links"])
+        for name in R.FIELDS:
+            assert np.array_equal(got[name].astype(np.int64), case["expect"][name]), name
+        res = eng.synteny_assess()
+    want = A.assess(as_tuples(got), case["k"], case["lengths"][1].tolist(), case["lengths"][0].tolist())
+    assert (want["n_chains"], want["covered_subject"], want["chained_subject"]) == (case["n_chains"], case["covered_subject"], case["chained_subject"])
+    for key in SCALARS:
+        assert res[key] == want[key], (key, res[key], want[key])
+    for name in A.CHAIN_FIELDS:
+        assert np.array_equal(res["chains"][name].astype(np.int64), np.array(want["chains"][name], dtype=np.int64)), "chain " + name
+    for name in A.BP_FIELDS:
+        assert np.array_equal(res["bps"][name].astype(np.int64), np.array(want["bps"][name], dtype=np.int64)), "breakpoint " + name
+    print(f"cover of {case['n_chains']} chains: {time.time() - t0:.1f} s")
 
 
 def test_piece_tables():

@@ -1,7 +1,8 @@
 """GPU tests of mxg_lift_prepare / mxg_lift_intervals / mxg_lift_bed (include/ntjoin_mx.h, row f15) against the restatement of the
 contract (tests/_lift_restatement.py: a linear scan over all pieces, no index) on the cases of tests/_lift_cases.py, and past the
-borders of the kernels: 256 threads a block, 1024 elements a tile of the scans and of the sort, 4096 tile sums a pass of the second
-scan level, one more 8-bit digit of the sort per 256-fold of source records.  The shapes are the smallest that cross them."""
+borders of the kernels: 256 threads a block, 1024 elements a tile of the scans and of the sort, 256 tiles a round of the running
+maximum's second pass (262 144 pieces), one more 8-bit digit of the sort per 256-fold of source records.  The shapes are the smallest
+that cross them; the largest table has 263 446 pieces, far below the 4096 tiles at which the 32-bit scans take a second pass."""
 import numpy as np
 import pytest
 
@@ -107,6 +108,19 @@ def test_one_source_record_in_4097_pieces_under_a_feature_that_spans_them(eng):
     status, part_first, parts = check(eng, table, [L], features)
     assert status == [R.PARTIAL, R.PARTIAL, R.LOST, R.WHOLE, R.PARTIAL]
     assert part_first[1] == 4097 and [p[3] for p in parts[:4097]] == [3 * j for j in range(4097)]
+
+
+@pytest.mark.parametrize("long_at,n_short", cases.CARRY_CASES)
+def test_lookups_that_live_on_the_carries(eng, long_at, n_short):
+    """one long piece on the last place of tile 0 and the first of tile 1, on the last place of the first round of k_pt_max_tiles
+    (256 tiles) and the first of the second, over everything behind it; a second record with a long piece on the last place of a later
+    tile.  tests/test_maxscan_model_cpu.py shows that these features lose their parts when rmax lacks the carry in question"""
+    table, source_length, features, statuses = cases.carry_case(long_at, n_short)
+    prepare(eng, table, source_length)
+    got = lift(eng, features)
+    assert got == cases.carry_expected(long_at, n_short) and got[0] == statuses
+    if n_short < 10000:
+        cases.check_spelling(table, source_length, features, *got)
 
 
 def test_nothing_to_lift_through_and_nothing_to_lift(eng):

@@ -1,9 +1,13 @@
 """GPU tests of the shared primitives by themselves -- launch_scan_u32 and count_publish / count_prefix (csrc/scan_kernels.h),
-launch_scan_u64 (csrc/scan64_kernels.h), launch_radix_sort (csrc/sort_kernels.h) -- past the borders where their carry code starts:
+launch_scan_u64 and launch_max_scan_u64 (csrc/scan64_kernels.h), launch_radix_sort (csrc/sort_kernels.h) -- past the borders where
+their carry code starts:
 
   * scan32 around the tile (1024), one pass of k_scan_sums (4096 tiles = 4 194 304 inputs) and two passes, with prefixes that pass
     2^32, and `total` on both sides of the limit the header states;
   * scan64 around the tile, one round of k_pt_scan_tiles (256 tiles = 262 144 inputs) and two rounds, with prefixes past 2^32;
+  * maxscan64, the running 64-bit maximum, around the block, the tile, one round of k_pt_max_tiles (262 144 inputs) and two rounds
+    plus one, against np.maximum.accumulate: rising (the output is the input), falling (every output lives on a carry), one value
+    among zeros on either side of a tile and of a round border, the callers' (record << 32) | x, words with the top bit set, zeros;
   * the sort around the wave, the round, the tile and past 2^16, with odd and even pass counts, against numpy's stable argsort bit
     for bit (values = indices, so every place of every equal key is checked: the direct test of its stability), and once with more
     than 16 384 tiles, where the scan over its counts takes a second pass;
@@ -20,6 +24,8 @@ import time
 
 import numpy as np
 import pytest
+
+from tests import _maxscan_model as MM
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -121,6 +127,17 @@ def test_scan64(n, pattern, tmp_path):
     same(got, np.cumsum(a, dtype=np.uint64) - a, f"scan64 {n} {pattern}")
     if pattern == "total_at_n":
         assert int(got[n]) == sum(a.tolist())
+
+
+# ---- maxscan64 ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,pattern,at", MM.cases(), ids=lambda v: "" if v is None else str(v))
+def test_maxscan64(n, pattern, at, tmp_path):
+    """the inputs are tests/_maxscan_model.py's, which says what each pattern is there for; tests/test_maxscan_model_cpu.py shows that
+    each would come out wrong under the carry faults it names"""
+    a = MM.pattern_input(n, pattern, at)
+    a.tofile(tmp_path / "in")
+    run("maxscan64", tmp_path / "in", tmp_path / "out")
+    same(np.fromfile(tmp_path / "out", dtype=np.uint64), np.maximum.accumulate(a), f"maxscan64 {n} {pattern} {at}")
 
 
 # ---- sort --------------------------------------------------------------------------------------------------------------------------

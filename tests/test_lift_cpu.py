@@ -135,6 +135,19 @@ def test_seeded_fuzz(exe, tmp_path):
     assert composed >= 100
 
 
+@pytest.mark.parametrize("long_at,n_short", cases.CARRY_CASES)
+def test_lookups_behind_a_long_piece(exe, tmp_path, long_at, n_short):
+    "the tables of tests/test_gpu_lift.py::test_lookups_that_live_on_the_carries: the header's two bisections on the host at these sizes"
+    table, source_length, features, statuses = cases.carry_case(long_at, n_short)
+    want = cases.carry_expected(long_at, n_short)
+    assert want[0] == statuses
+    if n_short < 10000:
+        cases.check_spelling(table, source_length, features, *want)
+    r = _run_intervals(exe, table, source_length, features, tmp_path)
+    assert r.returncode == 0, r.stderr
+    assert _parse(r.stdout) == want
+
+
 def test_no_records_no_sequence_pieces_no_features(exe, tmp_path):
     for table, features in (([], [(0, 0, 5)]), ([[(0, 0, 5, R.GAP)]], [(0, 0, 5), (1, 0, 1)]), (cases.TABLE, [])):
         want = R.lift(table, cases.SOURCE_LEN, features)

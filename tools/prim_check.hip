@@ -4,6 +4,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -I ntjoin_amd/csrc tools/prim_check.hip -o ntjoin_amd/bin/prim_check
 // Usage: prim_check scan32 <in.u32> <out.u32> <total.u64>           launch_scan_u32 (n >= 1)
 //        prim_check scan64 <in.u64> <out.u64>                       launch_scan_u64, in place (n >= 1)
+//        prim_check maxscan64 <in.u64> <out.u64>                    launch_max_scan_u64, in place (n >= 1)
 //        prim_check sort <key_bits> <keys.u64> <vals.u32> <keys_out.u64> <vals_out.u32>
 //                                                                   launch_radix_sort; prints "buffer: <its return value>" and writes
 //                                                                   the buffer that value names
@@ -180,6 +181,23 @@ static int run_scan64(char **a)
     return 0;
 }
 
+static int run_maxscan64(char **a)
+{
+    const std::vector<uint64_t> in = read_file<uint64_t>(a[0]);
+    const uint32_t n = count_of(in.size(), a[0]);
+    if (n == 0) {
+        fprintf(stderr, "maxscan64: n = 0 is outside launch_max_scan_u64's contract\n");
+        return 3;
+    }
+    const Guarded d_a = dev_array("a", (size_t)n * 8), d_tmax = dev_array("tmax", (size_t)((n + PT_TILE - 1) / PT_TILE) * 8);
+    upload(d_a, in.data(), (size_t)n * 8);
+    hipStream_t st = nullptr;
+    launch_max_scan_u64(st, d_a.as<uint64_t>(), n, d_tmax.as<uint64_t>());
+    finish(st);
+    download(a[1], d_a.as<uint64_t>(), n);
+    return 0;
+}
+
 static int run_sort(char **a)
 {
     const uint32_t key_bits = (uint32_t)strtoul(a[0], nullptr, 10);
@@ -238,12 +256,14 @@ int main(int argc, char **argv)
         rc = run_scan32(argv + 2);
     else if (op == "scan64" && argc == 4)
         rc = run_scan64(argv + 2);
+    else if (op == "maxscan64" && argc == 4)
+        rc = run_maxscan64(argv + 2);
     else if (op == "sort" && argc == 7)
         rc = run_sort(argv + 2);
     else if (op == "prefix" && argc == 4)
         rc = run_prefix(argv + 2);
     else {
-        fprintf(stderr, "usage: prim_check scan32 IN OUT TOTAL | scan64 IN OUT | sort KEY_BITS KEYS VALS KEYS_OUT VALS_OUT | prefix Q COUNTS\n");
+        fprintf(stderr, "usage: prim_check scan32 IN OUT TOTAL | scan64 IN OUT | maxscan64 IN OUT | sort KEY_BITS KEYS VALS KEYS_OUT VALS_OUT | prefix Q COUNTS\n");
         return 3;
     }
     if (rc) return rc;
