@@ -11,7 +11,8 @@
 //   k_fai_rows       scans its tile again behind that: the value at a record's last item is the record's summary -> its row
 //                    {length, offset, line bases, line width, first offending line}; the lowest refused record goes into one word.
 // Only that word (and the refused row) come to the host before the file is opened.  The rows stay on the device for the formatter:
-//   k_fai_len        bytes of every row's line (CountSink, text_dev.h) -> a 64-bit exclusive scan gives every line its place;
+//   k_fai_len        bytes of every row's line (CountSink, text_dev.h) -> the shared 64-bit exclusive scan (scan64_kernels.h) gives
+//                    every line its place;
 //   k_fai_bounds     per window the row that holds its first byte;  k_fai_emit  the bytes of a window (WinSink).
 // Output leaves window by window through write_windows (win_out.hip); MXG_FAI_WIN sets the bytes per window.
 // The rows of a scaffold file need no text: every record is one line, {name, len, offset, len, len + 1} with offset the exclusive
@@ -23,12 +24,12 @@
 
 #include "fai_scan.h"
 #include "mxg_internal.h"
+#include "scan64_kernels.h"
 #include "text_dev.h"
 #include "text_index.h"
 
 namespace mxg {
 
-constexpr uint32_t FAI_TILE = 1024;  // elements per work-group of the 64-bit scan (4 per thread)
 enum { FB_SUMS, FB_AGG, FB_EXCL, FB_ROWS, FB_ORG, FB_RLEN, FB_VERDICT, FB_IDOFF, FB_IDS, FB_KEEP, FB_OFF, FB_TSUM, FB_BOUNDS, FB_IV, FB_BUF_COUNT };
 static_assert(FB_BUF_COUNT <= 16, "mxg_handle::faibuf too small");
 
@@ -204,67 +205,6 @@ __global__ __launch_bounds__(256) void k_fai_len(const FaiFmt q)
     q.off[i] = c.n;  // (entry n: 0, so that the exclusive sums end with the total)
 }
 
-// exclusive prefix of per-thread sums `c` inside a block of 256; *total = the block's sum (all threads call)
-__device__ __forceinline__ uint64_t fai_block_exclusive(uint64_t c, uint64_t *sh, uint64_t *total)
-{
-    const uint32_t t = threadIdx.x;
-    sh[t] = c;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {
-        const uint64_t v = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        sh[t] += v;
-        __syncthreads();
-    }
-    const uint64_t incl = sh[t];
-    *total = sh[255];
-    __syncthreads();  // (sh is free for the next call)
-    return incl - c;
-}
-
-__global__ __launch_bounds__(256) void k_fai_tile_sum(const uint64_t *__restrict__ in, uint32_t n, uint64_t *__restrict__ tsum)
-{
-    __shared__ uint64_t sh[256];
-    const uint64_t base = (uint64_t)blockIdx.x * FAI_TILE + threadIdx.x * 4u;
-    uint64_t c = 0, total;
-    for (uint32_t u = 0; u < 4; ++u)
-        if (base + u < n) c += in[base + u];
-    (void)fai_block_exclusive(c, sh, &total);
-    if (threadIdx.x == 0) tsum[blockIdx.x] = total;
-}
-
-// tsum[0 .. n_tiles) -> its exclusive sums, in place, by ONE block
-__global__ __launch_bounds__(256) void k_fai_scan_tiles(uint64_t *__restrict__ tsum, uint32_t n_tiles)
-{
-    __shared__ uint64_t sh[256];
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < n_tiles; base += 256) {
-        const uint64_t i = base + threadIdx.x;
-        const uint64_t v = i < n_tiles ? tsum[i] : 0;
-        uint64_t total;
-        const uint64_t ex = fai_block_exclusive(v, sh, &total);
-        if (i < n_tiles) tsum[i] = carry + ex;
-        carry += total;
-    }
-}
-
-// a[i] -> the sum of a[0 .. i), in place (tsum: the tiles' exclusive sums)
-__global__ __launch_bounds__(256) void k_fai_tile_excl(uint64_t *__restrict__ a, uint32_t n, const uint64_t *__restrict__ tsum)
-{
-    __shared__ uint64_t sh[256];
-    const uint64_t base = (uint64_t)blockIdx.x * FAI_TILE + threadIdx.x * 4u;
-    uint64_t v[4], c = 0, total;
-    for (uint32_t u = 0; u < 4; ++u) {
-        v[u] = base + u < n ? a[base + u] : 0;
-        c += v[u];
-    }
-    uint64_t run = tsum[blockIdx.x] + fai_block_exclusive(c, sh, &total);
-    for (uint32_t u = 0; u < 4; ++u) {
-        if (base + u < n) a[base + u] = run;
-        run += v[u];
-    }
-}
-
 // bounds[c] = the row whose line holds byte c * win of the file (off: [n + 1] offsets, off[n] = the file's size > c * win)
 __global__ __launch_bounds__(256) void k_fai_bounds(const uint64_t *__restrict__ off, uint32_t n, uint64_t win, uint32_t n_win,
                                                     uint32_t *__restrict__ bounds)
@@ -309,14 +249,11 @@ __global__ __launch_bounds__(256) void k_fai_scaf_rows(const uint64_t *__restric
     rows[i] = row;
 }
 
-static int fai_scan_u64(mxg_handle *h, uint64_t *d_a, uint32_t n)  // d_a[0 .. n) -> exclusive sums, in place
+static int fai_scan_u64(mxg_handle *h, uint64_t *d_a, uint32_t n)  // d_a[0 .. n) -> exclusive sums, in place (scan64_kernels.h)
 {
-    const uint32_t n_tiles = (n + FAI_TILE - 1) / FAI_TILE;
+    const uint32_t n_tiles = (n + PT_TILE - 1) / PT_TILE;
     MXG_HIP(h, h->faibuf[FB_TSUM].ensure((size_t)n_tiles * 8));
-    uint64_t *tsum = h->faibuf[FB_TSUM].as<uint64_t>();
-    hipLaunchKernelGGL(k_fai_tile_sum, dim3(n_tiles), dim3(256), 0, h->stream, d_a, n, tsum);
-    hipLaunchKernelGGL(k_fai_scan_tiles, dim3(1), dim3(256), 0, h->stream, tsum, n_tiles);
-    hipLaunchKernelGGL(k_fai_tile_excl, dim3(n_tiles), dim3(256), 0, h->stream, d_a, n, tsum);
+    launch_scan_u64(h->stream, d_a, n, h->faibuf[FB_TSUM].as<uint64_t>());
     MXG_HIP(h, hipGetLastError());
     return MXG_OK;
 }

@@ -4,7 +4,12 @@ bytes of the file, so a record of a little over 12 288 bytes of text lies in thr
 
     shapes()   -> {name: text}            accepted files
     refusals() -> {name: (text, "bad")}   refused files and the id of the record that is refused
+    carry_text(at, span, ...) -> text     `at` work items of tiny records, then the record "long" over `span` items (CARRIES: the
+                                          places where the scan over the items carries from tile to tile and from round to round)
+    items_of(text) -> [items per record]  the cutting rule restated
+    tiny_records(n, dup) -> text          n records of a few bases under names of growing length (the offset scan's borders)
 """
+import functools
 import random
 
 TILE = 4096
@@ -127,3 +132,98 @@ def refusals():
         out["last_other_end_" + where] = wrap(base[:-1], behind=seq(rng, 30) + "\r\n")
         out["last_longer_end_of_file_" + where] = wrap(base[:-1], behind=seq(rng, 61), following=False)
     return {k: (v.encode("latin-1"), "bad") for k, v in out.items()}
+
+
+# ---- the carries of the scan over the work items (k_fai_tile_agg -> k_fai_tile_scan -> k_fai_rows) ----
+ITEMS_TILE = 256             # items a tile
+ITEMS_ROUND = 256 * 256      # items a round of k_fai_tile_scan: 256 tiles
+
+
+def _n_items(lo, se):
+    "text [lo, se) of one record cut at the aligned 4096-byte borders of the file"
+    return 0 if se <= lo else (se - 1) // TILE - lo // TILE + 1
+
+
+def items_of(text):
+    """work items per record: a record's text, from the byte behind its header line to the next header line (or the end of the
+    file), is cut at the multiples of 4096 bytes of the file; a record without text has none (the rule tools/fai_check.cpp states)"""
+    from tests import _fai_restatement as R
+    return [_n_items(lo, se) for _, lo, se in R.records(text)]
+
+
+def carry_text(at, span, tail=5, bad=(), seed=23):
+    """exactly `at` work items of tiny records with unique names (one in eleven without text, two in eleven with CRLF, text that
+    straddles a border of the file's tiles where it falls: two items), the last of them three full lines of 7 bases; then the record
+    "long" in lines of 60 bases + LF over exactly `span` items, ending with a short line 2000 bytes into its last item; then `tail`
+    small records and two without text.  bad: items of "long" (counted from 0) in which one whole line has 59 bases"""
+    assert at >= 1 and span >= 2
+    rng = random.Random(seed)
+    stock = seq(rng, 4099)
+    parts, pos, n, i = [], 0, 0, 0
+
+    def put(s):
+        nonlocal pos
+        parts.append(s)
+        pos += len(s)
+
+    while n < at:
+        kind = i % 11
+        eol = "\r\n" if kind in (3, 7) else "\n"
+        head = header("f%d" % i, eol=eol)
+        i += 1
+        front = n == at - 1  # (the record in front of "long": another width, no short last line)
+        if front:
+            body = fold(stock[i % 4000:i % 4000 + 21], 7)
+        elif kind == 5:
+            body = ""
+        else:
+            body = stock[i % 4000:i % 4000 + 3 + i % 9] + eol
+        k = _n_items(pos + len(head), pos + len(head) + len(body))
+        if n + k > (at if front else at - 1):  # (it would take the place of "long" or of the record in front: no text, try again)
+            body, k = "", 0
+        put(head + body)
+        n += k
+    head = header("long", " over %d items" % span)
+    lo = pos + len(head)
+    q, r = divmod((lo // TILE + span - 1) * TILE + 2000 - lo - 1, 61)
+    lines = [(stock * 2)[(7 * j) % 4000:(7 * j) % 4000 + 60] for j in range(q)] + [stock[:r or 30]]
+    for j in bad:
+        at_line = ((lo // TILE + j) * TILE - lo) // 61 + 2  # (a line that lies inside item j)
+        lines[at_line] = lines[at_line][:59]
+    put(head + "\n".join(lines) + "\n")
+    for j in range(tail):
+        put(header("t%d" % j, " tail") + fold(stock[j:j + 100 + j], 70))
+    put(">x\n>y\n")
+    return "".join(parts).encode("latin-1")
+
+
+_R = ITEMS_ROUND
+# name -> (arguments of carry_text, refused?); "long" begins on item `at`
+CARRIES = {
+    "tile": (dict(at=255, span=2), False),
+    "last_of_round": (dict(at=_R - 1, span=2), False),
+    "first_of_round": (dict(at=_R, span=2), False),
+    "across": (dict(at=_R - 300, span=600), False),
+    "second_round": (dict(at=2 * _R - 300, span=600), False),
+    "exact_round": (dict(at=_R - 2, span=2, tail=0), False),
+    "exact_round_plus_one": (dict(at=_R - 1, span=2, tail=0), False),
+    "refusal_behind": (dict(at=_R - 300, span=600, bad=(400,)), True),
+    "refusal_in_front": (dict(at=_R - 300, span=600, bad=(100, 400)), True),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def carry_case(name):
+    return carry_text(**CARRIES[name][0])
+
+
+# ---- the borders of the 64-bit scan over the rows' line sizes (1 024 offsets a tile, 262 144 a round) ----
+@functools.lru_cache(maxsize=None)
+def tiny_records(n, dup=()):
+    """n records of 1 .. 4 bases on one line; the names grow (r0, r1, ..., with a run of 'x' that gets longer every 37 records), so
+    the lines of the index differ in size; record i in `dup` bears the name of record i - 1 (it gets no line)"""
+    parts = []
+    for i in range(n):
+        j = i - 1 if i in dup else i
+        parts.append(">r%d%s\n%s\n" % (j, "x" * (j // 37 % 23), "ACGT"[:1 + i % 4]))
+    return "".join(parts).encode("latin-1")

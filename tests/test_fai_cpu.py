@@ -1,8 +1,9 @@
 """CPU tests of the FASTA index route: the restatement of mxg_write_fai's contract (tests/_fai_restatement.py) against the two
 `samtools faidx` outputs the reference records (tests/golden/fai/); the code of the device route (ntjoin_amd/csrc/fai_scan.h) run on
 the host by tools/fai_check.cpp, built plainly and with AddressSanitizer + UndefinedBehaviorSanitizer (the runtime linked into the
-program; nothing is preloaded), against the restatement on every shape and every refusal of tests/_fai_cases.py; the way back from a
-row to the bases; ntjoin_amd.fai's concatenation; --fai on the command line and in `ntJoin-mx scaffold`; the exported symbols."""
+program; nothing is preloaded), against the restatement on every shape and every refusal of tests/_fai_cases.py, and on the texts
+that put one long record on the tile and round borders of the scan over the work items, each of which must come out wrong under the
+fault of that scan it is listed for (fai_check FASTA FAULT); the way back from a row to the bases; ntjoin_amd.fai's concatenation; --fai on the command line and in `ntJoin-mx scaffold`; the exported symbols."""
 import os
 import random
 import re
@@ -57,16 +58,28 @@ def exe(request, tmp_path_factory):
         extra = _sanitizer_flags(cxx, td)
         if extra is None:
             pytest.skip("the host compiler has no AddressSanitizer runtime to link")
+    return _compile(cxx, td, extra)
+
+
+def _compile(cxx, td, extra):
     out = td / "fai_check"
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror"] + extra + ["-I", CSRC, os.path.join(REPO, "tools", "fai_check.cpp"),
                                                                                  "-o", str(out)])
     return str(out)
 
 
-def _run(exe, text, tmp_path):
+@pytest.fixture(scope="module")
+def plain_exe(tmp_path_factory):
+    "the plain build alone, for the runs with a fault switched on"
+    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++")
+    assert cxx, "no C++ compiler"
+    return _compile(cxx, tmp_path_factory.mktemp("fai_check_faults"), [])
+
+
+def _run(exe, text, tmp_path, fault=None):
     fa = tmp_path / "x.fa"
     fa.write_bytes(text)
-    return subprocess.run([exe, str(fa)], capture_output=True, timeout=120)
+    return subprocess.run([exe, str(fa)] + ([fault] if fault else []), capture_output=True, timeout=120)
 
 
 def check_fetch(rows, text, seed=1, tries=12):
@@ -144,6 +157,111 @@ def test_random_foldings_agree(exe, tmp_path):
     r = _run(exe, text, tmp_path)
     assert r.returncode == 0 and r.stdout == R.fai_bytes(text)
     check_fetch(R.parse(r.stdout), text, tries=4)
+
+
+# ---- the carries of the scan over the work items
+B = _fai_cases.ITEMS_ROUND
+# the faults tools/fai_check.cpp can switch on, and the cases that are there to show each.  A case stands where it does for the
+# faults it is listed under; under each of them the program's answer must differ from the restatement's.
+#   tile                  items 255 | 256: the first-level border.  The scan of the tiles' totals gives it excl[1] = the total of tile
+#                         0 in its first round, where the carry is empty: only a thread that takes its own value (inclusive) shows.
+#   last_of_round         "long" on items B - 1 | B: excl[256] is the round carry itself, written by thread 0.
+#   first_of_round        "long" begins on item B: nothing of round 0 may reach it (rows_plain: the record in front leaks into it).
+#   across                "long" on tiles 254 .. 257: excl[257] = combine(carry, sh[0]) needs the carry through thread 1.
+#   second_round          the same over the border of rounds 1 and 2: the carry there is a carry folded onto a carry, and with the
+#                         plain operator it drags round 0 along.
+#   exact_round_plus_one  257 tiles: a second round of one tile with one item (the partial-round guards; a loop over whole rounds).
+#   refusal_*             the offence's place travels in the summary: without the carry the verdict names another byte.
+CARRY_FAULTS = {
+    "tile": ("inclusive",),
+    "last_of_round": ("nocarry", "nocarry_t0", "early"),
+    "first_of_round": ("rows_plain",),
+    "across": ("nocarry", "nocarry_rest", "early"),
+    "second_round": ("nocarry_rest", "early", "plain"),
+    "exact_round_plus_one": ("nocarry_t0", "rounds"),
+    "refusal_behind": ("nocarry_rest",),
+    "refusal_in_front": ("nocarry_rest", "early"),
+}
+# and what a case must NOT show, which says that it stands on the place it names: thread 0 against the others; a file of exactly
+# 256 tiles has no second round, so no fault of the carry and no dropped partial round touches it (the other half of "exact").
+CARRY_BLIND = {
+    "last_of_round": ("nocarry_rest",),
+    "across": ("nocarry_t0",),
+    "exact_round": ("nocarry", "early", "rounds"),
+    # No case can show `restart` (the carry restarted from the round's total instead of folded onto the carry before).  The two
+    # differ only where a whole round holds no record's first item, for the total of a round that holds one forgets what is in
+    # front of it anyway: one record over 65 536 items of 4 096 bytes, 256 MB of text.  second_round is the only case that reads a
+    # carry made of two rounds, and it comes out right under it.
+    "second_round": ("restart",),
+}
+_WANT = {}
+
+
+def carry_want(name):
+    "(exit status, stdout) the restatement asks of the host program; computed once per case"
+    if name not in _WANT:
+        text = _fai_cases.carry_case(name)
+        try:
+            _WANT[name] = (0, R.fai_bytes(text))
+            assert not _fai_cases.CARRIES[name][1]
+        except R.Refused as err:
+            assert _fai_cases.CARRIES[name][1] and err.name == "long"
+            _WANT[name] = (3, ("refused %d long %d\n" % (err.record, err.offset)).encode())
+    return _WANT[name]
+
+
+def carry_place(name):
+    "(items in front of 'long', items of 'long', items of the text) by the cutting rule"
+    text = _fai_cases.carry_case(name)
+    items = _fai_cases.items_of(text)
+    at = [rec[0] for rec in R.records(text)].index("long")
+    return sum(items[:at]), items[at], sum(items)
+
+
+def test_items_of_states_the_cutting_rule():
+    t = _fai_cases
+    pad = t.padded_header(0, "a", 4090)  # (the text of "a" begins 6 bytes in front of a border of the file's tiles)
+    text = (pad + "ACGTAC\n" + ">b\n" + ">c\nAC\n" + t.padded_header(len(pad) + 17, "d", 4095) + "A" * 4098 + "\n>e").encode()
+    assert t.items_of(text) == [2, 0, 1, 3, 0]
+    assert t.items_of(b"") == [] and t.items_of(b">a") == [0] and t.items_of(b">a\n") == [0] and t.items_of(b">a\nA") == [1]
+
+
+@pytest.mark.parametrize("name", sorted(_fai_cases.CARRIES))
+def test_carry_cases_stand_where_they_say(name):
+    kw = _fai_cases.CARRIES[name][0]
+    at, span, total = carry_place(name)
+    assert (at, span) == (kw["at"], kw["span"])
+    if name.startswith("exact"):
+        assert total == at + span == (B if name == "exact_round" else B + 1)
+    text = _fai_cases.carry_case(name)
+    items = _fai_cases.items_of(text)
+    front = items[:[rec[0] for rec in R.records(text)].index("long")]
+    assert 0 in front and (2 in front or at < 4096 // 8) and b"\r\n" in text and front[-1] == 1
+
+
+@pytest.mark.parametrize("name", sorted(_fai_cases.CARRIES))
+def test_host_program_on_the_carries(exe, tmp_path, name):
+    r = _run(exe, _fai_cases.carry_case(name), tmp_path)
+    assert (r.returncode, r.stdout) == carry_want(name), (r.stdout[-300:], r.stderr[:2000])
+
+
+@pytest.mark.parametrize("name,fault", [(n, f) for n in sorted(CARRY_FAULTS) for f in CARRY_FAULTS[n]])
+def test_every_carry_case_shows_its_faults(plain_exe, tmp_path, name, fault):
+    r = _run(plain_exe, _fai_cases.carry_case(name), tmp_path, fault)
+    assert r.returncode in (0, 3), r.stderr[:2000]
+    assert (r.returncode, r.stdout) != carry_want(name)
+
+
+@pytest.mark.parametrize("name,fault", [(n, f) for n in sorted(CARRY_BLIND) for f in CARRY_BLIND[n]])
+def test_what_a_carry_case_cannot_show(plain_exe, tmp_path, name, fault):
+    r = _run(plain_exe, _fai_cases.carry_case(name), tmp_path, fault)
+    assert (r.returncode, r.stdout) == carry_want(name)
+
+
+def test_host_program_knows_its_faults(plain_exe, tmp_path):
+    assert _run(plain_exe, b">a\nAC\n", tmp_path, "no_such_fault").returncode == 2
+    assert sorted({f for fs in list(CARRY_FAULTS.values()) + list(CARRY_BLIND.values()) for f in fs}) == sorted(
+        ["nocarry", "nocarry_t0", "nocarry_rest", "early", "plain", "restart", "inclusive", "rounds", "rows_plain"])
 
 
 # ---- ntjoin_amd.fai

@@ -1,10 +1,14 @@
 """GPU tests of the FASTA index route (ntjoin_amd/csrc/fai.hip): mxg_write_fai against the two `samtools faidx` outputs the reference
 records (tests/golden/fai/) and, on every other input, against the restatement of its contract (tests/_fai_restatement.py): the
-shapes and refusals of tests/_fai_cases.py, assemblies without text, small windows, duplicate names, BGZF input with its .gzi; and
-MXG_SCAF_FAI on the goldens and fuzz seeds of the scaffold stage."""
+shapes and refusals of tests/_fai_cases.py, assemblies without text, small windows, duplicate names, BGZF input with its .gzi;
+MXG_SCAF_FAI on the goldens and fuzz seeds of the scaffold stage; and both routes past the borders of their scans: one long record
+on the tile and round borders of the scan over the work items (256 items, 65 536 items), the rows' offsets around 1 024 and
+262 144 entries of the shared 64-bit scan."""
+import functools
 import glob
 import os
 import random
+import re
 import zlib
 
 import pytest
@@ -13,7 +17,7 @@ from ntjoin_amd import fai as fai_mod
 from ntjoin_amd.engine import MxEngine, MxError
 from tests import _bgzf, _fai_cases, _fai_restatement as R, _oracle, _scaffold_cases as cases
 from tests.conftest import GOLDEN
-from tests.test_fai_cpu import check_fetch
+from tests.test_fai_cpu import carry_place, carry_want, check_fetch
 
 pytestmark = pytest.mark.gpu
 EINVAL = -1
@@ -284,3 +288,129 @@ def test_scaffold_indexes_with_borders_inside_records(seed, env, tmp_path):
     env["MXG_SCAF_WIN"] = "8192"
     env["MXG_FAI_WIN"] = "64"
     check_scaffold_indexes("fuzz", seed, tmp_path, 15, 10)
+
+
+# ---- the carries: the scan over the work items, and the offset scan at 1 024 and 262 144 entries
+B = _fai_cases.ITEMS_ROUND
+
+
+def indexed(env, tmp_path, capfd, text, win=None):
+    "-> (the .fai's bytes or the MxError, the items the witness line of MXG_DEBUG_IO names)"
+    env["MXG_DEBUG_IO"] = "1"
+    if win:
+        env["MXG_FAI_WIN"] = win
+    fa = tmp_path / "c.fa"
+    fa.write_bytes(text)
+    out = str(fa) + ".fai"
+    if os.path.exists(out):
+        os.remove(out)
+    with MxEngine(k=15, w=10) as eng:
+        a = eng.add_fasta("c", 1.0, str(fa))
+        capfd.readouterr()
+        try:
+            eng.write_fai(a, out)
+            got = read(out)
+        except MxError as err:
+            assert not os.path.exists(out)
+            got = err
+        assert (f"MXG_FAI_WIN={win}" in eng.knobs()) == bool(win)
+    witness = re.findall(r"^\[mxg\] fai items=(\d+) rows_ms=", capfd.readouterr().err, re.M)
+    assert len(witness) == 1
+    return got, int(witness[0])
+
+
+@pytest.mark.parametrize("name", sorted(_fai_cases.CARRIES))
+def test_row_scan_carries(name, env, tmp_path, capfd):
+    """"long" on the borders of k_fai_tile_scan's tiles and rounds (tests/test_fai_cpu.py says which fault each case is there for):
+    the file is the restatement's, or the refusal names the record and the restatement's byte; the items are the cutting rule's"""
+    kw, refused = _fai_cases.CARRIES[name]
+    text = _fai_cases.carry_case(name)
+    at, span, total = carry_place(name)
+    assert (at, span) == (kw["at"], kw["span"])  # (a builder that drifts fails here, not in the coverage)
+    status, want = carry_want(name)
+    got, n_items = indexed(env, tmp_path, capfd, text)
+    assert n_items == total
+    if name.startswith("exact"):
+        assert n_items == (B if name == "exact_round" else B + 1)
+    if refused:
+        with pytest.raises(R.Refused) as ref:
+            R.index(text)
+        assert status == 3 and isinstance(got, MxError) and got.code == EINVAL
+        assert "record 'long'" in str(got) and "the line at byte %d of the text" % ref.value.offset in str(got)
+        return
+    assert status == 0 and not isinstance(got, MxError), got
+    assert got == want
+    if name == "across":
+        rows = R.parse(got)
+        at_row = [row[0] for row in rows].index("long")
+        check_fetch(rows[:3] + rows[at_row - 3:at_row + 4] + rows[-3:], text, tries=6)
+
+
+OFFSET_DUP = (500, 100000)  # records that bear the name in front of them: no line, a size of 0 inside the scan
+
+
+@functools.lru_cache(maxsize=None)
+def offset_case(n):
+    "(text, the index by the restatement, items) of n tiny records"
+    text = _fai_cases.tiny_records(n, tuple(d for d in OFFSET_DUP if d < n))
+    rows, dropped = R.index(text)
+    assert len(rows) + len(dropped) == n and len(dropped) == sum(d < n for d in OFFSET_DUP)
+    assert len({len(R.format_rows([row])) for row in rows[:1024]}) >= 8  # (the sizes under the scan differ)
+    return text, R.format_rows(rows), sum(_fai_cases.items_of(text))
+
+
+@pytest.mark.parametrize("n,win", [(1022, None), (1023, None), (1024, None), (262143, None), (262143, "4093"), (262144, None), (262144, "4093")])
+def test_offset_scan_borders(n, win, env, tmp_path, capfd):
+    """n + 1 row sizes on either side of a tile (1 024) and of a round (262 144) of the 64-bit scan, a kept-out row in the first tile
+    and in the first round; with windows of 4093 bytes k_fai_bounds bisects offsets that live on the round carry"""
+    text, want, items = offset_case(n)
+    got, n_items = indexed(env, tmp_path, capfd, text, win)
+    assert not isinstance(got, MxError), got
+    assert n_items == items and items >= n
+    if n >= 4 * B:
+        assert n_items > 4 * B  # (a fifth round of the scan over the items as well)
+    assert got == want
+
+
+SCAF_RECORDS, SCAF_PATHS = 262150 + 2200, 1100
+fai_of_text = functools.lru_cache(maxsize=None)(R.fai_bytes)  # (both runs write the same two plain files)
+
+
+@pytest.mark.parametrize("bgzf", [False, True], ids=["plain", "bgzf"])
+def test_scaffold_indexes_past_the_scan_borders(bgzf, env, tmp_path):
+    """1 100 scaffolds of two records (ntJoin<i> rows past the tile border of both scans of write_fai_records) and 262 150 and more
+    unassigned records (id:lo-hi rows past the round border); as check_scaffold_indexes: the index of each file is the restatement's
+    over the plain file the same handle wrote, FASTA and BED do not change"""
+    recs = [("c%d%s" % (i, "y" * (i // 41 % 19)), ("ACGTTGCA" * 6)[i % 8:i % 8 + 9 + i % 31]) for i in range(SCAF_RECORDS)]
+    fasta = str(tmp_path / "t.fa")
+    cases.write_fasta(fasta, recs, 0)
+    rows, first = [], [0]
+    for p in range(SCAF_PATHS):
+        a, b = 2 * p, 2 * p + 1
+        cut = 2 if p % 10 == 0 else 0  # (some nodes leave the record's first bases unassigned: id:0-2)
+        rows += [(a, cut, len(recs[a][1]), 3 + p % 5, 0, 0, p % 3 == 1), (b, 0, len(recs[b][1]), 0, 0, 0, p % 2 == 1)]
+        first.append(len(rows))
+    with MxEngine(k=15, w=10) as eng:
+        asm = eng.add_fasta("t", 1.0, fasta)
+        outs = []
+        for tag, kw in (("plain", {}), ("idx", dict(fai=True, bgzf=bgzf))):
+            names = [str(tmp_path / tag) + s for s in (".assigned.fa", ".unassigned.fa", ".bed")]
+            res = eng.write_scaffolds(asm, rows, first, assigned=names[0], unassigned=names[1], bed=names[2], **kw)
+            outs.append((names, (res["lead_strip"].tolist(), res["tail_strip"].tolist(), res["n_unassigned"])))
+    (plain, res0), (idx, res1) = outs
+    assert res0 == res1 and read(idx[2]) == read(plain[2])
+    n_lines = []
+    for p, f in zip(plain[:2], idx[:2]):
+        text = read(p)
+        assert not os.path.exists(p + ".fai")
+        want = fai_of_text(text)
+        assert read(f + ".fai") == want
+        assert text.count(b">") == want.count(b"\n")
+        n_lines.append(want.count(b"\n"))
+        if bgzf:
+            blob, gzi = read(f), read(f + ".gzi")
+            assert gzi == R.gzi_bytes(members_of(blob))
+            check_random_access(blob, gzi, text, tries=20)
+        else:
+            assert read(f) == text and not os.path.exists(f + ".gzi")
+    assert n_lines[0] == SCAF_PATHS > 1025 and n_lines[1] == res0[2] > 262145
