@@ -2,7 +2,8 @@
 tools/seqstat_check.cpp -- serially, cut into pieces with the states composed, and with the compositions regrouped -- built with
 AddressSanitizer + UndefinedBehaviorSanitizer (the runtime linked into the program; nothing is preloaded) against the restatement
 (tests/_seqreport_restatement.py); the contiguity block against a brute-force version; --report on the command line and in
-`ntJoin-mx scaffold`; the exported symbols."""
+`ntJoin-mx scaffold`; the exported symbols.  The same program over the scaffold files of the window route's shapes
+(tests/_seqreport_cases.py window_shapes)."""
 import os
 import shutil
 import subprocess
@@ -76,6 +77,30 @@ SHAPES = cases.shapes()
 @pytest.mark.parametrize("name", sorted(SHAPES))
 def test_host_program_equals_restatement_on_shapes(exe, tmp_path, name):
     _check(exe, SHAPES[name], tmp_path, 11)
+
+
+WINDOW_SHAPES = cases.window_shapes()
+
+
+@pytest.mark.parametrize("name", sorted(WINDOW_SHAPES))
+def test_host_program_equals_restatement_on_the_window_shapes(exe, tmp_path, name):
+    """the scaffold files the restatement expects of the window route's shapes (tests/test_gpu_report_windows.py), through the lane
+    code on the host: the report's restatement and seqstat.h agree on exactly these texts before the GPU is asked"""
+    for fold in (False, True) if name in cases.FOLD_TOO else (False,):
+        assigned, unassigned = cases.window_texts(WINDOW_SHAPES[name], fold)
+        assert assigned.startswith(b">ntJoin0\n")
+        for seed, text in enumerate((assigned, unassigned, assigned + unassigned), 13):
+            _check(exe, text, tmp_path, seed)
+    if name.startswith("empty_files"):
+        want = R.report(unassigned)
+        assert unassigned == b"" and want["gap_len"] == want["contig_len"] == [] and want["scaffold"] == dict.fromkeys(R.BLOCK, 0)
+        assert not any(want[k] for k in ("n_records", "bases", "a", "c", "g", "t", "n", "other", "lower", "n_gaps", "gap_bases", "max_gap"))
+
+
+def test_host_program_on_a_tile_of_line_ends(exe, tmp_path):
+    text = cases.line_end_tile()
+    _check(exe, text, tmp_path, 17)
+    assert R.report(text)["gap_len"] == [25]
 
 
 def test_cuts_at_every_offset_of_a_small_file(exe, tmp_path):
