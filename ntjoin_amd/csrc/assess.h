@@ -30,7 +30,7 @@ SYN_HD SynBlock as_block(const uint32_t *blk, uint64_t n, uint64_t i)
 SYN_HD uint32_t as_piece_of(const uint32_t *pre, const uint32_t *first, uint32_t r, uint32_t x)
 {
     if (!pre) return 0u;
-    return cmp_piece_at(pre + first[r], first[r + 1] - first[r], x);
+    return last_le(pre + first[r], 0u, first[r + 1] - first[r], x);  // (its prefix starts at 0 and rises, at least one piece)
 }
 
 // does the border between block a and its successor b (same query record) fall on a change of piece
@@ -91,12 +91,8 @@ SYN_HD bool as_nx_reached(uint64_t s, uint32_t x, uint64_t d)
 SYN_HD uint64_t as_lx(const uint64_t *ex, uint64_t n, uint32_t x, uint64_t d)
 {
     if (!d || !n || !as_nx_reached(ex[n], x, d)) return 0;
-    uint64_t lo = 0, hi = n;  // ex[lo] does not reach it (lo == 0: x D > 0), ex[hi] does
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (as_nx_reached(ex[mid], x, d)) hi = mid; else lo = mid;
-    }
-    return hi;
+    // ex[0] does not reach it (x D > 0), ex[n] does
+    return first_where((uint64_t)1, n, [&](uint64_t j) { return as_nx_reached(ex[j], x, d); });
 }
 
 // ---- the union of subject intervals, chains in (s_record, s_start) order.  The running maximum of (s_record << 32 | s_end) over

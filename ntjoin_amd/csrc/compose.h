@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "bisect.h"
 #include "ntjoin_mx.h"
 
 #if defined(__HIPCC__)
@@ -31,22 +32,12 @@ constexpr uint64_t CMP_MAX_PIECES = 0x7FFFFFFFull;  // a table of 2^31 pieces or
 
 CMP_HD uint32_t cmp_len(const mxg_seq_piece &p) { return p.end - p.start; }
 
-// the piece of a record that holds base a: the largest j < m with pre[j] <= a   (pre[0] = 0, pre increasing, m >= 1)
-CMP_HD uint32_t cmp_piece_at(const uint32_t *pre, uint32_t m, uint32_t a)
-{
-    uint32_t lo = 0, hi = m;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (pre[mid] <= a) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the inner pieces [j_lo, j_hi] of a record that meet [a, b), a < b <= the record's length
+// the inner pieces [j_lo, j_hi] of a record that meet [a, b), a < b <= the record's length.  The piece of a record that holds
+// base a: the largest j < m with pre[j] <= a   (pre[0] = 0, pre increasing, m >= 1)
 CMP_HD void cmp_range(const uint32_t *pre, uint32_t m, uint32_t a, uint32_t b, uint32_t &j_lo, uint32_t &j_hi)
 {
-    j_lo = cmp_piece_at(pre, m, a);
-    j_hi = cmp_piece_at(pre, m, b - 1u);
+    j_lo = last_le(pre, 0u, m, a);
+    j_hi = last_le(pre, 0u, m, b - 1u);
 }
 
 // inner piece q, which starts at base `at` of its record, clipped to [a, b) of that record (they meet), as a piece of the outer

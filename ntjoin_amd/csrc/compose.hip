@@ -53,17 +53,6 @@ __global__ __launch_bounds__(256) void k_cmp_count(const mxg_seq_piece *__restri
     if (threadIdx.x == 0) bsum64[blockIdx.x] = sh[0];
 }
 
-// largest i < n with arr[i] <= key (arr[0] = 0, arr strictly increasing: every outer piece becomes at least one piece)
-__device__ __forceinline__ uint32_t cmp_owner(const uint32_t *__restrict__ arr, uint32_t n, uint32_t key)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (arr[mid] <= key) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void k_cmp_emit(const mxg_seq_piece *__restrict__ op, const uint32_t *__restrict__ orec, uint32_t n_op,
                                                   const mxg_seq_piece *__restrict__ ip, const uint32_t *__restrict__ ifirst,
                                                   const uint32_t *__restrict__ ipre, const uint32_t *__restrict__ escan, uint32_t n_exp,
@@ -71,7 +60,9 @@ __global__ __launch_bounds__(256) void k_cmp_emit(const mxg_seq_piece *__restric
 {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     if (g >= n_exp) return;
-    const uint32_t i = cmp_owner(escan, n_op, g);
+    // the outer piece that expanded piece g comes from: the largest i < n_op with escan[i] <= g (escan[0] = 0, escan strictly
+    // increasing: every outer piece becomes at least one piece)
+    const uint32_t i = last_le(escan, 0u, n_op, g);
     const mxg_seq_piece p = op[i];
     mxg_seq_piece o;
     if (p.kind == MXG_PIECE_GAP) {

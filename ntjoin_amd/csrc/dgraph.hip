@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "batch_ctrl.h"
+#include "bisect.h"
 #include "mxg_internal.h"
 #include "scan_kernels.h"
 
@@ -208,12 +209,7 @@ __global__ __launch_bounds__(256) void k_dg_compact(const DgAdjParams p)
 // owner of a global vertex id: bases[r] <= g < bases[r + 1]
 __device__ __forceinline__ uint32_t dg_vertex_owner(const uint32_t *__restrict__ bases, uint32_t world, uint32_t g)
 {
-    uint32_t lo = 0, hi = world;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (bases[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
+    return last_le(bases, 0u, world, g);
 }
 
 // Records cut between ranks (sub-record shards): the adjacency between the last shared minimizer of one rank's piece and

@@ -13,7 +13,7 @@
 // Only that word (and the refused row) come to the host before the file is opened.  The rows stay on the device for the formatter:
 //   k_fai_len        bytes of every row's line (CountSink, text_dev.h) -> the shared 64-bit exclusive scan (scan64_kernels.h) gives
 //                    every line its place;
-//   k_fai_bounds     per window the row that holds its first byte;  k_fai_emit  the bytes of a window (WinSink).
+//   k_win_bounds     (win_out.hip) per window the row that holds its first byte;  k_fai_emit  the bytes of a window (WinSink).
 // Output leaves window by window through write_windows (win_out.hip); MXG_FAI_WIN sets the bytes per window.
 // The rows of a scaffold file need no text: every record is one line, {name, len, offset, len, len + 1} with offset the exclusive
 // scan of header bytes + len + 1 (k_fai_scaf_rows).  The .gzi is host code over OutFile.
@@ -205,21 +205,6 @@ __global__ __launch_bounds__(256) void k_fai_len(const FaiFmt q)
     q.off[i] = c.n;  // (entry n: 0, so that the exclusive sums end with the total)
 }
 
-// bounds[c] = the row whose line holds byte c * win of the file (off: [n + 1] offsets, off[n] = the file's size > c * win)
-__global__ __launch_bounds__(256) void k_fai_bounds(const uint64_t *__restrict__ off, uint32_t n, uint64_t win, uint32_t n_win,
-                                                    uint32_t *__restrict__ bounds)
-{
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= n_win) return;
-    const uint64_t target = (uint64_t)c * win;
-    uint32_t lo = 0, hi = n;  // off[lo] <= target < off[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= target) lo = mid; else hi = mid;
-    }
-    bounds[c] = lo;
-}
-
 // rows [i0, i1): what their lines have inside the window [lo, hi) of the file
 __global__ __launch_bounds__(256) void k_fai_emit(const FaiFmt q, uint32_t i0, uint32_t i1, uint64_t lo, uint64_t hi, char *__restrict__ out)
 {
@@ -282,8 +267,8 @@ static int fai_emit_rows(mxg_handle *h, FaiFmt q, OutFile &of, const char *who, 
     if (n_win >= 0xFFFFFFFFull) return set_err(h, MXG_ELIMIT, "%s: %llu windows of MXG_FAI_WIN bytes for '%s'", who, (unsigned long long)n_win, of.path.c_str());
     std::vector<uint32_t> bounds(n_win);
     MXG_HIP(h, B[FB_BOUNDS].ensure(n_win * 4));
-    hipLaunchKernelGGL(k_fai_bounds, dim3((uint32_t)((n_win + 255) / 256)), dim3(256), 0, st, q.off, q.n, WIN, (uint32_t)n_win,
-                       B[FB_BOUNDS].as<uint32_t>());
+    // bounds[c] = the row whose line holds byte c * WIN of the file
+    launch_win_bounds(st, q.off, q.n, WIN, (uint32_t)n_win, B[FB_BOUNDS].as<uint32_t>());
     MXG_HIP(h, hipGetLastError());
     MXG_HIP(h, hipMemcpyAsync(bounds.data(), B[FB_BOUNDS].p, n_win * 4, hipMemcpyDeviceToHost, st));
     MXG_HIP(h, hipStreamSynchronize(st));

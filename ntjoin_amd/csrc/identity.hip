@@ -225,11 +225,7 @@ __global__ __launch_bounds__(256) void k_idy_build(const SynAnchor *__restrict__
 {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     if (g >= n_seg) return;
-    uint32_t lo = 0, hi = n_keep;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (koff[mid] <= g) lo = mid; else hi = mid;
-    }
+    const uint32_t lo = last_le(koff, 0u, n_keep, g);
     const uint32_t t = g - koff[lo], cnt = kcnt[lo], j = kfirst[lo];
     mxg_identity_seg o{};
     if (t < cnt && cnt >= 2u) {  // (else cannot be: g lies below the scan's total; lq = ls = 0 is passed over by the segment kernel)

@@ -15,6 +15,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "bisect.h"
 #include "ntjoin_mx.h"
 
 #if defined(__HIPCC__)
@@ -48,12 +49,7 @@ LFT_HD bool lift_valid(uint32_t r, uint32_t a, uint32_t b, uint64_t n_source, co
 // the first i in [0, m] with arr[i] >= k (strict = false) or arr[i] > k (strict = true); arr rises
 LFT_HD uint32_t lift_bound(const uint64_t *arr, uint32_t m, uint64_t k, bool strict)
 {
-    uint32_t lo = 0, hi = m;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (strict ? arr[mid] > k : arr[mid] >= k) hi = mid; else lo = mid + 1;
-    }
-    return lo;
+    return first_where(0u, m, [&](uint32_t i) { return strict ? arr[i] > k : arr[i] >= k; });
 }
 
 // the candidates [lo, hi) of feature (r, a, b); lo >= hi: none

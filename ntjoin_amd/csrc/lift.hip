@@ -10,7 +10,7 @@
 //                                64-bit sum, so the host knows the number of parts before anything is scanned in 32 bits
 //   scan, k_lf_emit              per feature: its parts, at the scanned place
 // The lifted BED is pathtext.hip's shape: one formatter over the two sinks of text_dev.h, a 64-bit scan of the lines' lengths,
-// per window the first part by bisection, then write_windows (win_out.hip); MXG_LIFT_WIN sets the bytes per window.
+// per window the first part by bisection (k_win_bounds), then write_windows (both win_out.hip); MXG_LIFT_WIN sets the bytes per window.
 // Plain loads and stores throughout; every write is at an index below the size its array was allocated for (see the launches).
 #include <algorithm>
 #include <chrono>
@@ -361,20 +361,6 @@ __global__ __launch_bounds__(256) void k_lf_bed_len(const LfBed q)
     q.loff[g] = c.n;  // (entry n_parts: 0, so that the exclusive sums end with the total)
 }
 
-// bounds[c] = the part whose line holds byte c * win (off: [n + 1] offsets, off[n] = the text's size > c * win)
-__global__ __launch_bounds__(256) void k_lf_bounds(const uint64_t *__restrict__ off, uint32_t n, uint64_t win, uint32_t n_win, uint32_t *__restrict__ bounds)
-{
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= n_win) return;
-    const uint64_t target = (uint64_t)c * win;
-    uint32_t lo = 0, hi = n;  // off[lo] <= target < off[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= target) lo = mid; else hi = mid;
-    }
-    bounds[c] = lo;
-}
-
 // parts [g0, g1): what their lines have inside the window [lo, hi)
 __global__ __launch_bounds__(256) void k_lf_bed_emit(const LfBed q, uint32_t g0, uint32_t g1, uint64_t lo, uint64_t hi, char *__restrict__ out)
 {
@@ -480,8 +466,8 @@ int lift_bed(mxg_handle *h, const char *bed_path, const char *const *source_name
                 return set_err(h, MXG_ELIMIT, "mxg_lift_bed: %llu windows of MXG_LIFT_WIN bytes for '%s'", (unsigned long long)n_win, lifted_path);
             std::vector<uint32_t> bounds(n_win);
             MXG_HIP(h, B[LF_BOUNDS].ensure(n_win * 4));
-            hipLaunchKernelGGL(k_lf_bounds, dim3((uint32_t)((n_win + 255) / 256)), dim3(256), 0, st, q.loff, n_parts, WIN, (uint32_t)n_win,
-                               B[LF_BOUNDS].as<uint32_t>());
+            // bounds[c] = the part whose line holds byte c * WIN
+            launch_win_bounds(st, q.loff, n_parts, WIN, (uint32_t)n_win, B[LF_BOUNDS].as<uint32_t>());
             MXG_HIP(h, hipGetLastError());
             MXG_HIP(h, hipMemcpyAsync(bounds.data(), B[LF_BOUNDS].p, n_win * 4, hipMemcpyDeviceToHost, st));
             MXG_HIP(h, hipStreamSynchronize(st));

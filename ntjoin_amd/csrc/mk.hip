@@ -18,6 +18,7 @@
 // 2^64 - 1 (a group of more than about 2 * 10^6 equal values) as an error.
 #include <algorithm>
 
+#include "bisect.h"
 #include "mxg_internal.h"
 
 namespace mxg {
@@ -53,37 +54,6 @@ __device__ __forceinline__ void mk_add_by_key(unsigned long long *arr, uint32_t 
     }
 }
 
-// largest k < m with arr[k] <= key (arr[0] = 0, arr increasing)
-__device__ __forceinline__ uint32_t mk_find(const uint32_t *__restrict__ arr, uint32_t m, uint32_t key)
-{
-    uint32_t lo = 0, hi = m;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (arr[mid] <= key) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t mk_lower(const uint32_t *a, uint32_t n, uint32_t x)  // #a[i] < x (a sorted)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t mk_upper(const uint32_t *a, uint32_t n, uint32_t x)  // #a[i] <= x (a sorted)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // One merge of sorted blocks of width w (a power of two) inside a run a[0, n): where element o (= x) goes, and what it adds
 // to s.  The blocks [p0, p0 + w) and [p0 + w, p0 + 2w) merge into [p0, min(p0 + 2w, n)): destinations are distinct and < n.
 __device__ __forceinline__ uint32_t mk_merge_dest(const uint32_t *a, uint32_t n, uint32_t o, uint32_t x, uint32_t w, int64_t &s)
@@ -91,11 +61,11 @@ __device__ __forceinline__ uint32_t mk_merge_dest(const uint32_t *a, uint32_t n,
     const uint32_t p0 = o & ~(2 * w - 1);
     if (o - p0 < w) {  // left block: behind the right block's values < x
         const uint32_t r0 = p0 + w;
-        return r0 < n ? o + mk_lower(a + r0, min(w, n - r0), x) : o;
+        return r0 < n ? o + first_ge(a + r0, 0u, min(w, n - r0), x) : o;
     }
     // right block (its left block is full); the upper bound needs a second search only where x occurs in the left block
-    const uint32_t lb = mk_lower(a + p0, w, x);
-    const uint32_t ub = lb < w && a[p0 + lb] == x ? lb + mk_upper(a + p0 + lb, w - lb, x) : lb;
+    const uint32_t lb = first_ge(a + p0, 0u, w, x);
+    const uint32_t ub = lb < w && a[p0 + lb] == x ? lb + first_gt(a + p0 + lb, 0u, w - lb, x) : lb;
     s += (int64_t)lb - (int64_t)(w - ub);
     return o - w + ub;
 }
@@ -133,7 +103,7 @@ __global__ __launch_bounds__(256) void mk_tiles(uint32_t *x, const uint32_t *__r
                                                 const uint32_t *__restrict__ lr_tile0, uint32_t m, unsigned long long *s_out)
 {
     __shared__ uint32_t buf[2][MK_TILE];
-    const uint32_t k = mk_find(lr_tile0, m, blockIdx.x), r = lr_run[k];
+    const uint32_t k = last_le(lr_tile0, 0u, m, blockIdx.x), r = lr_run[k];  // (lr_tile0[0] = 0, lr_tile0 increasing)
     const uint32_t q0 = (blockIdx.x - lr_tile0[k]) * MK_TILE;
     const uint32_t base = first[r] + q0, n = min(MK_TILE, first[r + 1] - first[r] - q0);
     for (uint32_t i = threadIdx.x; i < n; i += 256) buf[0][i] = x[base + i];
@@ -166,7 +136,7 @@ __global__ __launch_bounds__(256) void mk_level(const uint32_t *__restrict__ src
     uint32_t r = 0;
     int64_t s = 0;
     if (in) {
-        const uint32_t k = mk_find(lr_off, m, g);
+        const uint32_t k = last_le(lr_off, 0u, m, g);  // (lr_off[0] = 0, lr_off increasing)
         r = lr_run[k];
         const uint32_t o = g - lr_off[k], f = first[r], n = first[r + 1] - f;
         const uint32_t v = src[f + o];
@@ -186,7 +156,7 @@ __global__ __launch_bounds__(256) void mk_ties(const uint32_t *__restrict__ x0, 
     uint32_t r = 0;
     uint64_t term = 0;
     if (in) {
-        const uint32_t k = mk_find(lr_off, m, g);
+        const uint32_t k = last_le(lr_off, 0u, m, g);  // (lr_off[0] = 0, lr_off increasing)
         r = lr_run[k];
         const uint32_t o = g - lr_off[k], f = first[r], n = first[r + 1] - f;
         uint32_t odd = 0;
@@ -194,7 +164,7 @@ __global__ __launch_bounds__(256) void mk_ties(const uint32_t *__restrict__ x0, 
         const uint32_t *a = (odd ? x1 : x0) + f;
         const uint32_t v = a[o];
         if ((o > 0 && a[o - 1] == v) || (o + 1 < n && a[o + 1] == v)) {
-            const uint64_t t = mk_upper(a, n, v) - mk_lower(a, n, v);
+            const uint64_t t = first_gt(a, 0u, n, v) - first_ge(a, 0u, n, v);
             term = (t - 1) * (2 * t + 5);
         }
     }

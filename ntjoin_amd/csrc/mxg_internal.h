@@ -511,6 +511,9 @@ struct WinTimes {  // seconds: taking the buffers, waiting for the device, putti
 // `total` bytes into `of` behind its first `base` bytes, window by window (nothing at all for total = 0)
 int write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint64_t base, const WinFill &fill, const char *who,
                   WinTimes *times = nullptr);
+// what a fill starts from: bounds[c] = the item (node, row, block, line) whose text holds byte c * WIN of the file, for the n_win
+// windows; off: the [n + 1] offsets of the n items' texts, off[0] = 0, off[n] = the file's size > (n_win - 1) * WIN
+void launch_win_bounds(hipStream_t st, const uint64_t *off, uint32_t n, uint64_t WIN, uint32_t n_win, uint32_t *bounds);
 // bgzf_deflate.hip: text on the device -> a BGZF file (bgzf_deflate.h).  bgzf_payload: text bytes a member (MXG_BGZF_PAYLOAD);
 // bgzf_window_bytes: text bytes a window, whole units of lcm(tile, P); bgzf_write_windows: the file, window by window, deflated
 // between fill and copy; bgzf_write: host bytes (mxg_bgzf_write)

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "bisect.h"
 #include "mxg_internal.h"
 
 namespace mxg {
@@ -62,11 +63,14 @@ __device__ __forceinline__ uint64_t ext_hash(uint64_t h0, uint64_t mult)
 // locate strip s: run index lo with run_strip0[lo] <= s < run_strip0[lo+1]
 __device__ __forceinline__ uint32_t find_run(const uint32_t *__restrict__ run_strip0, uint32_t lo, uint32_t hi, uint32_t s)
 {
-    while (hi - lo > 1) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (run_strip0[mid] <= s) lo = mid; else hi = mid;
-    }
-    return lo;
+    return last_le(run_strip0, lo, hi, s);
+}
+
+// the run that holds valid-k-mer index kx of its contig, among the contig's runs [lo, hi) (Run or RunX): the last one with kidx0 <= kx
+template <class R>
+__device__ __forceinline__ uint32_t run_of_kmer(const R *runs, uint32_t lo, uint32_t hi, uint32_t kx)
+{
+    return last_where(lo, hi, [&](uint32_t i) { return runs[i].kidx0 <= kx; });
 }
 
 template <class T>

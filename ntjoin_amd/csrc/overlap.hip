@@ -27,6 +27,7 @@
 // budget (MXG_OVL_BATCH entries), so the scratch does not grow with the number of paths.  Integers only.
 #include <algorithm>
 
+#include "bisect.h"
 #include "mxg_internal.h"
 #include "nthash_dev.h"
 #include "text_dev.h"
@@ -72,11 +73,7 @@ __device__ __forceinline__ bool ov_kmer(const OvNode &nd, const uint32_t *__rest
     if (nd.maskL < nd.maskR && p + k > nd.maskL && p < nd.maskR) return false;
     const uint64_t a = nd.rev ? nd.g0 + nd.len - p - k : nd.g0 + p, b = a + k;
     if (nd.invn) {  // first interval that ends behind a
-        uint32_t lo = 0, hi = nd.invn;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (inv[nd.inv0 + mid].y <= a) lo = mid + 1; else hi = mid;
-        }
+        const uint32_t lo = first_where(0u, nd.invn, [&](uint32_t i) { return inv[nd.inv0 + i].y > a; });
         if (lo < nd.invn && inv[nd.inv0 + lo].x < b) return false;
     }
     H2 h = {0u, 0u, 0u, 0u};
@@ -313,21 +310,7 @@ __global__ __launch_bounds__(64) void ov_junction(const OvNode *__restrict__ nod
     const uint64_t *sh = o_hash + S.off, *th = o_hash + T.off;
     const uint32_t *sp = o_pos + S.off, *tp = o_pos + T.off;
     // source list: positions >= keepR (a suffix); target list: positions < the next node's keepL (a prefix)
-    uint32_t s0 = 0, nT = 0;
-    {
-        uint32_t lo = 0, hi = nS;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (sp[mid] < S.keepR) lo = mid + 1; else hi = mid;
-        }
-        s0 = lo;
-        lo = 0, hi = nTall;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (tp[mid] < T.keepL) lo = mid + 1; else hi = mid;
-        }
-        nT = lo;
-    }
+    const uint32_t s0 = first_ge(sp, 0u, nS, S.keepR), nT = first_ge(tp, 0u, nTall, T.keepL);
     uint32_t *ms = js + S.off, *mp = jp + S.off, *mt = jt + T.off;
     for (uint32_t t = lane; t < nT; t += 64) mt[t] = 0;
     __threadfence();

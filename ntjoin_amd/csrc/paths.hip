@@ -15,6 +15,7 @@
 //                         arcs of the source->target list know their vertex's index in the path
 #include <algorithm>
 
+#include "bisect.h"
 #include "mxg_internal.h"
 #include "scan_kernels.h"
 
@@ -571,12 +572,7 @@ __global__ __launch_bounds__(256) void ks_heads(const uint32_t *__restrict__ fla
     const uint32_t s = excl[i];
     seg_first[s] = i;
     seg_rec[s] = vrec[pv[i]];
-    uint32_t lo = 0, hi = n_paths;  // last path with path_first <= i
-    while (hi - lo > 1) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (path_first[mid] <= i) lo = mid; else hi = mid;
-    }
-    seg_path[s] = lo;
+    seg_path[s] = last_le(path_first, 0u, n_paths, i);  // last path with path_first <= i
 }
 
 // one wave per segment: {n, min pos, max pos, increasing pairs, decreasing pairs}

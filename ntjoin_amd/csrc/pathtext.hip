@@ -16,7 +16,7 @@
 //                number of tiles and the sum over ALL paths may wrap; part = 2 j + 1 for node j of its path.
 //   k_pt_len     per node: bytes of its two fragments from decimal digit counts (they need `at`, hence the second pass);
 //                two more scans turn them into file offsets.
-//   k_pt_bounds  per window: the node that holds the window's first byte (bisection over the offsets).
+//   k_win_bounds per window: the node that holds the window's first byte (bisection over the offsets; win_out.hip).
 //   k_pt_emit    per node of a window: the fragment's bytes that fall into [lo, hi).  A long id is a loop of one lane.
 // Output leaves window by window through write_windows (win_out.hip); MXG_PATH_WIN sets the bytes per window.
 // The first line of the .path file and the AGP's unassigned lines (one per interval, from the handle's copy of the last
@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <string>
 
+#include "bisect.h"
 #include "mxg_internal.h"
 #include "scan64_kernels.h"
 #include "text_dev.h"
@@ -58,11 +59,7 @@ struct PtNode {
 __device__ __forceinline__ PtNode pt_node(const PtParams &q, uint32_t i)
 {
     PtNode nd;
-    uint64_t lo = 0, hi = q.n_paths;  // path_first[lo] <= i < path_first[hi]
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (q.path_first[mid] <= i) lo = mid; else hi = mid;
-    }
+    const uint64_t lo = last_le(q.path_first, (uint64_t)0, q.n_paths, i);  // path_first[lo] <= i < path_first[lo + 1]
     const uint64_t f0 = q.path_first[lo], f1 = q.path_first[lo + 1];
     nd.p = lo, nd.j = (uint32_t)(i - f0), nd.m = (uint32_t)(f1 - f0);
     const mxg_scaffold_node in = q.nodes[i];
@@ -177,21 +174,6 @@ __global__ __launch_bounds__(256) void k_pt_len(const PtParams q)
     q.aoff[i] = ac.n;
 }
 
-// bounds[c] = the node whose fragment holds byte c * win of the file (off: [n + 1] offsets, off[n] = the file's size > c * win)
-__global__ __launch_bounds__(256) void k_pt_bounds(const uint64_t *__restrict__ off, uint32_t n, uint64_t win, uint32_t n_win,
-                                                   uint32_t *__restrict__ bounds)
-{
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= n_win) return;
-    const uint64_t target = (uint64_t)c * win;
-    uint32_t lo = 0, hi = n;  // off[lo] <= target < off[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= target) lo = mid; else hi = mid;
-    }
-    bounds[c] = lo;
-}
-
 // nodes [i0, i1): what their fragments have inside the window [lo, hi) of the .path file (agp = 0) or the AGP (agp = 1)
 __global__ __launch_bounds__(256) void k_pt_emit(const PtParams q, uint32_t agp, uint32_t i0, uint32_t i1, uint64_t lo, uint64_t hi,
                                                  char *__restrict__ out)
@@ -223,8 +205,8 @@ static int pt_emit_file(mxg_handle *h, const PtParams &q, uint32_t agp, uint64_t
     if (n_win >= 0xFFFFFFFFull) return set_err(h, MXG_ELIMIT, "mxg_write_paths: %llu windows of MXG_PATH_WIN bytes for '%s'", (unsigned long long)n_win, of.path.c_str());
     std::vector<uint32_t> bounds(n_win);
     MXG_HIP(h, h->ptbuf[PT_BOUNDS].ensure(n_win * 4));
-    hipLaunchKernelGGL(k_pt_bounds, dim3((uint32_t)((n_win + 255) / 256)), dim3(256), 0, st, agp ? q.aoff : q.poff, q.n, WIN, (uint32_t)n_win,
-                       h->ptbuf[PT_BOUNDS].as<uint32_t>());
+    // bounds[c] = the node whose fragment holds byte c * WIN of the file
+    launch_win_bounds(st, agp ? q.aoff : q.poff, q.n, WIN, (uint32_t)n_win, h->ptbuf[PT_BOUNDS].as<uint32_t>());
     MXG_HIP(h, hipGetLastError());
     MXG_HIP(h, hipMemcpyAsync(bounds.data(), h->ptbuf[PT_BOUNDS].p, n_win * 4, hipMemcpyDeviceToHost, st));
     MXG_HIP(h, hipStreamSynchronize(st));

@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <string>
 
+#include "bisect.h"
 #include "mxg_internal.h"
 #include "seqstat.h"
 #include "text_index.h"
@@ -105,23 +106,10 @@ __device__ __forceinline__ uint32_t rep_bits(uint32_t lo, uint32_t hi)  // bits 
     return ((1u << hi) - 1u) & ~((1u << lo) - 1u);
 }
 
-// the first j in [lo, hi) with a[j] >= x (hi: none)
-__device__ __forceinline__ uint32_t rep_lower_bound(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t x)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 // the last j in [lo, hi] with segs[j].out <= x (segs[lo].out <= x)
 __device__ __forceinline__ uint32_t rep_seg_of(const RepSeg *segs, uint32_t lo, uint32_t hi, uint64_t x)
 {
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo + 1) >> 1);
-        if (segs[mid].out <= x) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+    return last_where(lo, hi + 1u, [&](uint32_t j) { return segs[j].out <= x; });
 }
 
 struct RepLane {
@@ -148,15 +136,15 @@ __device__ __forceinline__ RepLane rep_fetch(const RepSrc &q, uint64_t i, uint32
         const uint64_t tile = i * REP_TILE, t_hi = min(q.len, tile + REP_TILE);
         a0 = tile + 16u * t;
         if (t == 0) {
-            s_rng[0] = rep_lower_bound(q.org, 0, q.n_org, tile);
-            s_rng[1] = rep_lower_bound(q.org, s_rng[0], q.n_org, t_hi);
+            s_rng[0] = first_ge(q.org, 0u, q.n_org, tile);  // the record starts [s_rng[0], s_rng[1]) inside the tile
+            s_rng[1] = first_ge(q.org, s_rng[0], q.n_org, t_hi);
         }
         __syncthreads();
         if (a0 < t_hi) {
             const uint64_t hi = min(a0 + 16u, t_hi);
             valid = rep_bits(0, (uint32_t)(hi - a0));
             if (s_rng[0] < s_rng[1])
-                for (uint32_t j = rep_lower_bound(q.org, s_rng[0], s_rng[1], a0); j < s_rng[1] && q.org[j] < hi; ++j)
+                for (uint32_t j = first_ge(q.org, s_rng[0], s_rng[1], a0); j < s_rng[1] && q.org[j] < hi; ++j)
                     out.r |= 1u << (uint32_t)(q.org[j] - a0);
         }
     } else {

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <string>
 
+#include "bisect.h"
 #include "mxg_internal.h"
 #include "scan_kernels.h"
 #include "text_index.h"
@@ -116,11 +117,8 @@ __global__ __launch_bounds__(256) void k_scaf_emit(const ScafText t, const ScafP
         tab[256 + tid] = fold && cc >= 'a' && cc <= 'z' ? cc - 32 : cc;
     }
     const uint64_t t_lo = win_lo + (uint64_t)blockIdx.x * SCAF_TILE, t_hi = min(win_hi, t_lo + SCAF_TILE);
-    uint32_t first = 0;  // the last piece that begins at or before t_lo (pieces[0].out = 0; pieces of no length are passed over)
-    for (uint32_t hi = n_pieces; hi - first > 1;) {
-        const uint32_t mid = (first + hi) >> 1;
-        if (pieces[mid].out <= t_lo) first = mid; else hi = mid;
-    }
+    // the last piece that begins at or before t_lo (pieces[0].out = 0; pieces of no length are passed over)
+    const uint32_t first = last_where(0u, n_pieces, [&](uint32_t i) { return pieces[i].out <= t_lo; });
     __syncthreads();
     for (uint32_t pi = first; pi < n_pieces; ++pi) {
         const ScafPiece pc = pieces[pi];

@@ -1121,12 +1121,7 @@ struct EmitParams {
 // number of keys < key in the sorted array keys[0..n)
 __device__ __forceinline__ uint32_t lower_bound_u64(const uint64_t *keys, uint32_t n, uint64_t key)
 {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    return first_ge(keys, 0u, n, key);
 }
 
 __global__ __launch_bounds__(256) void k_emit(const EmitParams p)
@@ -1326,10 +1321,7 @@ __global__ __launch_bounds__(256) void k_emit(const EmitParams p)
             pos0 = 0u;
         }
         if (hi - lo > 1 || !p.ctg_info) {
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (p.runs[mid].kidx0 <= kx) lo = mid; else hi = mid;
-            }
+            lo = run_of_kmer(p.runs, lo, hi, kx);
             pos0 = p.runs[lo].pos0;
             kidx0 = p.runs[lo].kidx0;
         }
@@ -1364,13 +1356,7 @@ struct MergeParams {
 
 __device__ __forceinline__ uint32_t lower_bound_key(const uint32_t *rec, const uint32_t *pos, uint32_t n, uint64_t key)
 {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        uint32_t mid = (lo + hi) >> 1;
-        uint64_t km = ((uint64_t)rec[mid] << 32) | pos[mid];
-        if (km < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    return first_where(0u, n, [&](uint32_t i) { return (((uint64_t)rec[i] << 32) | pos[i]) >= key; });
 }
 
 __global__ __launch_bounds__(256) void k_merge(const MergeParams p)
@@ -1459,11 +1445,7 @@ __device__ __forceinline__ void gap_fix_one(const GapFixParams &p, const uint32_
         p.r_cnt[j] = 0;
     }
     // the run holding k_lo; a stretch that is not inside one run (invalid bases in it) goes to the host
-    uint32_t lo = p.ctg_run0[c], hi = p.ctg_run0[c + 1];
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (p.runs[mid].kidx0 <= klo) lo = mid; else hi = mid;
-    }
+    const uint32_t lo = run_of_kmer(p.runs, p.ctg_run0[c], p.ctg_run0[c + 1], klo);
     // (a stretch may run across invalid bases: its k-mers are the valid ones of several runs, its bases one range of the packed
     // array with the invalid ones in it -- taken as long as the range fits the block's words)
     const uint32_t r_end = p.ctg_run0[c + 1];
@@ -1747,12 +1729,7 @@ __global__ __launch_bounds__(256) void k_stretch_tiles(const StretchParams p)
     // valid bases begins, rolling in between
     const uint32_t per = (m + 255u) / 256u, a0 = threadIdx.x * per, a1 = min(a0 + per, m);
     if (a0 < m) {
-        uint32_t lo = p.ctg_run0[c], hi = p.ctg_run0[c + 1];
-        const uint32_t ki = i_lo + a0;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (p.runs[mid].kidx0 <= ki) lo = mid; else hi = mid;
-        }
+        uint32_t lo = run_of_kmer(p.runs, p.ctg_run0[c], p.ctg_run0[c + 1], i_lo + a0);
         Run run = p.runs[lo];
         H2 h = {0u, 0u, 0u, 0u};
         bool fresh = true;
@@ -4421,12 +4398,8 @@ __global__ __launch_bounds__(256) void k_unpack_part(const UnpackPartParams p)
     if (bad || (long long)i >= mine) return;
     const unsigned char *reg = p.all + (size_t)r * p.part_bytes + XCHG_PART_HEAD;
     const uint32_t *starts = reinterpret_cast<const uint32_t *>(reg + 12 * p.cap);
-    uint32_t lo = 0, hi = (uint32_t)my_recs;  // the last record whose first entry is <= i (records without entries share the next one's)
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (starts[mid] <= (uint32_t)i) lo = mid + 1;
-        else hi = mid;
-    }
+    // the last record whose first entry is <= i (records without entries share the next one's)
+    const uint32_t lo = first_gt(starts, 0u, (uint32_t)my_recs, (uint32_t)i);
     const uint64_t o = start + i;
     p.hash[o] = reinterpret_cast<const uint64_t *>(reg)[i];
     p.pos[o] = reinterpret_cast<const uint32_t *>(reg + 8 * p.cap)[i];

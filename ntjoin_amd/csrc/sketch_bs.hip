@@ -445,12 +445,8 @@ __device__ __forceinline__ void sel_decide(const BsSelParams &p, SelCtx &c, cons
     }
     // ... and a contig's first k-mer reports the stretch in front of the contig's first candidate (contigs without any: all of it)
     if (lane >= H && lane < c.own_end && sr.len && sr.k0 == 0) {
-        uint32_t lo = 0, hi = nreal;  // first real candidate at or behind this strip
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if ((le[mid] >> 6) < f) lo = mid + 1u; else hi = mid;
-        }
-        report(sr.cg, 0u, sr.nk, lo);
+        // first real candidate at or behind this strip
+        report(sr.cg, 0u, sr.nk, first_where(0u, nreal, [&](uint32_t i) { return (le[i] >> 6) >= f; }));
     }
     sel_sync<GLOB>();
     if (lane == 0) {
@@ -922,12 +918,7 @@ __global__ __launch_bounds__(SST_WAVES * 64, 5) void k_sel_stretch(const SelStre
         uint64_t my_b = 0;
         bool my_ok = false;
         if (has) {
-            uint32_t lo = p.ctg_run0[mine.x], hi = p.ctg_run0[mine.x + 1u];
-            while (hi - lo > 1u) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (p.runs[mid].kidx0 <= mine.y) lo = mid; else hi = mid;
-            }
-            const Run run = p.runs[lo];
+            const Run run = p.runs[run_of_kmer(p.runs, p.ctg_run0[mine.x], p.ctg_run0[mine.x + 1u], mine.y)];
             my_ok = mine.z < run.kidx0 + run.n_kmers && mine.z - mine.y + 1u >= p.w && mine.z - mine.y + 1u - p.w <= p.amax * SEL_INL_PIECES;
             my_b = run.base_off + (mine.y - run.kidx0);
         }

@@ -10,6 +10,7 @@
 #pragma once
 #include <cstdint>
 
+#include "bisect.h"
 #include "ntjoin_mx.h"
 
 #if defined(__HIPCC__)
@@ -50,12 +51,7 @@ SYN_HD uint32_t syn_link_at(const SynAnchor *a, uint64_t n, int64_t i, uint32_t 
 SYN_HD uint64_t syn_lower_bound(const SynAnchor *a, uint64_t n, uint32_t rec, uint32_t pos)
 {
     const uint64_t key = (uint64_t)rec << 32 | pos;
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (((uint64_t)a[mid].qrec << 32 | a[mid].qpos) < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    return first_where((uint64_t)0, n, [&](uint64_t i) { return ((uint64_t)a[i].qrec << 32 | a[i].qpos) >= key; });
 }
 
 // the anchors [lo, hi) a FWD / REV piece takes: those of its record with start <= qpos and qpos + k <= end

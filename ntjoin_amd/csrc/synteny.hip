@@ -14,7 +14,7 @@
 //   k_syn_blocks   per block: its fields from the two anchors, and whether it is kept
 //   scan, k_syn_compact   the kept blocks, in order, as eight arrays
 // The PAF writer is pathtext.hip's shape: one formatter over the two sinks of text_dev.h, a 64-bit scan of the lines' lengths,
-// per window the first block by bisection, then write_windows (win_out.hip); MXG_SYN_WIN sets the bytes per window.
+// per window the first block by bisection (k_win_bounds), then write_windows (both win_out.hip); MXG_SYN_WIN sets the bytes per window.
 // Plain loads and stores throughout; every write is at an index below the size its array was allocated for (see the launches).
 #include <algorithm>
 #include <string>
@@ -85,12 +85,7 @@ __global__ __launch_bounds__(256) void k_syn_emit(const mxg_seq_piece *__restric
 {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     if (g >= n_exp) return;
-    uint32_t lo = 0, hi = n_pc;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (escan[mid] <= g) lo = mid; else hi = mid;
-    }
-    const uint32_t i = lo, t = g - escan[i];
+    const uint32_t i = last_le(escan, 0u, n_pc, g), t = g - escan[i];
     if (t >= cnt[i]) return;  // (cannot be: g lies below the scan's total)
     out[g] = syn_piece_anchor(in, pc[i], k, plo[i], (uint64_t)plo[i] + cnt[i], t, prec[i], poff[i]);
 }
@@ -407,20 +402,6 @@ __global__ __launch_bounds__(256) void k_syn_paf_len(const SynPaf q)
     q.loff[i] = c.n;  // (entry n: 0, so that the exclusive sums end with the total)
 }
 
-// bounds[c] = the block whose line holds byte c * win (off: [n + 1] offsets, off[n] = the text's size > c * win)
-__global__ __launch_bounds__(256) void k_syn_bounds(const uint64_t *__restrict__ off, uint32_t n, uint64_t win, uint32_t n_win, uint32_t *__restrict__ bounds)
-{
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= n_win) return;
-    const uint64_t target = (uint64_t)c * win;
-    uint32_t lo = 0, hi = n;  // off[lo] <= target < off[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= target) lo = mid; else hi = mid;
-    }
-    bounds[c] = lo;
-}
-
 // blocks [i0, i1): what their lines have inside the window [lo, hi)
 __global__ __launch_bounds__(256) void k_syn_paf_emit(const SynPaf q, uint32_t i0, uint32_t i1, uint64_t lo, uint64_t hi, char *__restrict__ out)
 {
@@ -502,7 +483,8 @@ int write_synteny_paf(mxg_handle *h, const char *const *query_names, const char 
             return set_err(h, MXG_ELIMIT, "mxg_write_synteny_paf: %llu windows of MXG_SYN_WIN bytes for '%s'", (unsigned long long)n_win, path);
         std::vector<uint32_t> bounds(n_win);
         MXG_HIP(h, B[SY_BOUNDS].ensure(n_win * 4));
-        hipLaunchKernelGGL(k_syn_bounds, dim3((uint32_t)((n_win + 255) / 256)), dim3(256), 0, st, q.loff, n, WIN, (uint32_t)n_win, B[SY_BOUNDS].as<uint32_t>());
+        // bounds[c] = the block whose line holds byte c * WIN
+        launch_win_bounds(st, q.loff, n, WIN, (uint32_t)n_win, B[SY_BOUNDS].as<uint32_t>());
         MXG_HIP(h, hipGetLastError());
         MXG_HIP(h, hipMemcpyAsync(bounds.data(), B[SY_BOUNDS].p, n_win * 4, hipMemcpyDeviceToHost, st));
         MXG_HIP(h, hipStreamSynchronize(st));

@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "bisect.h"
 #include "mxg_internal.h"
 
 namespace mxg {
@@ -62,11 +63,8 @@ __global__ __launch_bounds__(256) void k_synth(uint32_t *__restrict__ out, uint6
     const uint64_t wi = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (wi >= n_words) return;
     const uint64_t b0 = wi * 16u;
-    uint64_t lo = 0, hi = n_segs;  // last segment with dst_base <= b0
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (segs[mid].dst_base <= b0) lo = mid; else hi = mid;
-    }
+    // last segment with dst_base <= b0 (0 where there is none, and where there is no segment at all)
+    const uint64_t lo = last_where((uint64_t)0, n_segs, [&](uint64_t i) { return segs[i].dst_base <= b0; });
     uint32_t word = 0;
     if (n_segs && segs[lo].dst_base <= b0) {
         const mxg_synth_seg s = segs[lo];

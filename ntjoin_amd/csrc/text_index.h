@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "bisect.h"
+
 namespace mxg {
 
 constexpr uint32_t ING_TILE = 4096;  // text bytes per work item: one aligned tile of the file, cut at record borders
@@ -38,11 +40,7 @@ struct TextIndex {
 __device__ __forceinline__ uint64_t text_of_base(const TextIndex &p, uint32_t r, uint32_t pos)
 {
     const uint64_t want = p.rec_base[r] + pos;
-    uint64_t lo = p.rec_item0[r], hi = p.rec_item0[r + 1];
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (p.item_pbase[mid] <= want) lo = mid; else hi = mid;
-    }
+    const uint64_t lo = last_le(p.item_pbase, p.rec_item0[r], p.rec_item0[r + 1], want);
     const IngItem it = p.items[lo];
     uint32_t local = (uint32_t)(want - p.item_pbase[lo]);
     const uint64_t tile = it.lo & ~(uint64_t)(ING_TILE - 1);

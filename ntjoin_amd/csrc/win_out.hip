@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <chrono>
 
+#include "bisect.h"
 #include "mxg_internal.h"
 
 namespace mxg {
@@ -40,6 +41,21 @@ int copy_pieces(mxg_handle *h, char *dst_pinned, const void *src_dev, uint64_t n
         MXG_HIP(h, hipMemcpyAsync(dst_pinned + done, static_cast<const char *>(src_dev) + done, std::min<uint64_t>(PIN_PIECE_BYTES, n - done),
                                   hipMemcpyDeviceToHost, h->stream));
     return MXG_OK;
+}
+
+// bounds[c] = the item whose text holds byte c * win of the file (off: [n + 1] offsets, off[n] = the file's size > c * win)
+__global__ __launch_bounds__(256) void k_win_bounds(const uint64_t *__restrict__ off, uint32_t n, uint64_t win, uint32_t n_win,
+                                                    uint32_t *__restrict__ bounds)
+{
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= n_win) return;
+    const uint64_t target = (uint64_t)c * win;
+    bounds[c] = last_le(off, 0u, n, target);  // off[0] = 0 <= target < off[n]
+}
+
+void launch_win_bounds(hipStream_t st, const uint64_t *off, uint32_t n, uint64_t WIN, uint32_t n_win, uint32_t *bounds)
+{
+    hipLaunchKernelGGL(k_win_bounds, dim3((n_win + 255) / 256), dim3(256), 0, st, off, n, WIN, n_win, bounds);
 }
 
 int write_windows(mxg_handle *h, OutFile &of, uint64_t total, uint64_t WIN, uint64_t base, const WinFill &fill, const char *who, WinTimes *times)

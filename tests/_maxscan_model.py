@@ -59,7 +59,8 @@ def max_scan(a, fault=None, exclusive=False):
 
 
 def lift_bound(arr, m, k, strict):
-    "ntjoin_amd/csrc/lift.h, lift_bound, word for word: the first i in [0, m] with arr[i] >= k, or > k when strict; arr rises"
+    """what ntjoin_amd/csrc/lift.h's lift_bound returns (there first_where of csrc/bisect.h over the same predicate), restated on its
+    own: the first i in [0, m] with arr[i] >= k, or > k when strict; arr rises"""
     lo, hi = 0, m
     while lo < hi:
         mid = lo + ((hi - lo) >> 1)

@@ -362,7 +362,7 @@ def offset_case(n):
 @pytest.mark.parametrize("n,win", [(1022, None), (1023, None), (1024, None), (262143, None), (262143, "4093"), (262144, None), (262144, "4093")])
 def test_offset_scan_borders(n, win, env, tmp_path, capfd):
     """n + 1 row sizes on either side of a tile (1 024) and of a round (262 144) of the 64-bit scan, a kept-out row in the first tile
-    and in the first round; with windows of 4093 bytes k_fai_bounds bisects offsets that live on the round carry"""
+    and in the first round; with windows of 4093 bytes k_win_bounds bisects offsets that live on the round carry"""
     text, want, items = offset_case(n)
     got, n_items = indexed(env, tmp_path, capfd, text, win)
     assert not isinstance(got, MxError), got

@@ -13,6 +13,9 @@ their carry code starts:
     than 16 384 tiles, where the scan over its counts takes a second pass;
   * count_prefix around the super-count (256 producer blocks), the first lanes' own loads (16 384), and the first and second trip of
     the loop over the super-counts (16 640, 82 176);
+  * the two bisections of csrc/bisect.h over 1 to 65 537 keys with runs of equal ones and keys above 2^32, one thread per query with a
+    partial last block, once over 32-bit indices where (lo + hi) >> 1 would wrap; the device writers' one window-bounds kernel
+    (launch_win_bounds, win_out.hip) with windows of 1 byte, 4093 bytes and exactly one line, on and one byte before an offset;
   * one run of the public API -- build_graph, synteny_blocks, write_synteny_paf, synteny_assess -- on 4 456 499 anchors in 262 147
     blocks (tests/_synteny_scale.py), past both scan borders, against the closed form and the restatements.
 
@@ -218,6 +221,102 @@ def test_count_prefix(q, more, tmp_path):
     counts.tofile(tmp_path / "c")
     out = run("prefix", q, tmp_path / "c")
     assert f"prefix: {int(counts[:q].sum(dtype=np.uint64))}\n" in out, out
+
+
+# ---- the bisections (csrc/bisect.h) and the window-bounds kernel every device writer shares (win_out.hip) ---------------------------
+BISECT_N = [1, 2, 3, 64, 65, 256, 257, 65537]
+BISECT_NQ = [1, 255, 256, 257]   # one thread per query: a lone thread, a block less one, a whole block, a block and one thread
+# every n with one query count, the counts going round; the smallest odd n and the largest with every count
+BISECT_CASES = sorted({(n, BISECT_NQ[i % 4]) for i, n in enumerate(BISECT_N)} | {(n, nq) for n in (3, 65537) for nq in BISECT_NQ})
+
+
+def bisect_input(n, nq):
+    "rising keys with runs of equal ones, the upper half of them above 2^32; queries on, beside, below and above the keys"
+    rng = np.random.default_rng(5000 + n + nq)
+    reps = rng.integers(1, 4, n)
+    reps[0] = 2   # (a run of two at the front whenever n >= 3)
+    keys = np.repeat(np.arange(n, dtype=np.uint64) * np.uint64(3) + np.uint64(5), reps)[:n]
+    keys[(n + 1) // 2:] += np.uint64(1 << 40)
+    fixed = [0, int(keys[0]) - 1, int(keys[0]), int(keys[-1]), int(keys[-1]) + 1, (1 << 64) - 1]
+    picks = [int(keys[i]) + d for i, d in zip(rng.integers(0, n, nq).tolist(), rng.integers(-1, 2, nq).tolist())]
+    queries = np.array((picks[:max(nq - len(fixed), 1)] + fixed)[:nq], dtype=np.uint64)
+    assert len(queries) == nq and (n < 3 or keys[0] == keys[1]) and (np.diff(keys.astype(object)) >= 0).all()
+    return keys, queries
+
+
+@pytest.mark.parametrize("n,nq", BISECT_CASES)
+def test_bisect_owner(n, nq, tmp_path):
+    "last_le: the last key <= x (0 where every key is above x; keys[0] is never read)"
+    keys, queries = bisect_input(n, nq)
+    keys.tofile(tmp_path / "k")
+    queries.tofile(tmp_path / "q")
+    run("owner", tmp_path / "k", tmp_path / "q", tmp_path / "out")
+    want = np.maximum(np.searchsorted(keys, queries, side="right").astype(np.int64) - 1, 0)
+    same(np.fromfile(tmp_path / "out", dtype=np.uint32).astype(np.int64), want, f"owner {n} {nq}")
+
+
+@pytest.mark.parametrize("n,nq", BISECT_CASES)
+def test_bisect_first(n, nq, tmp_path):
+    "first_ge and first_gt: the first key >= x and the first key > x (n where there is none)"
+    keys, queries = bisect_input(n, nq)
+    keys.tofile(tmp_path / "k")
+    queries.tofile(tmp_path / "q")
+    run("first", tmp_path / "k", tmp_path / "q", tmp_path / "out")
+    got = np.fromfile(tmp_path / "out", dtype=np.uint32).astype(np.int64)
+    same(got[:nq], np.searchsorted(keys, queries, side="left").astype(np.int64), f"first_ge {n} {nq}")
+    same(got[nq:], np.searchsorted(keys, queries, side="right").astype(np.int64), f"first_gt {n} {nq}")
+
+
+def test_bisect_midpoint_does_not_wrap(tmp_path):
+    """tests/test_bisect_cpu.py's case on the device: 32-bit indices [0x80000000, 0xFFFFFFFF), where (lo + hi) >> 1 in 32 bits is
+    0x3FFFFFFF, below lo, and the predicate i >= t reads no memory"""
+    lo, hi = 0x80000000, 0xFFFFFFFF
+    assert ((lo + hi) & 0xFFFFFFFF) >> 1 == 0x3FFFFFFF < lo
+    t = np.array([0x80000000, 0x80000001, 0xA0000000, 0xBFFFFFFF, 0xC0000000, 0xC0000001, 0xFFFFFFFE, 0xFFFFFFFF, 0x7FFFFFFF], dtype=np.uint32)
+    t.tofile(tmp_path / "t")
+    run("wrap", lo, hi, tmp_path / "t", tmp_path / "out")
+    same(np.fromfile(tmp_path / "out", dtype=np.uint32), np.clip(t, lo, hi).astype(np.uint32), "wrap")
+
+
+def winbounds_input(kind, n_win):
+    """the offsets of the items' texts (off[0] = 0, off[n] = the file's size) and the window for n_win windows:
+    one_byte  windows of 1 byte over lines of 0 to 3 bytes (items without text share their successor's offset);
+    w4093     windows of 4093 bytes over lines of about 60: no window border is a line border but by chance;
+    one_line  every line as long as the window: every window starts exactly on an offset;
+    borders   windows of 100 bytes; window c starts exactly on an offset for odd c and one byte before one for even c"""
+    rng = np.random.default_rng(6000 + n_win)
+    if kind == "one_byte":
+        win, lens = 1, rng.integers(0, 4, 2 * n_win)
+    elif kind == "w4093":
+        win, lens = 4093, rng.integers(1, 120, 80 * n_win)
+    elif kind == "one_line":
+        win, lens = 61, np.full(n_win, 61)
+    else:
+        assert kind == "borders"
+        win = 100
+        marks = sorted({c * win + (0 if c & 1 else 1) for c in range(1, n_win)} | {c * win + 37 for c in range(n_win)} | {n_win * win})
+        return np.array([0] + marks, dtype=np.uint64), win
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    if kind != "one_line":   # cut to a size of n_win windows, the last of them of one byte
+        total = (n_win - 1) * win + 1
+        off = np.concatenate([off[off < total], [total]]).astype(np.uint64)
+    return off, win
+
+
+@pytest.mark.parametrize("n_win", [1, 256, 257])
+@pytest.mark.parametrize("kind", ["one_byte", "w4093", "one_line", "borders"])
+def test_win_bounds(kind, n_win, tmp_path):
+    "bounds[c] = the last item whose text starts at or before byte c * win"
+    off, win = winbounds_input(kind, n_win)
+    n, total = len(off) - 1, int(off[-1])
+    assert off[0] == 0 and (np.diff(off.astype(np.int64)) >= 0).all() and (total + win - 1) // win == n_win
+    targets = np.arange(n_win, dtype=np.uint64) * np.uint64(win)
+    if kind == "borders" and n_win > 2:
+        assert np.isin(targets[1::2], off).all() and np.isin(targets[2::2] + np.uint64(1), off).all() and not np.isin(targets[2::2], off).any()
+    off.tofile(tmp_path / "off")
+    run("winbounds", tmp_path / "off", win, tmp_path / "out")
+    want = np.searchsorted(off[:n], targets, side="right").astype(np.int64) - 1
+    same(np.fromfile(tmp_path / "out", dtype=np.uint32).astype(np.int64), want, f"winbounds {kind} {n_win}")
 
 
 # ---- one stage-level run past both scan borders ------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
-// prim_check.hip -- runs ONE of the shared primitives (ntjoin_amd/csrc/scan_kernels.h, scan64_kernels.h, sort_kernels.h) once on ONE
-// input and writes what came out.  It decides nothing about right and wrong: tests/test_gpu_primitives.py computes every expected
+// prim_check.hip -- runs ONE of the shared primitives (ntjoin_amd/csrc/scan_kernels.h, scan64_kernels.h, sort_kernels.h, bisect.h) once
+// on ONE input and writes what came out.  It decides nothing about right and wrong: tests/test_gpu_primitives.py computes every expected
 // value.  Arrays are raw little-endian files; the element count is the file's size.
-// Build: hipcc --offload-arch=gfx950 -O3 -I ntjoin_amd/csrc tools/prim_check.hip -o ntjoin_amd/bin/prim_check
+// Build: ntjoin_amd/csrc/Makefile (it links the library for launch_win_bounds)
 // Usage: prim_check scan32 <in.u32> <out.u32> <total.u64>           launch_scan_u32 (n >= 1)
 //        prim_check scan64 <in.u64> <out.u64>                       launch_scan_u64, in place (n >= 1)
 //        prim_check maxscan64 <in.u64> <out.u64>                    launch_max_scan_u64, in place (n >= 1)
@@ -10,6 +10,12 @@
 //                                                                   the buffer that value names
 //        prim_check prefix <q> <counts.u32>                         every producer block b publishes counts[b] (count_publish, sup
 //                                                                   zeroed before); one wave prints "prefix: <count_prefix(q)>"
+//        prim_check owner <keys.u64> <queries.u64> <out.u32>        one thread per query: last_le over all the keys (bisect.h)
+//        prim_check first <keys.u64> <queries.u64> <out.u32>        one thread per query q of nq: out[q] = first_ge, out[nq + q] = first_gt
+//        prim_check wrap <lo> <hi> <t.u32> <out.u32>                one thread per t: first_where over the 32-bit indices [lo, hi) of
+//                                                                   the predicate i >= t, which reads no memory
+//        prim_check winbounds <off.u64> <win> <out.u32>             launch_win_bounds (the library's, win_out.hip) over the n + 1 offsets
+//                                                                   of a text of off[n] >= 1 bytes in windows of `win` bytes
 // Every device array has exactly the size its header documents, between 64 guard bytes in front and 64 behind; after the run the
 // guards are read back: "guards: ok", or "guards: changed <array> ..." for every array whose guards differ.
 #include <hip/hip_runtime.h>
@@ -21,6 +27,8 @@
 #include <string>
 #include <vector>
 
+#include "bisect.h"
+#include "mxg_internal.h"
 #include "scan64_kernels.h"
 #include "scan_kernels.h"
 #include "sort_kernels.h"
@@ -248,6 +256,84 @@ static int run_prefix(char **a)
     return 0;
 }
 
+// one thread per query; mode 0: out[q] = last_le, mode 1: out[q] = first_ge and out[nq + q] = first_gt, over keys[0, n)
+static __global__ __launch_bounds__(256) void k_bisect(const uint64_t *__restrict__ keys, uint32_t n, const uint64_t *__restrict__ queries, uint32_t nq,
+                                                       uint32_t mode, uint32_t *__restrict__ out)
+{
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= nq) return;
+    const uint64_t x = queries[q];
+    if (mode == 0) {
+        out[q] = last_le(keys, 0u, n, x);
+    } else {
+        out[q] = first_ge(keys, 0u, n, x);
+        out[nq + q] = first_gt(keys, 0u, n, x);
+    }
+}
+static __global__ __launch_bounds__(256) void k_wrap(uint32_t lo, uint32_t hi, const uint32_t *__restrict__ ts, uint32_t nt, uint32_t *__restrict__ out)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= nt) return;
+    const uint32_t t = ts[j];
+    out[j] = first_where(lo, hi, [&](uint32_t i) { return i >= t; });
+}
+
+static int run_bisect(uint32_t mode, char **a)
+{
+    const std::vector<uint64_t> keys = read_file<uint64_t>(a[0]), queries = read_file<uint64_t>(a[1]);
+    const uint32_t n = count_of(keys.size(), a[0]), nq = count_of(queries.size(), a[1]);
+    if (nq == 0) {
+        fprintf(stderr, "%s: no queries\n", mode ? "first" : "owner");
+        return 3;
+    }
+    const size_t n_out = (size_t)nq * (mode ? 2 : 1);
+    const Guarded d_keys = dev_array("keys", (size_t)n * 8), d_q = dev_array("queries", (size_t)nq * 8), d_out = dev_array("out", n_out * 4);
+    upload(d_keys, keys.data(), (size_t)n * 8);
+    upload(d_q, queries.data(), (size_t)nq * 8);
+    hipStream_t st = nullptr;
+    hipLaunchKernelGGL(k_bisect, dim3((nq + 255) / 256), dim3(256), 0, st, d_keys.as<uint64_t>(), n, d_q.as<uint64_t>(), nq, mode, d_out.as<uint32_t>());
+    finish(st);
+    download(a[2], d_out.as<uint32_t>(), n_out);
+    return 0;
+}
+
+static int run_wrap(char **a)
+{
+    const uint32_t lo = (uint32_t)strtoull(a[0], nullptr, 0), hi = (uint32_t)strtoull(a[1], nullptr, 0);
+    const std::vector<uint32_t> ts = read_file<uint32_t>(a[2]);
+    const uint32_t nt = count_of(ts.size(), a[2]);
+    if (nt == 0 || lo > hi) {
+        fprintf(stderr, "wrap: %u values, [%u, %u)\n", nt, lo, hi);
+        return 3;
+    }
+    const Guarded d_t = dev_array("t", (size_t)nt * 4), d_out = dev_array("out", (size_t)nt * 4);
+    upload(d_t, ts.data(), (size_t)nt * 4);
+    hipStream_t st = nullptr;
+    hipLaunchKernelGGL(k_wrap, dim3((nt + 255) / 256), dim3(256), 0, st, lo, hi, d_t.as<uint32_t>(), nt, d_out.as<uint32_t>());
+    finish(st);
+    download(a[3], d_out.as<uint32_t>(), nt);
+    return 0;
+}
+
+static int run_winbounds(char **a)
+{
+    const std::vector<uint64_t> off = read_file<uint64_t>(a[0]);
+    const uint64_t win = strtoull(a[1], nullptr, 10);
+    if (off.size() < 2 || off.back() == 0 || win == 0) {
+        fprintf(stderr, "winbounds: %zu offsets, window %llu\n", off.size(), (unsigned long long)win);
+        return 3;
+    }
+    const uint32_t n = count_of(off.size(), a[0]) - 1u;
+    const uint32_t n_win = count_of((off[n] + win - 1) / win, "windows");  // (so that off[n] > (n_win - 1) * win)
+    const Guarded d_off = dev_array("off", (size_t)(n + 1) * 8), d_bounds = dev_array("bounds", (size_t)n_win * 4);
+    upload(d_off, off.data(), (size_t)(n + 1) * 8);
+    hipStream_t st = nullptr;
+    launch_win_bounds(st, d_off.as<uint64_t>(), n, win, n_win, d_bounds.as<uint32_t>());
+    finish(st);
+    download(a[2], d_bounds.as<uint32_t>(), n_win);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     const std::string op = argc > 1 ? argv[1] : "";
@@ -262,8 +348,15 @@ int main(int argc, char **argv)
         rc = run_sort(argv + 2);
     else if (op == "prefix" && argc == 4)
         rc = run_prefix(argv + 2);
+    else if ((op == "owner" || op == "first") && argc == 5)
+        rc = run_bisect(op == "first", argv + 2);
+    else if (op == "wrap" && argc == 6)
+        rc = run_wrap(argv + 2);
+    else if (op == "winbounds" && argc == 5)
+        rc = run_winbounds(argv + 2);
     else {
-        fprintf(stderr, "usage: prim_check scan32 IN OUT TOTAL | scan64 IN OUT | maxscan64 IN OUT | sort KEY_BITS KEYS VALS KEYS_OUT VALS_OUT | prefix Q COUNTS\n");
+        fprintf(stderr, "usage: prim_check scan32 IN OUT TOTAL | scan64 IN OUT | maxscan64 IN OUT | sort KEY_BITS KEYS VALS KEYS_OUT VALS_OUT | prefix Q COUNTS |\n"
+                        "       owner KEYS QUERIES OUT | first KEYS QUERIES OUT | wrap LO HI T OUT | winbounds OFF WIN OUT\n");
         return 3;
     }
     if (rc) return rc;
